@@ -5,14 +5,22 @@ One "step" = one pass of the hot path over one synthetic BraTS-shaped volume tha
 preprocessed and resident in HBM: tile gather -> U-Net forwards -> sigmoid -> Gaussian-weighted
 aggregation -> probabilities -> region labels pasted into the full 155x240x240 uint8 volume.
 Default workload = BASELINE.json configs[1]: one 4x240x240x155 volume, 128^3 patches, step 0.5,
-model A (base 32, BatchNorm), 1 fold, fp32, no TTA -> 8 forwards per volume.  The default run also
-carries, inside the same JSON line, `secondary` blocks for BASELINE.json configs[2] (8-way TTA,
-models A + B, label ensemble) in fp16 and fp32 and an `end_to_end` block (host volume -> H2D ->
+model A (base 32, BatchNorm), 1 fold, fp32, no TTA -> 8 forwards per volume.  A plain run sets up, warms up
+(W steps), times exactly K steps, writes the outputs of the last timed step if --dump-outputs is given, and prints
+the JSON line.  With --full the line also carries the CPU baseline and the parity blocks against the CPU oracle,
+the per-kernel HIP-event profile and roofline, and (config 2) `secondary` blocks for BASELINE.json configs[2]
+(8-way TTA, models A + B, label ensemble) in fp16 and fp32, an `end_to_end` block (host volume -> H2D ->
 crop -> z-score -> predict -> labels -> D2H) and a `reference_setting` block: the reference's own per-case setting
-(5 folds x 2 models x 8-way TTA) in fp16 and fp32, one timed step each.
+(5 folds x 2 models x 8-way TTA) in fp16 and fp32, three timed steps each.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4] [--dtype f32|f16] [--shard cases|tiles] [--folds F]
-                    [--no-cpu-baseline] [--no-secondary] [--no-reference-setting]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-secondary] [--no-reference-setting]]
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed, as float32 DIR/<name>.npy (at most 64 MB in
+all; inputs and weights are seeded, so the same arguments give the same inputs on every run): configs 2 / 3 `labels`
+(the full 155x240x240 label volume the step returns) and `probabilities_<model>` (a fixed, seeded sample of each ensemble
+member's probabilities); config 4 `labels_case<i>` (a fixed, seeded sample of each case's label volume, written by the rank
+that owns the case).
 
 --config 3 --shard tiles = SURVEY.md 8e partitioning B (single-case latency): every rank works on the SAME volume, the
 (fold, tile) work list of each ensemble member is dealt round-robin over the ranks (mi355_sw_partial_folds), the partial
@@ -67,15 +75,29 @@ WORKLOADS = {
 }
 
 
+def _at_least(lo):
+    def parse(v):
+        n = int(v)
+        if n < lo:
+            raise argparse.ArgumentTypeError(f"must be >= {lo}")
+        return n
+    return parse
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--steps", type=_at_least(1), default=10, help="timed steps")
+    ap.add_argument("--warmup", type=_at_least(0), default=2, help="untimed steps before them")
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4), help="BASELINE.json config (1-based)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the config-3 and end-to-end blocks of the default run")
-    ap.add_argument("--no-reference-setting", action="store_true", help="skip the 5-fold x 2-model x TTA block of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: CPU baseline and parity against the CPU oracle, "
+                         "per-kernel profile and roofline, and (config 2) the config-3, end-to-end and reference-setting blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and the parity blocks")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the config-3 and end-to-end blocks of a --full run")
+    ap.add_argument("--no-reference-setting", action="store_true", help="skip the 5-fold x 2-model x TTA block of a --full run")
     ap.add_argument("--batch-tiles", type=int, default=0)
     ap.add_argument("--cases", type=int, default=0, help="config 4: number of volumes in the batch (default 32)")
     ap.add_argument("--shard", choices=("cases", "tiles"), default="cases",
@@ -199,25 +221,32 @@ def committed_counter(fname, section, kernel, field):
     return entry[field], (have is None or now is None or have != now)
 
 
-def timed_region(ctx, step, steps, warmup, nets):
-    """W untimed steps, then exactly K steps between two barrier + synchronize brackets; per-kernel HIP-event
-    profile (events recorded by the library on the launch stream) of the timed steps - or, when the step runs on more than one
-    lane (predictor.predict_folds(lanes > 1): kernels of two streams overlap, so an event pair around one of them also times its
-    neighbours), of ONE extra, untimed step on a single lane after the timed region."""
+def timed_region(ctx, step, steps, warmup, nets, profile=True, capture=None):
+    """W untimed steps, then exactly K steps between two barrier + synchronize brackets; with `profile` (--full) the per-kernel
+    HIP-event profile (events recorded by the library on the launch stream) of the timed steps - or, when the step runs on more
+    than one lane (predictor.predict_folds(lanes > 1): kernels of two streams overlap, so an event pair around one of them also
+    times its neighbours), of ONE extra, untimed step on a single lane after the timed region; without it `prof` is None.
+    `capture` (--dump-outputs): a dict whose "on" is True during the last timed step only, for the step to keep what it computed."""
     from brats_amd import predictor
     lanes = predictor.default_lanes()
     out = None
     for _ in range(warmup):
         out = step()
-    if lanes == 1:
+    if profile and lanes == 1:
         for net in nets:
             net.profile(True)
     ctx.sync_all()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for i in range(steps):
+        if capture is not None and i == steps - 1:
+            capture["on"] = True
         out = step()
     ctx.sync_all()
     elapsed = ctx.max_over_ranks(time.perf_counter() - t0)
+    if capture is not None:
+        capture["on"] = False
+    if not profile:
+        return elapsed, None, out
     if lanes > 1:
         os.environ["MI355_LANES"] = "1"
         try:
@@ -286,6 +315,30 @@ def kernel_table(prof):
                     tflops=round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] > 0 else None,
                     gbs=round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else None)
             for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])}
+
+
+PROB_SAMPLE = 1 << 20           # --dump-outputs: probabilities kept per ensemble member (configs 2 / 3)
+CASE_LABEL_BUDGET = 12 << 20    # --dump-outputs: label voxels kept over all cases of config 4
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def seeded_sample(t, k, seed):
+    """A fixed, seeded sample of k entries of the flattened tensor `t` (positions drawn without replacement and sorted), float32."""
+    import torch
+    n = t.numel()
+    idx = np.sort(np.random.RandomState(seed).choice(n, min(k, n), replace=False))
+    return t.reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as float32 DIR/<name>.npy."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def first_tile(data, steps_tbl):
@@ -391,8 +444,10 @@ def parity_probs_block(got, ref, sample):
                 voxels=int(lr.size), dice_wt_tc_et_mean=round(d["mean"], 6))
 
 
-def run_single_volume(ctx, args, config, dtype, steps, warmup, data, props, steps_tbl, oracle=None, folds=1, tiles_mode=False):
-    """configs 2 / 3: one volume per rank per step.  Returns the result dict (without the top-level contract keys)."""
+def run_single_volume(ctx, args, config, dtype, steps, warmup, data, props, steps_tbl, oracle=None, folds=1, tiles_mode=False,
+                      profile=True, dump=False):
+    """configs 2 / 3: one volume per rank per step.  Returns the result dict (without the top-level contract keys); with `dump`,
+    "_outputs" holds the arrays of the last timed step (--dump-outputs)."""
     from brats_amd import predictor, ops, parallel
     wl = WORKLOADS[config]
     members = [build_nets([(name, seed + k) for k in range(folds)], dtype) for name, seed in wl["models"]]   # [member][fold]
@@ -402,16 +457,19 @@ def run_single_volume(ctx, args, config, dtype, steps, warmup, data, props, step
     n_tiles = int(np.prod([len(s) for s in steps_tbl]))
     n_mirrors = 8 if wl["tta"] else 1
     flops_per_volume = sum(n.flops(PATCH) for n in nets) * n_tiles * n_mirrors
+    capture = {"on": False} if dump else None
 
     def step():
         if tiles_mode:   # partitioning B: this rank's (fold, tile) items, ONE exchange per member, identical result on every rank
             all_probs = [parallel.predict_case_tile_sharded(fold_nets, data, PATCH, 0.5, wl["tta"], (0, 1, 2), True, "sigmoid") for fold_nets in members]
         else:            # (the ensemble members of one case: the lanes of predictor.predict_members take them in staggered order)
             all_probs = predictor.predict_members(members, data, PATCH, 0.5, wl["tta"], (0, 1, 2), True, "sigmoid", batch_tiles=args.batch_tiles)
+        if capture is not None and capture["on"]:
+            capture["probs"] = all_probs
         segs = [ops.regions_to_labels(probs, (1, 2, 3), lo, full) for probs in all_probs]
         return segs[0] if len(segs) == 1 else ops.label_ensemble(segs[0], segs[1])
 
-    elapsed, prof, seg = timed_region(ctx, step, steps, warmup, nets)
+    elapsed, prof, seg = timed_region(ctx, step, steps, warmup, nets, profile, capture)
     res = dict(dtype=dtype, steps=steps, warmup=warmup, ms_per_step=round(elapsed / steps * 1e3, 3),
                volumes_per_s=round((1 if tiles_mode else ctx.world) * steps / elapsed, 4),
                config={"workload": wl["name"] + (f" [{folds} folds per member]" if folds != 1 else ""), "patch": list(PATCH),
@@ -423,12 +481,17 @@ def run_single_volume(ctx, args, config, dtype, steps, warmup, data, props, step
                                    if tiles_mode else "cases (one volume per rank per step)",
                        "tflop_per_volume": round(flops_per_volume / 1e12, 3)},
                sustained_tflops_per_gpu=round(flops_per_volume * steps / elapsed / 1e12 / (ctx.world if tiles_mode else 1), 2),
-               roofline=roofline_of(prof, dtype, None if (args.batch_tiles or args.folds != 1 or tiles_mode) else f"config{config}_{dtype}"),
-               kernels=kernel_table(prof),
+               roofline=None if prof is None else
+               roofline_of(prof, dtype, None if (args.batch_tiles or args.folds != 1 or tiles_mode) else f"config{config}_{dtype}"),
+               kernels=None if prof is None else kernel_table(prof),
                label_histogram=ctx.torch.bincount(seg.flatten().to(ctx.torch.int64), minlength=4).tolist(),
                speedup_vs_nominal_5min=round(300.0 / (elapsed / steps), 1))
     res["_flops_per_volume"] = flops_per_volume
     res["_elapsed"] = elapsed
+    if dump:
+        res["_outputs"] = dict(labels=seg.cpu().numpy())
+        for (name, _), probs in zip(wl["models"], capture["probs"]):
+            res["_outputs"][f"probabilities_{name}"] = seeded_sample(probs, PROB_SAMPLE, seed=0)
     if oracle is not None and ctx.rank == 0:
         tile = first_tile(data, steps_tbl)
         par = {}
@@ -566,7 +629,10 @@ def run_config4(ctx, args, dtype):
     def step():
         return parallel.predict_cases_sharded([[n] for n in nets], cases, ctx.rank, ctx.world, PATCH, 0.5, True, weights=weights)
 
-    elapsed, prof, segs = timed_region(ctx, step, args.steps, args.warmup, nets)
+    elapsed, prof, segs = timed_region(ctx, step, args.steps, args.warmup, nets, args.full)
+    if args.dump_outputs:   # (each rank writes the cases it owns)
+        k = CASE_LABEL_BUDGET // n_cases
+        dump_outputs(args.dump_outputs, {f"labels_case{i:03d}": seeded_sample(seg, k, seed=i) for i, seg in segs.items()})
     hist = None
     if segs:
         first = segs[min(segs)]
@@ -577,7 +643,8 @@ def run_config4(ctx, args, dtype):
                         "sharding": "cases longest-first (tile count) onto the least loaded rank, no data-path collective",
                         "tflop_per_batch": round(flops_batch / 1e12, 2)},
                 sustained=flops_batch * args.steps / elapsed / 1e12 / ctx.world,
-                roofline=roofline_of(prof, dtype, None), kernels=kernel_table(prof), label_histogram=hist)
+                roofline=None if prof is None else roofline_of(prof, dtype, None), kernels=None if prof is None else kernel_table(prof),
+                label_histogram=hist)
 
 
 def main(argv=None):
@@ -612,7 +679,7 @@ def main(argv=None):
     raw = synthetic.make_volume(seed=1000 + (0 if tiles_mode else ctx.rank))   # tiles mode: every rank works on the SAME case
     data, props = preprocessing.preprocess_case(raw, ctx.device)
     steps_tbl = [ops.compute_steps(PATCH[a], max(PATCH[a], data.shape[1 + a]), 0.5) for a in range(3)]
-    want_cpu = not args.no_cpu_baseline and ctx.world == 1
+    want_cpu = args.full and not args.no_cpu_baseline and ctx.world == 1
     oracle = CpuOracle(first_tile(data, steps_tbl)) if (want_cpu and ctx.rank == 0) else None
     cpu = None
     if oracle is not None:
@@ -620,11 +687,14 @@ def main(argv=None):
         oracle.forward(name, seed, min_forwards=2, budget_s=10.0)  # >= 2 timed forwards, about 10 s of CPU work
 
     main_res = run_single_volume(ctx, args, args.config, dtype, args.steps, args.warmup, data, props, steps_tbl, oracle,
-                                 folds=args.folds, tiles_mode=tiles_mode)
+                                 folds=args.folds, tiles_mode=tiles_mode, profile=args.full,
+                                 dump=bool(args.dump_outputs) and ctx.rank == 0)
     flops_per_volume, elapsed = main_res.pop("_flops_per_volume"), main_res.pop("_elapsed")
+    if "_outputs" in main_res:   # (rank 0: in cases mode every rank has a volume of its own, in tiles mode they all hold the same)
+        dump_outputs(args.dump_outputs, main_res.pop("_outputs"))
 
     secondary = None
-    if args.config == 2 and dtype == "f32" and ctx.world == 1 and not args.no_secondary and not args.batch_tiles and args.folds == 1:
+    if args.full and args.config == 2 and dtype == "f32" and ctx.world == 1 and not args.no_secondary and not args.batch_tiles and args.folds == 1:
         # BASELINE.json configs[2] under the same clock and the same oracle tile (3 steps each), and the PCIe-inclusive leg
         secondary = {}
         for dt in ("f16", "f32"):

@@ -7,10 +7,10 @@ leg of ``bench.py`` do, and there only as the checker / the timed CPU baseline.
 What is pinned and what is not ("Oracle"):
 
 * ``unet_ref``  - restatement of ``model_architecture/generic_UNet.py`` in plain
-  torch-CPU fp32 functional ops.  PINNED: checked against the reference module
-  itself (imported from /root/reference through ``ref_shim``) and against the
-  golden vectors that ``gen_golden.py`` produced from that import
-  (``tests/golden/net_*.npz``).
+  torch-CPU fp32 functional ops.  PINNED: checked against the golden vectors
+  that ``gen_golden.py`` produced by importing the reference module itself
+  through ``ref_shim`` (``tests/golden/net_*.npz``: logits, stage moments,
+  state_dict keys and shapes).
 * ``tiler_ref`` - restatement of the *un-vendored* nnU-Net v1 runtime the
   reference driver calls (sliding-window steps, Gaussian importance map,
   mirror TTA, aggregation, region export, preprocessing).  The source of that

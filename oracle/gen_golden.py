@@ -13,6 +13,8 @@ were made.  Weights and inputs come from frozen np.random.RandomState streams
                     expression (run_brats2021_inference_singlethread.py:305).
   rag_kb.json       config 5: the seven knowledge-base articles and, per query, what the reference's own
                     DummyVectorStore / is_clinical_query return (see gen_rag_fixture).
+  net_module_*.npz  state_dict keys / shapes and full logits of the reference module itself (gen_module_fixture).
+  plans_Task500_BraTS2021.pkl.gz  the reference's plans file, byte for byte (gen_plans_fixture).
 
     python -m oracle.gen_golden
 """
@@ -82,7 +84,57 @@ def main():
     np.savez_compressed(os.path.join(OUT, "driver_tables.npz"),
                         label_round=np.round((a + b) / 2.0).astype(np.uint8))
     gen_rag_fixture()
+    gen_module_fixture()
+    gen_plans_fixture()
     print("wrote", sorted(os.listdir(OUT)))
+
+
+# (config of test_oracle_network.py::test_oracle_matches_live_reference_module, weight seed 99, input seed 3)
+MODULE_CFGS = [
+    dict(norm="batch", base=32, num_pool=3, max_feat=128, encoder_scale=1),
+    dict(norm="group", base=32, num_pool=3, max_feat=128, encoder_scale=2),
+    dict(norm="instance", base=32, num_pool=2, max_feat=320, encoder_scale=1),
+]
+
+
+def module_fixture_name(cfg):
+    return f"net_module_{cfg['norm']}_p{cfg['num_pool']}_f{cfg['max_feat']}_e{cfg['encoder_scale']}.npz"
+
+
+def gen_module_fixture():
+    """tests/golden/net_module_*.npz - the reference's own Generic_UNet built for each of MODULE_CFGS: the key and shape of every
+    entry of its state_dict, and its full logits on a seeded 2x4x32^3 input with the synthetic weights loaded."""
+    import brats_amd
+    from oracle import ref_shim
+    for cfg in MODULE_CFGS:
+        sd = brats_amd.synthetic.make_state_dict(seed=99, all_heads=True, **cfg)
+        net = ref_shim.build_reference_net(cfg["norm"], 16, base=cfg["base"], num_pool=cfg["num_pool"],
+                                           max_feat=cfg["max_feat"], encoder_scale=cfg["encoder_scale"])
+        ref_sd = net.state_dict()
+        keys = sorted(ref_sd)
+        shapes = np.full((len(keys), 5), -1, np.int64)
+        for i, k in enumerate(keys):
+            shapes[i, :ref_sd[k].dim()] = ref_sd[k].shape
+        ref_shim.load_numpy_state_dict(net, sd)
+        x = torch.from_numpy(np.random.RandomState(3).standard_normal((2, 4, 32, 32, 32)).astype(np.float32))
+        with torch.no_grad():
+            y = net(x)
+        np.savez_compressed(os.path.join(OUT, module_fixture_name(cfg)), logits=y.numpy(), sd_keys=np.array(keys),
+                            sd_shapes=shapes, weight_seed=99, input_seed=3)
+        print(module_fixture_name(cfg), "logits moments", moments(y))
+
+
+def gen_plans_fixture():
+    """tests/golden/plans_Task500_BraTS2021.pkl.gz - the reference's Task500_BraTS2021 plans file (data/temp_inference_output1),
+    byte for byte, gzip-compressed."""
+    import gzip
+    from oracle import ref_shim
+    src = os.path.join(ref_shim.REFERENCE_ROOT, "data", "temp_inference_output1")
+    with open(src, "rb") as f:
+        raw = f.read()
+    with gzip.GzipFile(os.path.join(OUT, "plans_Task500_BraTS2021.pkl.gz"), "wb", compresslevel=9, mtime=0) as g:
+        g.write(raw)
+    print("plans fixture:", len(raw), "bytes")
 
 
 RAG_QUERIES = [

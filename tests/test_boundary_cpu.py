@@ -1,4 +1,5 @@
 """not gpu: the file-level boundary (NIfTI, checkpoint folders, driver host logic)."""
+import gzip
 import os
 import pickle
 
@@ -64,6 +65,14 @@ def test_prepare_input_naming_and_missing_modality(amd, tmp_path, capsys):
     assert "Missing t1ce for BraTS-GLI-00005-000" in capsys.readouterr().out
 
 
+def _reference_plans(tmp_path):
+    """The reference's data/temp_inference_output1 (Task500_BraTS2021 plans pickle), unpacked from its golden copy."""
+    path = tmp_path / "temp_inference_output1"
+    with gzip.open(os.path.join(os.path.dirname(__file__), "golden", "plans_Task500_BraTS2021.pkl.gz"), "rb") as f:
+        path.write_bytes(f.read())
+    return path
+
+
 def test_checkpoint_folder_round_trip_and_safe_unpickle(amd, tmp_path):
     ck = amd.checkpoint
     sd, _ = amd.synthetic.make_model("B", num_pool=2, max_feat=64)
@@ -85,23 +94,18 @@ def test_checkpoint_folder_round_trip_and_safe_unpickle(amd, tmp_path):
     evil.write_bytes(pickle.dumps(Evil()))
     with pytest.raises(pickle.UnpicklingError):
         ck.safe_pickle_load(evil)
-    ref_plans = "/root/reference/data/temp_inference_output1"
-    if os.path.exists(ref_plans):  # the reference's stray plans.pkl
-        p = ck.safe_pickle_load(ref_plans)
-        assert list(p["plans_per_stage"][0]["patch_size"]) == [128, 128, 128] and p["base_num_features"] == 32
+    p = ck.safe_pickle_load(_reference_plans(tmp_path))  # the reference's stray plans.pkl
+    assert list(p["plans_per_stage"][0]["patch_size"]) == [128, 128, 128] and p["base_num_features"] == 32
 
 
-def test_default_plans_equal_the_references_plans_field_by_field(amd):
+def test_default_plans_equal_the_references_plans_field_by_field(amd, tmp_path):
     """pin what the reference DOES hold.  data/temp_inference_output1 is the Task500_BraTS2021 plans file
     the reference ships; every field of checkpoint.default_brats_plans() (what synthetic model folders, the smoke run and the
     bench are built from) must equal it, and preprocessing.check_plans / check_spacing must accept it as it is - i.e. the
     path's assumptions (identity transpose, nonCT + use_mask_for_norm on four modalities, 1 mm target spacing, 128^3 patch,
-    five 2x2x2 poolings, 3x3x3 convs) are the reference's own, not ours.  Build container only (the file is not on the GPU box)."""
-    ref_plans = "/root/reference/data/temp_inference_output1"
-    if not os.path.exists(ref_plans):
-        pytest.skip("reference tree absent (GPU box)")
+    five 2x2x2 poolings, 3x3x3 convs) are the reference's own, not ours.  The file is kept byte for byte under tests/golden/."""
     ck, pre = amd.checkpoint, amd.preprocessing
-    ref = ck.safe_pickle_load(ref_plans)
+    ref = ck.safe_pickle_load(_reference_plans(tmp_path))
     ours = ck.default_brats_plans()
 
     def norm(v):

@@ -131,7 +131,8 @@ def test_config5_segmentation_then_knowledge_base_retrieval(amd, gpu, tmp_path):
 def test_bench_config4_under_the_launcher(gpu):
     """The exact command shape the driver's SCALE run uses (python -m torch.distributed.run ... bench.py --gpus N --config 4),
     at N = 1 with two cases and one step: a real `nccl` process group, the tile-count exchange, longest-first sharding and
-    the one-line JSON contract.  Runs as a child process (the parent keeps its own HIP context; two processes on the card)."""
+    the one-line JSON contract (--full: with the per-kernel profile the roofline comes from).  Runs as a child process (the
+    parent keeps its own HIP context; two processes on the card)."""
     import subprocess
     import sys
     with socket.socket() as sk:
@@ -139,7 +140,7 @@ def test_bench_config4_under_the_launcher(gpu):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "4", "--cases", "2", "--steps", "1",
-           "--warmup", "0"]
+           "--warmup", "0", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
@@ -171,3 +172,26 @@ def test_bench_config3_tile_sharded_under_the_launcher(gpu):
     assert out["n_gpus"] == 1 and out["steps"] == 1 and out["scaling"] == "strong" and out["dtype"] == "f16"
     assert out["config"]["folds_per_member"] == 2 and out["config"]["sharding"].startswith("tiles")
     assert out["value"] > 0 and sum(out["label_histogram"]) == 155 * 240 * 240
+
+
+def test_bench_plain_run_dumps_its_last_step(gpu, tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, carries only the headline blocks, and --dump-outputs
+    writes what its last timed step computed: the full label volume (whose histogram the JSON line reports) and a seeded sample
+    of the probabilities."""
+    import subprocess
+    import sys
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out_dir)]
+    res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+    out = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["dtype"] == "f32"
+    assert out["unit"] == "volumes/s" and out["higher_is_better"] is True
+    assert abs(out["value"] - 1e3 / out["ms_per_step"]) <= 1e-3 * out["value"]
+    assert out["roofline"] is None and out["kernels"] is None and out["cpu_baseline"] is None and "secondary" not in out
+    assert sorted(os.listdir(out_dir)) == ["labels.npy", "probabilities_A.npy"]
+    labels = np.load(out_dir / "labels.npy")
+    assert labels.dtype == np.float32 and labels.shape == (155, 240, 240)
+    assert np.bincount(labels.astype(np.int64).ravel(), minlength=4).tolist() == out["label_histogram"]
+    probs = np.load(out_dir / "probabilities_A.npy")
+    assert probs.dtype == np.float32 and probs.shape == (1 << 20,) and 0.0 <= probs.min() and probs.max() <= 1.0 + 1e-6

@@ -157,6 +157,26 @@ def test_bench_self_launch_command(monkeypatch):
     assert not calls
 
 
+def test_bench_plain_defaults_and_dump_limit(tmp_path):
+    """A plain bench run is lean (--full is off by default), --steps counts at least one timed step, and --dump-outputs writes
+    float32 arrays and refuses more than 64 MB in all."""
+    import importlib
+    import sys
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    args = bench.parse_args([])
+    assert args.full is False and args.dump_outputs is None and args.steps == 10 and args.warmup == 2
+    assert bench.parse_args(["--full", "--dump-outputs", "d", "--steps", "3"]).steps == 3
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    bench.dump_outputs(str(tmp_path / "ok"), {"labels": np.arange(6, dtype=np.uint8).reshape(2, 3)})
+    got = np.load(tmp_path / "ok" / "labels.npy")
+    assert got.dtype == np.float32 and got.tolist() == [[0, 1, 2], [3, 4, 5]]
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"a": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)})
+    assert not (tmp_path / "big").exists()
+
+
 # ---------------------------------------------------------------- ISA gate of the build (round 5; _isa_gate.py)
 _GATE_KERNEL = """\t.text
 _ZN5mi35520conv3_f16_dma_kernelILb0ELb0EEEvNS_9ConvArgsHE:

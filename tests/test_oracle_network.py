@@ -2,15 +2,15 @@
 
 1. against golden vectors produced by importing the reference's own Generic_UNet
    (oracle/gen_golden.py -> tests/golden/net_*.npz);
-2. when /root/reference is present (build container), directly against the live reference
-   module on a fresh seed, so fixture and restatement cannot drift together."""
+2. against what the reference module itself builds and computes on a second seed (its
+   state_dict keys / shapes and full logits, oracle/gen_golden.py -> tests/golden/net_module_*.npz)."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from oracle import ref_shim, unet_ref
+from oracle import gen_golden, unet_ref
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -47,27 +47,22 @@ def test_oracle_matches_reference_golden_small(amd, norm, nonlin_first):
     assert np.abs(y - g["logits"]).max() <= 1e-5 * max(1.0, float(np.abs(g["logits"]).max()))
 
 
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="/root/reference absent (GPU box)")
-@pytest.mark.parametrize("cfg", [
-    dict(norm="batch", base=32, num_pool=3, max_feat=128, encoder_scale=1),
-    dict(norm="group", base=32, num_pool=3, max_feat=128, encoder_scale=2),
-    dict(norm="instance", base=32, num_pool=2, max_feat=320, encoder_scale=1),
-])
+@pytest.mark.parametrize("cfg", gen_golden.MODULE_CFGS)
 def test_oracle_matches_live_reference_module(amd, cfg):
-    sd = amd.synthetic.make_state_dict(seed=99, all_heads=True, **cfg)
-    net = ref_shim.build_reference_net(cfg["norm"], 16, base=cfg["base"], num_pool=cfg["num_pool"],
-                                       max_feat=cfg["max_feat"], encoder_scale=cfg["encoder_scale"])
+    g = np.load(os.path.join(GOLD, gen_golden.module_fixture_name(cfg)))
+    sd = amd.synthetic.make_state_dict(seed=int(g["weight_seed"]), all_heads=True, **cfg)
     # every key / shape the synthetic generator emits is what the reference constructor builds
-    ref_sd = net.state_dict()
-    assert set(sd.keys()) == set(ref_sd.keys())
+    ref_shapes = {str(k): tuple(int(d) for d in s if d >= 0) for k, s in zip(g["sd_keys"], g["sd_shapes"])}
+    assert set(sd.keys()) == set(ref_shapes)
     for k in sd:
-        assert tuple(sd[k].shape) == tuple(ref_sd[k].shape), k
-    ref_shim.load_numpy_state_dict(net, sd)
-    x = torch.from_numpy(np.random.RandomState(3).standard_normal((2, 4, 32, 32, 32)).astype(np.float32))
-    with torch.no_grad():
-        want = net(x)
+        assert tuple(sd[k].shape) == ref_shapes[k], k
+    x = torch.from_numpy(np.random.RandomState(int(g["input_seed"])).standard_normal((2, 4, 32, 32, 32)).astype(np.float32))
     got = unet_ref.unet_forward(sd, x, unet_ref.default_cfg(norm=cfg["norm"], num_groups=16))
-    assert torch.equal(got, want)
+    want = torch.from_numpy(g["logits"])
+    assert got.shape == want.shape
+    # same torch ops in the same order as the reference module: bit-identical on the CPU the fixture was made on; oneDNN picks
+    # other kernels on other instruction sets (AVX2 / SSE4.1 against AVX-512: up to 3.7e-6 of max |logit|)
+    assert (got - want).abs().max().item() <= 1e-5 * want.abs().max().item()
 
 
 def test_flop_count_matches_survey(amd):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fills the R4_* placeholders of DESIGN.md section 0 from a `python bench.py` JSON line (one-off helper of round 4)."""
+"""Fills the R4_* placeholders of DESIGN.md section 0 from a `python bench.py --full` JSON line (one-off helper of round 4)."""
 import json
 import sys
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One-screen summary of bench.py JSON lines: ms per step, dominant kernel, conv-stage fraction, the top kernels."""
+"""One-screen summary of `bench.py --full` JSON lines: ms per step, dominant kernel, conv-stage fraction, the top kernels."""
 import json
 import sys
 for f in sys.argv[1:]:
