@@ -108,7 +108,7 @@ __device__ __forceinline__ double quantise_partial(double v, int k, long voxels)
 // 16-lane row its row total; one cross-row exchange finishes.  Round 3: the Instance/GroupNorm statistics epilogues used a
 // five-step __shfl_xor butterfly per value - hipcc lowers every step to ds_swizzle / ds_bpermute, i.e. an LDS round trip,
 // and 640 of them in dependent chains cost the fp16 LDS-DMA kernel 16.6k cycles per tile (20.2k against 3.5k for the
-// epilogue without statistics, tools/h16_probe.hip stamps: 31 % of a 4-chunk tile).
+// epilogue without statistics, profiles/r03_h16_dma_stamps_reduce_scatter.txt: 31 % of a 4-chunk tile).
 template <int CTRL>
 __device__ __forceinline__ float dpp_perm(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));  // (bound_ctrl: no 'old' operand to materialise)

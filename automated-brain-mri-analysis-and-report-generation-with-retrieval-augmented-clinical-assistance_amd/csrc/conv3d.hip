@@ -12,7 +12,6 @@
 //   * f32-input MFMA is an exact k-ordered fmaf chain (no TF32 on gfx950).
 // Kernels in this file (dispatch: conv3d_mfma_f32 at the bottom; DESIGN.md section 5 has the measurements):
 //   conv3_f32_wino2_kernel      stride 1, large launches: Winograd F(2x2,3x3) over (z,y), LDS-DMA bricks   [default]
-//   conv3_f32_wino_kernel       stride 1, large launches: Winograd F(2,3) along y                   (MI355_WINOGRAD=1)
 //   conv3_f32_s2dma_kernel      stride 2, large launches: LDS-DMA bricks, weight planes through an LDS ring
 //   conv3_f32_mfma_pipe_kernel  stride 1, mid-size launches: persistent, register-staged double-buffered brick
 //   conv3_f32_mfma_kernel       everything else (one tile per workgroup, stride 1|2), also the split-K slices of the
@@ -188,7 +187,7 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[MF][NF], const ConvA
 
 // Whole-line variant of the plain epilogue (no statistics, no fused head).  In the accumulator layout a lane holds 16
 // couts of ONE voxel, so a 16-B store instruction touches 32 different 128-B lines, a quarter of each: the store tail of
-// a 4x4x32x32 tile took 13.7k cycles of a workgroup's time (tools/wino2_probe.hip stamps, round 2) - issue-bound on
+// a 4x4x32x32 tile took 13.7k cycles of a workgroup's time (profiles/r02_wino2_stamps_round1_kernel.txt) - issue-bound on
 // partial lines, not bandwidth-bound.  Here each 32-voxel x 32-cout fragment is transposed through LDS (a wave-private
 // 32 x 36-float image: ds_write_b128 by voxel row, ds_read_b128 by line) so that 8 consecutive lanes store one whole
 // 128-B line and an instruction covers 8 full lines; bias and LeakyReLU are applied after the transposition (one bias
@@ -235,12 +234,8 @@ __device__ __forceinline__ void conv_epilogue_lines(f32x16 (&acc)[MF][NF], const
                 asm("v_max_f32 %0, %1, %2" : "=v"(val[1]) : "v"(x0[1]), "v"(y0[1]));  // canonicalising max per value
                 asm("v_max_f32 %0, %1, %2" : "=v"(val[2]) : "v"(x1[0]), "v"(y1[0]));
                 asm("v_max_f32 %0, %1, %2" : "=v"(val[3]) : "v"(x1[1]), "v"(y1[1]));
-#ifdef MI355_W2_ABL_NOSTORE
-                asm volatile("" :: "v"(val), "v"(ok), "v"(oz), "v"(oy), "v"(ox));
-#else
                 if (ok)
                     *(f32x4 *)(p.out + ((((size_t)n * p.Do + oz) * p.Ho + oy) * p.Wo + ox) * p.Cout + co_blk + nf * 32 + spiece * 4) = val;
-#endif
             }
         }
     }
@@ -651,150 +646,6 @@ __global__ void conv3_direct_kernel(const float *in0, const float *in1, int C0, 
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// Winograd F(2,3) along y.  The f32 convs are MFMA-bound (exact fp32 multiplies, no TF32), so the lever left is the
-// number of multiplies: for an output row pair (2p, 2p+1) of the 4x4x32 tile the three dy taps
-//     y0 = w0 d0 + w1 d1 + w2 d2,   y1 = w0 d1 + w1 d2 + w2 d3       (d0..d3 = input rows 2p-1 .. 2p+2)
-// are computed as        m0 = (d0-d2) w0, m1 = (d1+d2)(w0+w1+w2)/2, m2 = (d2-d1)(w0-w1+w2)/2, m3 = (d1-d3) w2,
-//                        y0 = m0+m1+m2,   y1 = m1-m2-m3
-// i.e. 4 MFMA K-steps per (dz, dx, channel) for two output rows instead of 6: 2/3 of the direct kernel's MFMAs.
-// The row direction is the one that costs nothing else: lane = x as before (conflict-free ds_read_b128), the
-// transform is 16 VALU ops per pair and step on registers the lane already holds, a wave (one z plane of the tile)
-// reads the SIX brick rows of its two pairs once per step (the direct kernel reads 12 fragments for the same 3 dy
-// taps), and the brick, the staging and the epilogue are those of conv3_f32_mfma_kernel<1,16,4,1>.
-// The transformed weights U_f = G w are computed in fp64 on the host (conv_weights_upload) and rounded once to fp32.
-// Accumulators: 2 pairs x 4 components x 16 = 128 VGPRs per wave.
-// Rounding: the 1-D transform adds one fp32 rounding on the input differences and one on U; measured against the
-// CPU oracle the logits move by < 2x the direct kernel's summation-order noise (tests/test_gpu_ops.py).
-__global__ __launch_bounds__(256, 2) void conv3_f32_wino_kernel(ConvArgs p) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int CC = 16, Q = CC / 4, G = CC / 8;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int half = lane >> 5;
-    const int l31 = lane & 31;
-
-    const int bid = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-    const int n = (int)fdiv((uint32_t)bid, p.div_tiles_per_n);
-    int t = bid - n * (int)p.div_tiles_per_n.d;
-    const int tzy = (int)fdiv((uint32_t)t, p.div_tiles_x);
-    const int tile_x = t - tzy * p.tiles_x;
-    const int tile_z = (int)fdiv((uint32_t)tzy, p.div_tiles_y);
-    const int tile_y = tzy - tile_z * p.tiles_y;
-    const int oz0 = tile_z << 2, oy0 = tile_y << 2, ox0 = tile_x << 5;  // tile is fixed: 4 x 4 x 32
-    const int iz0 = oz0 - 1, iy0 = oy0 - 1, ix0 = ox0 - 1;
-    constexpr int IX = 34, IY = 6, IZ = 6;
-    constexpr int brickvox = IX * IY * IZ;
-    constexpr int npieces = brickvox * Q;
-    constexpr int plane = brickvox * 4;
-
-    // wave = z plane of the tile; lane's brick row 0 at tap (dz, dx) = (0, 0), channel quad `half`
-    const int a_base = half * plane + (wave * IY * IX + l31) * 4;
-
-    f32x16 acc[2][4];
-#pragma unroll
-    for (int pr = 0; pr < 2; ++pr)
-#pragma unroll
-        for (int f = 0; f < 4; ++f)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[pr][f][r] = 0.f;
-
-    // packed U: [cout block][chunk][step = dz*3+dx][g][f][lane][4]
-    const float *wblk = p.wp + (size_t)blockIdx.y * p.nchunks * (9 * G * 4 * 256) + lane * 4;
-
-    for (int ch = 0; ch < p.nchunks; ++ch) {
-        const int cglob = ch * CC;
-        const float *src;
-        int Csrc, coff;
-        if (cglob < p.C0) {
-            src = p.in0; Csrc = p.C0; coff = cglob;
-        } else {
-            src = p.in1; Csrc = p.C1; coff = cglob - p.C0;
-        }
-        src += (size_t)n * p.Di * p.Hi * p.Wi * Csrc + coff;
-        constexpr int U = 4;
-        for (int i0 = tid; i0 < npieces; i0 += 256 * U) {
-            f32x4 v[U];
-            int dst[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int i = i0 + u * 256;
-                const int bv = i / Q, q = i - bv * Q;
-                const int r = bv / IX, bx = bv - r * IX;
-                const int bz = r / IY, by = r - bz * IY;
-                const int iz = iz0 + bz, iy = iy0 + by, ix = ix0 + bx;
-                const bool ok = (i < npieces) && ((unsigned)iz < (unsigned)p.Di) &&
-                                ((unsigned)iy < (unsigned)p.Hi) && ((unsigned)ix < (unsigned)p.Wi);
-                dst[u] = (i < npieces) ? q * plane + bv * 4 : -1;
-                f32x4 val = {0.f, 0.f, 0.f, 0.f};
-                if (ok)
-                    val = *(const f32x4 *)(src + ((size_t)(iz * p.Hi + iy) * p.Wi + ix) * Csrc + q * 4);
-                v[u] = val;
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-                if (dst[u] >= 0)
-                    *(f32x4 *)(lds + dst[u]) = v[u];
-        }
-        __syncthreads();
-
-        const float *wch = wblk + (size_t)ch * (9 * G * 4 * 256);
-        f32x4 rows[6], u_cur[4], u_nxt[4];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) rows[r] = *(const f32x4 *)(lds + a_base + r * IX * 4);
-#pragma unroll
-        for (int f = 0; f < 4; ++f) u_cur[f] = *(const f32x4 *)(wch + f * 256);
-
-        for (int st = 0; st < 9; ++st) {
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                // input transform B^T d of both row pairs (rows 0..3 and 2..5)
-                f32x4 V[2][4];
-#pragma unroll
-                for (int pr = 0; pr < 2; ++pr) {
-                    V[pr][0] = rows[2 * pr] - rows[2 * pr + 2];
-                    V[pr][1] = rows[2 * pr + 1] + rows[2 * pr + 2];
-                    V[pr][2] = rows[2 * pr + 2] - rows[2 * pr + 1];
-                    V[pr][3] = rows[2 * pr + 1] - rows[2 * pr + 3];
-                }
-                int nst = st, ng = g + 1;
-                if (ng == G) { ng = 0; nst = st + 1; }
-                if (nst < 9) {
-                    const int dz = nst / 3, dx = nst - dz * 3;
-                    const int off = (dz * IY * IX + dx) * 4 + ng * 2 * plane;
-#pragma unroll
-                    for (int r = 0; r < 6; ++r) rows[r] = *(const f32x4 *)(lds + a_base + off + r * IX * 4);
-                    const float *wn = wch + (size_t)(nst * G + ng) * (4 * 256);
-#pragma unroll
-                    for (int f = 0; f < 4; ++f) u_nxt[f] = *(const f32x4 *)(wn + f * 256);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int pr = 0; pr < 2; ++pr)
-#pragma unroll
-                        for (int f = 0; f < 4; ++f)
-                            acc[pr][f] = __builtin_amdgcn_mfma_f32_32x32x2f32(u_cur[f][j], V[pr][f][j], acc[pr][f], 0, 0, 0);
-#pragma unroll
-                for (int f = 0; f < 4; ++f) u_cur[f] = u_nxt[f];
-            }
-        }
-        __syncthreads();  // brick is overwritten by the next chunk
-    }
-
-    // output transform A^T m -> the four rows of this wave's z plane, then the shared epilogue (voxel fragment mf = row)
-    f32x16 out[4][1];
-#pragma unroll
-    for (int pr = 0; pr < 2; ++pr)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            out[2 * pr][0][r] = acc[pr][0][r] + acc[pr][1][r] + acc[pr][2][r];
-            out[2 * pr + 1][0][r] = acc[pr][1][r] - acc[pr][2][r] - acc[pr][3][r];
-        }
-    conv_epilogue<4, 1>(out, p, n, oz0, oy0, ox0, (int)blockIdx.y * 32);
-}
-
 // ------------------------------------------------------------------ host side
 // Which stride-1 kernel a launch gets (env MI355_CONV_IMPL: "0" = always the one-tile-per-workgroup kernel,
 // "1" = always the pipelined persistent kernel, default "auto").  Measured on MI355X (bench.py, config 2):
@@ -812,12 +663,12 @@ static int conv_impl() {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Winograd F(2x2, 3x3) over (z, y): the nested form of the kernel above.  A wave owns one 2x2 (z, y) output block of
-// the 4x4x32 tile at 32 x positions; per (dx, channel) it reads the block's 4x4 input rows, transforms them to 16
-// components V = B^T D B (32 packed adds on 2-channel pairs) and issues 16 MFMA K-steps - 4 per output row instead
-// of 9 (direct) or 6 (F(2,3) along y only).  The 16 component accumulators are 256 registers, so the kernel runs ONE
-// wave per SIMD (512-register budget, accumulators in AGPRs), one persistent workgroup per CU, and everything that a
-// second workgroup used to hide is overlapped inside the wave:
+// Winograd F(2x2, 3x3) over (z, y).  The f32 convs are MFMA-bound (exact fp32 multiplies, no TF32), so the lever left
+// is the number of multiplies.  A wave owns one 2x2 (z, y) output block of the 4x4x32 tile at 32 x positions; per
+// (dx, channel) it reads the block's 4x4 input rows, transforms them to 16 components V = B^T D B (32 packed adds on
+// 2-channel pairs) and issues 16 MFMA K-steps - 4 per output row instead of 9 (direct).  The 16 component accumulators
+// are 256 registers, so the kernel runs ONE wave per SIMD (512-register budget, accumulators in AGPRs), one persistent
+// workgroup per CU, and everything that a second workgroup used to hide is overlapped inside the wave:
 //   * a step is (channel quad, dx): one 8-B LDS read per row (lane half h holds channels 2h, 2h+1 of the quad), two
 //     MFMAs per component; rows and weights of step s+1 are fetched while the 32 MFMAs of step s run;
 //   * the 16-channel halo brick is double-buffered (2 x 77 KB of the 160 KB LDS) and filled by LDS-DMA
@@ -832,26 +683,6 @@ struct Wino2Args {
     TileOrder order;  // blocked tile order (common.h)
 };
 
-// Ablation switches of the diagnostic harness (tools/wino2_probe.hip -DMI355_W2_ABL=<bits>; results are then wrong by
-// design): 1 no epilogue, 2 no accumulator reset, 4 no brick DMA, 8 no weight loads, 16 no input transform,
-// 32 no global stores, 64 no store phase (read-back, bias, activation, stores).
-#ifndef MI355_W2_ABL
-#define MI355_W2_ABL 0
-#endif
-#ifdef MI355_W2_STAMPS
-// Diagnostic build only (tools/wino2_probe.hip): per-workgroup cycle sums of the kernel's phases, wave 0, via s_memtime.
-// Slots: 0 = chunk prologue, 1 = step loop, 2 = chunk-end drain + barrier, 3 = output transform, 4 = shared epilogue,
-// 5 = whole kernel, 6 = chunks, 7 = tiles, 8 = barrier after the epilogue, 9 = accumulator reset + tile set-up.  The shipped kernel contains no stamp.
-__device__ unsigned long long w2_stamps[1024 * 16];
-#define W2_T(var) __builtin_amdgcn_sched_barrier(0); const unsigned long long var = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0)
-#define W2_ACC(slot, a, b) do { if (threadIdx.x == 0) w2_stamps[(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (slot)] += (b) - (a); } while (0)
-#define W2_CNT(slot) do { if (threadIdx.x == 0) w2_stamps[(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (slot)] += 1; } while (0)
-#else
-#define W2_T(var)
-#define W2_ACC(slot, a, b)
-#define W2_CNT(slot)
-#endif
-
 constexpr int W2_IX = 34, W2_IY = 6, W2_IZ = 6, W2_BV = W2_IX * W2_IY * W2_IZ;  // 1224 brick voxels
 constexpr int W2_BUF_FLOATS = (4 * W2_BV + 56) * 4;  // 4 quad planes + the overrun of the last DMA range
 constexpr size_t W2_LDS_BYTES = (size_t)(2 * W2_BUF_FLOATS + 4 * 32 * 2) * sizeof(float);
@@ -859,7 +690,7 @@ constexpr size_t W2_LDS_BYTES = (size_t)(2 * W2_BUF_FLOATS + 4 * 32 * 2) * sizeo
 // PLAIN = bias + LeakyReLU + store only (BatchNorm-folded / un-normalised layers): the whole-line epilogue below, and no
 // code for statistics or the fused head in the instantiation - their register demand made the allocator spill loop
 // invariants at kernel entry, and the epilogue's reloads missed every cache level after a chunk of streaming DMA traffic
-// (9-11k cycles per tile, tools/wino2_probe.hip stamps, round 2).
+// (9-11k cycles per tile, profiles/r02_wino2_stamps_round1_kernel.txt).
 // EPI: 0 = plain (above), 1 = fused 1x1x1 segmentation head (the network's last conv: only the logits are written),
 //      2 = the shared epilogue (Instance/GroupNorm statistics).
 template <int EPI>
@@ -922,20 +753,10 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino2_kernel(Wino2Args pa) {
         else { src = p.in1; Csrc = p.C1; coff = cglob - p.C0; }
         // wave-uniform part (SALU); the per-lane part fits 32 bits (host check)
         src += ((((size_t)tc.n * p.Di + (tc.oz0 - 1)) * p.Hi + (tc.oy0 - 1)) * p.Wi + (tc.ox0 - 1)) * (long)Csrc + coff;
-#ifdef MI355_W2_RECOMPUTE_PK
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        int bvv = rng * 64 + ln;
-        const int over = bvv >= BV ? 1 : 0;
-        bvv -= over * BV;
-        const int rrr = bvv / IX, bx = bvv - rrr * IX;
-        const int rz = rrr / IY, ry = rrr - rz * IY;
-#else
         unsigned pk = dma_pk[k];
         asm volatile("" : "+v"(pk));  // unpack HERE, every time: hoisted out of the tile loop the unpacked fields and the 64-bit
                                       // offsets built from them are ~40 registers that get spilled to scratch at kernel entry
         const int rz = pk & 15, ry = (pk >> 4) & 15, bx = (pk >> 8) & 255, over = pk >> 16;
-#endif
         const bool in_vol = ((unsigned)(tc.oz0 - 1 + rz) < (unsigned)p.Di) && ((unsigned)(tc.oy0 - 1 + ry) < (unsigned)p.Hi) &&
                             ((unsigned)(tc.ox0 - 1 + bx) < (unsigned)p.Wi);
         const int voff = ((rz * p.Hi + ry) * p.Wi + bx) * Csrc + over * 4;
@@ -975,14 +796,6 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino2_kernel(Wino2Args pa) {
                  :                                                                                                     \
                  : "memory")
 
-#ifdef MI355_W2_STAGGER
-    {   // experiment: desynchronise the workgroups so that their store bursts do not coincide
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-        const unsigned long long wait = (unsigned long long)(((int)blockIdx.x >> 3) & 7) * (MI355_W2_STAGGER);
-        while (__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(8);
-    }
-#endif
-    W2_T(t_kernel0);
     TileCoord cur = decode(tile);
 #pragma unroll
     for (int k = 0; k < 5; ++k) dma_group(cur, 0, k, lds);
@@ -1019,23 +832,15 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino2_kernel(Wino2Args pa) {
     // tile loop outside, chunk loop inside, accumulators scoped to one tile: a conditional reset inside a single
     // flattened loop makes the register allocator spill the 256 accumulators at every back edge
     for (; tile < hi; tile += nl) {
-        W2_T(t_t0);
         f32x16 acc[16];
 #pragma unroll
         for (int f = 0; f < 16; ++f) {
-            if constexpr ((MI355_W2_ABL & 2) != 0) { asm volatile("" : "=a"(acc[f])); continue; }
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[f][r] = 0.f;
         }
         const int ntile = tile + nl;
         const TileCoord nxt_tile = ntile < hi ? decode(ntile) : cur;
 
-#ifdef MI355_W2_STAMPS
-#pragma unroll
-        for (int f = 0; f < 16; ++f) asm volatile("" : "+a"(acc[f]));
-#endif
-        W2_T(t_t1);
-        W2_ACC(9, t_t0, t_t1);
         for (int ch = 0; ch < p.nchunks; ++ch) {
             const bool last_ch = ch == p.nchunks - 1;
             const bool have_next = !last_ch || ntile < hi;
@@ -1048,7 +853,6 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino2_kernel(Wino2Args pa) {
             const float *wnx = wblk + (size_t)nch_eff * (STEPS * 16 * 128);
 
             // chunk prologue (exposed once per chunk): V of step 0, rows of step 1
-            W2_T(t_c0);
             f32x2 d[16], T[16], V[2][16];
 #pragma unroll
             for (int k = 0; k < 16; ++k) d[k] = row_read(bufc, 0, k);
@@ -1059,8 +863,6 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino2_kernel(Wino2Args pa) {
 #pragma unroll
             for (int k = 0; k < 16; ++k) d[k] = row_read(bufc, 1, k);
             __builtin_amdgcn_sched_barrier(0);
-            W2_T(t_c1);
-            W2_ACC(0, t_c0, t_c1);
 
             // One step = 32 MFMAs (64 cycles each); everything else of the pipeline is dealt out between them, one
             // scheduling fence per MFMA: the transform of step st+1 (its rows were read during step st-1), the weight
@@ -1081,8 +883,7 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino2_kernel(Wino2Args pa) {
                     // the transform of step st+1 in four bunches of eight packed adds: a gap that holds any VALU work costs
                     // the matrix pipe ~5 cycles plus ~4.4 per instruction (tools/coissue_probe.hip), so 32 adds dealt one
                     // per gap cost twice what they cost in four gaps
-                    if constexpr ((MI355_W2_ABL & 16) != 0) {
-                    } else if constexpr (st + 1 < STEPS && (i == 0 || i == 2)) {
+                    if constexpr (st + 1 < STEPS && (i == 0 || i == 2)) {
                         static_for<0, 8>([&](auto u) { t_op(d, T, 4 * i + decltype(u)::value); });
                     } else if constexpr (st + 1 < STEPS && (i == 16 || i == 18)) {
                         static_for<0, 8>([&](auto u) { v_op(T, V[pp ^ 1], 4 * (i - 16) + decltype(u)::value); });
@@ -1092,34 +893,24 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino2_kernel(Wino2Args pa) {
                     if constexpr (i < 16 && (i & 1) == 0) {
                         constexpr int k = i >> 1;
                         auto &un = uq[pp ^ 1]; const unsigned wl = k < 4 ? wl0 : wl1; const float *wb = wn;
-                        if constexpr ((MI355_W2_ABL & 8) == 0)
-                            if (st + 1 < STEPS || !last_ch) W2_ULOAD(un[k], wl, wb, (k & 3) * 1024);
+                        if (st + 1 < STEPS || !last_ch) W2_ULOAD(un[k], wl, wb, (k & 3) * 1024);
                     }
                     if constexpr (st + 2 < STEPS && i >= 8 && i < 16) {  // two rows per group (one ds_read2_b64), right after
                         d[2 * (i - 8)] = row_read(bufc, st + 2, 2 * (i - 8));          // the T ops released d: the data is
                         d[2 * (i - 8) + 1] = row_read(bufc, st + 2, 2 * (i - 8) + 1);  // needed 16 MFMAs later
                     }
-                    if constexpr ((MI355_W2_ABL & 4) == 0 && (st & 1) == 0 && st < 10 && i == 20) dma_group(nxt, nch_eff, st >> 1, bufn);
+                    if constexpr ((st & 1) == 0 && st < 10 && i == 20) dma_group(nxt, nch_eff, st >> 1, bufn);
                     __builtin_amdgcn_sched_barrier(0);
                 });
             });
-            W2_T(t_c2);
-            W2_ACC(1, t_c1, t_c2);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // explicit: a ds_read is ordered behind an LDS-DMA only by the issuer's vmcnt + a barrier
             __syncthreads();  // retires this chunk's DMA (vmcnt(0)) and orders it before the next chunk's ds_reads
             buf ^= 1;
-            W2_T(t_c3);
-            W2_ACC(2, t_c2, t_c3);
-            W2_CNT(6);
         }
-        W2_T(t_e0);
 
         // Y = A^T M A: along y within each z component, then along z; rows ordered mf = 2*zrow + yrow (packed over
         // accumulator register pairs: the epilogue is pure VALU time on a SIMD that has nothing else to run)
-        if constexpr ((MI355_W2_ABL & 1) != 0) {
-#pragma unroll
-            for (int f = 0; f < 16; ++f) asm volatile("" :: "a"(acc[f]));
-        } else if constexpr (EPI == 0 || EPI == 2) {
+        if constexpr (EPI == 0 || EPI == 2) {
             // (EPI == 2, round 3: the Instance/GroupNorm statistics ride on this epilogue - eight registers of running sums
             //  over the values a lane stores - instead of materialising the 64 outputs for the shared conv_epilogue, which
             //  spilled 59 registers and reloaded them from scratch in every tile)
@@ -1162,8 +953,6 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino2_kernel(Wino2Args pa) {
                 // registers first, and that peak is what spills the tile loop's invariants to scratch
                 __builtin_amdgcn_sched_barrier(0);
             }
-            W2_T(t_e1);
-            W2_ACC(3, t_e0, t_e1);
             const int srow = lane_e >> 3, spiece = lane_e & 7;
             const float *rd = stage + srow * EPI_PITCH + spiece * 4;
             const int zb = cur.oz0 + 2 * bz, yb = cur.oy0 + 2 * by;
@@ -1185,7 +974,6 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino2_kernel(Wino2Args pa) {
             float st1[4] = {0.f, 0.f, 0.f, 0.f}, st2[4] = {0.f, 0.f, 0.f, 0.f};  // EPI == 2: sum x, sum x^2 of couts 4 spiece .. + 3
 #pragma unroll
             for (int mf = 0; mf < 4; ++mf) {
-                if constexpr ((MI355_W2_ABL & 64) != 0) continue;
                 f32x4 raw[4];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) raw[t] = *(const f32x4 *)(rd + mf * EPI_STAGE_FLOATS + 8 * t * EPI_PITCH);
@@ -1209,11 +997,10 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino2_kernel(Wino2Args pa) {
                             for (int k = 0; k < 4; ++k) { st1[k] += val[k]; st2[k] = fmaf(val[k], val[k], st2[k]); }
                         }
                     }
-                    if constexpr ((MI355_W2_ABL & 32) != 0) asm volatile("" :: "v"(val));
                     // sc1: the line leaves the XCD's L2 with the store.  Nothing on this XCD reads it again, and kept in L2 the
                     // output (as many bytes as the input at Cin = Cout) evicts brick lines between the two half-line chunks of
                     // a 32-channel voxel: FETCH_SIZE of the 32 -> 32 layer at 128^3 fell by 38 % with this flag alone.
-                    else if (xok[t]) { float *gp = rowp + lane_off + t * t_stride; asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 0" :: "v"(gp), "v"(val) : "memory"); }
+                    if (xok[t]) { float *gp = rowp + lane_off + t * t_stride; asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 0" :: "v"(gp), "v"(val) : "memory"); }
                 }
             }
             if constexpr (EPI == 2) {
@@ -1229,7 +1016,6 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino2_kernel(Wino2Args pa) {
                     }
                 }
             }
-            W2_T(t_e3);
             // the barrier keeps the next chunk's DMAs of a faster wave out of the staging area until every wave has read its
             // image back.  Raw barrier + lgkmcnt only: a __syncthreads() would also drain the stores (vmcnt(0)).
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1244,8 +1030,6 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino2_kernel(Wino2Args pa) {
                     atomicAdd(p.stats + ((size_t)cur.n * p.Cout + co0 + c) * 2 + k, quantise_partial(tot, k, (long)p.Do * p.Ho * p.Wo));  // exact, hence order-independent (common.h)
                 }
             }
-            W2_T(t_e4);
-            W2_ACC(8, t_e3, t_e4);
         } else if constexpr (EPI == 1) {
             // Fused segmentation head: logit[c] = sum_cout w[c][cout] * act(y[cout] + b[cout]) + hb[c].  A lane holds 16 couts of
             // its voxel (the other 16 sit in lane ^ 32), so the head is a dot product over registers plus one cross-half add,
@@ -1329,12 +1113,7 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino2_kernel(Wino2Args pa) {
                 W2_ULOAD(u0[k], wl, wb, (k & 3) * 1024);
             });
         }
-        W2_T(t_e2);
-        W2_ACC(4, t_e0, t_e2);  // transform + stores (slot 3 = the transform part, PLAIN kernel only)
-        W2_CNT(7);
     }
-    W2_T(t_kernel1);
-    W2_ACC(5, t_kernel0, t_kernel1);
 #undef W2_ULOAD
 #undef W2_UWAIT
 }
@@ -1529,39 +1308,11 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_s2dma_kernel(Wino2Args pa) {
     }
 }
 
-// MI355_WINOGRAD: 0 = direct kernels only, 1 = F(2,3) along y, 2 (default) = F(2x2,3x3) over (z, y)
-static int winograd_mode() {
+// MI355_WINOGRAD: 0 = direct kernels only; anything else (default) = F(2x2,3x3) over (z, y)
+static bool winograd_enabled() {
     static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("MI355_WINOGRAD");
-        v = !e ? 2 : (e[0] == '0' ? 0 : (e[0] == '1' ? 1 : 2));
-    }
-    return v;
-}
-
-// Winograd-y pack (floats): [cout block of 32][chunk of 16][step = dz*3+dx][g][f 0..3][lane][j] with
-//   cout = block*32 + (lane&31), cin = chunk*16 + g*8 + (lane>>5)*4 + j and U_f = (G w)_f over the dy taps,
-//   G = [[1,0,0],[1/2,1/2,1/2],[1/2,-1/2,1/2],[0,0,1]], evaluated in fp64 and rounded once.
-static void pack_conv_weights_wino(const float *w, int cin, int cin_pad, int cout, std::vector<float> &out) {
-    const int nchunks = cin_pad / 16, nblk = cout / 32;
-    out.assign((size_t)nblk * nchunks * 9 * 2 * 4 * 256, 0.f);
-    size_t o = 0;
-    for (int b = 0; b < nblk; ++b)
-        for (int ch = 0; ch < nchunks; ++ch)
-            for (int st = 0; st < 9; ++st)
-                for (int g = 0; g < 2; ++g)
-                    for (int f = 0; f < 4; ++f)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int j = 0; j < 4; ++j, ++o) {
-                                const int co = b * 32 + (lane & 31);
-                                const int ci = ch * 16 + g * 8 + (lane >> 5) * 4 + j;
-                                if (ci >= cin) continue;
-                                const int dz = st / 3, dx = st % 3;
-                                const float *wk = &w[((size_t)co * cin + ci) * 27 + dz * 9 + dx];  // dy stride 3
-                                const double w0 = wk[0], w1 = wk[3], w2 = wk[6];
-                                const double u = f == 0 ? w0 : f == 1 ? 0.5 * (w0 + w1 + w2) : f == 2 ? 0.5 * (w0 - w1 + w2) : w2;
-                                out[o] = (float)u;
-                            }
+    if (v < 0) { const char *e = getenv("MI355_WINOGRAD"); v = (e && e[0] == '0') ? 0 : 1; }
+    return v != 0;
 }
 
 // 2-D Winograd pack (floats): [cout block of 32][chunk of 16][step = q*3+dx][f/2][lane][f&1][j 0..1], f = fz*4+fy, with
@@ -1632,13 +1383,11 @@ int conv_weights_upload(const float *w_host, const float *bias_host, int cin, in
             pack_conv_weights_f32(w_host, cin, cin_pad, cout, 16, cw.nf, packed);
             MI355_HIP(hipMalloc(&cw.wp16_dev, packed.size() * sizeof(float)));
             MI355_HIP(hipMemcpy(cw.wp16_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-            if (winograd_mode() != 0) {
-                cw.wino2 = winograd_mode() == 2;
-                if (cw.wino2) pack_conv_weights_wino2(w_host, cin, cin_pad, cout, packed);
-                else pack_conv_weights_wino(w_host, cin, cin_pad, cout, packed);
+            if (winograd_enabled()) {
+                pack_conv_weights_wino2(w_host, cin, cin_pad, cout, packed);
                 MI355_HIP(hipMalloc(&cw.wpw_dev, packed.size() * sizeof(float)));
                 MI355_HIP(hipMemcpy(cw.wpw_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-                if (cw.wino2 && conv3d_wino3_enabled()) {  // F(2x2x2, 3x3x3): the launches that are whole 4 x 8 x 8 tiles (conv3d_wino3.hip)
+                if (conv3d_wino3_enabled()) {  // F(2x2x2, 3x3x3): the launches that are whole 4 x 8 x 8 tiles (conv3d_wino3.hip)
                     pack_conv_weights_wino3(w_host, cin, cin_pad, cout, packed);
                     MI355_HIP(hipMalloc(&cw.wp3_dev, packed.size() * sizeof(float)));
                     MI355_HIP(hipMemcpy(cw.wp3_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -1763,7 +1512,7 @@ int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, cons
     }
     MI355_REQUIRE(!c.in_scale, "conv %d->%d: a pending input normalisation reached a kernel that cannot apply it", w.cin, w.cout);
     if (w.wpw_dev) {
-        // auto mode, large launches: Winograd F(2,3) along y on fixed 4x4x32 tiles, 32 couts per workgroup
+        // auto mode, large launches: Winograd F(2x2,3x3) on fixed 4x4x32 tiles, 32 couts per workgroup
         ConvArgs b = a;
         b.lz = 2; b.ly = 2; b.lx = 5;
         b.tiles_x = ceil_div(b.Wo, 32); b.tiles_y = ceil_div(b.Ho, 4); b.tiles_z = ceil_div(b.Do, 4);
@@ -1774,17 +1523,14 @@ int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, cons
         b.div_IX = make_fastdiv(b.IX);
         b.div_IY = make_fastdiv(b.IY);
         const long tiles = (long)b.tiles_x * b.tiles_y * b.tiles_z * c.N;
-        const size_t brick_bytes = (size_t)34 * 6 * 6 * 16 * sizeof(float);
         // the fixed tile wastes lanes on thin volumes: only when every tile dim is at least half used
         if (tiles * (w.cout / 32) >= 512 && tiles < (1l << 30) && b.Wo >= 16 && b.Ho >= 4 && b.Do >= 4 &&
             (long)c.Di * c.Hi * c.Wi * (c.C0 > c.C1 ? c.C0 : c.C1) < (1l << 31) &&
             (!c.head_out || w.cout == 32)) {
             b.wp = w.wpw_dev;
             b.nchunks = w.cin_pad / 16;
-            dim3 grid((unsigned)tiles, w.cout / 32);
             static bool attr_set = false;
             if (!attr_set) {
-                MI355_HIP(hipFuncSetAttribute((const void *)conv3_f32_wino_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)brick_bytes));
                 MI355_HIP(hipFuncSetAttribute((const void *)conv3_f32_wino2_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W2_LDS_BYTES));
                 MI355_HIP(hipFuncSetAttribute((const void *)conv3_f32_wino2_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W2_LDS_BYTES));
                 MI355_HIP(hipFuncSetAttribute((const void *)conv3_f32_wino2_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W2_LDS_BYTES));
@@ -1794,22 +1540,18 @@ int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, cons
             MI355_TRY(device_scratch(SCR_ZEROS, s, 256, (void **)&zeros, true));
             const int epi = c.head_out ? 1 : (c.stats ? 2 : 0);
             static const char *const w2_names[3] = {"conv3_f32_wino2_kernel<0>", "conv3_f32_wino2_kernel<1>", "conv3_f32_wino2_kernel<2>"};
-            *kernel_name = w.wino2 ? w2_names[epi] : "conv3_f32_wino_kernel";
-            if (w.wino2) {
-                Wino2Args wa;
-                wa.c = b; wa.total_tiles = (int)tiles; wa.zeros = zeros;
-                wa.order = make_tile_order(b.tiles_x, b.tiles_y, b.tiles_z);
-                const int gy = w.cout / 32;
-                int gx = 256 / gy;                      // one persistent workgroup per CU
-                gx = gx < 8 ? 8 : (gx / 8) * 8;         // multiple of 8: blockIdx.x & 7 labels the XCD group
-                const int need = (int)((tiles + 7) / 8) * 8;
-                if (gx > need) gx = need;
-                if (epi == 0) hipLaunchKernelGGL(conv3_f32_wino2_kernel<0>, dim3(gx, gy), dim3(256), W2_LDS_BYTES, s, wa);
-                else if (epi == 1) hipLaunchKernelGGL(conv3_f32_wino2_kernel<1>, dim3(gx, gy), dim3(256), W2_LDS_BYTES, s, wa);
-                else hipLaunchKernelGGL(conv3_f32_wino2_kernel<2>, dim3(gx, gy), dim3(256), W2_LDS_BYTES, s, wa);
-            } else {
-                hipLaunchKernelGGL(conv3_f32_wino_kernel, grid, dim3(256), brick_bytes, s, b);
-            }
+            *kernel_name = w2_names[epi];
+            Wino2Args wa;
+            wa.c = b; wa.total_tiles = (int)tiles; wa.zeros = zeros;
+            wa.order = make_tile_order(b.tiles_x, b.tiles_y, b.tiles_z);
+            const int gy = w.cout / 32;
+            int gx = 256 / gy;                      // one persistent workgroup per CU
+            gx = gx < 8 ? 8 : (gx / 8) * 8;         // multiple of 8: blockIdx.x & 7 labels the XCD group
+            const int need = (int)((tiles + 7) / 8) * 8;
+            if (gx > need) gx = need;
+            if (epi == 0) hipLaunchKernelGGL(conv3_f32_wino2_kernel<0>, dim3(gx, gy), dim3(256), W2_LDS_BYTES, s, wa);
+            else if (epi == 1) hipLaunchKernelGGL(conv3_f32_wino2_kernel<1>, dim3(gx, gy), dim3(256), W2_LDS_BYTES, s, wa);
+            else hipLaunchKernelGGL(conv3_f32_wino2_kernel<2>, dim3(gx, gy), dim3(256), W2_LDS_BYTES, s, wa);
             MI355_HIP(hipGetLastError());
             return MI355_OK;
         }

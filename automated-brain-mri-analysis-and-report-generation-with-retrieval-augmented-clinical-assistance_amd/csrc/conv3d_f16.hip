@@ -694,16 +694,6 @@ __global__ __launch_bounds__(256, 2) void conv3_f16_mfma_pipe_kernel(ConvArgsH p
 //   The loads issued after W(t) are those of taps t-8 .. t-1: 16 + the DMAs among them (DmaGeomH::pending); after the last
 //   DMA of a chunk come the weight loads of the remaining taps, and that many may be outstanding at the barrier that
 //   publishes the brick.
-#ifdef MI355_H16_STAMPS
-// tools/h16_probe.hip: cycle sums of wave 0 per workgroup. 0 taps 0-8, 1 taps 9-17, 2 taps 18-26, 3 drain + barrier, 4 epilogue,
-// 5 whole kernel, 6 chunks, 7 tiles, 8 accumulator init + set-up
-__device__ unsigned long long h16_stamps[1024 * 16];
-#define H16_T(v) unsigned long long v = 0; if (stamp_on) v = __builtin_readcyclecounter()
-#define H16_ACC(k, a, b) if (stamp_on) h16_acc[k] += (b) - (a)
-#else
-#define H16_T(v)
-#define H16_ACC(k, a, b)
-#endif
 template <int EVERY_, int NF_ = 2, int D_ = 9>
 struct DmaGeomH {
     static constexpr int IX = 10, IY = 10, IZ = 10, BV = IX * IY * IZ;
@@ -777,7 +767,7 @@ __device__ __forceinline__ void conv3_f16_dma_body(const ConvArgsH &p) {
     int tile = lo + li;
     if (tile >= hi) return;
     // (Measured in round 5 and removed: starting the second half of the Cout = 32 grid - the CUs' second workgroups - half a chunk late,
-    //  MI355X_MICROARCH.md "Two waves per SIMD" item 9: s_sleep 40 / 80 / 127 against none, tools/h16_probe c: no difference beyond
+    //  MI355X_MICROARCH.md "Two waves per SIMD" item 9: s_sleep 40 / 80 / 127 against none: no difference beyond
     //  the +-4 % between repeats, profiles/r05_c32_stagger.txt.  The two workgroups of a CU drift apart by themselves.)
 
     struct TileCoord { int n, oz0, oy0, ox0; };
@@ -819,16 +809,9 @@ __device__ __forceinline__ void conv3_f16_dma_body(const ConvArgsH &p) {
         src += (((long)tc.n * (Csrc >> 3) + (coff >> 3) + (k >> 2)) * Vi + ((long)(tc.oz0 - 1) * p.Hi + (tc.oy0 - 1)) * p.Wi + (tc.ox0 - 1)) * 8;
         unsigned pk = dma_pk[k & 3];
         asm volatile("" : "+v"(pk));
-        bool inside = (pk & ((unsigned)(faces | 64) << 24)) == 0;
-#if defined(MI355_H16_ABL_DMA) && MI355_H16_ABL_DMA == 1   // (probe only: every piece reads the 16-B zero page - the same instructions, nothing fetched from beyond the L1; results wrong)
-        inside = false;
-#endif
+        const bool inside = (pk & ((unsigned)(faces | 64) << 24)) == 0;
         unsigned off = (pk & 0xffffffu) << 4;  // bytes: 16 per voxel of a block (< 2^32: host check)
-#if defined(MI355_H16_ABL_DMA) && MI355_H16_ABL_DMA == 2   // (probe only: real data, but every piece comes from the first 256 KiB of the tensor - L2-resident; results wrong.
-        const char *gin = (const char *)p.in0 + (off & 0x3fff0u);   //  Based at the TENSOR, not at the brick origin, which may lie in front of it)
-#else
         const char *gin = (const char *)src + off;
-#endif
         asm volatile("" : "+v"(gin));  // (computed for every lane: left to itself the compiler branches around it, and a basic-block
                                        //  boundary between the MFMAs of a tap makes it wait for every outstanding LDS read there)
         const char *g = inside ? gin : (const char *)p.zeros;  // the zero page holds both planes' pieces
@@ -935,11 +918,6 @@ __device__ __forceinline__ void conv3_f16_dma_body(const ConvArgsH &p) {
             }
     }
 
-#ifdef MI355_H16_STAMPS
-    const bool stamp_on = tid == 0 && blockIdx.y == 0;
-    unsigned long long h16_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    H16_T(t_k0);
     TileCoord cur = decode(tile);
     f16x8 wq[G::D][NF];
     {
@@ -965,7 +943,6 @@ __device__ __forceinline__ void conv3_f16_dma_body(const ConvArgsH &p) {
 
     int buf = 0;
     for (; tile < hi; tile += nl) {
-        H16_T(t_t0);
         f32x16 acc[MF][NF];
         {   // bias from LDS (a global load here is an L2 round trip per tile with nothing to hide it behind)
             typedef const __attribute__((address_space(3))) f32x4 lds_cf32x4;
@@ -984,16 +961,7 @@ __device__ __forceinline__ void conv3_f16_dma_body(const ConvArgsH &p) {
         }
         const int ntile = tile + nl;
         const TileCoord nxt_tile = ntile < hi ? decode(ntile) : cur;
-#ifdef MI355_H16_STAMPS
-#pragma unroll
-        for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-            for (int nf = 0; nf < NF; ++nf) asm volatile("" : "+a"(acc[mf][nf]));
-#endif
-        H16_T(t_t1);
-        H16_ACC(8, t_t0, t_t1);
         for (int ch = 0; ch < p.nchunks; ++ch) {
-            H16_T(t_c0);
             const bool last_ch = ch == p.nchunks - 1;
             const bool have_next = !last_ch || ntile < hi;
             const TileCoord nxt = last_ch ? nxt_tile : cur;
@@ -1017,9 +985,6 @@ __device__ __forceinline__ void conv3_f16_dma_body(const ConvArgsH &p) {
 #pragma unroll
             for (int mf = 0; mf < MF; ++mf) a[0][mf] = *(lds_cf16x8 *)(ab[mf]);
 
-#ifdef MI355_H16_STAMPS
-            unsigned long long t_seg = t_c0;
-#endif
             AffStage aff_st;
             unsigned aff_pb = 0, aff_ta = 0, aff_tb = 0;
             if constexpr (INAFF) aff_bases(bufn, nxt, nch_eff, aff_pb, aff_ta, aff_tb);
@@ -1031,10 +996,7 @@ __device__ __forceinline__ void conv3_f16_dma_body(const ConvArgsH &p) {
                 // the first MFMAs go out before the tap's memory instructions: the compiler waits for ALL outstanding LDS
                 // reads before the first MFMA of a tap (lgkmcnt(0): it will not count past an LDS-DMA), so the reads of tap
                 // t+1 are issued behind two MFMAs of tap t (NF = 2: six more to land behind) or behind one (NF = 1: three more)
-#ifndef MI355_C32_MEM_AT
-#define MI355_C32_MEM_AT 0
-#endif
-                constexpr int MEM_AT = NF == 2 ? 1 : MI355_C32_MEM_AT;
+                constexpr int MEM_AT = NF == 2 ? 1 : 0;
                 static_for<0, MF * NF>([&](auto i_c) {
                     constexpr int i = decltype(i_c)::value;
                     constexpr int mf = i / NF, nf = i % NF;
@@ -1084,36 +1046,20 @@ __device__ __forceinline__ void conv3_f16_dma_body(const ConvArgsH &p) {
                 __builtin_amdgcn_sched_barrier(0);
                 {
                     constexpr int k = tap + G::D;
-#ifdef MI355_H16_ABL_W   // (probe only: every tap reads the same 2 KB of weights - L1-resident, no L2 traffic; results wrong)
-                    const char *wb = wblk;
-#else
                     const char *wb = (k < 27) ? wch + k * (NF * 1024) : wnx + (k - 27) * (NF * 1024);
-#endif
                     const unsigned wl = wlane;
                     H16_WLOAD(wc[0], wb, 0);
                     if constexpr (NF == 2) H16_WLOAD(wc[1], wb, 1024);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-#ifdef MI355_H16_STAMPS
-                if constexpr (tap == 8 || tap == 17 || tap == 26) {
-                    if (stamp_on) { const unsigned long long t = __builtin_readcyclecounter(); h16_acc[tap / 9] += t - t_seg; t_seg = t; }
-                }
-#endif
             });
             // this wave's DMAs have landed once at most the weight loads issued after DMA 7 are outstanding; the barrier
             // publishes the brick (a ds_read is ordered behind an LDS-DMA only by the issuer's vmcnt + a barrier)
-            H16_T(t_c2);
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::after_last_dma) : "memory");
             if constexpr (INAFF) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the in-place writes of the normalised pieces
             __builtin_amdgcn_s_barrier();
             buf ^= 1;
-            H16_T(t_c3);
-            H16_ACC(3, t_c2, t_c3);
-#ifdef MI355_H16_STAMPS
-            if (stamp_on) h16_acc[6] += 1;
-#endif
         }
-        H16_T(t_e0);
         // The ring already holds the next tile's first nine taps, still in flight.  The compiler knows nothing of that: if it
         // moved one of those registers during the epilogue (a spill copy to an AGPR) it would copy what was there BEFORE the
         // load landed.  So the loads are retired here, with the ring as operands of the wait.
@@ -1158,9 +1104,6 @@ __device__ __forceinline__ void conv3_f16_dma_body(const ConvArgsH &p) {
         } else {
             // ---- epilogue: LeakyReLU + fp16 in registers, whole-line stores straight from registers (v_permlane32_swap, round 3)
             const float slope = p.act == ACT_LRELU ? p.slope : 1.0f;  // max(x, 1*x) = x
-#ifndef MI355_H16_SC1
-#define MI355_H16_SC1 1
-#endif
             // voxel l31 of fragment mf = (z = 2 wave + (mf >> 1), y = 4 (mf & 1) + (l31 >> 3), x = l31 & 7); lanes 32-63 store the
             // next cout block (one block plane = Vo voxels x 16 B further)
             const size_t Vo_sw = (size_t)p.Do * p.Ho * p.Wo;
@@ -1231,8 +1174,7 @@ __device__ __forceinline__ void conv3_f16_dma_body(const ConvArgsH &p) {
                             //  the store: a VALU write of the data registers of a 16-byte store needs a wait state after its issue - hipcc
                             //  pads its own stores, it does not look into inline asm, and the next pair's v_cvt_pk reuses these four
                             //  registers at once: without the pad the statistics instantiations stored garbage)
-                            if constexpr (MI355_H16_SC1 != 0) asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(lo), "v"(v), "s"(row) : "memory");
-                            else asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(lo), "v"(v), "s"(row) : "memory");
+                            asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(lo), "v"(v), "s"(row) : "memory");
                         }
                     if constexpr (STATS) {
                         // (round 3) transposing reduction, common.h: every lane ends with ONE total over the 32 voxel lanes of its
@@ -1255,19 +1197,7 @@ __device__ __forceinline__ void conv3_f16_dma_body(const ConvArgsH &p) {
             }
         }
         cur = nxt_tile;
-        H16_T(t_e1);
-        H16_ACC(4, t_e0, t_e1);
-#ifdef MI355_H16_STAMPS
-        if (stamp_on) h16_acc[7] += 1;
-#endif
     }
-#ifdef MI355_H16_STAMPS
-    if (stamp_on) {
-        const unsigned long long t_k1 = __builtin_readcyclecounter();
-        h16_acc[5] = t_k1 - t_k0;
-        for (int k = 0; k < 10; ++k) h16_stamps[(blockIdx.x & 1023) * 16 + k] += h16_acc[k];
-    }
-#endif
 #undef H16_WLOAD
 }
 

@@ -56,35 +56,6 @@ struct Wino3Args {
     float in_slope;  // LeakyReLU slope of that activation, 1 = none
 };
 
-#ifdef MI355_W3_STAMPS
-// Diagnostic build only (tools/wino3_probe.hip): cycle sums per phase, wave 0 of every workgroup.
-// Slots: 0 chunk prologue, 1 step loop, 2 chunk drain + barrier, 3 epilogue phase 1 (in-wave output transform), 4 whole epilogue,
-// 5 kernel, 6 chunks, 7 tiles, 9 accumulator reset, 10 whole chunk body (steps 0-3 + barrier), 11-14 steps 0-3 (MFMA loop only).
-__device__ unsigned long long w3_stamps[1024 * 16];
-#define W3_T(var) __builtin_amdgcn_sched_barrier(0); const unsigned long long var = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0)
-// (sums live in scalar registers and are written once at the end: a read-modify-write in global memory per stamp put its own
-// vmcnt waits into the phase that followed it)
-#define W3_DECL unsigned long long w3_loc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define W3_ACC(slot, a, b) w3_loc[slot] += (b) - (a)
-#define W3_CNT(slot) w3_loc[slot] += 1
-#define W3_FLUSH do { if (threadIdx.x == 0) for (int s_ = 0; s_ < 16; ++s_) w3_stamps[(blockIdx.y * gridDim.x + blockIdx.x) * 16 + s_] += w3_loc[s_]; } while (0)
-#else
-#define W3_T(var)
-#define W3_DECL
-#define W3_ACC(slot, a, b)
-#define W3_CNT(slot)
-#define W3_FLUSH
-#endif
-#ifndef MI355_W3_PIN
-#define MI355_W3_PIN 1   // epilogue phase 1: the accumulator reads are pinned every MI355_W3_PIN register pairs (see there)
-#endif
-#ifndef MI355_W3_TWOBODY
-#define MI355_W3_TWOBODY 1  // a second copy of the chunk body for a tile's chunk 0 whose first MFMAs take C = 0 (see the tile loop); 0: one body
-#endif
-#ifndef MI355_W3_ABL
-#define MI355_W3_ABL 0  // ablation bits (probe only, results wrong): 1 no epilogue, 4 no brick DMA, 8 no weight loads, 16 no input transform, 32 no stores
-#endif
-
 constexpr int W3_IZ = 6, W3_IY = 10, W3_IX = 10, W3_BV = W3_IZ * W3_IY * W3_IX;  // 600 brick voxels
 constexpr int W3_PS = 640;                      // slots per quad plane: 10 DMA ranges of 64
 constexpr int W3_BUF = 4 * W3_PS * 4;           // floats per brick buffer (4 quad planes)
@@ -357,8 +328,6 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino3_kernel(Wino3Args p) {
     //                         the weights of that step, and DMA group 0 of chunk c + 2 into buffer c.
     // The brick DMA therefore runs as its own stream of (tile, chunk) positions, one chunk ahead of the MFMAs and across tile
     // boundaries; past the last chunk it re-stages the last one (nobody reads it), so the wait counts stay fixed.
-    W3_DECL;
-    W3_T(t_kernel0);
     TileCoord cur = decode(tile);
     // The stream's next position, in eight scalar pieces (adv0 .. adv5) that the chunk loop deals over eight MFMA gaps of step 1,
     // behind the issue of group 2: branch-free (a branch would cut the MFMA stream into basic blocks), ~10-15 scalar
@@ -463,32 +432,22 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino3_kernel(Wino3Args p) {
     int stat_n = -1;
     int buf = 0;
     for (; tile < hi; tile += nl) {
-        W3_T(t_t0);
         f32x16 acc[16];
-#if !MI355_W3_TWOBODY
-#pragma unroll
-        for (int f = 0; f < 16; ++f)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[f][r] = 0.f;
-#endif
         const int ntile = tile + nl;
         const TileCoord nxt_tile = ntile < hi ? decode(ntile) : cur;
-        W3_T(t_t1);
-        W3_ACC(9, t_t0, t_t1);
-        // Two bodies (MI355_W3_TWOBODY, round 5): a second copy of the chunk body for a tile's chunk 0 whose first MFMAs take the
-        // constant 0 as C saves the 256 v_accvgpr_write of the accumulator clear (1 - 3 % per launch, tools/wino3_probe).  Round 4
+        // Two bodies (round 5): a second copy of the chunk body for a tile's chunk 0 whose first MFMAs take the constant 0 as C
+        // saves the 256 v_accvgpr_write of the accumulator clear (1 - 3 % per launch, profiles/r05_wino3_two_body.txt).  Round 4
         // abandoned it after "a memory access fault on every shape".  The cause, from that build's listing: with the second body
         // the allocator spilled the weight base of a step to a VGPR lane and reloaded it (v_readlane_b32) one instruction in
         // front of the inline-asm load that uses it as scalar base - five wait states short (W3_ULOAD0 above).  The build gate
         // (_isa_gate.py) checks every listing for that sequence; positive and negative control in profiles/r05_wino3_two_body.txt.
         auto chunk_body = [&](auto first_c, const int ch) {
-            constexpr bool FIRST = decltype(first_c)::value;  // two-body build: a tile's chunk 0, whose first MFMAs take C = 0
+            constexpr bool FIRST = decltype(first_c)::value;  // a tile's chunk 0, whose first MFMAs take C = 0
             const bool last_ch = ch == p.nchunks - 1;
             const float *bufc = lds + buf * W3_BUF;
             float *bufn = lds + (buf ^ 1) * W3_BUF;
             const float *wch = wblk + (size_t)ch * (STEPS * 4 * 2048);
             const float *wnx = wblk + (size_t)(last_ch ? 0 : ch + 1) * (STEPS * 4 * 2048);
-            W3_T(t_c1);
             AffPair aff, aff2;
             static_for<0, STEPS>([&](auto st_c) {
                 constexpr int st = decltype(st_c)::value;
@@ -497,14 +456,13 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino3_kernel(Wino3Args p) {
                 // this step's weights: everything older than the 4 brick DMAs the previous step issued behind them.  A tile's first
                 // step finds its weights retired already (the epilogue waits for them before its stores); step 3 follows the
                 // chunk barrier's vmcnt(0)
-                if constexpr (st == 0) { if constexpr (!FIRST) { if (MI355_W3_TWOBODY || ch != 0) W3_UWAIT(uc, 4); } }
+                if constexpr (st == 0) { if constexpr (!FIRST) W3_UWAIT(uc, 4); }
                 else if constexpr (st == 1) { W3_UWAIT(uc, 4); if constexpr (INAFF) aff_table_landed(); }
                 else if constexpr (st == 2) W3_UWAIT(uc, 2);  // (group 2 is two DMAs)
                 else W3_UWAIT(uc, 0);
                 const float *wn = (st + 1 < STEPS) ? wch + (size_t)(st + 1) * (4 * 2048) : wnx;
                 const float *rb = (st + 1 < STEPS) ? bufc : bufn;   // brick the next quad is read from
                 constexpr int rq = (st + 1) & 3;
-                W3_T(t_s0);
                 static_for<0, 32>([&](auto i_c) {
                     constexpr int i = decltype(i_c)::value;
                     constexpr int f = i & 15, j = i >> 4;
@@ -513,24 +471,20 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino3_kernel(Wino3Args p) {
                         acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(uq[pp][f >> 1][(f & 1) * 2 + j], V[pp][f][j], zero16, 0, 0, 0);
                     } else
                     acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(uq[pp][f >> 1][(f & 1) * 2 + j], V[pp][f][j], acc[f], 0, 0, 0);
-                    if constexpr ((MI355_W3_ABL & 16) == 0) {
-                        // V of the next quad, dealt over the MFMA gaps in bunches (a gap that holds VALU work costs the matrix
-                        // pipe ~5 cycles + ~4.4 per instruction, tools/coissue_probe.hip)
-                        if constexpr (i == 0) read8(rb, rq, 0, dA, dB);
-                        if constexpr (i == 6) z_op(dA, dB, T, 0);
-                        if constexpr (i == 7) read8(rb, rq, 1, dA, dB);
-                        if constexpr (i == 13) z_op(dA, dB, T, 1);
-                        if constexpr (i == 14) { y_op(T, Y, 0); y_op(T, Y, 1); }
-                        if constexpr (i == 15) { y_op(T, Y, 2); y_op(T, Y, 3); }
-                        if constexpr (i == 17) { x_op(Y, V[pp ^ 1], 0); x_op(Y, V[pp ^ 1], 1); }
-                        if constexpr (i == 18) { x_op(Y, V[pp ^ 1], 2); x_op(Y, V[pp ^ 1], 3); }
-                    }
+                    // V of the next quad, dealt over the MFMA gaps in bunches (a gap that holds VALU work costs the matrix
+                    // pipe ~5 cycles + ~4.4 per instruction, tools/coissue_probe.hip)
+                    if constexpr (i == 0) read8(rb, rq, 0, dA, dB);
+                    if constexpr (i == 6) z_op(dA, dB, T, 0);
+                    if constexpr (i == 7) read8(rb, rq, 1, dA, dB);
+                    if constexpr (i == 13) z_op(dA, dB, T, 1);
+                    if constexpr (i == 14) { y_op(T, Y, 0); y_op(T, Y, 1); }
+                    if constexpr (i == 15) { y_op(T, Y, 2); y_op(T, Y, 3); }
+                    if constexpr (i == 17) { x_op(Y, V[pp ^ 1], 0); x_op(Y, V[pp ^ 1], 1); }
+                    if constexpr (i == 18) { x_op(Y, V[pp ^ 1], 2); x_op(Y, V[pp ^ 1], 3); }
                     if constexpr (i < 16 && (i & 1) == 0) {  // the next step's weights - unconditionally: a branch per load would cut
                         constexpr int k = i >> 1;            // the MFMA stream into basic blocks.  A tile's last step fetches the next
                         auto &un = uq[pp ^ 1]; const unsigned wl = k < 4 ? wl0 : wl1; const float *wb = wn;  // tile's first fragments
-                        if constexpr ((MI355_W3_ABL & 8) == 0) {                                               // (same cout block, chunk 0)
-                            if constexpr (k == 0) W3_ULOAD0(un[k], wl, wb, (k & 3) * 1024); else W3_ULOAD(un[k], wl, wb, (k & 3) * 1024);
-                        }
+                        if constexpr (k == 0) W3_ULOAD0(un[k], wl, wb, (k & 3) * 1024); else W3_ULOAD(un[k], wl, wb, (k & 3) * 1024);  // (same cout block, chunk 0)
                     }
                     if constexpr (INAFF && st == 2) {
                         // the brick of chunk c + 1 (in the other buffer) is normalised here, in front of the barrier that publishes it.
@@ -559,13 +513,13 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino3_kernel(Wino3Args p) {
                         if constexpr (i == 27) aff_apply(I2{}, I0{}, I1{}, aff);
                         if constexpr (i == 28) aff_write(bufn, I2{}, I0{}, aff);
                     }
-                    if constexpr ((MI355_W3_ABL & 4) == 0 && (i == 20 || i == 21)) {
+                    if constexpr (i == 20 || i == 21) {
                         typedef std::integral_constant<int, i - 20> Part;
                         if constexpr (st == 0) dma_group(I1{}, Part{}, bufn);
                         if constexpr (st == 1 && i == 20) { dma_group(I2{}, I0{}, bufn); t_n = d_tc.n; t_ch = d_ch; }
                         if constexpr (st == 3) dma_group(I0{}, Part{}, const_cast<float *>(bufc));
                     }
-                    if constexpr ((MI355_W3_ABL & 4) == 0 && st == 1) {  // the stream moves on: one scalar piece per gap
+                    if constexpr (st == 1) {  // the stream moves on: one scalar piece per gap
                         if constexpr (i == 21) adv0();
                         if constexpr (i == 22) adv1();
                         if constexpr (i == 23) adv2a();
@@ -578,230 +532,200 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino3_kernel(Wino3Args p) {
                     if constexpr (INAFF && st == 0 && i == 17) aff_table_load(d_tc.n, d_ch);  // (the chunk whose DMA groups 1, 2 follow)
                     __builtin_amdgcn_sched_barrier(0);
                 });
-                W3_T(t_s1);
-                W3_ACC(11 + st, t_s0, t_s1);
                 if constexpr (st == 2) {
-                    W3_T(t_c2);
-                    W3_ACC(1, t_c1, t_c2);
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // a ds_read is ordered behind an LDS-DMA only by the issuer's vmcnt + a barrier
                     __syncthreads();
-                    W3_T(t_c3);
-                    W3_ACC(2, t_c2, t_c3);
                 }
             });
-            W3_T(t_c4);
-            W3_ACC(10, t_c1, t_c4);
             buf ^= 1;
-            W3_CNT(6);
         };
-#if MI355_W3_TWOBODY
         chunk_body(std::true_type{}, 0);
         for (int ch = 1; ch < p.nchunks; ++ch) chunk_body(std::false_type{}, ch);
-#else
-        for (int ch = 0; ch < p.nchunks; ++ch) chunk_body(std::false_type{}, ch);
-#endif
-        W3_T(t_e0);
-        if constexpr ((MI355_W3_ABL & 1) != 0) {
+        // ---- phase 1: A^T along y and x inside the wave (16 components -> 4 partial outputs per cout), one accumulator
+        // register pair at a time; the partials go to this wave's four staged images [oy * 2 + ox][block][cout]
+        int lane_e;  // rebuilt from the hardware lane id: a tile-loop invariant would be hoisted to the kernel entry and spilled
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+        float *wr = stage + wave * (4 * W3_IMG) + (lane_e & 31) * W3_PITCH + 4 * (lane_e >> 5);
 #pragma unroll
-            for (int f = 0; f < 16; ++f) asm volatile("" :: "a"(acc[f]));
-        } else {
-            // ---- phase 1: A^T along y and x inside the wave (16 components -> 4 partial outputs per cout), one accumulator
-            // register pair at a time; the partials go to this wave's four staged images [oy * 2 + ox][block][cout]
-            int lane_e;  // rebuilt from the hardware lane id: a tile-loop invariant would be hoisted to the kernel entry and spilled
-            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
-            float *wr = stage + wave * (4 * W3_IMG) + (lane_e & 31) * W3_PITCH + 4 * (lane_e >> 5);
+        for (int r = 0; r < 16; r += 2) {
+            // The accumulators are "redefined" by an empty asm at the top of every register pair: the 32 v_accvgpr_read of pair r
+            // cannot be hoisted above it.  A scheduling barrier alone did not hold them: hipcc read ~170 accumulator registers
+            // into VGPRs before the first staged write, which is what put every instantiation at the 256-VGPR limit with 7-10
+            // spilled loop invariants (without the epilogue the kernel needs 152 registers).
 #pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                // The accumulators are "redefined" by an empty asm at the top of every register pair: the 32 v_accvgpr_read of pair r
-                // cannot be hoisted above it.  A scheduling barrier alone did not hold them: hipcc read ~170 accumulator registers
-                // into VGPRs before the first staged write, which is what put every instantiation at the 256-VGPR limit with 7-10
-                // spilled loop invariants (without the epilogue the kernel needs 152 registers).
-                if ((r / 2) % MI355_W3_PIN == 0) {
+            for (int f = 0; f < 16; ++f) asm volatile("" : "+a"(acc[f]));
+            f32x2 P[2][4];  // [oy][xi_x]
 #pragma unroll
-                    for (int f = 0; f < 16; ++f) asm volatile("" : "+a"(acc[f]));
-                }
-                f32x2 P[2][4];  // [oy][xi_x]
-#pragma unroll
-                for (int fx = 0; fx < 4; ++fx) {
-                    const f32x2 a0 = {acc[0 * 4 + fx][r], acc[0 * 4 + fx][r + 1]}, a1 = {acc[1 * 4 + fx][r], acc[1 * 4 + fx][r + 1]};
-                    const f32x2 a2 = {acc[2 * 4 + fx][r], acc[2 * 4 + fx][r + 1]}, a3 = {acc[3 * 4 + fx][r], acc[3 * 4 + fx][r + 1]};
-                    P[0][fx] = pk_add(pk_add(a0, a1), a2);
-                    P[1][fx] = pk_sub(pk_sub(a1, a2), a3);
-                }
-                const int co = (r & 3) + 8 * (r >> 2);  // + 4 * half: in wr
-#pragma unroll
-                for (int oy = 0; oy < 2; ++oy) {
-                    *(f32x2 *)(wr + (oy * 2 + 0) * W3_IMG + co) = pk_add(pk_add(P[oy][0], P[oy][1]), P[oy][2]);
-                    *(f32x2 *)(wr + (oy * 2 + 1) * W3_IMG + co) = pk_sub(pk_sub(P[oy][1], P[oy][2]), P[oy][3]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
+            for (int fx = 0; fx < 4; ++fx) {
+                const f32x2 a0 = {acc[0 * 4 + fx][r], acc[0 * 4 + fx][r + 1]}, a1 = {acc[1 * 4 + fx][r], acc[1 * 4 + fx][r + 1]};
+                const f32x2 a2 = {acc[2 * 4 + fx][r], acc[2 * 4 + fx][r + 1]}, a3 = {acc[3 * 4 + fx][r], acc[3 * 4 + fx][r + 1]};
+                P[0][fx] = pk_add(pk_add(a0, a1), a2);
+                P[1][fx] = pk_sub(pk_sub(a1, a2), a3);
             }
-            W3_T(t_e1);
-            W3_ACC(3, t_e0, t_e1);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();  // (raw: a __syncthreads() would also drain the brick DMAs of the next tile)
-            asm volatile("" ::: "memory");  // the intrinsic is IntrNoMem: without this hipcc may issue the read-back ABOVE the barrier
-            // the next tile's first weight fragments (fetched during step 3) are retired BEFORE this tile's stores are issued: loads
-            // and stores of a wave may complete out of order with each other, a count-based wait taken behind the stores could not
-            // tell them apart.  The next tile's first step then starts without any wait.
-            { auto &u0 = uq[0]; W3_UWAIT(u0, 0); }
+            const int co = (r & 3) + 8 * (r >> 2);  // + 4 * half: in wr
+#pragma unroll
+            for (int oy = 0; oy < 2; ++oy) {
+                *(f32x2 *)(wr + (oy * 2 + 0) * W3_IMG + co) = pk_add(pk_add(P[oy][0], P[oy][1]), P[oy][2]);
+                *(f32x2 *)(wr + (oy * 2 + 1) * W3_IMG + co) = pk_sub(pk_sub(P[oy][1], P[oy][2]), P[oy][3]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();  // (raw: a __syncthreads() would also drain the brick DMAs of the next tile)
+        asm volatile("" ::: "memory");  // the intrinsic is IntrNoMem: without this hipcc may issue the read-back ABOVE the barrier
+        // the next tile's first weight fragments (fetched during step 3) are retired BEFORE this tile's stores are issued: loads
+        // and stores of a wave may complete out of order with each other, a count-based wait taken behind the stores could not
+        // tell them apart.  The next tile's first step then starts without any wait.
+        { auto &u0 = uq[0]; W3_UWAIT(u0, 0); }
 
-            // ---- phase 2: wave (oy, ox) adds the four xi_z partials (A^T along z), bias, LeakyReLU, whole-line stores.
-            // Lane = (block row srow + 8 t, 4 couts `piece`): 8 lanes hold the 32 couts = the 128-B line of one voxel.
-            const int oy = wave >> 1, ox = wave & 1;
-            const int srow = lane_e >> 3, piece = lane_e & 7;
-            const float *rd = stage + wave * W3_IMG + srow * W3_PITCH + piece * 4;
-            const int co0 = (int)blockIdx.y * 32;
-            f32x4 bias = bias_k;
-            asm volatile("" : "+v"(bias));  // (a copy per tile: the register pairs below are formed from it)
-            const f32x2 b01 = {bias[0], bias[1]}, b23 = {bias[2], bias[3]};
-            float slope = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.act == ACT_LRELU ? p.slope : 1.0f)));
-            asm volatile("" : "+s"(slope));
-            const f32x2 slope2 = {slope, slope};
-            // voxel of block b = 8 t + srow: bx = b & 3, by = (b >> 2) & 3 = 2 (t & 1) + (srow >> 2), bz = b >> 4 = t >> 1
-            const int vx = cur.ox0 + 2 * (srow & 3) + ox;
-            const size_t row_elems = (size_t)p.W * p.Cout;
-            float *obase = p.out + (((size_t)cur.n * p.D + cur.oz0) * p.H + cur.oy0 + oy) * row_elems + co0;  // wave-uniform
-            const unsigned lane_off = (unsigned)(((2 * (srow >> 2)) * p.W + vx) * p.Cout + piece * 4);
-            float st1[4] = {0.f, 0.f, 0.f, 0.f}, st2[4] = {0.f, 0.f, 0.f, 0.f};
-            // EPI == 1: logit[c] = sum_cout w[c][cout] * act(y[cout] + b[cout]) + hb[c] (generic_UNet.py:389-391, 1x1x1, no bias in the
-            // reference's head).  A lane holds four couts of its voxel and the other 28 sit in the seven lanes beside it: four fmas per
-            // class, then three DPP additions across the 8-lane group; lane `piece` = c stores class c.
-            // Round 4 (SQ pass: 7.6 VALU per MFMA, pipe 0.53 busy on this instantiation): the store address is a scalar base per output
-            // row + ONE tile-invariant lane offset (was: a 64-bit index product per row and lane), the class a lane stores is
-            // picked with v_cndmask from totals that are computed unconditionally (hipcc had sunk them into 35 branches).
-            constexpr int KMAX = 4;
-            f32x4 hq[KMAX];
-            float hb = 0.f;
-            const unsigned Vo = (unsigned)(p.D * p.H * p.W);  // (host: head_ncls * D * H * W * 4 < 2^32)
-            unsigned lane_h = 0;
-            int pc = 0;
-            float *hrow0 = nullptr;
-            if constexpr (EPI == 1) {
+        // ---- phase 2: wave (oy, ox) adds the four xi_z partials (A^T along z), bias, LeakyReLU, whole-line stores.
+        // Lane = (block row srow + 8 t, 4 couts `piece`): 8 lanes hold the 32 couts = the 128-B line of one voxel.
+        const int oy = wave >> 1, ox = wave & 1;
+        const int srow = lane_e >> 3, piece = lane_e & 7;
+        const float *rd = stage + wave * W3_IMG + srow * W3_PITCH + piece * 4;
+        const int co0 = (int)blockIdx.y * 32;
+        f32x4 bias = bias_k;
+        asm volatile("" : "+v"(bias));  // (a copy per tile: the register pairs below are formed from it)
+        const f32x2 b01 = {bias[0], bias[1]}, b23 = {bias[2], bias[3]};
+        float slope = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.act == ACT_LRELU ? p.slope : 1.0f)));
+        asm volatile("" : "+s"(slope));
+        const f32x2 slope2 = {slope, slope};
+        // voxel of block b = 8 t + srow: bx = b & 3, by = (b >> 2) & 3 = 2 (t & 1) + (srow >> 2), bz = b >> 4 = t >> 1
+        const int vx = cur.ox0 + 2 * (srow & 3) + ox;
+        const size_t row_elems = (size_t)p.W * p.Cout;
+        float *obase = p.out + (((size_t)cur.n * p.D + cur.oz0) * p.H + cur.oy0 + oy) * row_elems + co0;  // wave-uniform
+        const unsigned lane_off = (unsigned)(((2 * (srow >> 2)) * p.W + vx) * p.Cout + piece * 4);
+        float st1[4] = {0.f, 0.f, 0.f, 0.f}, st2[4] = {0.f, 0.f, 0.f, 0.f};
+        // EPI == 1: logit[c] = sum_cout w[c][cout] * act(y[cout] + b[cout]) + hb[c] (generic_UNet.py:389-391, 1x1x1, no bias in the
+        // reference's head).  A lane holds four couts of its voxel and the other 28 sit in the seven lanes beside it: four fmas per
+        // class, then three DPP additions across the 8-lane group; lane `piece` = c stores class c.
+        // Round 4 (SQ pass: 7.6 VALU per MFMA, pipe 0.53 busy on this instantiation): the store address is a scalar base per output
+        // row + ONE tile-invariant lane offset (was: a 64-bit index product per row and lane), the class a lane stores is
+        // picked with v_cndmask from totals that are computed unconditionally (hipcc had sunk them into 35 branches).
+        constexpr int KMAX = 4;
+        f32x4 hq[KMAX];
+        float hb = 0.f;
+        const unsigned Vo = (unsigned)(p.D * p.H * p.W);  // (host: head_ncls * D * H * W * 4 < 2^32)
+        unsigned lane_h = 0;
+        int pc = 0;
+        float *hrow0 = nullptr;
+        if constexpr (EPI == 1) {
 #pragma unroll
-                for (int c = 0; c < KMAX; ++c) hq[c] = hq_k[c];
-                pc = piece < p.head_ncls ? piece : 0;
-                hb = hb_k;
-                lane_h = (unsigned)pc * Vo + (unsigned)((2 * (srow >> 2)) * p.W + 2 * (srow & 3));
-                // voxel (oz0, oy0 + oy, ox0 + ox) of class 0 of this sample: wave-uniform
-                hrow0 = p.head_out + (size_t)cur.n * p.head_ncls * Vo + ((size_t)cur.oz0 * p.H + cur.oy0 + oy) * p.W + cur.ox0 + ox;
-            }
+            for (int c = 0; c < KMAX; ++c) hq[c] = hq_k[c];
+            pc = piece < p.head_ncls ? piece : 0;
+            hb = hb_k;
+            lane_h = (unsigned)pc * Vo + (unsigned)((2 * (srow >> 2)) * p.W + 2 * (srow & 3));
+            // voxel (oz0, oy0 + oy, ox0 + ox) of class 0 of this sample: wave-uniform
+            hrow0 = p.head_out + (size_t)cur.n * p.head_ncls * Vo + ((size_t)cur.oz0 * p.H + cur.oy0 + oy) * p.W + cur.ox0 + ox;
+        }
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                f32x4 pz[4];
+        for (int t = 0; t < 4; ++t) {
+            f32x4 pz[4];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) pz[k] = *(const f32x4 *)(rd + k * (4 * W3_IMG) + 8 * t * W3_PITCH);
-                // row of blocks (bz = t >> 1, by = 2 (t & 1) + ...): z = oz0 + 2 bz + oz, y = oy0 + 2 by + oy
-                float *rowp = obase + ((size_t)(2 * (t >> 1)) * p.H + 4 * (t & 1)) * row_elems;
+            for (int k = 0; k < 4; ++k) pz[k] = *(const f32x4 *)(rd + k * (4 * W3_IMG) + 8 * t * W3_PITCH);
+            // row of blocks (bz = t >> 1, by = 2 (t & 1) + ...): z = oz0 + 2 bz + oz, y = oy0 + 2 by + oy
+            float *rowp = obase + ((size_t)(2 * (t >> 1)) * p.H + 4 * (t & 1)) * row_elems;
 #pragma unroll
-                for (int oz = 0; oz < 2; ++oz) {
-                    f32x2 x0, x1, y0, y1;
-                    if (oz == 0) {
-                        x0 = pk_add(pk_add(f32x2{pz[0][0], pz[0][1]}, f32x2{pz[1][0], pz[1][1]}), f32x2{pz[2][0], pz[2][1]});
-                        x1 = pk_add(pk_add(f32x2{pz[0][2], pz[0][3]}, f32x2{pz[1][2], pz[1][3]}), f32x2{pz[2][2], pz[2][3]});
-                    } else {
-                        x0 = pk_sub(pk_sub(f32x2{pz[1][0], pz[1][1]}, f32x2{pz[2][0], pz[2][1]}), f32x2{pz[3][0], pz[3][1]});
-                        x1 = pk_sub(pk_sub(f32x2{pz[1][2], pz[1][3]}, f32x2{pz[2][2], pz[2][3]}), f32x2{pz[3][2], pz[3][3]});
-                    }
-                    f32x4 val;
-                    asm("v_pk_add_f32 %0, %1, %2" : "=v"(x0) : "v"(x0), "v"(b01));
-                    asm("v_pk_add_f32 %0, %1, %2" : "=v"(x1) : "v"(x1), "v"(b23));
-                    asm("v_pk_mul_f32 %0, %1, %2" : "=v"(y0) : "v"(x0), "v"(slope2));
-                    asm("v_pk_mul_f32 %0, %1, %2" : "=v"(y1) : "v"(x1), "v"(slope2));
-                    asm("v_max_f32 %0, %1, %2" : "=v"(val[0]) : "v"(x0[0]), "v"(y0[0]));
-                    asm("v_max_f32 %0, %1, %2" : "=v"(val[1]) : "v"(x0[1]), "v"(y0[1]));
-                    asm("v_max_f32 %0, %1, %2" : "=v"(val[2]) : "v"(x1[0]), "v"(y1[0]));
-                    asm("v_max_f32 %0, %1, %2" : "=v"(val[3]) : "v"(x1[1]), "v"(y1[1]));
-                    if constexpr (EPI == 2) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) { st1[k] += val[k]; st2[k] = fmaf(val[k], val[k], st2[k]); }
-                    }
-                    if constexpr (EPI == 1) {
-                        float tot[KMAX];
-#pragma unroll
-                        for (int c = 0; c < KMAX; ++c) {
-                            float v = val[0] * hq[c][0];
-                            v = fmaf(val[1], hq[c][1], v); v = fmaf(val[2], hq[c][2], v); v = fmaf(val[3], hq[c][3], v);
-                            v += dpp_perm<0xB1>(v);   // lane ^ 1
-                            v += dpp_perm<0x4E>(v);   // lane ^ 2
-                            v += dpp_perm<0x141>(v);  // row_half_mirror: the other quad of the 8-lane group
-                            tot[c] = v;
-                        }
-                        asm volatile("" : "+v"(tot[0]), "+v"(tot[1]), "+v"(tot[2]), "+v"(tot[3]));  // (no sinking into the selects)
-                        float mine = tot[0];   // (lanes beyond the last class repeat lane 0's store: same address, same value - no exec mask, no branch)
-                        mine = pc == 1 ? tot[1] : mine;
-                        mine = pc == 2 ? tot[2] : mine;
-                        mine = pc == 3 ? tot[3] : mine;
-                        // row (z = oz0 + 2 (t >> 1) + oz, y = oy0 + oy + 4 (t & 1) [+ 2 (srow >> 2): in lane_h])
-                        float *hrow = hrow0 + (size_t)((2 * (t >> 1) + oz) * p.H + 4 * (t & 1)) * p.W;
-                        hrow[lane_h] = mine + hb;
-                    } else if constexpr ((MI355_W3_ABL & 32) != 0) asm volatile("" :: "v"(val));
-                    else {
-                        float *gp = rowp + (size_t)oz * p.H * row_elems + lane_off;
-                        // sc1: nothing on this XCD reads the line again (conv3d.hip, FETCH_SIZE -38 % on the 32 -> 32 layer).
-                        // s_nop 2: the VALU instructions of the next output row may be allocated onto these four data registers right
-                        // behind the store; with one wait state (what conv3d.hip's stores carry) dword 1 of the lanes that are read out
-                        // last came out as the NEXT row's intermediate (tools/wino3_probe: couts 17, 21, 25, 29 of every other block)
-                        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 2" :: "v"(gp), "v"(val) : "memory");
-                    }
+            for (int oz = 0; oz < 2; ++oz) {
+                f32x2 x0, x1, y0, y1;
+                if (oz == 0) {
+                    x0 = pk_add(pk_add(f32x2{pz[0][0], pz[0][1]}, f32x2{pz[1][0], pz[1][1]}), f32x2{pz[2][0], pz[2][1]});
+                    x1 = pk_add(pk_add(f32x2{pz[0][2], pz[0][3]}, f32x2{pz[1][2], pz[1][3]}), f32x2{pz[2][2], pz[2][3]});
+                } else {
+                    x0 = pk_sub(pk_sub(f32x2{pz[1][0], pz[1][1]}, f32x2{pz[2][0], pz[2][1]}), f32x2{pz[3][0], pz[3][1]});
+                    x1 = pk_sub(pk_sub(f32x2{pz[1][2], pz[1][3]}, f32x2{pz[2][2], pz[2][3]}), f32x2{pz[3][2], pz[3][3]});
                 }
-            }
-            if constexpr (EPI == 2) {
-                // The eight lanes with the same `piece` (lane bits 3..5) hold the same four couts of different voxels: 8 values per lane
-                // (sum x and sum x^2 of 4 couts) to be added over those three lane bits.  A halving reduce-scatter (common.h,
-                // half32_reduce_scatter): v_permlane32_swap pairs lane ^ 32 (lanes 0-31 keep the sums, lanes 32-63 the sums of
-                // squares), v_permlane16_swap lane ^ 16 (rows 0, 2 keep couts 0, 1, rows 1, 3 couts 2, 3), one DPP row_ror:8 step
-                // lane ^ 8 - 7 additions and 6 swaps; every lane ends with ONE total.  (Was: a three-step __shfl_xor butterfly per
-                // value = 24 ds_bpermute round trips in dependent chains; stamps: this epilogue 6 100 cycles per tile against
-                // 4 270 without statistics.)
-                float y[4];
+                f32x4 val;
+                asm("v_pk_add_f32 %0, %1, %2" : "=v"(x0) : "v"(x0), "v"(b01));
+                asm("v_pk_add_f32 %0, %1, %2" : "=v"(x1) : "v"(x1), "v"(b23));
+                asm("v_pk_mul_f32 %0, %1, %2" : "=v"(y0) : "v"(x0), "v"(slope2));
+                asm("v_pk_mul_f32 %0, %1, %2" : "=v"(y1) : "v"(x1), "v"(slope2));
+                asm("v_max_f32 %0, %1, %2" : "=v"(val[0]) : "v"(x0[0]), "v"(y0[0]));
+                asm("v_max_f32 %0, %1, %2" : "=v"(val[1]) : "v"(x0[1]), "v"(y0[1]));
+                asm("v_max_f32 %0, %1, %2" : "=v"(val[2]) : "v"(x1[0]), "v"(y1[0]));
+                asm("v_max_f32 %0, %1, %2" : "=v"(val[3]) : "v"(x1[1]), "v"(y1[1]));
+                if constexpr (EPI == 2) {
 #pragma unroll
-                for (int k = 0; k < 4; k += 2) {
-                    float a0 = st1[k], a1 = st1[k + 1], c0 = st2[k], c1 = st2[k + 1];
-                    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3\n\ts_nop 1" : "+v"(a0), "+v"(a1), "+v"(c0), "+v"(c1));
-                    y[k] = a0 + c0; y[k + 1] = a1 + c1;
+                    for (int k = 0; k < 4; ++k) { st1[k] += val[k]; st2[k] = fmaf(val[k], val[k], st2[k]); }
                 }
-                float z0, z1;
-                {
-                    float a0 = y[0], a1 = y[1], c0 = y[2], c1 = y[3];
-                    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3\n\ts_nop 1" : "+v"(a0), "+v"(a1), "+v"(c0), "+v"(c1));
-                    z0 = a0 + c0; z1 = a1 + c1;
-                }
-                const bool b3 = lane_e & 8;
-                const float tot_l = (b3 ? z1 : z0) + dpp_perm<0x128>(b3 ? z0 : z1);  // row_ror:8 = lane ^ 8
-                // this lane's value: statistic lane >> 5, cout 4 piece + 2 (lane >> 4 & 1) + (lane >> 3 & 1)
-                red[(wave * 32 + 4 * piece + 2 * ((lane_e >> 4) & 1) + ((lane_e >> 3) & 1)) * 2 + (lane_e >> 5)] = tot_l;
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-                if (wave == 0) {
-                    const int c = lane_e >> 1, k = lane_e & 1;
-                    double tot = 0.0;
+                if constexpr (EPI == 1) {
+                    float tot[KMAX];
 #pragma unroll
-                    for (int w = 0; w < 4; ++w) tot += (double)red[(w * 32 + c) * 2 + k];
-                    // quantised partials add exactly in fp64 in any order (common.h): they are gathered per workgroup and sample and
-                    // go out as ONE atomic per (sample, cout, statistic) and workgroup instead of one per tile - 65 536 tiles of a
-                    // 128^3 x 8 layer were 4.2 M fp64 atomics on 512 addresses
-                    if (cur.n != stat_n) {
-                        if (stat_n >= 0) atomicAdd(p.stats + ((size_t)stat_n * p.Cout + co0 + c) * 2 + k, stat_acc);
-                        stat_acc = 0.0; stat_n = cur.n;
+                    for (int c = 0; c < KMAX; ++c) {
+                        float v = val[0] * hq[c][0];
+                        v = fmaf(val[1], hq[c][1], v); v = fmaf(val[2], hq[c][2], v); v = fmaf(val[3], hq[c][3], v);
+                        v += dpp_perm<0xB1>(v);   // lane ^ 1
+                        v += dpp_perm<0x4E>(v);   // lane ^ 2
+                        v += dpp_perm<0x141>(v);  // row_half_mirror: the other quad of the 8-lane group
+                        tot[c] = v;
                     }
-                    stat_acc += quantise_partial(tot, k, (long)p.D * p.H * p.W);
+                    asm volatile("" : "+v"(tot[0]), "+v"(tot[1]), "+v"(tot[2]), "+v"(tot[3]));  // (no sinking into the selects)
+                    float mine = tot[0];   // (lanes beyond the last class repeat lane 0's store: same address, same value - no exec mask, no branch)
+                    mine = pc == 1 ? tot[1] : mine;
+                    mine = pc == 2 ? tot[2] : mine;
+                    mine = pc == 3 ? tot[3] : mine;
+                    // row (z = oz0 + 2 (t >> 1) + oz, y = oy0 + oy + 4 (t & 1) [+ 2 (srow >> 2): in lane_h])
+                    float *hrow = hrow0 + (size_t)((2 * (t >> 1) + oz) * p.H + 4 * (t & 1)) * p.W;
+                    hrow[lane_h] = mine + hb;
+                } else {
+                    float *gp = rowp + (size_t)oz * p.H * row_elems + lane_off;
+                    // sc1: nothing on this XCD reads the line again (conv3d.hip, FETCH_SIZE -38 % on the 32 -> 32 layer).
+                    // s_nop 2: the VALU instructions of the next output row may be allocated onto these four data registers right
+                    // behind the store; with one wait state (what conv3d.hip's stores carry) dword 1 of the lanes that are read out
+                    // last came out as the NEXT row's intermediate (couts 17, 21, 25, 29 of every other block, docs/history/r01-r04_fp32_kernels.md)
+                    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 2" :: "v"(gp), "v"(val) : "memory");
                 }
             }
         }
+        if constexpr (EPI == 2) {
+            // The eight lanes with the same `piece` (lane bits 3..5) hold the same four couts of different voxels: 8 values per lane
+            // (sum x and sum x^2 of 4 couts) to be added over those three lane bits.  A halving reduce-scatter (common.h,
+            // half32_reduce_scatter): v_permlane32_swap pairs lane ^ 32 (lanes 0-31 keep the sums, lanes 32-63 the sums of
+            // squares), v_permlane16_swap lane ^ 16 (rows 0, 2 keep couts 0, 1, rows 1, 3 couts 2, 3), one DPP row_ror:8 step
+            // lane ^ 8 - 7 additions and 6 swaps; every lane ends with ONE total.  (Was: a three-step __shfl_xor butterfly per
+            // value = 24 ds_bpermute round trips in dependent chains; stamps: this epilogue 6 100 cycles per tile against
+            // 4 270 without statistics.)
+            float y[4];
+#pragma unroll
+            for (int k = 0; k < 4; k += 2) {
+                float a0 = st1[k], a1 = st1[k + 1], c0 = st2[k], c1 = st2[k + 1];
+                asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3\n\ts_nop 1" : "+v"(a0), "+v"(a1), "+v"(c0), "+v"(c1));
+                y[k] = a0 + c0; y[k + 1] = a1 + c1;
+            }
+            float z0, z1;
+            {
+                float a0 = y[0], a1 = y[1], c0 = y[2], c1 = y[3];
+                asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3\n\ts_nop 1" : "+v"(a0), "+v"(a1), "+v"(c0), "+v"(c1));
+                z0 = a0 + c0; z1 = a1 + c1;
+            }
+            const bool b3 = lane_e & 8;
+            const float tot_l = (b3 ? z1 : z0) + dpp_perm<0x128>(b3 ? z0 : z1);  // row_ror:8 = lane ^ 8
+            // this lane's value: statistic lane >> 5, cout 4 piece + 2 (lane >> 4 & 1) + (lane >> 3 & 1)
+            red[(wave * 32 + 4 * piece + 2 * ((lane_e >> 4) & 1) + ((lane_e >> 3) & 1)) * 2 + (lane_e >> 5)] = tot_l;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            if (wave == 0) {
+                const int c = lane_e >> 1, k = lane_e & 1;
+                double tot = 0.0;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) tot += (double)red[(w * 32 + c) * 2 + k];
+                // quantised partials add exactly in fp64 in any order (common.h): they are gathered per workgroup and sample and
+                // go out as ONE atomic per (sample, cout, statistic) and workgroup instead of one per tile - 65 536 tiles of a
+                // 128^3 x 8 layer were 4.2 M fp64 atomics on 512 addresses
+                if (cur.n != stat_n) {
+                    if (stat_n >= 0) atomicAdd(p.stats + ((size_t)stat_n * p.Cout + co0 + c) * 2 + k, stat_acc);
+                    stat_acc = 0.0; stat_n = cur.n;
+                }
+                stat_acc += quantise_partial(tot, k, (long)p.D * p.H * p.W);
+            }
+        }
         cur = nxt_tile;
-        W3_T(t_e2);
-        W3_ACC(4, t_e0, t_e2);
-        W3_CNT(7);
     }
     if constexpr (EPI == 2) {
         if (wave == 0 && stat_n >= 0)
             atomicAdd(p.stats + ((size_t)stat_n * p.Cout + (int)blockIdx.y * 32 + (lane >> 1)) * 2 + (lane & 1), stat_acc);
     }
-    W3_T(t_kernel1);
-    W3_ACC(5, t_kernel0, t_kernel1);
-    W3_FLUSH;
 #undef W3_ULOAD
 #undef W3_UWAIT
 }

@@ -4,80 +4,15 @@
 // (model_architecture/generic_UNet.py:363-364, applied at :435).  With kernel == stride the
 // op is 8 independent 1x1x1 GEMMs, one per output parity (a,b,c):
 //     out[n, 2z+a, 2y+b, 2x+c, co] = sum_ci in[n,z,y,x,ci] * W[ci, co, a, b, c]
-// M = input voxels (flattened N*D*H*W), K = Cin, N = Cout per parity.  A fragments are read
+// M = input voxels (flattened N*D*H*W), K = Cin, N = Cout per parity.  Voxel fragments are read
 // straight from global (16 B per lane: 4 channels of one voxel; lanes 0-31 / 32-63 take the two
-// halves of an 8-channel group, same K pairing as conv3d.hip); B fragments come from a
+// halves of an 8-channel group, same K pairing as conv3d.hip); weight fragments come from a
 // host-permuted pack.  1.6 % of the network's flops, so no LDS staging.
 #include "kernels.h"
 
 #include <vector>
 
 namespace mi355 {
-
-template <int MF>
-__global__ __launch_bounds__(256) void tconv2_f32_mfma_kernel(const float *__restrict__ in,
-                                                             const float *__restrict__ wp, float *out,
-                                                             int M, int Cin, int Cout, int D, int H, int W,
-                                                             FastDiv divW, FastDiv divH, FastDiv divD) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int half = lane >> 5, l31 = lane & 31;
-    const int nblk = Cout >> 5;
-    const int pos = (int)blockIdx.y / nblk, nb = (int)blockIdx.y - pos * nblk;
-    const int G = Cin >> 3;
-    const int m0 = ((int)blockIdx.x * 4 + wave) * (MF * 32);
-
-    const float *arow[MF];
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf) {
-        int v = m0 + mf * 32 + l31;
-        if (v >= M) v = M - 1;  // clamp: rows past the end are computed and discarded
-        arow[mf] = in + (size_t)v * Cin + half * 4;
-    }
-    const float *wrow = wp + ((size_t)(pos * nblk + nb) * G) * 256 + lane * 4;
-
-    f32x16 acc[MF];
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            acc[mf][r] = 0.f;
-
-#pragma unroll 2
-    for (int g = 0; g < G; ++g) {
-        f32x4 a[MF];
-#pragma unroll
-        for (int mf = 0; mf < MF; ++mf)
-            a[mf] = *(const f32x4 *)(arow[mf] + g * 8);
-        const f32x4 b = *(const f32x4 *)(wrow + (size_t)g * 256);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int mf = 0; mf < MF; ++mf)
-                acc[mf] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mf][j], b[j], acc[mf], 0, 0, 0);
-    }
-
-    const int pa = pos >> 2, pb = (pos >> 1) & 1, pc = pos & 1;
-    const int co = nb * 32 + l31;
-    const int Ho = 2 * H, Wo = 2 * W, Do = 2 * D;
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
-            const int v = m0 + mf * 32 + row;
-            if (v < M) {
-                const uint32_t q1 = fdiv((uint32_t)v, divW);
-                const int x = v - (int)q1 * W;
-                const uint32_t q2 = fdiv(q1, divH);
-                const int y = (int)q1 - (int)q2 * H;
-                const uint32_t n = fdiv(q2, divD);
-                const int z = (int)q2 - (int)n * D;
-                out[((((size_t)n * Do + 2 * z + pa) * Ho + 2 * y + pb) * Wo + 2 * x + pc) * Cout + co] =
-                    acc[mf][r];
-            }
-        }
-    }
-}
 
 // Version 2: one workgroup = 128 input voxels (4 voxel fragments) x 32 couts x ALL 8 output parities; wave w owns
 // parities {2w, 2w+1}.  Per 8-channel group a wave reads 4 voxel fragments (B operand, straight from global, L1-shared
@@ -185,7 +120,7 @@ __global__ __launch_bounds__(256) void tconv2_f32_mfma_v2_kernel(const float *__
 // Version 3 (round 4; the fp16 kernel has had it since round 3): version 2 made persistent, with the wave's weights in registers.
 // A workgroup of version 2 re-reads its weight block (Cin x 1 KiB) from the L2 for every 128 voxels, waits for each fragment in
 // front of the MFMAs that use it, and has nothing to overlap its load - compute - store sequence with but the other
-// workgroups of its CU.  Here the two parities' fragments of a wave stay in 8 G = Cin registers (G = Cin / 8 = 8 or 16) and the
+// workgroups of its CU.  Here the two parities' fragments of a wave stay in 8 G = Cin registers (G = Cin / 8; Cin = 64 only, see tconv2_mfma_f32) and the
 // workgroup strides over the voxel tiles; per tile only the 128 x Cin input block comes through the L1.
 template <int G>
 __global__ __launch_bounds__(256, G <= 8 ? 2 : 1) void tconv2_f32_mfma_v3_kernel(const float *__restrict__ in,
@@ -309,107 +244,32 @@ int tconv2_mfma_f32(const TConvWeights &w, const float *in, int N, int D, int H,
                     hipStream_t s, const char **kernel_name) {
     const long M = (long)N * D * H * W;
     MI355_REQUIRE(M > 0 && M < (1l << 30), "tconv: %ld voxels out of range", M);
-    static int v1 = -1;
-    if (v1 < 0) { const char *e = getenv("MI355_TCONV_V1"); v1 = (e && e[0] == '1') ? 1 : 0; }
     static int v3 = -1;
-    if (v3 < 0) { const char *e = getenv("MI355_TCONV_V3"); v3 = (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1); }
+    if (v3 < 0) { const char *e = getenv("MI355_TCONV_V3"); v3 = (e && e[0] == '0') ? 0 : 1; }
     const long ntiles = (M + 127) / 128;
-    // (Cin = 128 - 128 weight registers, one workgroup per CU - measured slower than version 2: 3.4 against 3.0 ms for 128 -> 64 @ 8 x 32^3;
-    //  MI355_TCONV_V3=2 still takes it)
-    if (!v1 && v3 && (w.cin == 64 || (w.cin == 128 && v3 == 2)) && ntiles >= 1024) {
-        // persistent: the resident slots (two workgroups per CU at Cin = 64, one at 128: 128 weight registers) shared by the cout blocks
+    // (Cin = 64 only: at Cin = 128 - 128 weight registers, one workgroup per CU - version 3 measured slower than version 2,
+    //  3.4 against 3.0 ms for 128 -> 64 @ 8 x 32^3)
+    if (v3 && w.cin == 64 && ntiles >= 1024) {
+        // persistent: two workgroups per CU and cout block share the 512 resident slots
         const int nblk = w.cout / 32;
-        long gx = (w.cin == 64 ? 512 : 256) / nblk;
+        long gx = 512 / nblk;
         if (gx < 8) gx = 8;
         if (gx > ntiles) gx = ntiles;
         dim3 grid3((unsigned)gx, nblk);
-        if (kernel_name) *kernel_name = w.cin == 64 ? "tconv2_f32_mfma_v3_kernel<8>" : "tconv2_f32_mfma_v3_kernel<16>";
-        if (w.cin == 64) hipLaunchKernelGGL(tconv2_f32_mfma_v3_kernel<8>, grid3, dim3(256), 0, s, in, w.wp_dev, out, (int)M, w.cout, D, H, W, make_fastdiv(W), make_fastdiv(H), make_fastdiv(D));
-        else hipLaunchKernelGGL(tconv2_f32_mfma_v3_kernel<16>, grid3, dim3(256), 0, s, in, w.wp_dev, out, (int)M, w.cout, D, H, W, make_fastdiv(W), make_fastdiv(H), make_fastdiv(D));
+        if (kernel_name) *kernel_name = "tconv2_f32_mfma_v3_kernel<8>";
+        hipLaunchKernelGGL(tconv2_f32_mfma_v3_kernel<8>, grid3, dim3(256), 0, s, in, w.wp_dev, out, (int)M, w.cout, D, H, W, make_fastdiv(W), make_fastdiv(H), make_fastdiv(D));
         MI355_HIP(hipGetLastError());
         return MI355_OK;
     }
-    if (kernel_name) *kernel_name = v1 ? "tconv2_f32_mfma_kernel<2>" : "tconv2_f32_mfma_v2_kernel";
-    if (!v1) {
-        dim3 grid((unsigned)((M + 127) / 128), w.cout / 32);
-        hipLaunchKernelGGL(tconv2_f32_mfma_v2_kernel, grid, dim3(256), 0, s, in, w.wp_dev, out, (int)M, w.cin, w.cout, D, H, W,
-                           make_fastdiv(W), make_fastdiv(H), make_fastdiv(D));
-        MI355_HIP(hipGetLastError());
-        return MI355_OK;
-    }
-    constexpr int MF = 2;
-    dim3 grid((unsigned)((M + 4 * MF * 32 - 1) / (4 * MF * 32)), 8 * (w.cout / 32));
-    hipLaunchKernelGGL(tconv2_f32_mfma_kernel<MF>, grid, dim3(256), 0, s, in, w.wp_dev, out, (int)M, w.cin,
-                       w.cout, D, H, W, make_fastdiv(W), make_fastdiv(H), make_fastdiv(D));
+    if (kernel_name) *kernel_name = "tconv2_f32_mfma_v2_kernel";
+    dim3 grid((unsigned)((M + 127) / 128), w.cout / 32);
+    hipLaunchKernelGGL(tconv2_f32_mfma_v2_kernel, grid, dim3(256), 0, s, in, w.wp_dev, out, (int)M, w.cin, w.cout, D, H, W,
+                       make_fastdiv(W), make_fastdiv(H), make_fastdiv(D));
     MI355_HIP(hipGetLastError());
     return MI355_OK;
 }
 
 // ------------------------------------------------------------------ fp16 storage variant
-// D[cout][voxel] = W^T x X per output parity on v_mfma_f32_32x32x16_f16: weights are the A operand (lane: cout l&31,
-// channels 8*(l>>5)..+7), input voxels the B operand read straight from global (16 B per lane); a lane ends up with
-// 4 consecutive couts per register quad -> 8-byte stores.
-template <int MF>
-__global__ __launch_bounds__(256) void tconv2_f16_mfma_kernel(const _Float16 *__restrict__ in,
-                                                             const _Float16 *__restrict__ wp, _Float16 *out, int M,
-                                                             int Cin, int Cout, int D, int H, int W, FastDiv divW,
-                                                             FastDiv divH, FastDiv divD) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int half = lane >> 5, l31 = lane & 31;
-    const int nblk = Cout >> 5;
-    const int pos = (int)blockIdx.y / nblk, nb = (int)blockIdx.y - pos * nblk;
-    const int G = Cin >> 4;
-    const int m0 = ((int)blockIdx.x * 4 + wave) * (MF * 32);
-    // fp16 tensors are channel-blocked ([N][C / 8][V][8], common.h): voxel v of sample n, block 2 g + half
-    const long Vi = (long)D * H * W;
-    const _Float16 *xrow[MF];
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf) {
-        int v = m0 + mf * 32 + l31;
-        if (v >= M) v = M - 1;
-        const uint32_t n = fdiv(fdiv(fdiv((uint32_t)v, divW), divH), divD);
-        xrow[mf] = in + ((long)n * (Cin >> 3) * Vi + (v - (long)n * Vi) + half * Vi) * 8;
-    }
-    const _Float16 *wrow = wp + ((size_t)(pos * nblk + nb) * G) * 512 + lane * 8;
-    f32x16 acc[MF];
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mf][r] = 0.f;
-#pragma unroll 2
-    for (int g = 0; g < G; ++g) {
-        const f16x8 wf = *(const f16x8 *)(wrow + (size_t)g * 512);
-#pragma unroll
-        for (int mf = 0; mf < MF; ++mf) {
-            const f16x8 xf = *(const f16x8 *)(xrow[mf] + (long)g * Vi * 16);
-            acc[mf] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, xf, acc[mf], 0, 0, 0);
-        }
-    }
-    const int pa = pos >> 2, pb = (pos >> 1) & 1, pc = pos & 1;
-    const int Ho = 2 * H, Wo = 2 * W, Do = 2 * D;
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf) {
-        const int v = m0 + mf * 32 + l31;
-        if (v < M) {
-            const uint32_t q1 = fdiv((uint32_t)v, divW);
-            const int x = v - (int)q1 * W;
-            const uint32_t q2 = fdiv(q1, divH);
-            const int y = (int)q1 - (int)q2 * H;
-            const uint32_t n = fdiv(q2, divD);
-            const int z = (int)q2 - (int)n * D;
-            // couts nb * 32 + 8 g + 4 half .. + 3 = block nb * 4 + g, position 4 half of the blocked output
-            const long Vo = (long)Do * Ho * Wo;
-            _Float16 *o = out + (((long)n * (Cout >> 3) + nb * 4) * Vo + (((long)2 * z + pa) * Ho + 2 * y + pb) * Wo + 2 * x + pc) * 8 + 4 * half;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f16x4 hv = {(_Float16)acc[mf][4 * g], (_Float16)acc[mf][4 * g + 1], (_Float16)acc[mf][4 * g + 2],
-                            (_Float16)acc[mf][4 * g + 3]};
-                *(f16x4 *)(o + (long)g * Vo * 8) = hv;
-            }
-        }
-    }
-}
-
 // Version 2 (same decomposition as tconv2_f32_mfma_v2_kernel): 128 voxels x 32 couts x 8 parities per workgroup.
 // Two workgroups per CU (round 2): left to itself hipcc spread this kernel over 146 VGPRs + 128 AGPRs, one wave per SIMD, and a
 // workgroup that loads, computes and stores in sequence had nothing to overlap with (137 -> 111 us per launch; three per CU spill).
@@ -635,12 +495,10 @@ int tconv2_mfma_f16(const TConvWeightsH &w, const _Float16 *in, int N, int D, in
     if (kernel_name) *kernel_name = "tconv2_f16_mfma_v2_kernel";
     const long M = (long)N * D * H * W;
     MI355_REQUIRE(M > 0 && M < (1l << 30), "tconv: %ld voxels out of range", M);
-    static int v1 = -1;
-    if (v1 < 0) { const char *e = getenv("MI355_TCONV_V1"); v1 = (e && e[0] == '1') ? 1 : 0; }
     static int v3 = -1;
     if (v3 < 0) { const char *e = getenv("MI355_TCONV_V3"); v3 = (e && e[0] == '0') ? 0 : 1; }
     const long ntiles = (M + 127) / 128;
-    if (!v1 && v3 && (w.cin == 32 || w.cin == 64 || w.cin == 128) && ntiles >= 1024) {
+    if (v3 && (w.cin == 32 || w.cin == 64 || w.cin == 128) && ntiles >= 1024) {
         // persistent: two workgroups per CU and cout block share the 512 resident slots
         const int nblk = w.cout / 32;
         long gx = 512 / nblk;
@@ -654,17 +512,8 @@ int tconv2_mfma_f16(const TConvWeightsH &w, const _Float16 *in, int N, int D, in
         MI355_HIP(hipGetLastError());
         return MI355_OK;
     }
-    if (!v1) {
-        dim3 grid2((unsigned)((M + 127) / 128), w.cout / 32);
-        hipLaunchKernelGGL(tconv2_f16_mfma_v2_kernel, grid2, dim3(256), 0, s, in, w.wp_dev, out, (int)M, w.cin, w.cout, D, H,
-                           W, make_fastdiv(W), make_fastdiv(H), make_fastdiv(D));
-        MI355_HIP(hipGetLastError());
-        return MI355_OK;
-    }
-    constexpr int MF = 2;
-    if (kernel_name) *kernel_name = "tconv2_f16_mfma_kernel<2>";
-    dim3 grid((unsigned)((M + 4 * MF * 32 - 1) / (4 * MF * 32)), 8 * (w.cout / 32));
-    hipLaunchKernelGGL(tconv2_f16_mfma_kernel<MF>, grid, dim3(256), 0, s, in, w.wp_dev, out, (int)M, w.cin, w.cout, D, H,
+    dim3 grid2((unsigned)((M + 127) / 128), w.cout / 32);
+    hipLaunchKernelGGL(tconv2_f16_mfma_v2_kernel, grid2, dim3(256), 0, s, in, w.wp_dev, out, (int)M, w.cin, w.cout, D, H,
                        W, make_fastdiv(W), make_fastdiv(H), make_fastdiv(D));
     MI355_HIP(hipGetLastError());
     return MI355_OK;

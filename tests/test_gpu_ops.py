@@ -136,7 +136,7 @@ def test_tconv_matches_torch(amd, gpu, case):
 @pytest.mark.parametrize("case", [(1, 33, 63, 65, 64, 32), (2, 32, 32, 64, 64, 32)])
 def test_tconv_f32_persistent_kernel_matches_torch(amd, gpu, case):
     """Round 4: tconv2_f32_mfma_v3_kernel (persistent, the wave's weights in registers; Cin 64 and >= 1024 tiles of 128 input
-    voxels - the largest decoder level of the fp32 path; the Cin = 128 instantiation is behind MI355_TCONV_V3=2).  One case is ragged (33 x 63 x 65 = 135135 voxels: the clamped tail
+    voxels - the largest decoder level of the fp32 path).  One case is ragged (33 x 63 x 65 = 135135 voxels: the clamped tail
     tile and its store predicate); the kernel that ran is asserted."""
     n, d, h, w, cin, cout = case
     rs = np.random.RandomState(16)
@@ -145,7 +145,7 @@ def test_tconv_f32_persistent_kernel_matches_torch(amd, gpu, case):
     ref = F.conv_transpose3d(torch.from_numpy(x).permute(0, 4, 1, 2, 3), torch.from_numpy(wt), None, stride=2)
     ref = ref.permute(0, 2, 3, 4, 1).contiguous().numpy()
     y = amd.ops.tconv3d_ndhwc(torch.from_numpy(x).to(gpu), wt).cpu().numpy()
-    if "MI355_TCONV_V3" not in os.environ and "MI355_TCONV_V1" not in os.environ:
+    if "MI355_TCONV_V3" not in os.environ:
         assert amd.ops.last_conv_kernel().startswith("tconv2_f32_mfma_v3_kernel<"), amd.ops.last_conv_kernel()
     assert y.shape == ref.shape
     assert np.abs(y - ref).max() <= 2e-5 * max(1.0, np.abs(ref).max())
@@ -430,7 +430,7 @@ print("OK", worst)
 """
 
 
-@pytest.mark.parametrize("env", [{"MI355_WINOGRAD": "0"}, {"MI355_WINOGRAD": "1"}, {"MI355_WINO3": "0"}, {"MI355_S2_DMA": "0", "MI355_SPLITK": "0"},
+@pytest.mark.parametrize("env", [{"MI355_WINOGRAD": "0"}, {"MI355_WINO3": "0"}, {"MI355_S2_DMA": "0", "MI355_SPLITK": "0"},
                                  {"MI355_CONV_IMPL": "0"}, {"MI355_F16_DMA": "0"}])
 def test_conv_dispatch_switches_keep_working(amd, gpu, env):
     """The A/B switches select the older kernels behind the same entry points (direct instead of Winograd, simple
