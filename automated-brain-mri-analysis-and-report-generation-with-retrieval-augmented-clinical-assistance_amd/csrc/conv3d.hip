@@ -1511,7 +1511,10 @@ int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, cons
         if (taken) return MI355_OK;
     }
     MI355_REQUIRE(!c.in_scale, "conv %d->%d: a pending input normalisation reached a kernel that cannot apply it", w.cin, w.cout);
-    if (w.wpw_dev) {
+    // the 16-channel-chunk kernels below pick in0 or in1 once per chunk: a concat split that is a multiple of 8 only (w.cc of
+    // the pipelined build) would make a chunk straddle the two halves; such calls go to the 8-channel kernels
+    const bool split16 = c.C0 % 16 == 0 && c.C1 % 16 == 0;
+    if (w.wpw_dev && split16) {
         // auto mode, large launches: Winograd F(2x2,3x3) on fixed 4x4x32 tiles, 32 couts per workgroup
         ConvArgs b = a;
         b.lz = 2; b.ly = 2; b.lx = 5;
@@ -1556,7 +1559,7 @@ int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, cons
             return MI355_OK;
         }
     }
-    if (w.wp16_dev) {
+    if (w.wp16_dev && split16) {
         // auto mode: 512-voxel tiles + 16-channel chunks when that fills the chip
         ConvArgs b = a;
         fill_geometry(b, 1, 512);
@@ -1623,8 +1626,11 @@ int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, cons
         if (w.nf == 2 || tiles * (w.cout / 32) < 512 || a.IX * a.IY * a.IZ > 11 * 128) {
             MF = 2; NF = w.nf;
             geom(2);
-            if (tiles * (w.cout / (32 * NF)) < 384) NF = 1;
-            if (tiles * (w.cout / (32 * NF)) < 384) { MF = 1; geom(1); }
+            // the fused head sums all of a voxel's couts in one workgroup (conv_epilogue): with 64 couts it keeps NF = 2 (and so
+            // MF = 2, there is no <1, 2> instantiation) - two 32-cout blocks would each store a partial sum into the same logits
+            const bool keep_nf = c.head_out && w.nf == 2;
+            if (!keep_nf && tiles * (w.cout / (32 * NF)) < 384) NF = 1;
+            if (!keep_nf && tiles * (w.cout / (32 * NF)) < 384) { MF = 1; geom(1); }
         }
         const int gy = w.cout / (32 * NF);
         MI355_REQUIRE(tiles < (1l << 30), "conv grid too large");
@@ -1720,6 +1726,9 @@ int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, cons
 int conv3d_direct_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s) {
     MI355_REQUIRE(w.w_plain_dev != nullptr, "conv %d->%d has no plain weights", w.cin, w.cout);
     MI355_REQUIRE(c.C0 + c.C1 == w.cin_pad, "conv input channels %d+%d != %d", c.C0, c.C1, w.cin_pad);
+    // (the statistics epilogue is here; the fused head and the fused input normalisation are not)
+    MI355_REQUIRE(!c.head_out && !c.in_scale, "conv %d->%d: the direct kernel has no fused head or input normalisation", w.cin, w.cout);
+    MI355_REQUIRE(c.out != nullptr, "conv %d->%d: no output tensor", w.cin, w.cout);
     const int st = w.stride;
     const int Do = (c.Di - 1) / st + 1, Ho = (c.Hi - 1) / st + 1, Wo = (c.Wi - 1) / st + 1;
     const size_t total = (size_t)c.N * Do * Ho * Wo * w.cout;

@@ -898,13 +898,29 @@ extern "C" int mi355_sw_predict(const mi355_unet_t *nets, int n_nets, const floa
 
 // `sums` (device, [n][cout][2] doubles, zeroed here) != nullptr: the launch also carries the Instance/GroupNorm statistics
 // epilogue (sum x, sum x^2 of its output per sample and channel) exactly as a run-time-norm block of the network does.
+// `f` (optional): the fused operands of a network conv (ConvCall): the second half of a virtual concat, the producer's
+// normalisation applied while staging, the 1x1x1 head.  They go to the dispatchers unchanged (mi355_conv3d_fused_ndhwc).
+namespace {
+struct FusedOps {
+    const void *x1 = nullptr;  // [n,d,h,w,c1] plain NDHWC, or null
+    int c1 = 0;
+    const float *in_scale = nullptr, *in_shift = nullptr;  // [n][cin - c1] device fp32, or null
+    int in_act = ACT_NONE;
+    const float *head_w = nullptr, *head_b = nullptr;  // [ncls][cout], [ncls] device fp32
+    float *head_out = nullptr;                         // [n][ncls][Vo] fp32 logits; the conv output is then not stored
+    int head_ncls = 0;
+    bool any() const { return x1 || c1 || in_scale || in_shift || head_w || head_b || head_out; }
+};
+}  // namespace
+
 static int conv3d_ndhwc_f32_impl(const float *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
                                  const float *bias_host, int cout, int stride, int act, float slope, int impl, float *y_dev,
-                                 double *sums, void *stream) {
+                                 double *sums, void *stream, const FusedOps &f = FusedOps()) {
     MI355_TRY(require_device());
     MI355_REQUIRE(act != ACT_LRELU || (slope >= 0.f && slope <= 1.f), "LeakyReLU slope %g outside [0, 1]", (double)slope);
+    MI355_REQUIRE(f.c1 >= 0 && f.c1 < cin && (f.c1 == 0) == (f.x1 == nullptr), "bad concat split %d of %d channels", f.c1, cin);
     if (sums) MI355_HIP(hipMemsetAsync(sums, 0, (size_t)n * cout * 2 * sizeof(double), (hipStream_t)stream));
-    if (cin == 4 && stride == 1 && impl == 0 && cout % 32 == 0) {  // the network's first-layer kernel
+    if (cin == 4 && stride == 1 && impl == 0 && cout % 32 == 0 && !f.any()) {  // the network's first-layer kernel
         StemWeights sw;
         MI355_TRY(stem_weights_upload(weight_host, bias_host, cin, cout, MI355_F32, &sw));
         int rc = conv3d_stem(sw, x_dev, n, d, h, w, y_dev, sums, act, slope, (hipStream_t)stream);
@@ -917,8 +933,11 @@ static int conv3d_ndhwc_f32_impl(const float *x_dev, int n, int d, int h, int w,
     ConvWeights cw;
     MI355_TRY(conv_weights_upload(weight_host, bias_host, cin, cin, cout, stride, impl == 1, &cw));
     ConvCall c;
-    c.in0 = x_dev; c.C0 = cin; c.N = n; c.Di = d; c.Hi = h; c.Wi = w; c.out = y_dev; c.act = act; c.slope = slope;
+    c.in0 = x_dev; c.C0 = cin - f.c1; c.in1 = (const float *)f.x1; c.C1 = f.c1;
+    c.N = n; c.Di = d; c.Hi = h; c.Wi = w; c.out = y_dev; c.act = act; c.slope = slope;
     c.stats = sums;
+    c.in_scale = f.in_scale; c.in_shift = f.in_shift; c.in_act = f.in_act;
+    c.head_w = f.head_w; c.head_b = f.head_b; c.head_out = f.head_out; c.head_ncls = f.head_ncls;
     MI355_REQUIRE(!sums || impl != 1, "the direct cross-check kernel carries no statistics epilogue");
     const char *kname = "conv3_direct_kernel";
     int rc = (impl == 1) ? conv3d_direct_f32(cw, c, (hipStream_t)stream) : conv3d_mfma_f32(cw, c, (hipStream_t)stream, &kname);
@@ -960,10 +979,11 @@ struct TmpBuf {
 
 static int conv3d_ndhwc_f16_impl(const void *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
                                  const float *bias_host, int cout, int stride, int act, float slope, void *y_dev,
-                                 double *sums, void *stream) {
+                                 double *sums, void *stream, const FusedOps &f = FusedOps()) {
     MI355_TRY(require_device());
     MI355_REQUIRE(stride == 1 || stride == 2, "conv stride %d unsupported", stride);
     MI355_REQUIRE(act != ACT_LRELU || (slope >= 0.f && slope <= 1.f), "LeakyReLU slope %g outside [0, 1]", (double)slope);
+    MI355_REQUIRE(f.c1 >= 0 && f.c1 < cin && (f.c1 == 0) == (f.x1 == nullptr), "bad concat split %d of %d channels", f.c1, cin);
     hipStream_t s = (hipStream_t)stream;
     if (sums) MI355_HIP(hipMemsetAsync(sums, 0, (size_t)n * cout * 2 * sizeof(double), s));
     const int64_t Vi = (int64_t)d * h * w;
@@ -971,8 +991,10 @@ static int conv3d_ndhwc_f16_impl(const void *x_dev, int n, int d, int h, int w, 
     MI355_REQUIRE(cout % 8 == 0, "fp16 conv needs cout %% 8 == 0 (got %d)", cout);
     TmpBuf yb;
     MI355_HIP(hipMalloc(&yb.p, (size_t)n * Vo * cout * 2));
+    // all-NaN (0xFFFF) before the launch: a voxel the kernel fails to store cannot pass for a result
+    MI355_HIP(hipMemsetAsync(yb.p, 0xFF, (size_t)n * Vo * cout * 2, s));
     int rc;
-    if (cin == 4 && stride == 1 && cout % 32 == 0) {  // the network's first-layer kernel: plain NDHW4 input
+    if (cin == 4 && stride == 1 && cout % 32 == 0 && !f.any()) {  // the network's first-layer kernel: plain NDHW4 input
         StemWeights sw;
         MI355_TRY(stem_weights_upload(weight_host, bias_host, cin, cout, MI355_F16, &sw));
         rc = conv3d_stem(sw, x_dev, n, d, h, w, yb.p, sums, act, slope, s);
@@ -983,19 +1005,27 @@ static int conv3d_ndhwc_f16_impl(const void *x_dev, int n, int d, int h, int w, 
         if (rc == MI355_OK && e != hipSuccess) { set_error("stem conv kernel failed: %s", hipGetErrorString(e)); rc = MI355_ERR_HIP; }
         return rc;
     }
-    MI355_REQUIRE(cin % 8 == 0, "fp16 conv needs cin %% 8 == 0 (got %d)", cin);
-    TmpBuf xb;
-    MI355_HIP(hipMalloc(&xb.p, (size_t)n * Vi * cin * 2));
-    MI355_TRY(ndhwc_to_b8((const _Float16 *)x_dev, n, cin, Vi, (_Float16 *)xb.p, s));
+    MI355_REQUIRE(cin % 8 == 0 && f.c1 % 8 == 0, "fp16 conv needs cin %% 8 == 0 on both inputs (got %d, %d)", cin - f.c1, f.c1);
+    const int c0 = cin - f.c1;
+    TmpBuf xb, x1b;
+    MI355_HIP(hipMalloc(&xb.p, (size_t)n * Vi * c0 * 2));
+    MI355_TRY(ndhwc_to_b8((const _Float16 *)x_dev, n, c0, Vi, (_Float16 *)xb.p, s));
+    if (f.x1) {
+        MI355_HIP(hipMalloc(&x1b.p, (size_t)n * Vi * f.c1 * 2));
+        MI355_TRY(ndhwc_to_b8((const _Float16 *)f.x1, n, f.c1, Vi, (_Float16 *)x1b.p, s));
+    }
     ConvWeightsH cw;
     MI355_TRY(conv_weights_upload_f16(weight_host, bias_host, cin, cin, cout, stride, &cw));
     ConvCallH c;
-    c.in0 = (const _Float16 *)xb.p; c.C0 = cin; c.N = n; c.Di = d; c.Hi = h; c.Wi = w; c.out = (_Float16 *)yb.p;
+    c.in0 = (const _Float16 *)xb.p; c.C0 = c0; c.in1 = (const _Float16 *)x1b.p; c.C1 = f.c1;
+    c.N = n; c.Di = d; c.Hi = h; c.Wi = w; c.out = f.head_out ? nullptr : (_Float16 *)yb.p;  // head mode stores logits only (run_block)
     c.act = act; c.slope = slope; c.stats = sums;
+    c.in_scale = f.in_scale; c.in_shift = f.in_shift; c.in_act = f.in_act;
+    c.head_w = f.head_w; c.head_b = f.head_b; c.head_out = f.head_out; c.head_ncls = f.head_ncls;
     const char *kname = nullptr;
     rc = conv3d_mfma_f16(cw, c, s, &kname);
     g_last_conv_kernel = kname ? kname : "";
-    if (rc == MI355_OK) rc = b8_to_ndhwc((const _Float16 *)yb.p, n, cout, Vo, (_Float16 *)y_dev, s);
+    if (rc == MI355_OK && !f.head_out) rc = b8_to_ndhwc((const _Float16 *)yb.p, n, cout, Vo, (_Float16 *)y_dev, s);
     hipError_t e = hipStreamSynchronize(s);
     conv_weights_free_f16(&cw);
     if (rc == MI355_OK && e != hipSuccess) { set_error("conv kernel failed: %s", hipGetErrorString(e)); rc = MI355_ERR_HIP; }
@@ -1019,6 +1049,29 @@ extern "C" int mi355_conv3d_sums_ndhwc(const void *x_dev, int dtype, int n, int 
                                  sums_dev, stream);
 }
 
+extern "C" int mi355_conv3d_fused_ndhwc(const void *x0_dev, const void *x1_dev, int dtype, int n, int d, int h, int w, int c0,
+                                        int c1, const float *weight_host, const float *bias_host, int cout, int stride, int act,
+                                        float slope, int impl, const float *in_scale_dev, const float *in_shift_dev, int in_act,
+                                        const float *head_w_dev, const float *head_b_dev, int head_ncls, float *head_out_dev,
+                                        void *y_dev, double *sums_dev, void *stream) {
+    MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_F16, "unknown dtype %d", dtype);
+    MI355_REQUIRE(x0_dev && c0 > 0 && c1 >= 0 && (c1 == 0) == (x1_dev == nullptr), "bad conv inputs (c0 %d, c1 %d)", c0, c1);
+    MI355_REQUIRE((y_dev == nullptr) == (head_out_dev != nullptr), "give exactly one of y (feature map) and head_out (logits)");
+    MI355_REQUIRE(!in_scale_dev == !in_shift_dev, "in_scale and in_shift come together");
+    MI355_REQUIRE(in_act != ACT_LRELU || (slope >= 0.f && slope <= 1.f), "LeakyReLU slope %g outside [0, 1]", (double)slope);
+    FusedOps f;
+    f.x1 = x1_dev; f.c1 = c1;
+    f.in_scale = in_scale_dev; f.in_shift = in_shift_dev; f.in_act = in_act;
+    f.head_w = head_w_dev; f.head_b = head_b_dev; f.head_out = head_out_dev; f.head_ncls = head_out_dev ? head_ncls : 0;
+    if (dtype == MI355_F16) {
+        MI355_REQUIRE(impl == 0, "the fp16 path has no direct kernel");
+        return conv3d_ndhwc_f16_impl(x0_dev, n, d, h, w, c0 + c1, weight_host, bias_host, cout, stride, act, slope, y_dev, sums_dev,
+                                     stream, f);
+    }
+    return conv3d_ndhwc_f32_impl((const float *)x0_dev, n, d, h, w, c0 + c1, weight_host, bias_host, cout, stride, act, slope, impl,
+                                 (float *)y_dev, sums_dev, stream, f);
+}
+
 extern "C" int mi355_tconv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
                                        int cout, void *y_dev, void *stream) {
     MI355_TRY(require_device());
@@ -1027,6 +1080,7 @@ extern "C" int mi355_tconv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, i
     TmpBuf xb, yb;
     MI355_HIP(hipMalloc(&xb.p, (size_t)n * Vi * cin * 2));
     MI355_HIP(hipMalloc(&yb.p, (size_t)n * Vi * 8 * cout * 2));
+    MI355_HIP(hipMemsetAsync(yb.p, 0xFF, (size_t)n * Vi * 8 * cout * 2, s));  // all-NaN: an unstored voxel cannot pass for a result
     TConvWeightsH tw;
     MI355_TRY(tconv_weights_upload_f16(weight_host, cin, cout, &tw));
     int rc = ndhwc_to_b8((const _Float16 *)x_dev, n, cin, Vi, (_Float16 *)xb.p, s);

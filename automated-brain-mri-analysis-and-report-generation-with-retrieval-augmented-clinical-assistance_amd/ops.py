@@ -156,7 +156,7 @@ def conv3d_ndhwc(x, weight, bias=None, stride=1, act=0, slope=0.01, impl="mfma")
         cout = weight.shape[0]
         b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
         do, ho, wo = (d - 1) // stride + 1, (h - 1) // stride + 1, (w - 1) // stride + 1
-        y = torch.empty((n, do, ho, wo, cout), dtype=torch.float16, device=x.device)
+        y = torch.full((n, do, ho, wo, cout), float("nan"), dtype=torch.float16, device=x.device)
         _lib.check(_lib.load().mi355_conv3d_ndhwc_f16(x.data_ptr(), n, d, h, w, cin, _lib.fptr(weight), _lib.fptr(b), cout,
                                                       stride, act, slope, y.data_ptr(), _stream(x)), "mi355_conv3d_ndhwc_f16")
         return y
@@ -166,7 +166,7 @@ def conv3d_ndhwc(x, weight, bias=None, stride=1, act=0, slope=0.01, impl="mfma")
     cout = weight.shape[0]
     b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
     do, ho, wo = (d - 1) // stride + 1, (h - 1) // stride + 1, (w - 1) // stride + 1
-    y = torch.empty((n, do, ho, wo, cout), dtype=torch.float32, device=x.device)
+    y = torch.full((n, do, ho, wo, cout), float("nan"), dtype=torch.float32, device=x.device)
     _lib.check(_lib.load().mi355_conv3d_ndhwc(x.data_ptr(), n, d, h, w, cin, _lib.fptr(weight), _lib.fptr(b), cout,
                                               stride, act, slope, {"mfma": 0, "direct": 1}[impl], y.data_ptr(),
                                               _stream(x)), "mi355_conv3d_ndhwc")
@@ -185,12 +185,54 @@ def conv3d_sums_ndhwc(x, weight, bias=None, stride=1, act=0, slope=0.01):
     cout = weight.shape[0]
     b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
     do, ho, wo = (d - 1) // stride + 1, (h - 1) // stride + 1, (w - 1) // stride + 1
-    y = torch.empty((n, do, ho, wo, cout), dtype=x.dtype, device=x.device)
-    sums = torch.empty((n, cout, 2), dtype=torch.float64, device=x.device)
+    y = torch.full((n, do, ho, wo, cout), float("nan"), dtype=x.dtype, device=x.device)
+    sums = torch.full((n, cout, 2), float("nan"), dtype=torch.float64, device=x.device)
     _lib.check(_lib.load().mi355_conv3d_sums_ndhwc(x.data_ptr(), 1 if f16 else 0, n, d, h, w, cin, _lib.fptr(weight), _lib.fptr(b),
                                                    cout, stride, act, slope, y.data_ptr(), sums.data_ptr(), _stream(x)),
                "mi355_conv3d_sums_ndhwc")
     return y, sums
+
+
+#: NaN elements every conv3d_fused_ndhwc output carries behind its end (a kernel that stores past the end shows there)
+FUSED_GUARD = 64
+
+
+def conv3d_fused_ndhwc(x0, weight, bias=None, x1=None, in_scale=None, in_shift=None, in_act=0, head_w=None, head_b=None,
+                       stats=False, stride=1, act=0, slope=0.01, impl="mfma"):
+    """One conv with the fused operands of a network conv (test entry point, ``mi355_conv3d_fused_ndhwc``).
+    x0: CUDA fp32 or fp16 [N,D,H,W,C0]; x1: the same dtype [N,D,H,W,C1] or None (virtual concat, x0 first); weight: numpy
+    [Cout,C0+C1,3,3,3]; in_scale / in_shift: CUDA fp32 [N,C0] (producer norm applied to x0 while staging, LeakyReLU when
+    in_act = 1); head_w / head_b: CUDA fp32 [ncls,Cout] / [ncls] (fused 1x1x1 head: the result is fp32 logits [N,ncls,Do,Ho,Wo]
+    instead of the NDHWC feature map).  Returns (y or logits, sums [N,Cout,2] fp64 or None).  Outputs start as NaN and are
+    the front of a buffer with FUSED_GUARD more NaN elements."""
+    import torch
+    f16 = x0.dtype == torch.float16
+    dt = torch.float16 if f16 else torch.float32
+    x0 = _require_cuda(x0, dt, "x0")
+    n, d, h, w, c0 = x0.shape
+    c1 = 0
+    if x1 is not None:
+        x1 = _require_cuda(x1, dt, "x1")
+        assert tuple(x1.shape[:4]) == (n, d, h, w), (x1.shape, x0.shape)
+        c1 = x1.shape[4]
+    weight = np.ascontiguousarray(weight, dtype=np.float32)
+    cout = weight.shape[0]
+    b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+    in_scale, in_shift, head_w, head_b = (None if t is None else _require_cuda(t, torch.float32, name) for t, name in (
+        (in_scale, "in_scale"), (in_shift, "in_shift"), (head_w, "head_w"), (head_b, "head_b")))
+    do, ho, wo = (d - 1) // stride + 1, (h - 1) // stride + 1, (w - 1) // stride + 1
+    head = head_w is not None
+    ncls = head_w.shape[0] if head else 0
+    shape = (n, ncls, do, ho, wo) if head else (n, do, ho, wo, cout)
+    numel = int(np.prod(shape))
+    out = torch.full((numel + FUSED_GUARD,), float("nan"), dtype=torch.float32 if head else dt, device=x0.device)[:numel].view(shape)
+    sums = torch.full((n, cout, 2), float("nan"), dtype=torch.float64, device=x0.device) if stats else None
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    _lib.check(_lib.load().mi355_conv3d_fused_ndhwc(
+        x0.data_ptr(), ptr(x1), 1 if f16 else 0, n, d, h, w, c0, c1, _lib.fptr(weight), _lib.fptr(b), cout, stride, act, slope,
+        {"mfma": 0, "direct": 1}[impl], ptr(in_scale), ptr(in_shift), in_act, ptr(head_w), ptr(head_b), ncls,
+        out.data_ptr() if head else None, None if head else out.data_ptr(), ptr(sums), _stream(x0)), "mi355_conv3d_fused_ndhwc")
+    return out, sums
 
 
 def last_conv_kernel() -> str:
@@ -206,7 +248,7 @@ def tconv3d_ndhwc(x, weight):
         n, d, h, w, cin = x.shape
         weight = np.ascontiguousarray(weight, dtype=np.float32)
         cout = weight.shape[1]
-        y = torch.empty((n, 2 * d, 2 * h, 2 * w, cout), dtype=torch.float16, device=x.device)
+        y = torch.full((n, 2 * d, 2 * h, 2 * w, cout), float("nan"), dtype=torch.float16, device=x.device)
         _lib.check(_lib.load().mi355_tconv3d_ndhwc_f16(x.data_ptr(), n, d, h, w, cin, _lib.fptr(weight), cout, y.data_ptr(),
                                                        _stream(x)), "mi355_tconv3d_ndhwc_f16")
         return y
@@ -214,7 +256,7 @@ def tconv3d_ndhwc(x, weight):
     n, d, h, w, cin = x.shape
     weight = np.ascontiguousarray(weight, dtype=np.float32)
     cout = weight.shape[1]
-    y = torch.empty((n, 2 * d, 2 * h, 2 * w, cout), dtype=torch.float32, device=x.device)
+    y = torch.full((n, 2 * d, 2 * h, 2 * w, cout), float("nan"), dtype=torch.float32, device=x.device)
     _lib.check(_lib.load().mi355_tconv3d_ndhwc(x.data_ptr(), n, d, h, w, cin, _lib.fptr(weight), cout, y.data_ptr(),
                                                _stream(x)), "mi355_tconv3d_ndhwc")
     return y

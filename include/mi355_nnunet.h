@@ -243,6 +243,20 @@ int mi355_tconv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, int w, int c
 int mi355_conv3d_sums_ndhwc(const void *x_dev, int dtype, int n, int d, int h, int w, int cin, const float *weight_host,
                             const float *bias_host, int cout, int stride, int act, float slope, void *y_dev,
                             double *sums_dev, void *stream);
+/* One convolution with any combination of the fused operands a network conv carries (test aid for those paths of every conv
+ * kernel; dtype, stride, act, slope, impl and sums_dev as in the entry points above, impl = 0 for MI355_F16):
+ *   x1_dev != NULL: virtual concat cat(x0, x1) along channels, x0 [n,d,h,w,c0] first, x1 [n,d,h,w,c1] (plain NDHWC of dtype),
+ *     read as two tensors and never concatenated; weight_host [cout][c0 + c1][3][3][3];
+ *   in_scale_dev / in_shift_dev != NULL (device fp32 [n][c0]): x0 is a producer's raw output, normalised while staging as
+ *     x0 * in_scale + in_shift, then LeakyReLU(slope) when in_act = 1, BEFORE the zero padding;
+ *   head_out_dev != NULL: fused 1x1x1 head, head_out [n][head_ncls][Vo] fp32 = head_w [head_ncls][cout] . act(conv) + head_b
+ *     (device fp32); the feature map is not stored and y_dev must be NULL.  Otherwise y_dev receives it (plain NDHWC).
+ * Combinations go to the kernel dispatchers unchanged: whatever they cannot run is refused (MI355_ERR_*, mi355_last_error). */
+int mi355_conv3d_fused_ndhwc(const void *x0_dev, const void *x1_dev, int dtype, int n, int d, int h, int w, int c0, int c1,
+                             const float *weight_host, const float *bias_host, int cout, int stride, int act, float slope,
+                             int impl, const float *in_scale_dev, const float *in_shift_dev, int in_act,
+                             const float *head_w_dev, const float *head_b_dev, int head_ncls, float *head_out_dev,
+                             void *y_dev, double *sums_dev, void *stream);
 /* Name of the kernel instantiation the calling thread's last mi355_conv3d_ndhwc / mi355_conv3d_ndhwc_f16 call dispatched
  * (the names rocprofv3 and mi355_profile_read show).  Test aid: a parity case written for one kernel can assert that it
  * ran on that kernel.  No reference counterpart (torch.nn.Conv3d, generic_UNet.py:56, has one implementation). */
