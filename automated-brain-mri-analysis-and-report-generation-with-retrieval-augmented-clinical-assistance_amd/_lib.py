@@ -27,7 +27,7 @@ EXPORTS = [
     "mi355_profile_read", "mi355_conv3d_ndhwc_f16", "mi355_tconv3d_ndhwc_f16",
     "mi355_label_remap", "mi355_label_confusion", "mi355_cosine_topk", "mi355_crop_mask", "mi355_label_stats",
     "mi355_last_conv_kernel",
-    "mi355_conv3d_sums_ndhwc", "mi355_conv3d_fused_ndhwc",
+    "mi355_conv3d_sums_ndhwc", "mi355_conv3d_fused_ndhwc", "mi355_conv3d_plan",
     "mi355_sw_partial_folds", "mi355_sw_finish_folds",
     "mi355_resize_axis", "mi355_clip_to_range_of", "mi355_threshold_ge", "mi355_mask_to_float",
 ]
@@ -64,6 +64,11 @@ class SwOpts(C.Structure):
 class ProfEntry(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
+
+
+class ConvPlan(C.Structure):
+    _fields_ = [("rc", C.c_int32), ("kernel", C.c_char * 96), ("grid", C.c_int32 * 3), ("lds_bytes", C.c_int64),
+                ("splitk", C.c_int32), ("tile", C.c_int32 * 3), ("fuses_in_norm", C.c_int32)]
 
 
 class Mi355Error(RuntimeError):
@@ -131,6 +136,7 @@ def load():
     lib.mi355_conv3d_fused_ndhwc.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p,
                                              c_float_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, C.c_int, vp, vp,
                                              C.c_int, vp, vp, vp, vp]
+    lib.mi355_conv3d_plan.argtypes = [C.c_int] * 13 + [C.POINTER(ConvPlan)]
     lib.mi355_label_remap.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_uint8), vp]
     lib.mi355_label_confusion.argtypes = [vp, vp, C.c_int64, C.c_int, C.POINTER(C.c_uint64), vp]
     lib.mi355_cosine_topk.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_float_p, vp]

@@ -10,7 +10,7 @@
 //     holds channels g*8 + 4*(l>>5) + j of voxel l&31; MFMA j contracts the channel pair {g*8+j, g*8+4+j});
 //   * weights are pre-permuted on the host into fragment order (1 KiB per (tap, 8-channel group, 32 couts));
 //   * f32-input MFMA is an exact k-ordered fmaf chain (no TF32 on gfx950).
-// Kernels in this file (dispatch: conv3d_mfma_f32 at the bottom; DESIGN.md section 5 has the measurements):
+// Kernels in this file (selection: plan_conv_f32, launch: conv3d_mfma_f32, both at the bottom; DESIGN.md section 5 has the measurements):
 //   conv3_f32_wino2_kernel      stride 1, large launches: Winograd F(2x2,3x3) over (z,y), LDS-DMA bricks   [default]
 //   conv3_f32_s2dma_kernel      stride 2, large launches: LDS-DMA bricks, weight planes through an LDS ring
 //   conv3_f32_mfma_pipe_kernel  stride 1, mid-size launches: persistent, register-staged double-buffered brick
@@ -19,7 +19,7 @@
 //   conv3_direct_kernel         reference-order direct convolution (tests, odd channel counts)
 // Shared epilogue: + bias, LeakyReLU, predicated wide NDHWC stores; optionally per-(n, channel) sum / sum of squares
 // for Instance/GroupNorm (wave reduction -> LDS -> one fp64 atomic per channel and workgroup) or the fused 1x1x1 head.
-#include "kernels.h"
+#include "conv_plan.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -653,14 +653,7 @@ __global__ void conv3_direct_kernel(const float *in0, const float *in1, int C0, 
 // of the f32 MFMA peak and moves ~40 % fewer bytes through the fabric, but needs >= 512 workgroups of that size;
 // launches with fewer tiles (deep levels, small batches) and the 8-channel stem go to the pipelined kernel, which
 // keeps 2 workgroups per CU busy with 256-voxel tiles.  Auto mode therefore keeps two weight packs per layer.
-static int conv_impl() {
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("MI355_CONV_IMPL");
-        v = !e ? 2 : (e[0] == '0' ? 0 : (e[0] == '1' ? 1 : 2));
-    }
-    return v;
-}
+// (conv_impl() itself is in conv_plan.h: the fp16 dispatch reads the same switch.)
 
 // ---------------------------------------------------------------------------------------------------------------
 // Winograd F(2x2, 3x3) over (z, y).  The f32 convs are MFMA-bound (exact fp32 multiplies, no TF32), so the lever left
@@ -1309,11 +1302,7 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_s2dma_kernel(Wino2Args pa) {
 }
 
 // MI355_WINOGRAD: 0 = direct kernels only; anything else (default) = F(2x2,3x3) over (z, y)
-static bool winograd_enabled() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("MI355_WINOGRAD"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v != 0;
-}
+static bool winograd_enabled() { return env_switch("MI355_WINOGRAD"); }
 
 // 2-D Winograd pack (floats): [cout block of 32][chunk of 16][step = q*3+dx][f/2][lane][f&1][j 0..1], f = fz*4+fy, with
 //   cout = block*32 + (lane&31), cin = chunk*16 + q*4 + (lane>>5)*2 + j, U = G w G^T over the (dz, dy) taps.
@@ -1362,40 +1351,54 @@ static void pack_conv_weights_f32(const float *w, int cin, int cin_pad, int cout
                             }
 }
 
-int conv_weights_upload(const float *w_host, const float *bias_host, int cin, int cin_pad, int cout,
-                        int stride, bool keep_plain, ConvWeights *out) {
+int conv_pack_layout(int cin, int cin_pad, int cout, int stride, ConvPackLayout *out) {
     MI355_REQUIRE(stride == 1 || stride == 2, "conv stride %d unsupported", stride);
     MI355_REQUIRE(cin_pad >= cin && cin_pad % 4 == 0, "bad cin_pad %d for cin %d", cin_pad, cin);
+    ConvPackLayout &l = *out;
+    l = ConvPackLayout();
+    l.mfma = (cout % 32 == 0) && (cin_pad % 8 == 0);
+    if (!l.mfma) return MI355_OK;
+    // stride 2 bricks are ~8x the output tile: keep them to 8 channels per pass
+    l.pipe = (stride == 1) && conv_impl() != 0;
+    l.cc = (!l.pipe && stride == 1 && cin_pad % 16 == 0) ? 16 : 8;
+    l.nf = (cout % 64 == 0) ? 2 : 1;
+    l.c16 = stride == 1 && conv_impl() == 2 && cin_pad % 16 == 0;
+    l.wino2 = l.c16 && winograd_enabled();
+    l.wino3 = l.wino2 && conv3d_wino3_enabled();  // F(2x2x2, 3x3x3): the launches that are whole 4 x 8 x 8 tiles (conv3d_wino3.hip)
+    return MI355_OK;
+}
+
+int conv_weights_upload(const float *w_host, const float *bias_host, int cin, int cin_pad, int cout,
+                        int stride, bool keep_plain, ConvWeights *out) {
+    ConvPackLayout l;
+    MI355_TRY(conv_pack_layout(cin, cin_pad, cout, stride, &l));
     ConvWeights cw;
     cw.cin = cin; cw.cin_pad = cin_pad; cw.cout = cout; cw.stride = stride;
-    const bool mfma_ok = (cout % 32 == 0) && (cin_pad % 8 == 0);
-    if (mfma_ok) {
-        // stride 2 bricks are ~8x the output tile: keep them to 8 channels per pass
-        cw.pipe = (stride == 1) && conv_impl() != 0;
-        cw.cc = (!cw.pipe && stride == 1 && cin_pad % 16 == 0) ? 16 : 8;
-        cw.nf = (cout % 64 == 0) ? 2 : 1;
+    cw.cc = l.cc; cw.nf = l.nf; cw.pipe = l.pipe;
+    auto upload_pack = [](const std::vector<float> &packed, float **dev) -> int {
+        MI355_HIP(hipMalloc(dev, packed.size() * sizeof(float)));
+        MI355_HIP(hipMemcpy(*dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+        return MI355_OK;
+    };
+    if (l.mfma) {
         std::vector<float> packed;
         pack_conv_weights_f32(w_host, cin, cin_pad, cout, cw.cc, cw.nf, packed);
         cw.wp_bytes = packed.size() * sizeof(float);
-        MI355_HIP(hipMalloc(&cw.wp_dev, cw.wp_bytes));
-        MI355_HIP(hipMemcpy(cw.wp_dev, packed.data(), cw.wp_bytes, hipMemcpyHostToDevice));
-        if (stride == 1 && conv_impl() == 2 && cin_pad % 16 == 0) {
+        MI355_TRY(upload_pack(packed, &cw.wp_dev));
+        if (l.c16) {
             pack_conv_weights_f32(w_host, cin, cin_pad, cout, 16, cw.nf, packed);
-            MI355_HIP(hipMalloc(&cw.wp16_dev, packed.size() * sizeof(float)));
-            MI355_HIP(hipMemcpy(cw.wp16_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-            if (winograd_enabled()) {
-                pack_conv_weights_wino2(w_host, cin, cin_pad, cout, packed);
-                MI355_HIP(hipMalloc(&cw.wpw_dev, packed.size() * sizeof(float)));
-                MI355_HIP(hipMemcpy(cw.wpw_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-                if (conv3d_wino3_enabled()) {  // F(2x2x2, 3x3x3): the launches that are whole 4 x 8 x 8 tiles (conv3d_wino3.hip)
-                    pack_conv_weights_wino3(w_host, cin, cin_pad, cout, packed);
-                    MI355_HIP(hipMalloc(&cw.wp3_dev, packed.size() * sizeof(float)));
-                    MI355_HIP(hipMemcpy(cw.wp3_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-                }
-            }
+            MI355_TRY(upload_pack(packed, &cw.wp16_dev));
+        }
+        if (l.wino2) {
+            pack_conv_weights_wino2(w_host, cin, cin_pad, cout, packed);
+            MI355_TRY(upload_pack(packed, &cw.wpw_dev));
+        }
+        if (l.wino3) {
+            pack_conv_weights_wino3(w_host, cin, cin_pad, cout, packed);
+            MI355_TRY(upload_pack(packed, &cw.wp3_dev));
         }
     }
-    if (keep_plain || !mfma_ok) {
+    if (keep_plain || !l.mfma) {
         // the direct kernel indexes channels of the (possibly zero-padded) input tensors
         std::vector<float> plain((size_t)cout * cin_pad * 27, 0.f);
         for (int co = 0; co < cout; ++co)
@@ -1424,206 +1427,96 @@ void conv_weights_free(ConvWeights *w) {
     *w = ConvWeights();
 }
 
-// Output tile (power-of-two dims, 128*MF voxels): x as long as the volume allows (up to 32:
-// x-consecutive lanes are the conflict-free LDS pattern and give the longest contiguous global
-// rows), then the (y, z) split with the smallest input brick.
-static void choose_tile(int Do, int Ho, int Wo, int stride, int voxels, int *lz, int *ly, int *lx) {
-    auto p2cap = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    const int cz = p2cap(Do), cy = p2cap(Ho), cx = p2cap(Wo);
-    const int L = ilog2_exact(voxels);
-    int x = cx < 5 ? cx : 5;
-    if (x > L) x = L;
-    long best = -1;
-    int bz = L - x, by = 0;
-    for (int y = 0; x + y <= L; ++y) {
-        const int z = L - x - y;
-        const int oy = y > cy ? y - cy : 0, oz = z > cz ? z - cz : 0;  // lanes wasted past the volume
-        const long brick = (long)(((1 << y) - 1) * stride + 3) * (((1 << z) - 1) * stride + 3);
-        const long cost = ((long)(oy + oz) << 32) + brick;
-        if (best < 0 || cost < best) {
-            best = cost; bz = z; by = y;
-        }
-    }
-    *lz = bz; *ly = by; *lx = x;
-}
+// Every instantiation conv3d_mfma_f32 launches from this file (the F(2x2x2,3x3x3) kernel's rows are in conv3d_wino3.hip).
+static KernelRow f32_rows[] = {
+    MI355_KERNEL_ROW(conv3_f32_wino2_kernel<0>),
+    MI355_KERNEL_ROW(conv3_f32_wino2_kernel<1>),
+    MI355_KERNEL_ROW(conv3_f32_wino2_kernel<2>),
+    MI355_KERNEL_ROW(conv3_f32_s2dma_kernel<5>),
+    MI355_KERNEL_ROW(conv3_f32_s2dma_kernel<4>),
+    MI355_KERNEL_ROW(conv3_f32_mfma_pipe_kernel<4, 1>),
+    MI355_KERNEL_ROW(conv3_f32_mfma_pipe_kernel<2, 2>),
+    MI355_KERNEL_ROW(conv3_f32_mfma_pipe_kernel<2, 1>),
+    MI355_KERNEL_ROW(conv3_f32_mfma_pipe_kernel<1, 1>),
+    MI355_KERNEL_ROW(conv3_f32_mfma_kernel<1, 16, 4, 2>),
+    MI355_KERNEL_ROW(conv3_f32_mfma_kernel<1, 16, 4, 1>),
+    MI355_KERNEL_ROW(conv3_f32_mfma_kernel<1, 8, 4, 1>),
+    MI355_KERNEL_ROW(conv3_f32_mfma_kernel<1, 16, 2, 1>),
+    MI355_KERNEL_ROW(conv3_f32_mfma_kernel<1, 16, 2, 2>),
+    MI355_KERNEL_ROW(conv3_f32_mfma_kernel<1, 8, 2, 1>),
+    MI355_KERNEL_ROW(conv3_f32_mfma_kernel<1, 8, 2, 2>),
+    MI355_KERNEL_ROW(conv3_f32_mfma_kernel<2, 8, 1, 1>),
+    MI355_KERNEL_ROW(conv3_f32_mfma_kernel<2, 8, 1, 2>),
+};
 
-template <int STRIDE, int CC, int MF, int NF>
-static int launch_conv(const ConvArgs &a, dim3 grid, size_t lds_bytes, hipStream_t s) {
-    auto kern = conv3_f32_mfma_kernel<STRIDE, CC, MF, NF>;
-    static size_t attr_bytes = 48 * 1024;  // raise the dynamic-LDS limit on demand (one process per GPU)
-    if (lds_bytes > attr_bytes) {
-        MI355_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        attr_bytes = lds_bytes;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, s, a);
-    MI355_HIP(hipGetLastError());
-    return MI355_OK;
-}
-
-template <int MF, int NF>
-static int launch_pipe(const PipeArgs &a, dim3 grid, size_t lds_bytes, hipStream_t s) {
-    auto kern = conv3_f32_mfma_pipe_kernel<MF, NF>;
-    static size_t attr_bytes = 48 * 1024;
-    if (lds_bytes > attr_bytes) {
-        MI355_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        attr_bytes = lds_bytes;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, s, a);
-    MI355_HIP(hipGetLastError());
-    return MI355_OK;
-}
-
-static void fill_geometry(ConvArgs &a, int st, int voxels) {
-    choose_tile(a.Do, a.Ho, a.Wo, st, voxels, &a.lz, &a.ly, &a.lx);
-    const int TX = 1 << a.lx, TY = 1 << a.ly, TZ = 1 << a.lz;
-    a.tiles_x = ceil_div(a.Wo, TX); a.tiles_y = ceil_div(a.Ho, TY); a.tiles_z = ceil_div(a.Do, TZ);
-    a.IX = (TX - 1) * st + 3; a.IY = (TY - 1) * st + 3; a.IZ = (TZ - 1) * st + 3;
-    a.div_tiles_per_n = make_fastdiv(a.tiles_x * a.tiles_y * a.tiles_z);
-    a.div_tiles_x = make_fastdiv(a.tiles_x);
-    a.div_tiles_y = make_fastdiv(a.tiles_y);
-    a.div_IX = make_fastdiv(a.IX);
-    a.div_IY = make_fastdiv(a.IY);
-}
-
-int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, const char **kernel_name) {
-    const char *kn_dummy;
-    if (!kernel_name) kernel_name = &kn_dummy;
+// Which kernel an fp32 call goes to, with which tile, grid, LDS size and weight pack.  No side effects: the error text is set
+// only when the call is refused.
+int plan_conv_f32(const ConvWeights &w, const ConvCall &c, ConvPlan *p) {
+    *p = ConvPlan();
     MI355_REQUIRE(w.wp_dev != nullptr, "conv %d->%d has no MFMA weight pack", w.cin, w.cout);
     MI355_REQUIRE(c.C0 + c.C1 == w.cin_pad, "conv input channels %d+%d != %d", c.C0, c.C1, w.cin_pad);
     MI355_REQUIRE(c.C0 % w.cc == 0 && c.C1 % w.cc == 0, "concat split %d/%d not a multiple of %d", c.C0, c.C1, w.cc);
     MI355_REQUIRE(c.C1 == 0 || c.in1 != nullptr, "second conv input missing");
-    ConvArgs a;
-    a.in0 = c.in0; a.in1 = c.in1; a.C0 = c.C0; a.C1 = c.C1;
-    a.wp = w.wp_dev; a.bias = w.bias_dev; a.out = c.out; a.stats = c.stats;
-    a.head_w = c.head_w; a.head_b = c.head_b; a.head_out = c.head_out; a.head_ncls = c.head_ncls;
     MI355_REQUIRE(!c.head_out || (w.cout == 32 * w.nf && !c.stats && c.head_ncls >= 1 && c.head_ncls <= 4 && c.head_w && c.head_b),
                   "fused head needs Cout (%d) == one workgroup's couts, no statistics, 1..4 classes", w.cout);
-    a.N = c.N; a.Di = c.Di; a.Hi = c.Hi; a.Wi = c.Wi;
     const int st = w.stride;
-    a.Do = (c.Di - 1) / st + 1; a.Ho = (c.Hi - 1) / st + 1; a.Wo = (c.Wi - 1) / st + 1;  // k=3, p=1
-    a.Cout = w.cout;
-    a.nchunks = w.cin_pad / w.cc;
-    a.act = c.act; a.slope = c.slope;
-    a.ksplit = 1; a.partial = nullptr; a.zero_bias = nullptr; a.out_elems = 0;
-    if (w.wp3_dev) {
-        bool taken = false;
-        MI355_TRY(conv3d_wino3_f32(w, c, s, kernel_name, &taken));
-        if (taken) return MI355_OK;
-    }
+    const int Do = (c.Di - 1) / st + 1, Ho = (c.Hi - 1) / st + 1, Wo = (c.Wi - 1) / st + 1;  // k=3, p=1
+    const int nchunks = w.cin_pad / w.cc;
+    const int gy_nf = w.cout / (32 * w.nf);  // cout blocks when a workgroup takes all w.nf fragments
+    p->nf = w.nf;
+    if (plan_wino3(w, c, p)) return MI355_OK;
     MI355_REQUIRE(!c.in_scale, "conv %d->%d: a pending input normalisation reached a kernel that cannot apply it", w.cin, w.cout);
     // the 16-channel-chunk kernels below pick in0 or in1 once per chunk: a concat split that is a multiple of 8 only (w.cc of
     // the pipelined build) would make a chunk straddle the two halves; such calls go to the 8-channel kernels
     const bool split16 = c.C0 % 16 == 0 && c.C1 % 16 == 0;
+    const bool in_fits_32bit = (long)c.Di * c.Hi * c.Wi * (c.C0 > c.C1 ? c.C0 : c.C1) < (1l << 31);
     if (w.wpw_dev && split16) {
         // auto mode, large launches: Winograd F(2x2,3x3) on fixed 4x4x32 tiles, 32 couts per workgroup
-        ConvArgs b = a;
-        b.lz = 2; b.ly = 2; b.lx = 5;
-        b.tiles_x = ceil_div(b.Wo, 32); b.tiles_y = ceil_div(b.Ho, 4); b.tiles_z = ceil_div(b.Do, 4);
-        b.IX = 34; b.IY = 6; b.IZ = 6;
-        b.div_tiles_per_n = make_fastdiv(b.tiles_x * b.tiles_y * b.tiles_z);
-        b.div_tiles_x = make_fastdiv(b.tiles_x);
-        b.div_tiles_y = make_fastdiv(b.tiles_y);
-        b.div_IX = make_fastdiv(b.IX);
-        b.div_IY = make_fastdiv(b.IY);
-        const long tiles = (long)b.tiles_x * b.tiles_y * b.tiles_z * c.N;
+        const TileGeom g = fixed_tile(Do, Ho, Wo, 2, 2, 5, W2_IZ, W2_IY, W2_IX);
+        const long tiles = g.tiles_per_n() * c.N;
         // the fixed tile wastes lanes on thin volumes: only when every tile dim is at least half used
-        if (tiles * (w.cout / 32) >= 512 && tiles < (1l << 30) && b.Wo >= 16 && b.Ho >= 4 && b.Do >= 4 &&
-            (long)c.Di * c.Hi * c.Wi * (c.C0 > c.C1 ? c.C0 : c.C1) < (1l << 31) &&
+        if (tiles * (w.cout / 32) >= 512 && tiles < (1l << 30) && Wo >= 16 && Ho >= 4 && Do >= 4 && in_fits_32bit &&
             (!c.head_out || w.cout == 32)) {
-            b.wp = w.wpw_dev;
-            b.nchunks = w.cin_pad / 16;
-            static bool attr_set = false;
-            if (!attr_set) {
-                MI355_HIP(hipFuncSetAttribute((const void *)conv3_f32_wino2_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W2_LDS_BYTES));
-                MI355_HIP(hipFuncSetAttribute((const void *)conv3_f32_wino2_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W2_LDS_BYTES));
-                MI355_HIP(hipFuncSetAttribute((const void *)conv3_f32_wino2_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W2_LDS_BYTES));
-                attr_set = true;
-            }
-            float *zeros = nullptr;  // the zero page out-of-volume DMA pieces read
-            MI355_TRY(device_scratch(SCR_ZEROS, s, 256, (void **)&zeros, true));
-            const int epi = c.head_out ? 1 : (c.stats ? 2 : 0);
-            static const char *const w2_names[3] = {"conv3_f32_wino2_kernel<0>", "conv3_f32_wino2_kernel<1>", "conv3_f32_wino2_kernel<2>"};
-            *kernel_name = w2_names[epi];
-            Wino2Args wa;
-            wa.c = b; wa.total_tiles = (int)tiles; wa.zeros = zeros;
-            wa.order = make_tile_order(b.tiles_x, b.tiles_y, b.tiles_z);
-            const int gy = w.cout / 32;
-            int gx = 256 / gy;                      // one persistent workgroup per CU
-            gx = gx < 8 ? 8 : (gx / 8) * 8;         // multiple of 8: blockIdx.x & 7 labels the XCD group
-            const int need = (int)((tiles + 7) / 8) * 8;
-            if (gx > need) gx = need;
-            if (epi == 0) hipLaunchKernelGGL(conv3_f32_wino2_kernel<0>, dim3(gx, gy), dim3(256), W2_LDS_BYTES, s, wa);
-            else if (epi == 1) hipLaunchKernelGGL(conv3_f32_wino2_kernel<1>, dim3(gx, gy), dim3(256), W2_LDS_BYTES, s, wa);
-            else hipLaunchKernelGGL(conv3_f32_wino2_kernel<2>, dim3(gx, gy), dim3(256), W2_LDS_BYTES, s, wa);
-            MI355_HIP(hipGetLastError());
+            const int gy = w.cout / 32;  // one persistent workgroup per CU
+            plan_set(p, find_row(f32_rows, "conv3_f32_wino2_kernel<%d>", c.head_out ? 1 : (c.stats ? 2 : 0)), FAM_WINO2, g, tiles,
+                     persistent_grid_x(256, gy, tiles), gy, W2_LDS_BYTES);
+            p->pack = PACK_WINO2; p->nf = 1;
             return MI355_OK;
         }
     }
     if (w.wp16_dev && split16) {
         // auto mode: 512-voxel tiles + 16-channel chunks when that fills the chip
-        ConvArgs b = a;
-        fill_geometry(b, 1, 512);
-        const long tiles = (long)b.tiles_x * b.tiles_y * b.tiles_z * c.N;
-        const size_t brick_bytes = (size_t)b.IX * b.IY * b.IZ * 16 * sizeof(float);
-        if (tiles * (w.cout / (32 * w.nf)) >= 512 && brick_bytes <= 80 * 1024 && tiles < (1l << 30)) {
-            b.wp = w.wp16_dev;
-            b.nchunks = w.cin_pad / 16;
-            dim3 grid((unsigned)tiles, w.cout / (32 * w.nf));
-            if (w.nf == 2) { *kernel_name = "conv3_f32_mfma_kernel<1, 16, 4, 2>"; return launch_conv<1, 16, 4, 2>(b, grid, brick_bytes, s); }
-            *kernel_name = "conv3_f32_mfma_kernel<1, 16, 4, 1>";
-            return launch_conv<1, 16, 4, 1>(b, grid, brick_bytes, s);
+        const TileGeom g = chosen_tile(Do, Ho, Wo, 1, 512);
+        const long tiles = g.tiles_per_n() * c.N;
+        const size_t brick_bytes = (size_t)g.brickvox() * 16 * sizeof(float);
+        if (tiles * gy_nf >= 512 && brick_bytes <= 80 * 1024 && tiles < (1l << 30)) {
+            plan_set(p, find_row(f32_rows, "conv3_f32_mfma_kernel<1, 16, 4, %d>", w.nf), FAM_SIMPLE, g, tiles, (unsigned)tiles, gy_nf, brick_bytes);
+            p->pack = PACK_C16;
+            return MI355_OK;
         }
     }
-    {
-        // Small launches (deep levels: few voxels, hundreds of channels) leave most CUs idle and run one long serial chain
-        // of chunks per workgroup: split the channel chunks over blockIdx.z, write raw partial sums, add them in slice
-        // order in a finishing pass (deterministic).  Only without run-time statistics / fused head.
-        static int splitk = -1;
-        if (splitk < 0) { const char *e = getenv("MI355_SPLITK"); splitk = (e && e[0] == '0') ? 0 : 1; }
-        if (splitk && !c.stats && !c.head_out && w.cc == 8 && a.nchunks >= 8) {
-            ConvArgs b = a;
-            const int MFs = st == 1 ? 2 : 1;
-            fill_geometry(b, st, 128 * MFs);
-            const long tiles = (long)b.tiles_x * b.tiles_y * b.tiles_z * c.N;
-            const int gy = w.cout / (32 * w.nf);
-            const long units = tiles * gy;
-            const size_t brick_bytes = (size_t)b.IX * b.IY * b.IZ * 8 * sizeof(float);
-            // as many slices as still fit the chip in ONE round of workgroups (256 CUs x 2): rounding up (round 2) gave the 8^3 level
-            // 80 x 7 = 560 workgroups - 48 of them ran behind the other 512 and doubled the launch's critical path
-            int S = (int)(512 / units);
-            if (S > a.nchunks / 4) S = a.nchunks / 4;
-            if (S > 8) S = 8;
-            if (units < 256 && S >= 2 && brick_bytes <= 80 * 1024 && w.cout <= 4096) {
-                float *partial = nullptr, *zero_bias = nullptr;
-                const long out_elems = (long)c.N * a.Do * a.Ho * a.Wo * w.cout;
-                const size_t need = (size_t)S * out_elems * sizeof(float);
-                MI355_TRY(device_scratch(SCR_ZERO_BIAS, s, 4096 * sizeof(float), (void **)&zero_bias, true));
-                MI355_TRY(device_scratch(SCR_SPLITK_F32, s, need, (void **)&partial));
-                b.ksplit = S; b.partial = partial; b.zero_bias = zero_bias; b.out_elems = out_elems;
-                const size_t lds_bytes = brick_bytes < 4096 ? 4096 : brick_bytes;
-                dim3 grid((unsigned)tiles, gy, S);
-                int rc;
-                if (st == 1 && w.nf == 1) { *kernel_name = "conv3_f32_mfma_kernel<1, 8, 2, 1> split-K"; rc = launch_conv<1, 8, 2, 1>(b, grid, lds_bytes, s); }
-                else if (st == 1) { *kernel_name = "conv3_f32_mfma_kernel<1, 8, 2, 2> split-K"; rc = launch_conv<1, 8, 2, 2>(b, grid, lds_bytes, s); }
-                else if (w.nf == 1) { *kernel_name = "conv3_f32_mfma_kernel<2, 8, 1, 1> split-K"; rc = launch_conv<2, 8, 1, 1>(b, grid, lds_bytes, s); }
-                else { *kernel_name = "conv3_f32_mfma_kernel<2, 8, 1, 2> split-K"; rc = launch_conv<2, 8, 1, 2>(b, grid, lds_bytes, s); }
-                if (rc != MI355_OK) return rc;
-                const long total4 = out_elems / 4;
-                hipLaunchKernelGGL(splitk_finish_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, partial, S, total4, w.cout / 4,
-                                   w.bias_dev, c.act, c.slope, c.out);
-                MI355_HIP(hipGetLastError());
-                return MI355_OK;
-            }
+    // split-K for small launches (splitk_slices, conv_plan.h).  Only without run-time statistics / fused head.
+    if (env_switch("MI355_SPLITK") && !c.stats && !c.head_out && w.cc == 8 && nchunks >= 8) {
+        const TileGeom g = chosen_tile(Do, Ho, Wo, st, st == 1 ? 256 : 128);
+        const long tiles = g.tiles_per_n() * c.N;
+        const size_t brick_bytes = (size_t)g.brickvox() * 8 * sizeof(float);
+        const int S = splitk_slices(tiles * gy_nf, nchunks);
+        if (S && brick_bytes <= 80 * 1024 && w.cout <= 4096) {
+            plan_set(p, find_row(f32_rows, "conv3_f32_mfma_kernel<%d, 8, %d, %d>", st, st == 1 ? 2 : 1, w.nf), FAM_SIMPLE, g, tiles, (unsigned)tiles, gy_nf,
+                     brick_bytes < 4096 ? 4096 : brick_bytes);
+            p->name = p->row->name_splitk; p->gz = S; p->ksplit = S;
+            return MI355_OK;
         }
     }
     if (w.pipe) {
         // tile size / couts per workgroup: as large as still gives the chip >= ~2 workgroups per CU; launches with
         // few voxels and many channels (deep levels) fall back to 256- then 128-voxel tiles and 32-cout blocks
         int MF = 4, NF = 1;
+        TileGeom g;
         long tiles = 0;
-        auto geom = [&](int mf) { fill_geometry(a, 1, 128 * mf); tiles = (long)a.tiles_x * a.tiles_y * a.tiles_z * c.N; };
+        auto geom = [&](int mf) { g = chosen_tile(Do, Ho, Wo, 1, 128 * mf); tiles = g.tiles_per_n() * c.N; };
         geom(4);
-        if (w.nf == 2 || tiles * (w.cout / 32) < 512 || a.IX * a.IY * a.IZ > 11 * 128) {
+        if (w.nf == 2 || tiles * (w.cout / 32) < 512 || g.brickvox() > 11 * 128) {
             MF = 2; NF = w.nf;
             geom(2);
             // the fused head sums all of a voxel's couts in one workgroup (conv_epilogue): with 64 couts it keeps NF = 2 (and so
@@ -1634,101 +1527,108 @@ int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, cons
         }
         const int gy = w.cout / (32 * NF);
         MI355_REQUIRE(tiles < (1l << 30), "conv grid too large");
-        const int brickvox = a.IX * a.IY * a.IZ;
-        MI355_REQUIRE(brickvox <= (MF == 4 ? 11 : 8) * 128, "conv brick of %d voxels exceeds the staging slots", brickvox);
-        PipeArgs pa;
-        pa.c = a;
-        pa.total_tiles = (int)tiles;
-        pa.plane = brickvox * 4;
-        pa.buf_floats = 2 * pa.plane;
-        pa.w_split = w.nf / NF;
-        const size_t lds_bytes = (size_t)(2 * pa.buf_floats + 4 * NF * 32 * 2) * sizeof(float);
+        MI355_REQUIRE(g.brickvox() <= (MF == 4 ? 11 : 8) * 128, "conv brick of %d voxels exceeds the staging slots", g.brickvox());
+        // two buffers of two planes of brickvox * 4 floats (PipeArgs) + the statistics scratch
+        const size_t lds_bytes = (size_t)(2 * 2 * g.brickvox() * 4 + 4 * NF * 32 * 2) * sizeof(float);
         MI355_REQUIRE(lds_bytes <= 160 * 1024, "conv brick needs %zu B of LDS", lds_bytes);
-        int gx = 512 / gy;                      // ~2 resident workgroups per CU in total
-        gx = gx < 8 ? 8 : (gx / 8) * 8;         // multiple of 8: blockIdx.x & 7 labels the XCD group
-        const int need = (int)((tiles + 7) / 8) * 8;
-        if (gx > need) gx = need;
-        dim3 grid(gx, gy);
-        if (MF == 4) { *kernel_name = "conv3_f32_mfma_pipe_kernel<4, 1>"; return launch_pipe<4, 1>(pa, grid, lds_bytes, s); }
-        if (MF == 2 && NF == 2) { *kernel_name = "conv3_f32_mfma_pipe_kernel<2, 2>"; return launch_pipe<2, 2>(pa, grid, lds_bytes, s); }
-        if (MF == 2) { *kernel_name = "conv3_f32_mfma_pipe_kernel<2, 1>"; return launch_pipe<2, 1>(pa, grid, lds_bytes, s); }
-        *kernel_name = "conv3_f32_mfma_pipe_kernel<1, 1>";
-        return launch_pipe<1, 1>(pa, grid, lds_bytes, s);
+        // ~2 resident workgroups per CU in total
+        plan_set(p, find_row(f32_rows, "conv3_f32_mfma_pipe_kernel<%d, %d>", MF, NF), FAM_PIPE, g, tiles, persistent_grid_x(512, gy, tiles), gy, lds_bytes);
+        p->nf = NF;
+        return MI355_OK;
     }
     if (st == 2 && w.cc == 8 && w.nf == 2 && !c.head_out) {
-        static int s2dma = -1;
-        if (s2dma < 0) { const char *e = getenv("MI355_S2_DMA"); s2dma = (e && e[0] == '0') ? 0 : 1; }
-        ConvArgs b = a;
-        const int txl = b.Wo >= 24 ? 5 : 4;  // 2 x 2 x 32 tiles, or 2 x 4 x 16 on narrow volumes
+        const int txl = Wo >= 24 ? 5 : 4;  // 2 x 2 x 32 tiles, or 2 x 4 x 16 on narrow volumes
         const int TX = 1 << txl, TY = 64 >> txl;
-        b.lz = 1; b.ly = 6 - txl; b.lx = txl;
-        b.tiles_x = ceil_div(b.Wo, TX); b.tiles_y = ceil_div(b.Ho, TY); b.tiles_z = ceil_div(b.Do, 2);
-        b.IX = 2 * TX + 1; b.IY = 2 * TY + 1; b.IZ = 5;
-        b.div_tiles_per_n = make_fastdiv(b.tiles_x * b.tiles_y * b.tiles_z);
-        b.div_tiles_x = make_fastdiv(b.tiles_x);
-        b.div_tiles_y = make_fastdiv(b.tiles_y);
-        b.div_IX = make_fastdiv(b.IX);
-        b.div_IY = make_fastdiv(b.IY);
-        const long tiles = (long)b.tiles_x * b.tiles_y * b.tiles_z * c.N;
+        const TileGeom g = fixed_tile(Do, Ho, Wo, 1, 6 - txl, txl, 5, 2 * TY + 1, 2 * TX + 1);
+        const long tiles = g.tiles_per_n() * c.N;
         const int gy = w.cout / 64;
         // persistent workgroups need a few tiles each, and the fixed tiles waste lanes on very small volumes
-        if (s2dma && tiles * gy >= 768 && tiles < (1l << 30) && b.Wo >= 12 && b.Ho >= 3 &&
-            (long)c.Di * c.Hi * c.Wi * (c.C0 > c.C1 ? c.C0 : c.C1) < (1l << 31)) {
-            static bool attr_set = false;
-            if (!attr_set) {
-                MI355_HIP(hipFuncSetAttribute((const void *)conv3_f32_s2dma_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2Geom<5>::LDS_BYTES));
-                MI355_HIP(hipFuncSetAttribute((const void *)conv3_f32_s2dma_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2Geom<4>::LDS_BYTES));
-                attr_set = true;
-            }
-            float *zeros = nullptr;
-            MI355_TRY(device_scratch(SCR_ZEROS, s, 256, (void **)&zeros, true));
-            Wino2Args wa;
-            wa.c = b; wa.total_tiles = (int)tiles; wa.zeros = zeros;
-            wa.order = make_tile_order(b.tiles_x, b.tiles_y, b.tiles_z);
-            int gx = 256 / gy;
-            gx = gx < 8 ? 8 : (gx / 8) * 8;
-            const int need = (int)((tiles + 7) / 8) * 8;
-            if (gx > need) gx = need;
-            *kernel_name = txl == 5 ? "conv3_f32_s2dma_kernel<5>" : "conv3_f32_s2dma_kernel<4>";
-            if (txl == 5) hipLaunchKernelGGL(conv3_f32_s2dma_kernel<5>, dim3(gx, gy), dim3(256), S2Geom<5>::LDS_BYTES, s, wa);
-            else hipLaunchKernelGGL(conv3_f32_s2dma_kernel<4>, dim3(gx, gy), dim3(256), S2Geom<4>::LDS_BYTES, s, wa);
-            MI355_HIP(hipGetLastError());
+        if (env_switch("MI355_S2_DMA") && tiles * gy >= 768 && tiles < (1l << 30) && Wo >= 12 && Ho >= 3 && in_fits_32bit) {
+            plan_set(p, find_row(f32_rows, "conv3_f32_s2dma_kernel<%d>", txl), FAM_S2DMA, g, tiles, persistent_grid_x(256, gy, tiles), gy,
+                     txl == 5 ? S2Geom<5>::LDS_BYTES : S2Geom<4>::LDS_BYTES);
             return MI355_OK;
         }
     }
     int MF = (st == 1) ? 4 : 1;
-    fill_geometry(a, st, 128 * MF);
-    if (st == 1 && ((long)a.tiles_x * a.tiles_y * a.tiles_z * c.N * (w.cout / (32 * w.nf)) < 512 ||
-                    (size_t)a.IX * a.IY * a.IZ * w.cc * 4 > 80 * 1024 || (w.cc == 8 && w.nf == 2))) {
+    TileGeom g = chosen_tile(Do, Ho, Wo, st, 128 * MF);
+    if (st == 1 && (g.tiles_per_n() * c.N * gy_nf < 512 || (size_t)g.brickvox() * w.cc * 4 > 80 * 1024 || (w.cc == 8 && w.nf == 2))) {
         MF = 2;
-        fill_geometry(a, st, 128 * MF);
+        g = chosen_tile(Do, Ho, Wo, st, 128 * MF);
     }
-    const int tiles_per_n = a.tiles_x * a.tiles_y * a.tiles_z;
-    MI355_REQUIRE((long)tiles_per_n * c.N < (1l << 30), "conv grid too large");
-    const int brickvox = a.IX * a.IY * a.IZ;
-    const size_t brick_bytes = (size_t)brickvox * w.cc * sizeof(float);
+    const long tiles = g.tiles_per_n() * c.N;
+    MI355_REQUIRE(tiles < (1l << 30), "conv grid too large");
+    const size_t brick_bytes = (size_t)g.brickvox() * w.cc * sizeof(float);
     const size_t lds_bytes = brick_bytes < 4096 ? 4096 : brick_bytes;  // >= the stats scratch
     MI355_REQUIRE(lds_bytes <= 160 * 1024, "conv brick needs %zu B of LDS", lds_bytes);
-    dim3 grid(tiles_per_n * c.N, w.cout / (32 * w.nf));
-    if (st == 1 && w.cc == 16 && MF == 4 && w.nf == 2) { *kernel_name = "conv3_f32_mfma_kernel<1, 16, 4, 2>"; return launch_conv<1, 16, 4, 2>(a, grid, lds_bytes, s); }
-    if (st == 1 && w.cc == 16 && MF == 4) { *kernel_name = "conv3_f32_mfma_kernel<1, 16, 4, 1>"; return launch_conv<1, 16, 4, 1>(a, grid, lds_bytes, s); }
-    if (st == 1 && w.cc == 8 && MF == 4 && w.nf == 1) { *kernel_name = "conv3_f32_mfma_kernel<1, 8, 4, 1>"; return launch_conv<1, 8, 4, 1>(a, grid, lds_bytes, s); }
-    if (st == 1 && w.cc == 16 && w.nf == 1) { *kernel_name = "conv3_f32_mfma_kernel<1, 16, 2, 1>"; return launch_conv<1, 16, 2, 1>(a, grid, lds_bytes, s); }
-    if (st == 1 && w.cc == 16 && w.nf == 2) { *kernel_name = "conv3_f32_mfma_kernel<1, 16, 2, 2>"; return launch_conv<1, 16, 2, 2>(a, grid, lds_bytes, s); }
-    if (st == 1 && w.cc == 8 && w.nf == 1) { *kernel_name = "conv3_f32_mfma_kernel<1, 8, 2, 1>"; return launch_conv<1, 8, 2, 1>(a, grid, lds_bytes, s); }
-    if (st == 1 && w.cc == 8 && w.nf == 2) { *kernel_name = "conv3_f32_mfma_kernel<1, 8, 2, 2>"; return launch_conv<1, 8, 2, 2>(a, grid, lds_bytes, s); }
-    if (st == 2 && w.cc == 8 && w.nf == 1) { *kernel_name = "conv3_f32_mfma_kernel<2, 8, 1, 1>"; return launch_conv<2, 8, 1, 1>(a, grid, lds_bytes, s); }
-    if (st == 2 && w.cc == 8 && w.nf == 2) { *kernel_name = "conv3_f32_mfma_kernel<2, 8, 1, 2>"; return launch_conv<2, 8, 1, 2>(a, grid, lds_bytes, s); }
-    set_error("no conv kernel for stride %d cc %d nf %d", st, w.cc, w.nf);
-    return MI355_ERR_UNSUPPORTED;
+    KernelRow *row = find_row(f32_rows, "conv3_f32_mfma_kernel<%d, %d, %d, %d>", st, w.cc, MF, w.nf);
+    if (!row) {
+        set_error("no conv kernel for stride %d cc %d nf %d", st, w.cc, w.nf);
+        return MI355_ERR_UNSUPPORTED;
+    }
+    plan_set(p, row, FAM_SIMPLE, g, tiles, (unsigned)tiles, gy_nf, lds_bytes);
+    return MI355_OK;
 }
 
-int conv3d_direct_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s) {
+int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, const char **kernel_name) {
+    ConvPlan p;
+    MI355_TRY(plan_conv_f32(w, c, &p));
+    if (kernel_name) *kernel_name = p.name;
+    if (p.family == FAM_WINO3) return launch_wino3(w, c, p, s);
+    ConvArgs a;
+    a.in0 = c.in0; a.in1 = c.in1; a.C0 = c.C0; a.C1 = c.C1;
+    a.wp = p.pack == PACK_WINO2 ? w.wpw_dev : (p.pack == PACK_C16 ? w.wp16_dev : w.wp_dev);
+    a.bias = w.bias_dev; a.out = c.out; a.stats = c.stats;
+    a.head_w = c.head_w; a.head_b = c.head_b; a.head_out = c.head_out; a.head_ncls = c.head_ncls;
+    a.N = c.N; a.Di = c.Di; a.Hi = c.Hi; a.Wi = c.Wi;
+    a.Do = (c.Di - 1) / w.stride + 1; a.Ho = (c.Hi - 1) / w.stride + 1; a.Wo = (c.Wi - 1) / w.stride + 1;
+    a.Cout = w.cout;
+    a.nchunks = w.cin_pad / (p.pack == PACK_MAIN ? w.cc : 16);
+    a.act = c.act; a.slope = c.slope;
+    a.ksplit = 1; a.partial = nullptr; a.zero_bias = nullptr; a.out_elems = 0;
+    set_geometry(a, p.g);
+    const dim3 grid(p.gx, p.gy, p.gz);
+    if (p.family == FAM_WINO2 || p.family == FAM_S2DMA) {
+        float *zeros = nullptr;  // the zero page out-of-volume DMA pieces read
+        MI355_TRY(device_scratch(SCR_ZEROS, s, 256, (void **)&zeros, true));
+        Wino2Args wa;
+        wa.c = a; wa.total_tiles = (int)p.tiles; wa.zeros = zeros;
+        wa.order = make_tile_order(p.g.tiles_x, p.g.tiles_y, p.g.tiles_z);
+        return launch_row(*p.row, grid, p.lds_bytes, s, &wa);
+    }
+    if (p.family == FAM_PIPE) {
+        PipeArgs pa;
+        pa.c = a;
+        pa.total_tiles = (int)p.tiles;
+        pa.plane = p.g.brickvox() * 4;
+        pa.buf_floats = 2 * pa.plane;
+        pa.w_split = w.nf / p.nf;
+        return launch_row(*p.row, grid, p.lds_bytes, s, &pa);
+    }
+    if (p.ksplit == 1) return launch_row(*p.row, grid, p.lds_bytes, s, &a);
+    float *partial = nullptr, *zero_bias = nullptr;
+    const long out_elems = (long)c.N * a.Do * a.Ho * a.Wo * w.cout;
+    MI355_TRY(device_scratch(SCR_ZERO_BIAS, s, 4096 * sizeof(float), (void **)&zero_bias, true));
+    MI355_TRY(device_scratch(SCR_SPLITK_F32, s, (size_t)p.ksplit * out_elems * sizeof(float), (void **)&partial));
+    a.ksplit = p.ksplit; a.partial = partial; a.zero_bias = zero_bias; a.out_elems = out_elems;
+    MI355_TRY(launch_row(*p.row, grid, p.lds_bytes, s, &a));
+    const long total4 = out_elems / 4;
+    hipLaunchKernelGGL(splitk_finish_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, partial, p.ksplit, total4, w.cout / 4,
+                       w.bias_dev, c.act, c.slope, c.out);
+    MI355_HIP(hipGetLastError());
+    return MI355_OK;
+}
+
+int plan_conv_direct(const ConvWeights &w, const ConvCall &c) {
     MI355_REQUIRE(w.w_plain_dev != nullptr, "conv %d->%d has no plain weights", w.cin, w.cout);
     MI355_REQUIRE(c.C0 + c.C1 == w.cin_pad, "conv input channels %d+%d != %d", c.C0, c.C1, w.cin_pad);
     // (the statistics epilogue is here; the fused head and the fused input normalisation are not)
     MI355_REQUIRE(!c.head_out && !c.in_scale, "conv %d->%d: the direct kernel has no fused head or input normalisation", w.cin, w.cout);
     MI355_REQUIRE(c.out != nullptr, "conv %d->%d: no output tensor", w.cin, w.cout);
+    return MI355_OK;
+}
+
+int conv3d_direct_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s) {
+    MI355_TRY(plan_conv_direct(w, c));
     const int st = w.stride;
     const int Do = (c.Di - 1) / st + 1, Ho = (c.Hi - 1) / st + 1, Wo = (c.Wi - 1) / st + 1;
     const size_t total = (size_t)c.N * Do * Ho * Wo * w.cout;

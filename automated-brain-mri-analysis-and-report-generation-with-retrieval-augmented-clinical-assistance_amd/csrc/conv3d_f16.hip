@@ -18,7 +18,7 @@
 // extra MFMAs; its STRIDE = 2 instantiation with 128-output tiles serves the large stride-2 launches), and the simple
 // conv3_f16_mfma_kernel (one tile per workgroup, stride 1|2; also the split-K slices of the deep levels, finished by
 // splitk_finish_f16_kernel).
-#include "kernels.h"
+#include "conv_plan.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -1225,14 +1225,19 @@ __global__ __launch_bounds__(256, 2) void conv3_f16_c32_kernel(ConvArgsH p) {
 // ------------------------------------------------------------------ host side
 // Packed layout (halfs): [cout_block][chunk][tap][nf][lane 0..63][j 0..7] with
 //   cout = (cout_block*NF + nf)*32 + (lane&31),  cin = chunk*16 + (lane>>5)*8 + j.
-int conv_weights_upload_f16(const float *w_host, const float *bias_host, int cin, int cin_pad, int cout, int stride,
-                            ConvWeightsH *out) {
+int conv_pack_layout_f16(int cin, int cin_pad, int cout, int stride, int *nf) {
     MI355_REQUIRE(stride == 1 || stride == 2, "conv stride %d unsupported", stride);
     MI355_REQUIRE(cin_pad >= cin && cin_pad % 16 == 0, "fp16 conv needs cin_pad %% 16 == 0 (got %d for cin %d)", cin_pad, cin);
     MI355_REQUIRE(cout % 32 == 0, "fp16 conv needs cout %% 32 == 0 (got %d)", cout);
+    *nf = (cout % 64 == 0) ? 2 : 1;
+    return MI355_OK;
+}
+
+int conv_weights_upload_f16(const float *w_host, const float *bias_host, int cin, int cin_pad, int cout, int stride,
+                            ConvWeightsH *out) {
     ConvWeightsH cw;
     cw.cin = cin; cw.cin_pad = cin_pad; cw.cout = cout; cw.stride = stride;
-    cw.nf = (cout % 64 == 0) ? 2 : 1;
+    MI355_TRY(conv_pack_layout_f16(cin, cin_pad, cout, stride, &cw.nf));
     const int nchunks = cin_pad / 16, nblk = cout / (32 * cw.nf);
     std::vector<half_t> packed((size_t)nblk * nchunks * 27 * cw.nf * 512);
     size_t o = 0;
@@ -1261,287 +1266,191 @@ void conv_weights_free_f16(ConvWeightsH *w) {
     *w = ConvWeightsH();
 }
 
-static void choose_tile_h(int Do, int Ho, int Wo, int stride, int voxels, int *lz, int *ly, int *lx) {
-    auto p2cap = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    const int cz = p2cap(Do), cy = p2cap(Ho), cx = p2cap(Wo);
-    const int L = ilog2_exact(voxels);
-    int x = cx < 5 ? cx : 5;
-    if (x > L) x = L;
-    long best = -1;
-    int bz = L - x, by = 0;
-    for (int y = 0; x + y <= L; ++y) {
-        const int z = L - x - y;
-        const int oy = y > cy ? y - cy : 0, oz = z > cz ? z - cz : 0;
-        const long brick = (long)(((1 << y) - 1) * stride + 3) * (((1 << z) - 1) * stride + 3);
-        const long cost = ((long)(oy + oz) << 32) + brick;
-        if (best < 0 || cost < best) { best = cost; bz = z; by = y; }
-    }
-    *lz = bz; *ly = by; *lx = x;
-}
+// Every instantiation conv3d_mfma_f16 launches from this file (the stride-2 LDS-DMA kernel's rows are in conv3d_f16_s2.hip).
+// Template arguments are spelled out, defaults included: the names are the instantiations as rocprofv3 prints them
+// (pipelined kernel: <MF, NF, HEAD, INAFF, STRIDE, WHOLE>).
+static KernelRow f16_rows[] = {
+    MI355_KERNEL_ROW(conv3_f16_mfma_kernel<1, 2, 1>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_kernel<1, 2, 2>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_kernel<2, 1, 1>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_kernel<2, 1, 2>),
+    MI355_KERNEL_ROW(conv3_f16_c32_kernel<false, false, true>),
+    MI355_KERNEL_ROW(conv3_f16_c32_kernel<true, true, false>),
+    MI355_KERNEL_ROW(conv3_f16_c32_kernel<false, true, false>),
+    MI355_KERNEL_ROW(conv3_f16_c32_kernel<true, false, false>),
+    MI355_KERNEL_ROW(conv3_f16_c32_kernel<false, false, false>),
+    MI355_KERNEL_ROW(conv3_f16_dma_kernel<true, true>),
+    MI355_KERNEL_ROW(conv3_f16_dma_kernel<false, true>),
+    MI355_KERNEL_ROW(conv3_f16_dma_kernel<true, false>),
+    MI355_KERNEL_ROW(conv3_f16_dma_kernel<false, false>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<4, 1, true, false, 1, true>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<4, 1, true, false, 1, false>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<2, 1, true, false, 1, false>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<4, 1, false, true, 1, true>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<2, 1, false, true, 1, true>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<2, 2, false, true, 1, true>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<4, 1, false, false, 1, true>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<2, 1, false, false, 1, true>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<2, 2, false, false, 1, true>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<4, 1, false, false, 1, false>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<2, 1, false, false, 1, false>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<2, 2, false, false, 1, false>),
+    MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<1, 2, false, false, 2, false>),
+};
 
-static void fill_geometry_h(ConvArgsH &a, int st, int voxels) {
-    choose_tile_h(a.Do, a.Ho, a.Wo, st, voxels, &a.lz, &a.ly, &a.lx);
-    const int TX = 1 << a.lx, TY = 1 << a.ly, TZ = 1 << a.lz;
-    a.tiles_x = ceil_div(a.Wo, TX); a.tiles_y = ceil_div(a.Ho, TY); a.tiles_z = ceil_div(a.Do, TZ);
-    a.IX = (TX - 1) * st + 3; a.IY = (TY - 1) * st + 3; a.IZ = (TZ - 1) * st + 3;
-    a.div_tiles_per_n = make_fastdiv(a.tiles_x * a.tiles_y * a.tiles_z);
-    a.div_tiles_x = make_fastdiv(a.tiles_x);
-    a.div_tiles_y = make_fastdiv(a.tiles_y);
-    a.div_IX = make_fastdiv(a.IX);
-    a.div_IY = make_fastdiv(a.IY);
-    a.plane_bytes = a.IX * a.IY * a.IZ * 16;
-}
-
-template <typename K>
-static int launch_h(K kern, const ConvArgsH &a, dim3 grid, size_t lds_bytes, hipStream_t s, size_t *attr_bytes) {
-    if (lds_bytes > *attr_bytes) {
-        MI355_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        *attr_bytes = lds_bytes;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, s, a);
-    MI355_HIP(hipGetLastError());
-    return MI355_OK;
-}
-
-static bool use_pipe_h() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("MI355_CONV_IMPL"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v == 1;
-}
-
-// Whether conv3d_mfma_f16 would run this call on a kernel that can apply the producer's normalisation to its input: the
-// pipelined stride-1 kernel (while staging through registers) or the LDS-DMA kernel (in LDS); the split-K and stride-2
-// kernels cannot.  Mirrors the dispatch below.
+// Can conv `w` apply the producer's normalisation to the input of call `c` (N, Di, Hi, Wi, C0, stats and head set as it will be
+// called)?  Then plan_conv_f16 accepts the call with in_scale set: on the pipelined stride-1 kernel (which normalises while staging
+// through registers) or an LDS-DMA kernel (in LDS); the split-K and stride-2 kernels cannot.  Deliberately conservative about
+// split-K: a call that might be split is refused whatever its size.
 bool conv3d_f16_fuses_input_norm(const ConvWeightsH &w, const ConvCallH &c) {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("MI355_FUSE_NORM"); on = (e && e[0] == '0') ? 0 : 1; }
-    if (!on || w.stride != 1 || !use_pipe_h() || c.head_out || c.C0 % 16 != 0) return false;
-    static int splitk = -1;
-    if (splitk < 0) { const char *e = getenv("MI355_SPLITK"); splitk = (e && e[0] == '0') ? 0 : 1; }
-    if (splitk && !c.stats && w.cin_pad / 16 >= 8) return false;  // might take the split-K path: keep it simple
+    if (!env_switch("MI355_FUSE_NORM") || w.stride != 1 || conv_impl() == 0 || c.head_out || c.C0 % 16 != 0) return false;
+    if (env_switch("MI355_SPLITK") && !c.stats && w.cin_pad / 16 >= 8) return false;
     // the register-staged kernels apply the norm on volumes that are whole tiles only (512- or 256-voxel tiles, whichever
     // the launch picks; the LDS-DMA kernel's 8 x 8 x 8 tiles divide whatever these divide)
-    for (int vox : {512, 256}) {
-        int lz, ly, lx;
-        choose_tile_h(c.Di, c.Hi, c.Wi, 1, vox, &lz, &ly, &lx);
-        if (c.Di % (1 << lz) || c.Hi % (1 << ly) || c.Wi % (1 << lx)) return false;
-    }
+    for (int vox : {512, 256})
+        if (!chosen_tile(c.Di, c.Hi, c.Wi, 1, vox).whole(c.Di, c.Hi, c.Wi)) return false;
     return true;
 }
 
-int conv3d_mfma_f16(const ConvWeightsH &w, const ConvCallH &c, hipStream_t s, const char **kernel_name) {
+// Which kernel an fp16 call goes to, with which tile, grid and LDS size.  No side effects: the error text is set only when the
+// call is refused.
+int plan_conv_f16(const ConvWeightsH &w, const ConvCallH &c, ConvPlan *p) {
+    *p = ConvPlan();
     MI355_REQUIRE(c.C0 + c.C1 == w.cin_pad, "conv input channels %d+%d != %d", c.C0, c.C1, w.cin_pad);
     MI355_REQUIRE(c.C0 % 16 == 0 && c.C1 % 16 == 0, "fp16 concat split %d/%d not a multiple of 16", c.C0, c.C1);
     MI355_REQUIRE(c.C1 == 0 || c.in1 != nullptr, "second conv input missing");
-    ConvArgsH a;
+    const int st = w.stride;
+    const bool pipe = conv_impl() != 0;  // MI355_CONV_IMPL=0: the one-tile-per-workgroup kernels only
+    MI355_REQUIRE(!c.head_out || (st == 1 && pipe && w.cout == 32 * w.nf && !c.stats && c.head_ncls >= 1 && c.head_ncls <= 4 && c.head_w && c.head_b),
+                  "fused head needs Cout (%d) == one workgroup's couts, no statistics, 1..4 classes", w.cout);
+    const int Do = (c.Di - 1) / st + 1, Ho = (c.Hi - 1) / st + 1, Wo = (c.Wi - 1) / st + 1;
+    const int nchunks = w.cin_pad / 16;
+    MI355_REQUIRE(!c.in_scale || (c.in_shift && conv3d_f16_fuses_input_norm(w, c)), "input normalisation can only be fused into the stride-1 kernels");
+    const int gy = w.cout / (32 * w.nf);
+    p->nf = w.nf;
+    // LDS of the one-tile-per-workgroup kernel: two 8-channel planes (>= the statistics scratch); of the pipelined kernel: two
+    // buffers of them + the statistics scratch
+    auto lds_simple = [](const TileGeom &g) { const size_t b = (size_t)2 * g.brickvox() * 16; return b < 4096 ? (size_t)4096 : b; };
+    auto lds_pipe = [&](const TileGeom &g) { return (size_t)4 * g.brickvox() * 16 + 4 * w.nf * 32 * 2 * sizeof(float); };
+    // split-K for small launches (deep levels; splitk_slices, conv_plan.h): fp32 partial sums, deterministic finishing pass
+    if (env_switch("MI355_SPLITK") && !c.stats && !c.head_out && nchunks >= 8) {
+        const TileGeom g = chosen_tile(Do, Ho, Wo, st, st == 1 ? 256 : 128);
+        const long tiles = g.tiles_per_n() * c.N;
+        const int S = splitk_slices(tiles * gy, nchunks);
+        if (S && lds_simple(g) <= 80 * 1024) {
+            plan_set(p, find_row(f16_rows, "conv3_f16_mfma_kernel<%d, %d, %d>", st, st == 1 ? 2 : 1, w.nf), FAM_SIMPLE, g, tiles, (unsigned)tiles, gy, lds_simple(g));
+            p->name = p->row->name_splitk; p->gz = S; p->ksplit = S;
+            return MI355_OK;
+        }
+    }
+    if (st == 1 && pipe && (w.nf == 2 ? !c.head_out : (w.cout == 32 && (!c.head_out || (!c.stats && !c.in_scale))))) {
+        // LDS-DMA kernels: 8 x 8 x 8 tiles; conv3_f16_dma_kernel = 64 couts per workgroup, one workgroup per CU; conv3_f16_c32_kernel
+        // (round 5) = the Cout = 32 layers, two workgroups per CU (MI355_F16_DMA=0: the register-staged kernels)
+        const bool c32 = w.nf == 1;
+        const TileGeom g = fixed_tile(Do, Ho, Wo, 3, 3, 3, 10, 10, 10);
+        const long tiles = g.tiles_per_n() * c.N;
+        typedef DmaGeomH<2, 2> GA;
+        typedef DmaGeomH<2, 1> GA1;
+        static_assert(GA::LDS_BYTES == GA1::LDS_BYTES && GA::TAB_OFF == GA1::TAB_OFF, "one LDS layout");  // (for both fragment counts)
+        const int wg_per_cu = c32 ? GA1::WG_PER_CU : GA::WG_PER_CU;
+        const size_t tab_bytes = c.in_scale ? (size_t)c.N * c.C0 * 4 : 0;  // fused input norm: fp16 scale + shift tables in LDS
+        const size_t tab_max = c32 ? (size_t)GA1::TAB_MAX_BYTES : (size_t)GA::TAB_MAX_BYTES;
+        if (env_switch("MI355_F16_DMA") && (!c32 || env_switch("MI355_F16_C32")) && tiles * gy >= 256 * wg_per_cu && tiles < (1l << 30) &&
+            Do % 8 == 0 && Ho % 8 == 0 && Wo % 8 == 0 &&
+            (long)10 * c.Hi * c.Wi < (1l << 24) && ((long)10 * c.Hi * c.Wi + 8l * c.Di * c.Hi * c.Wi) * 16 < (1l << 32) &&
+            (!c.in_scale || (c.C1 == 0 && tab_bytes <= tab_max)) &&
+            (!c.head_out || (long)c.head_ncls * c.Di * c.Hi * c.Wi * 4 < (1l << 32))) {
+            const char *stats = tf(c.stats != nullptr), *inaff = tf(c.in_scale != nullptr);
+            KernelRow *row = c32 ? find_row(f16_rows, "conv3_f16_c32_kernel<%s, %s, %s>", stats, inaff, tf(c.head_out != nullptr))
+                                 : find_row(f16_rows, "conv3_f16_dma_kernel<%s, %s>", stats, inaff);
+            plan_set(p, row, FAM_DMA, g, tiles, persistent_grid_x(256 * wg_per_cu, gy, tiles), gy,
+                     c.in_scale ? (size_t)GA::TAB_OFF + tab_bytes : (size_t)GA::LDS_BYTES);
+            return MI355_OK;
+        }
+    }
+    if (st == 1 && pipe) {
+        int MF = 4;
+        TileGeom g = chosen_tile(Do, Ho, Wo, 1, 128 * MF);
+        if (g.tiles_per_n() * c.N * gy < 512 || g.brickvox() > 11 * 128 || w.nf == 2) {
+            MF = 2;
+            g = chosen_tile(Do, Ho, Wo, 1, 128 * MF);
+        }
+        const long tiles = g.tiles_per_n() * c.N;
+        MI355_REQUIRE(tiles < (1l << 30), "conv grid too large");
+        MI355_REQUIRE(g.brickvox() <= (MF == 4 ? 11 : 8) * 128, "conv brick exceeds the staging slots");
+        MI355_REQUIRE((long)g.IZ * c.Hi * c.Wi < (1l << 24) && ((long)g.IZ * c.Hi * c.Wi + (long)c.Di * c.Hi * c.Wi) * 16 < (1l << 31),
+                      "volume too large for the 32-bit staging offsets");
+        MI355_REQUIRE(lds_pipe(g) <= 160 * 1024, "conv brick needs %zu B of LDS", lds_pipe(g));
+        const bool whole = g.whole(Do, Ho, Wo);
+        MI355_REQUIRE(!c.head_out || w.nf == 1, "fused head: fp16 path supports Cout = 32 only");
+        // the producer's normalisation + activation applied while the brick is staged
+        MI355_REQUIRE(c.head_out || !c.in_scale || whole, "fused input normalisation needs a volume of whole tiles (conv3d_f16_fuses_input_norm)");
+        // (the fused head has a whole-tile instantiation for 512-voxel tiles only)
+        KernelRow *row = find_row(f16_rows, "conv3_f16_mfma_pipe_kernel<%d, %d, %s, %s, 1, %s>", MF, w.nf, tf(c.head_out != nullptr),
+                                  tf(!c.head_out && c.in_scale), tf(c.head_out ? (MF == 4 && whole) : whole));
+        plan_set(p, row, FAM_PIPE, g, tiles, persistent_grid_x(512, gy, tiles), gy, lds_pipe(g));
+        return MI355_OK;
+    }
+    // round 3: Cout % 128 == 0 on whole 4 x 4 x 8 output tiles -> conv3d_f16_s2.hip
+    if (st == 2 && pipe && plan_f16_s2dma(w, c, p)) return MI355_OK;
+    if (st == 2 && w.nf == 2 && !c.head_out && pipe) {
+        // round 2: the pipelined kernel with STRIDE = 2 (register-staged, two lanes per voxel) for the large stride-2 launches
+        // (MI355_S2_DMA=0: the one-tile-per-workgroup kernel instead (the switch of the f32 stride-2 kernel))
+        const TileGeom g = chosen_tile(Do, Ho, Wo, 2, 128);
+        const long tiles = g.tiles_per_n() * c.N;
+        if (env_switch("MI355_S2_DMA") && tiles * gy >= 768 && tiles < (1l << 30) && g.brickvox() <= 13 * 128 && lds_pipe(g) <= 160 * 1024 &&
+            (long)g.IZ * c.Hi * c.Wi < (1l << 24) && ((long)g.IZ * c.Hi * c.Wi + (long)c.Di * c.Hi * c.Wi) * 16 < (1l << 31) && !c.in_scale) {
+            // one workgroup per CU: the double-buffered brick takes about 100 KB of LDS
+            plan_set(p, find_row(f16_rows, "conv3_f16_mfma_pipe_kernel<1, 2, false, false, 2, false>"), FAM_PIPE, g, tiles, persistent_grid_x(256, gy, tiles), gy,
+                     lds_pipe(g));
+            return MI355_OK;
+        }
+    }
+    const TileGeom g = chosen_tile(Do, Ho, Wo, st, st == 1 ? 256 : 128);
+    const long tiles = g.tiles_per_n() * c.N;
+    MI355_REQUIRE(tiles < (1l << 30), "conv grid too large");
+    MI355_REQUIRE(lds_simple(g) <= 160 * 1024, "conv brick needs %zu B of LDS", lds_simple(g));
+    plan_set(p, find_row(f16_rows, "conv3_f16_mfma_kernel<%d, %d, %d>", st, st == 1 ? 2 : 1, w.nf), FAM_SIMPLE, g, tiles, (unsigned)tiles, gy, lds_simple(g));
+    return MI355_OK;
+}
+
+int conv3d_mfma_f16(const ConvWeightsH &w, const ConvCallH &c, hipStream_t s, const char **kernel_name) {
+    ConvPlan p;
+    MI355_TRY(plan_conv_f16(w, c, &p));
+    if (kernel_name) *kernel_name = p.name;
+    if (p.family == FAM_S2DMA) return launch_f16_s2dma(w, c, p, s);
+    ConvArgsH a = ConvArgsH();
     a.in0 = c.in0; a.in1 = c.in1; a.C0 = c.C0; a.C1 = c.C1;
     a.wp = w.wp_dev; a.bias = w.bias_dev; a.out = c.out; a.stats = c.stats;
     a.head_w = c.head_w; a.head_b = c.head_b; a.head_out = c.head_out; a.head_ncls = c.head_ncls;
     a.N = c.N; a.Di = c.Di; a.Hi = c.Hi; a.Wi = c.Wi;
-    const int st = w.stride;
-    MI355_REQUIRE(!c.head_out || (st == 1 && use_pipe_h() && w.cout == 32 * w.nf && !c.stats && c.head_ncls >= 1 && c.head_ncls <= 4 && c.head_w && c.head_b),
-                  "fused head needs Cout (%d) == one workgroup's couts, no statistics, 1..4 classes", w.cout);
-    a.Do = (c.Di - 1) / st + 1; a.Ho = (c.Hi - 1) / st + 1; a.Wo = (c.Wi - 1) / st + 1;
+    a.Do = (c.Di - 1) / w.stride + 1; a.Ho = (c.Hi - 1) / w.stride + 1; a.Wo = (c.Wi - 1) / w.stride + 1;
     a.Cout = w.cout;
     a.nchunks = w.cin_pad / 16;
     a.act = c.act; a.slope = c.slope;
-    a.total_tiles = 0;
+    a.total_tiles = p.family == FAM_SIMPLE ? 0 : (int)p.tiles;
     a.ksplit = 1; a.partial = nullptr; a.out_elems = 0;
     a.in_scale = c.in_scale; a.in_shift = c.in_shift; a.in_act = c.in_act;
-    MI355_REQUIRE(!c.in_scale || (c.in_shift && conv3d_f16_fuses_input_norm(w, c)), "input normalisation can only be fused into the stride-1 kernels");
-    const int gy = w.cout / (32 * w.nf);
-    static size_t attr[8] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
-    {
-        // split-K for small launches (deep levels), as in conv3d.hip: fp32 partial sums, deterministic finishing pass
-        static int splitk = -1;
-        if (splitk < 0) { const char *e = getenv("MI355_SPLITK"); splitk = (e && e[0] == '0') ? 0 : 1; }
-        if (splitk && !c.stats && !c.head_out && a.nchunks >= 8) {
-            ConvArgsH b = a;
-            const int MFs = st == 1 ? 2 : 1;
-            fill_geometry_h(b, st, 128 * MFs);
-            const long tiles = (long)b.tiles_x * b.tiles_y * b.tiles_z * c.N;
-            const long units = tiles * gy;
-            // as many slices as still fit the chip in ONE round of workgroups (256 CUs x 2): rounding up (round 2) gave the 8^3 level
-            // 80 x 7 = 560 workgroups - 48 of them ran behind the other 512 and doubled the launch's critical path
-            int S = (int)(512 / units);
-            if (S > a.nchunks / 4) S = a.nchunks / 4;
-            if (S > 8) S = 8;
-            size_t lds_bytes = (size_t)2 * b.plane_bytes;
-            if (lds_bytes < 4096) lds_bytes = 4096;
-            if (units < 256 && S >= 2 && lds_bytes <= 80 * 1024) {
-                float *partial = nullptr;
-                const long out_elems = (long)c.N * a.Do * a.Ho * a.Wo * w.cout;
-                const size_t need = (size_t)S * out_elems * sizeof(float);
-                MI355_TRY(device_scratch(SCR_SPLITK_F16, s, need, (void **)&partial));
-                b.ksplit = S; b.partial = partial; b.out_elems = out_elems;
-                dim3 grid((unsigned)tiles, gy, S);
-                int rc;
-                static size_t attr_sk[4] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
-                if (st == 1 && w.nf == 1) { if (kernel_name) *kernel_name = "conv3_f16_mfma_kernel<1, 2, 1> split-K"; rc = launch_h(conv3_f16_mfma_kernel<1, 2, 1>, b, grid, lds_bytes, s, &attr_sk[0]); }
-                else if (st == 1) { if (kernel_name) *kernel_name = "conv3_f16_mfma_kernel<1, 2, 2> split-K"; rc = launch_h(conv3_f16_mfma_kernel<1, 2, 2>, b, grid, lds_bytes, s, &attr_sk[1]); }
-                else if (w.nf == 1) { if (kernel_name) *kernel_name = "conv3_f16_mfma_kernel<2, 1, 1> split-K"; rc = launch_h(conv3_f16_mfma_kernel<2, 1, 1>, b, grid, lds_bytes, s, &attr_sk[2]); }
-                else { if (kernel_name) *kernel_name = "conv3_f16_mfma_kernel<2, 1, 2> split-K"; rc = launch_h(conv3_f16_mfma_kernel<2, 1, 2>, b, grid, lds_bytes, s, &attr_sk[3]); }
-                if (rc != MI355_OK) return rc;
-                const long total4 = out_elems / 4;
-                hipLaunchKernelGGL(splitk_finish_f16_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, partial, S, total4, c.act, c.slope, c.out,
-                                   w.cout, (long)a.Do * a.Ho * a.Wo);
-                MI355_HIP(hipGetLastError());
-                return MI355_OK;
-            }
-        }
+    set_geometry(a, p.g);
+    a.plane_bytes = p.g.brickvox() * 16;
+    const dim3 grid(p.gx, p.gy, p.gz);
+    if (p.family == FAM_DMA) {
+        void *zeros = nullptr;  // the zero page out-of-volume DMA pieces read
+        MI355_TRY(device_scratch(SCR_ZEROS, s, 256, &zeros, true));
+        a.zeros = zeros;
+        a.order = make_tile_order(p.g.tiles_x, p.g.tiles_y, p.g.tiles_z);
     }
-    if (st == 1 && use_pipe_h() && (w.nf == 2 ? !c.head_out : (w.cout == 32 && (!c.head_out || (!c.stats && !c.in_scale))))) {
-        // LDS-DMA kernels: 8 x 8 x 8 tiles; conv3_f16_dma_kernel = 64 couts per workgroup, one workgroup per CU; conv3_f16_c32_kernel
-        // (round 5) = the Cout = 32 layers, two workgroups per CU (MI355_F16_DMA=0: the register-staged kernels)
-        static int dmak = -1;
-        if (dmak < 0) { const char *e = getenv("MI355_F16_DMA"); dmak = (e && e[0] == '0') ? 0 : 1; }
-        static int c32k = -1;
-        if (c32k < 0) { const char *e = getenv("MI355_F16_C32"); c32k = (e && e[0] == '0') ? 0 : 1; }
-        const bool c32 = w.nf == 1;
-        ConvArgsH b = a;
-        b.lx = b.ly = b.lz = 3;
-        b.tiles_x = ceil_div(b.Wo, 8); b.tiles_y = ceil_div(b.Ho, 8); b.tiles_z = ceil_div(b.Do, 8);
-        b.IX = b.IY = b.IZ = 10;
-        b.div_tiles_per_n = make_fastdiv(b.tiles_x * b.tiles_y * b.tiles_z);
-        const long tiles = (long)b.tiles_x * b.tiles_y * b.tiles_z * c.N;
-        typedef DmaGeomH<2, 2> GA;
-        typedef DmaGeomH<2, 1> GA1;
-        const int wg_per_cu = c32 ? GA1::WG_PER_CU : GA::WG_PER_CU;
-        const size_t tab_bytes = c.in_scale ? (size_t)c.N * c.C0 * 4 : 0;  // fused input norm: fp16 scale + shift tables in LDS
-        const size_t tab_max = c32 ? (size_t)GA1::TAB_MAX_BYTES : (size_t)GA::TAB_MAX_BYTES;
-        if (dmak && (!c32 || c32k) && tiles * gy >= 256 * wg_per_cu && tiles < (1l << 30) && b.Do % 8 == 0 && b.Ho % 8 == 0 && b.Wo % 8 == 0 &&
-            (long)10 * c.Hi * c.Wi < (1l << 24) && ((long)10 * c.Hi * c.Wi + 8l * c.Di * c.Hi * c.Wi) * 16 < (1l << 32) &&
-            (!c.in_scale || (c.C1 == 0 && tab_bytes <= tab_max)) &&
-            (!c.head_out || (long)c.head_ncls * c.Di * c.Hi * c.Wi * 4 < (1l << 32))) {
-            void *zeros = nullptr;  // the zero page out-of-volume DMA pieces read
-            MI355_TRY(device_scratch(SCR_ZEROS, s, 256, &zeros, true));
-            b.zeros = zeros;
-            b.total_tiles = (int)tiles;
-            b.order = make_tile_order(b.tiles_x, b.tiles_y, b.tiles_z);
-            int gx = 256 * wg_per_cu / gy;
-            gx = gx < 8 ? 8 : (gx / 8) * 8;
-            const int need = (int)((tiles + 7) / 8) * 8;
-            if (gx > need) gx = need;
-            const size_t lds_plain = GA::LDS_BYTES, lds_aff = (size_t)GA::TAB_OFF + tab_bytes;   // (the same layout for both fragment counts)
-            static_assert(GA::LDS_BYTES == GA1::LDS_BYTES && GA::TAB_OFF == GA1::TAB_OFF, "one LDS layout");
-            if (c32) {
-                static size_t attr_c32[5] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
-                if (c.head_out) {
-                    if (kernel_name) *kernel_name = "conv3_f16_c32_kernel<false, false, true>";
-                    return launch_h(conv3_f16_c32_kernel<false, false, true>, b, dim3(gx, gy), lds_plain, s, &attr_c32[4]);
-                }
-                if (c.in_scale) {
-                    if (kernel_name) *kernel_name = c.stats ? "conv3_f16_c32_kernel<true, true, false>" : "conv3_f16_c32_kernel<false, true, false>";
-                    if (c.stats) return launch_h(conv3_f16_c32_kernel<true, true>, b, dim3(gx, gy), lds_aff, s, &attr_c32[2]);
-                    return launch_h(conv3_f16_c32_kernel<false, true>, b, dim3(gx, gy), lds_aff, s, &attr_c32[3]);
-                }
-                if (kernel_name) *kernel_name = c.stats ? "conv3_f16_c32_kernel<true, false, false>" : "conv3_f16_c32_kernel<false, false, false>";
-                if (c.stats) return launch_h(conv3_f16_c32_kernel<true>, b, dim3(gx, gy), lds_plain, s, &attr_c32[0]);
-                return launch_h(conv3_f16_c32_kernel<false>, b, dim3(gx, gy), lds_plain, s, &attr_c32[1]);
-            }
-            static size_t attr_dma[4] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
-            if (c.in_scale) {
-                if (kernel_name) *kernel_name = c.stats ? "conv3_f16_dma_kernel<true, true>" : "conv3_f16_dma_kernel<false, true>";
-                if (c.stats) return launch_h(conv3_f16_dma_kernel<true, true>, b, dim3(gx, gy), lds_aff, s, &attr_dma[2]);
-                return launch_h(conv3_f16_dma_kernel<false, true>, b, dim3(gx, gy), lds_aff, s, &attr_dma[3]);
-            }
-            if (kernel_name) *kernel_name = c.stats ? "conv3_f16_dma_kernel<true, false>" : "conv3_f16_dma_kernel<false, false>";
-            if (c.stats) return launch_h(conv3_f16_dma_kernel<true>, b, dim3(gx, gy), lds_plain, s, &attr_dma[0]);
-            return launch_h(conv3_f16_dma_kernel<false>, b, dim3(gx, gy), lds_plain, s, &attr_dma[1]);
-        }
-    }
-    if (st == 1 && use_pipe_h()) {
-        int MF = 4;
-        fill_geometry_h(a, 1, 128 * MF);
-        long tiles = (long)a.tiles_x * a.tiles_y * a.tiles_z * c.N;
-        if (tiles * gy < 512 || a.IX * a.IY * a.IZ > 11 * 128 || w.nf == 2) {
-            MF = 2;
-            fill_geometry_h(a, 1, 128 * MF);
-            tiles = (long)a.tiles_x * a.tiles_y * a.tiles_z * c.N;
-        }
-        MI355_REQUIRE(tiles < (1l << 30), "conv grid too large");
-        MI355_REQUIRE(a.IX * a.IY * a.IZ <= (MF == 4 ? 11 : 8) * 128, "conv brick exceeds the staging slots");
-        MI355_REQUIRE((long)a.IZ * c.Hi * c.Wi < (1l << 24) && ((long)a.IZ * c.Hi * c.Wi + (long)c.Di * c.Hi * c.Wi) * 16 < (1l << 31),
-                      "volume too large for the 32-bit staging offsets");
-        a.total_tiles = (int)tiles;
-        const size_t lds_bytes = (size_t)4 * a.plane_bytes + 4 * w.nf * 32 * 2 * sizeof(float);
-        MI355_REQUIRE(lds_bytes <= 160 * 1024, "conv brick needs %zu B of LDS", lds_bytes);
-        int gx = 512 / gy;
-        gx = gx < 8 ? 8 : (gx / 8) * 8;
-        const int need = (int)((tiles + 7) / 8) * 8;
-        if (gx > need) gx = need;
-        dim3 grid(gx, gy);
-        const bool whole = a.Do % (1 << a.lz) == 0 && a.Ho % (1 << a.ly) == 0 && a.Wo % (1 << a.lx) == 0;
-        // (names = the instantiations as rocprofv3 prints them: <MF, NF, HEAD, INAFF, STRIDE, WHOLE>)
-        if (c.head_out) {
-            MI355_REQUIRE(w.nf == 1, "fused head: fp16 path supports Cout = 32 only");
-            static size_t attr_head[4] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};  // one slot per kernel: the attribute is per function
-            if (MF == 4 && whole) { if (kernel_name) *kernel_name = "conv3_f16_mfma_pipe_kernel<4, 1, true, false, 1, true>"; return launch_h(conv3_f16_mfma_pipe_kernel<4, 1, true, false, 1, true>, a, grid, lds_bytes, s, &attr_head[0]); }
-            if (MF == 4) { if (kernel_name) *kernel_name = "conv3_f16_mfma_pipe_kernel<4, 1, true, false, 1, false>"; return launch_h(conv3_f16_mfma_pipe_kernel<4, 1, true>, a, grid, lds_bytes, s, &attr_head[1]); }
-            if (kernel_name) *kernel_name = "conv3_f16_mfma_pipe_kernel<2, 1, true, false, 1, false>";
-            return launch_h(conv3_f16_mfma_pipe_kernel<2, 1, true>, a, grid, lds_bytes, s, &attr_head[2]);
-        }
-        if (c.in_scale) {  // the producer's normalisation + activation applied while the brick is staged
-            MI355_REQUIRE(whole, "fused input normalisation needs a volume of whole tiles (conv3d_f16_fuses_input_norm)");
-            static size_t attr_aff[3] = {48 * 1024, 48 * 1024, 48 * 1024};
-            if (kernel_name) *kernel_name = MF == 4 ? "conv3_f16_mfma_pipe_kernel<4, 1, false, true, 1, true>" : (w.nf == 1 ? "conv3_f16_mfma_pipe_kernel<2, 1, false, true, 1, true>" : "conv3_f16_mfma_pipe_kernel<2, 2, false, true, 1, true>");
-            if (MF == 4) return launch_h(conv3_f16_mfma_pipe_kernel<4, 1, false, true, 1, true>, a, grid, lds_bytes, s, &attr_aff[0]);
-            if (w.nf == 1) return launch_h(conv3_f16_mfma_pipe_kernel<2, 1, false, true, 1, true>, a, grid, lds_bytes, s, &attr_aff[1]);
-            return launch_h(conv3_f16_mfma_pipe_kernel<2, 2, false, true, 1, true>, a, grid, lds_bytes, s, &attr_aff[2]);
-        }
-        if (whole) {
-            static size_t attr_w[3] = {48 * 1024, 48 * 1024, 48 * 1024};
-            if (kernel_name) *kernel_name = MF == 4 ? "conv3_f16_mfma_pipe_kernel<4, 1, false, false, 1, true>" : (w.nf == 1 ? "conv3_f16_mfma_pipe_kernel<2, 1, false, false, 1, true>" : "conv3_f16_mfma_pipe_kernel<2, 2, false, false, 1, true>");
-            if (MF == 4) return launch_h(conv3_f16_mfma_pipe_kernel<4, 1, false, false, 1, true>, a, grid, lds_bytes, s, &attr_w[0]);
-            if (w.nf == 1) return launch_h(conv3_f16_mfma_pipe_kernel<2, 1, false, false, 1, true>, a, grid, lds_bytes, s, &attr_w[1]);
-            return launch_h(conv3_f16_mfma_pipe_kernel<2, 2, false, false, 1, true>, a, grid, lds_bytes, s, &attr_w[2]);
-        }
-        if (kernel_name) *kernel_name = MF == 4 ? "conv3_f16_mfma_pipe_kernel<4, 1, false, false, 1, false>" : (w.nf == 1 ? "conv3_f16_mfma_pipe_kernel<2, 1, false, false, 1, false>" : "conv3_f16_mfma_pipe_kernel<2, 2, false, false, 1, false>");
-        if (MF == 4) return launch_h(conv3_f16_mfma_pipe_kernel<4, 1>, a, grid, lds_bytes, s, &attr[0]);
-        if (w.nf == 1) return launch_h(conv3_f16_mfma_pipe_kernel<2, 1>, a, grid, lds_bytes, s, &attr[1]);
-        return launch_h(conv3_f16_mfma_pipe_kernel<2, 2>, a, grid, lds_bytes, s, &attr[2]);
-    }
-    if (st == 2 && use_pipe_h()) {  // round 3: Cout % 128 == 0 on whole 4 x 4 x 8 output tiles -> conv3d_f16_s2.hip
-        bool taken = false;
-        MI355_TRY(conv3d_f16_s2dma(w, c, s, kernel_name, &taken));
-        if (taken) return MI355_OK;
-    }
-    if (st == 2 && w.nf == 2 && !c.head_out && use_pipe_h()) {
-        // round 2: the pipelined kernel with STRIDE = 2 (register-staged, two lanes per voxel) for the large stride-2 launches
-        static int s2pipe = -1;  // MI355_S2_DMA=0: the one-tile-per-workgroup kernel instead (the switch of the f32 stride-2 kernel)
-        if (s2pipe < 0) { const char *e = getenv("MI355_S2_DMA"); s2pipe = (e && e[0] == '0') ? 0 : 1; }
-        ConvArgsH b = a;
-        fill_geometry_h(b, 2, 128);
-        const long tiles = (long)b.tiles_x * b.tiles_y * b.tiles_z * c.N;
-        const size_t lds_bytes = (size_t)4 * b.plane_bytes + 4 * w.nf * 32 * 2 * sizeof(float);
-        if (s2pipe && tiles * gy >= 768 && tiles < (1l << 30) && b.IX * b.IY * b.IZ <= 13 * 128 && lds_bytes <= 160 * 1024 &&
-            (long)b.IZ * c.Hi * c.Wi < (1l << 24) && ((long)b.IZ * c.Hi * c.Wi + (long)c.Di * c.Hi * c.Wi) * 16 < (1l << 31) && !c.in_scale) {
-            b.total_tiles = (int)tiles;
-            int gx = 256 / gy;   // one workgroup per CU: the double-buffered brick takes about 100 KB of LDS
-            gx = gx < 8 ? 8 : (gx / 8) * 8;
-            const int need = (int)((tiles + 7) / 8) * 8;
-            if (gx > need) gx = need;
-            if (kernel_name) *kernel_name = "conv3_f16_mfma_pipe_kernel<1, 2, false, false, 2, false>";
-            static size_t attr_s2 = 48 * 1024;
-            return launch_h(conv3_f16_mfma_pipe_kernel<1, 2, false, false, 2>, b, dim3(gx, gy), lds_bytes, s, &attr_s2);
-        }
-    }
-    const int MF = (st == 1) ? 2 : 1;
-    fill_geometry_h(a, st, 128 * MF);
-    const long tiles = (long)a.tiles_x * a.tiles_y * a.tiles_z * c.N;
-    MI355_REQUIRE(tiles < (1l << 30), "conv grid too large");
-    size_t lds_bytes = (size_t)2 * a.plane_bytes;
-    if (lds_bytes < 4096) lds_bytes = 4096;
-    MI355_REQUIRE(lds_bytes <= 160 * 1024, "conv brick needs %zu B of LDS", lds_bytes);
-    dim3 grid((unsigned)tiles, gy);
-    if (st == 1) {
-        if (kernel_name) *kernel_name = w.nf == 1 ? "conv3_f16_mfma_kernel<1, 2, 1>" : "conv3_f16_mfma_kernel<1, 2, 2>";
-        if (w.nf == 1) return launch_h(conv3_f16_mfma_kernel<1, 2, 1>, a, grid, lds_bytes, s, &attr[3]);
-        return launch_h(conv3_f16_mfma_kernel<1, 2, 2>, a, grid, lds_bytes, s, &attr[4]);
-    }
-    if (kernel_name) *kernel_name = w.nf == 1 ? "conv3_f16_mfma_kernel<2, 1, 1>" : "conv3_f16_mfma_kernel<2, 1, 2>";
-    if (w.nf == 1) return launch_h(conv3_f16_mfma_kernel<2, 1, 1>, a, grid, lds_bytes, s, &attr[5]);
-    return launch_h(conv3_f16_mfma_kernel<2, 1, 2>, a, grid, lds_bytes, s, &attr[6]);
+    if (p.ksplit == 1) return launch_row(*p.row, grid, p.lds_bytes, s, &a);
+    float *partial = nullptr;
+    const long out_elems = (long)c.N * a.Do * a.Ho * a.Wo * w.cout;
+    MI355_TRY(device_scratch(SCR_SPLITK_F16, s, (size_t)p.ksplit * out_elems * sizeof(float), (void **)&partial));
+    a.ksplit = p.ksplit; a.partial = partial; a.out_elems = out_elems;
+    MI355_TRY(launch_row(*p.row, grid, p.lds_bytes, s, &a));
+    const long total4 = out_elems / 4;
+    hipLaunchKernelGGL(splitk_finish_f16_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, partial, p.ksplit, total4, c.act, c.slope, c.out,
+                       w.cout, (long)a.Do * a.Ho * a.Wo);
+    MI355_HIP(hipGetLastError());
+    return MI355_OK;
 }
 
 }  // namespace mi355

@@ -31,7 +31,7 @@
 // 0.42-busy matrix pipe as issue stalls.  Green on every test, and SLOWER: <true, 128> 751 against 860 TFLOP/s, <false, 64> 392
 // against 469 (same bench, boxes 6 % apart on the stride-1 kernels).  The pipe is not waiting for this wave's instruction
 // stream: a chunk's 52-KiB brick arrives in ~8 000 cycles whoever asks for it.
-#include "kernels.h"
+#include "conv_plan.h"
 
 #include <cstdlib>
 
@@ -326,55 +326,45 @@ __global__ __launch_bounds__(256, 1) void conv3_f16_s2dma_kernel(S2ArgsH p) {
 #undef S2_WWAIT
 }
 
-// Launches the kernel above when the call fits it; *taken says whether it did (the caller falls back to the older kernels).
-int conv3d_f16_s2dma(const ConvWeightsH &w, const ConvCallH &c, hipStream_t s, const char **kernel_name, bool *taken) {
+static KernelRow s2h_rows[] = {
+    MI355_KERNEL_ROW(conv3_f16_s2dma_kernel<true, 128>),
+    MI355_KERNEL_ROW(conv3_f16_s2dma_kernel<false, 128>),
+    MI355_KERNEL_ROW(conv3_f16_s2dma_kernel<true, 64>),
+    MI355_KERNEL_ROW(conv3_f16_s2dma_kernel<false, 64>),
+};
+
+// Does the kernel above take this call (otherwise the older stride-2 kernels do)?  One input tensor, whole 4 x 4 x 8 output tiles,
+// Cout % 64 == 0 and enough tiles for one persistent workgroup per CU.
+bool plan_f16_s2dma(const ConvWeightsH &w, const ConvCallH &c, ConvPlan *p) {
     typedef S2GeomH G;
-    *taken = false;
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("MI355_F16_S2"); on = (e && e[0] == '0') ? 0 : 1; }
-    if (!on || w.stride != 2 || w.nf != 2 || w.cout % 64 != 0 || c.head_out || c.C1 != 0 || c.in_scale || c.C0 != w.cin_pad || c.C0 % 16 != 0) return MI355_OK;
-    if ((c.Di | c.Hi | c.Wi) & 1) return MI355_OK;
+    if (!env_switch("MI355_F16_S2") || w.stride != 2 || w.nf != 2 || w.cout % 64 != 0 || c.head_out || c.C1 != 0 || c.in_scale || c.C0 != w.cin_pad || c.C0 % 16 != 0) return false;
+    if ((c.Di | c.Hi | c.Wi) & 1) return false;
     const int Do = c.Di / 2, Ho = c.Hi / 2, Wo = c.Wi / 2;
-    if (Do % G::TZ || Ho % G::TY || Wo % G::TX) return MI355_OK;
-    const int tiles_x = Wo / G::TX, tiles_y = Ho / G::TY, tiles_z = Do / G::TZ;
-    const long tiles = (long)tiles_x * tiles_y * tiles_z * c.N;
+    if (Do % G::TZ || Ho % G::TY || Wo % G::TX) return false;
+    const TileGeom g = fixed_tile(Do, Ho, Wo, 2, 2, 3, G::IZ, G::IY, G::IX);
+    const long tiles = g.tiles_per_n() * c.N;
     const int cw = w.cout % 128 == 0 ? 128 : 64;
     const int gy = w.cout / cw;
-    if (tiles * gy < 256 || tiles >= (1l << 30)) return MI355_OK;
-    if ((long)G::IZ * c.Hi * c.Wi >= (1l << 24) || (long)G::IZ * c.Hi * c.Wi * 16 >= (1l << 32) || (long)Do * Ho * Wo * 64 >= (1l << 32)) return MI355_OK;
+    if (tiles * gy < 256 || tiles >= (1l << 30)) return false;
+    if ((long)G::IZ * c.Hi * c.Wi >= (1l << 24) || (long)G::IZ * c.Hi * c.Wi * 16 >= (1l << 32) || (long)Do * Ho * Wo * 64 >= (1l << 32)) return false;
+    plan_set(p, find_row(s2h_rows, "conv3_f16_s2dma_kernel<%s, %d>", tf(c.stats != nullptr), cw), FAM_S2DMA, g, tiles, persistent_grid_x(256, gy, tiles), gy,
+             G::LDS_BYTES);
+    p->nf = cw / 32;
+    return true;
+}
+
+int launch_f16_s2dma(const ConvWeightsH &w, const ConvCallH &c, const ConvPlan &p, hipStream_t s) {
     S2ArgsH a;
     a.in = c.in0; a.wp = w.wp_dev; a.bias = w.bias_dev; a.out = c.out; a.stats = c.stats;
-    a.C = c.C0; a.N = c.N; a.Di = c.Di; a.Hi = c.Hi; a.Wi = c.Wi; a.Do = Do; a.Ho = Ho; a.Wo = Wo; a.Cout = w.cout;
+    a.C = c.C0; a.N = c.N; a.Di = c.Di; a.Hi = c.Hi; a.Wi = c.Wi; a.Do = c.Di / 2; a.Ho = c.Hi / 2; a.Wo = c.Wi / 2; a.Cout = w.cout;
     a.nchunks = w.cin_pad / 16; a.act = c.act; a.slope = c.slope;
-    a.total_tiles = (int)tiles;
-    a.div_tiles_per_n = make_fastdiv(tiles_x * tiles_y * tiles_z);
-    a.order = make_tile_order(tiles_x, tiles_y, tiles_z);
+    a.total_tiles = (int)p.tiles;
+    a.div_tiles_per_n = make_fastdiv((uint32_t)p.g.tiles_per_n());
+    a.order = make_tile_order(p.g.tiles_x, p.g.tiles_y, p.g.tiles_z);
     void *zeros = nullptr;
     MI355_TRY(device_scratch(SCR_ZEROS, s, 256, &zeros, true));
     a.zeros = zeros;
-    int gx = 256 / gy;
-    gx = gx < 8 ? 8 : (gx / 8) * 8;
-    const int need = (int)((tiles + 7) / 8) * 8;
-    if (gx > need) gx = need;
-    static bool attr_set[4] = {false, false, false, false};
-    auto launch = [&](auto kern, int idx) -> int {
-        if (!attr_set[idx]) {
-            MI355_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES));
-            attr_set[idx] = true;
-        }
-        hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), G::LDS_BYTES, s, a);
-        MI355_HIP(hipGetLastError());
-        return MI355_OK;
-    };
-    *taken = true;
-    if (cw == 64) {
-        if (kernel_name) *kernel_name = c.stats ? "conv3_f16_s2dma_kernel<true, 64>" : "conv3_f16_s2dma_kernel<false, 64>";
-        if (c.stats) return launch(conv3_f16_s2dma_kernel<true, 64>, 2);
-        return launch(conv3_f16_s2dma_kernel<false, 64>, 3);
-    }
-    if (kernel_name) *kernel_name = c.stats ? "conv3_f16_s2dma_kernel<true, 128>" : "conv3_f16_s2dma_kernel<false, 128>";
-    if (c.stats) return launch(conv3_f16_s2dma_kernel<true, 128>, 0);
-    return launch(conv3_f16_s2dma_kernel<false, 128>, 1);
+    return launch_row(*p.row, dim3(p.gx, p.gy), p.lds_bytes, s, &a);
 }
 
 }  // namespace mi355

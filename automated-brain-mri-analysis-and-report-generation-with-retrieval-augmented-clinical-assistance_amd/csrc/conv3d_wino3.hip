@@ -27,7 +27,7 @@
 // Numerics: U = G w G^T per axis in fp64, rounded once; tests/diagnostics/wino3d_numerics.py (CPU emulation of the whole
 // network, sequential fp32 accumulation chains) gives a smaller logit error than the 2-D form (shorter chains: K = Cin
 // per component instead of 3 Cin).
-#include "kernels.h"
+#include "conv_plan.h"
 
 #include <cstdlib>
 #include <vector>
@@ -782,18 +782,13 @@ void pack_conv_weights_wino3(const float *w, int cin, int cin_pad, int cout, std
                             }
 }
 
-static int wino3_mode() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("MI355_WINO3"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v;
-}
-bool conv3d_wino3_enabled() { return wino3_mode() != 0; }
+bool conv3d_wino3_enabled() { return env_switch("MI355_WINO3"); }
 
 // Does the F(2x2x2, 3x3x3) kernel take this call?  Stride 1, whole 4 x 8 x 8 tiles, 16-channel chunks on both halves of a virtual
 // concat, enough tiles to fill the chip; the fused head needs Cout = 32; the fused input norm (INAFF) a single input tensor and
 // the statistics instantiation (its consumer is a block of the same Instance/GroupNorm stage).
 static bool wino3_fits(const ConvWeights &w, const ConvCall &c) {
-    if (!wino3_mode() || !w.wp3_dev || w.stride != 1) return false;
+    if (!conv3d_wino3_enabled() || !w.wp3_dev || w.stride != 1) return false;
     if (c.head_out && (w.cout != 32 || c.stats || c.head_ncls < 1 || c.head_ncls > 4 || !c.head_w || !c.head_b)) return false;
     if (c.head_out && (long)c.head_ncls * c.Di * c.Hi * c.Wi >= (1l << 30)) return false;  // the head's lane offset is 32 bits
     if (c.in_scale && (c.C1 != 0 || !c.stats || c.head_out || !c.in_shift)) return false;
@@ -811,61 +806,45 @@ static bool wino3_fits(const ConvWeights &w, const ConvCall &c) {
 
 // Can the conv `w` of call shape `c` (N, Di, Hi, Wi, C0, stats set as it will be called) apply its producer's normalisation itself?
 bool conv3d_wino3_fuses_input_norm(const ConvWeights &w, const ConvCall &c) {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("MI355_FUSE_NORM"); on = (e && e[0] == '0') ? 0 : 1; }
-    if (!on) return false;
+    if (!env_switch("MI355_FUSE_NORM")) return false;
     ConvCall t = c;
     static const float dummy = 0.f;
     t.in_scale = &dummy; t.in_shift = &dummy;
     return wino3_fits(w, t);
 }
 
-int conv3d_wino3_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, const char **kernel_name, bool *taken) {
-    *taken = false;
-    if (!wino3_fits(w, c)) return MI355_OK;
-    const int tx = c.Wi / 8, ty = c.Hi / 8, tz = c.Di / 4;
-    const long tiles = (long)tx * ty * tz * c.N;
+static KernelRow wino3_rows[] = {
+    MI355_KERNEL_ROW(conv3_f32_wino3_kernel<0, false>),
+    MI355_KERNEL_ROW(conv3_f32_wino3_kernel<1, false>),
+    MI355_KERNEL_ROW(conv3_f32_wino3_kernel<2, false>),
+    MI355_KERNEL_ROW(conv3_f32_wino3_kernel<2, true>),
+};
+
+bool plan_wino3(const ConvWeights &w, const ConvCall &c, ConvPlan *p) {
+    if (!wino3_fits(w, c)) return false;
+    const TileGeom g = fixed_tile(c.Di, c.Hi, c.Wi, 2, 3, 3, W3_IZ, W3_IY, W3_IX);
+    const long tiles = g.tiles_per_n() * c.N;
+    const int gy = w.cout / 32;  // one persistent workgroup per CU
+    plan_set(p, find_row(wino3_rows, "conv3_f32_wino3_kernel<%d, %s>", c.in_scale ? 2 : (c.head_out ? 1 : (c.stats ? 2 : 0)), tf(c.in_scale != nullptr)),
+             FAM_WINO3, g, tiles, persistent_grid_x(256, gy, tiles), gy, W3_LDS_BYTES);
+    p->pack = PACK_WINO3; p->nf = 1;
+    return true;
+}
+
+int launch_wino3(const ConvWeights &w, const ConvCall &c, const ConvPlan &p, hipStream_t s) {
     Wino3Args a;
     a.in0 = c.in0; a.in1 = c.in1; a.wp = w.wp3_dev; a.bias = w.bias_dev; a.out = c.out; a.stats = c.stats;
     a.C0 = c.C0; a.C1 = c.C1; a.N = c.N; a.D = c.Di; a.H = c.Hi; a.W = c.Wi; a.Cout = w.cout;
     a.nchunks = w.cin_pad / 16; a.act = c.act; a.slope = c.slope;
-    a.total_tiles = (int)tiles;
-    a.div_tiles_per_n = make_fastdiv(tx * ty * tz);
-    a.order = make_tile_order(tx, ty, tz);
+    a.total_tiles = (int)p.tiles;
+    a.div_tiles_per_n = make_fastdiv((uint32_t)p.g.tiles_per_n());
+    a.order = make_tile_order(p.g.tiles_x, p.g.tiles_y, p.g.tiles_z);
     a.head_w = c.head_w; a.head_b = c.head_b; a.head_out = c.head_out; a.head_ncls = c.head_ncls;
     a.in_scale = c.in_scale; a.in_shift = c.in_shift; a.in_slope = c.in_act == ACT_LRELU ? c.slope : 1.0f;
     float *zeros = nullptr;
     MI355_TRY(device_scratch(SCR_ZEROS, s, 256, (void **)&zeros, true));
     a.zeros = zeros;
-    static bool attr_set = false;
-    if (!attr_set) {
-        MI355_HIP(hipFuncSetAttribute((const void *)conv3_f32_wino3_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W3_LDS_BYTES));
-        MI355_HIP(hipFuncSetAttribute((const void *)conv3_f32_wino3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W3_LDS_BYTES));
-        MI355_HIP(hipFuncSetAttribute((const void *)conv3_f32_wino3_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W3_LDS_BYTES));
-        MI355_HIP(hipFuncSetAttribute((const void *)conv3_f32_wino3_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W3_LDS_BYTES));
-        attr_set = true;
-    }
-    const int gy = w.cout / 32;
-    int gx = 256 / gy;                      // one persistent workgroup per CU
-    gx = gx < 8 ? 8 : (gx / 8) * 8;         // multiple of 8: blockIdx.x & 7 labels the XCD group
-    const int need = (int)((tiles + 7) / 8) * 8;
-    if (gx > need) gx = need;
-    if (c.in_scale) {
-        if (kernel_name) *kernel_name = "conv3_f32_wino3_kernel<2, true>";
-        hipLaunchKernelGGL((conv3_f32_wino3_kernel<2, true>), dim3(gx, gy), dim3(256), W3_LDS_BYTES, s, a);
-    } else if (c.head_out) {
-        if (kernel_name) *kernel_name = "conv3_f32_wino3_kernel<1, false>";
-        hipLaunchKernelGGL(conv3_f32_wino3_kernel<1>, dim3(gx, gy), dim3(256), W3_LDS_BYTES, s, a);
-    } else if (c.stats) {
-        if (kernel_name) *kernel_name = "conv3_f32_wino3_kernel<2, false>";
-        hipLaunchKernelGGL(conv3_f32_wino3_kernel<2>, dim3(gx, gy), dim3(256), W3_LDS_BYTES, s, a);
-    } else {
-        if (kernel_name) *kernel_name = "conv3_f32_wino3_kernel<0, false>";
-        hipLaunchKernelGGL(conv3_f32_wino3_kernel<0>, dim3(gx, gy), dim3(256), W3_LDS_BYTES, s, a);
-    }
-    MI355_HIP(hipGetLastError());
-    *taken = true;
-    return MI355_OK;
+    return launch_row(*p.row, dim3(p.gx, p.gy), p.lds_bytes, s, &a);
 }
 
 }  // namespace mi355

@@ -24,16 +24,27 @@ struct ConvWeights {
     size_t wp_bytes = 0;
 };
 
+// Which packs a layer gets, or why the layer is refused (pure: conv_weights_upload follows it; a plan can be computed from it
+// without uploading anything).
+struct ConvPackLayout {
+    bool mfma = false;  // the MFMA pack exists (cout % 32 == 0, cin_pad % 8 == 0); otherwise the layer runs on the direct kernel
+    int cc = 0, nf = 1;
+    bool pipe = false;
+    bool c16 = false, wino2 = false, wino3 = false;  // the second 16-channel-chunk pack, the F(2x2,3x3) and F(2x2x2,3x3x3) packs
+};
+int conv_pack_layout(int cin, int cin_pad, int cout, int stride, ConvPackLayout *out);
 int conv_weights_upload(const float *w_host, const float *bias_host, int cin, int cin_pad, int cout,
                         int stride, bool keep_plain, ConvWeights *out);
 void conv_weights_free(ConvWeights *w);
 
-struct ConvCall {
-    const float *in0 = nullptr;  // [N,Di,Hi,Wi,C0]
-    const float *in1 = nullptr;  // [N,Di,Hi,Wi,C1] second half of a virtual concat, or null
+// One 3x3x3 conv call; T = the element type of the activations (ConvCall = fp32 NDHWC, ConvCallH = fp16 channel-blocked).
+template <typename T>
+struct ConvCallT {
+    const T *in0 = nullptr;  // [N,Di,Hi,Wi,C0]
+    const T *in1 = nullptr;  // [N,Di,Hi,Wi,C1] second half of a virtual concat, or null
     int C0 = 0, C1 = 0;
     int N = 0, Di = 0, Hi = 0, Wi = 0;
-    float *out = nullptr;     // [N,Do,Ho,Wo,Cout]
+    T *out = nullptr;         // [N,Do,Ho,Wo,Cout]
     double *stats = nullptr;  // [N][Cout][2] (sum, sum of squares) accumulated when non-null
     int act = ACT_NONE;
     float slope = 0.01f;
@@ -43,16 +54,19 @@ struct ConvCall {
     float *head_out = nullptr;
     int head_ncls = 0;
     // in0 is the RAW conv output of the previous block: apply x * in_scale[n][c] + in_shift[n][c] (+ LeakyReLU when in_act) while
-    // staging it (only where conv3d_wino3_fuses_input_norm says so: the F(2x2x2,3x3x3) kernel normalises its brick in LDS)
+    // staging it (only where conv3d_wino3_fuses_input_norm / conv3d_f16_fuses_input_norm says so: the F(2x2x2,3x3x3) kernel
+    // normalises its brick in LDS, the fp16 kernels while staging)
     const float *in_scale = nullptr, *in_shift = nullptr;
     int in_act = ACT_NONE;
 };
+typedef ConvCallT<float> ConvCall;
+typedef ConvCallT<_Float16> ConvCallH;
 int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, const char **kernel_name = nullptr);
-// F(2x2x2, 3x3x3) kernel (conv3d_wino3.hip): launches when the call fits it and says so in *taken
+// F(2x2x2, 3x3x3) kernel (conv3d_wino3.hip)
 void pack_conv_weights_wino3(const float *w, int cin, int cin_pad, int cout, std::vector<float> &out);
 bool conv3d_wino3_enabled();
 bool conv3d_wino3_fuses_input_norm(const ConvWeights &w, const ConvCall &c);
-int conv3d_wino3_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, const char **kernel_name, bool *taken);
+int plan_conv_direct(const ConvWeights &w, const ConvCall &c);  // the direct kernel's own refusals
 int conv3d_direct_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s);
 
 // first conv of the network (Cin <= 4): x-taps folded into K, NDHW4 input (conv_stem.hip)
@@ -72,29 +86,12 @@ struct ConvWeightsH {
     _Float16 *wp_dev = nullptr;
     float *bias_dev = nullptr;
 };
+int conv_pack_layout_f16(int cin, int cin_pad, int cout, int stride, int *nf);  // as conv_pack_layout: the refusals and nf
 int conv_weights_upload_f16(const float *w_host, const float *bias_host, int cin, int cin_pad, int cout, int stride,
                             ConvWeightsH *out);
 void conv_weights_free_f16(ConvWeightsH *w);
-struct ConvCallH {
-    const _Float16 *in0 = nullptr, *in1 = nullptr;
-    int C0 = 0, C1 = 0;
-    int N = 0, Di = 0, Hi = 0, Wi = 0;
-    _Float16 *out = nullptr;
-    double *stats = nullptr;
-    int act = ACT_NONE;
-    float slope = 0.01f;
-    const float *head_w = nullptr, *head_b = nullptr;  // fused segmentation head, see ConvCall
-    float *head_out = nullptr;
-    int head_ncls = 0;
-    // in0 is the RAW conv output of the previous block: apply x * in_scale[n][c] + in_shift[n][c] (+ LeakyReLU when in_act)
-    // while staging it (only where conv3d_f16_fuses_input_norm says so)
-    const float *in_scale = nullptr, *in_shift = nullptr;
-    int in_act = ACT_NONE;
-};
 bool conv3d_f16_fuses_input_norm(const ConvWeightsH &w, const ConvCallH &c);
 int conv3d_mfma_f16(const ConvWeightsH &w, const ConvCallH &c, hipStream_t s, const char **kernel_name = nullptr);
-// stride-2 LDS-DMA kernel (conv3d_f16_s2.hip): launches when the call fits it and says so in *taken
-int conv3d_f16_s2dma(const ConvWeightsH &w, const ConvCallH &c, hipStream_t s, const char **kernel_name, bool *taken);
 
 // ---------------------------------------------------------------- transposed conv k=2 s=2
 struct TConvWeights {

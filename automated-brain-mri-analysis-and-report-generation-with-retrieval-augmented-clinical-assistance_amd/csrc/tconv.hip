@@ -8,7 +8,7 @@
 // straight from global (16 B per lane: 4 channels of one voxel; lanes 0-31 / 32-63 take the two
 // halves of an 8-channel group, same K pairing as conv3d.hip); weight fragments come from a
 // host-permuted pack.  1.6 % of the network's flops, so no LDS staging.
-#include "kernels.h"
+#include "conv_plan.h"
 
 #include <vector>
 
@@ -244,8 +244,7 @@ int tconv2_mfma_f32(const TConvWeights &w, const float *in, int N, int D, int H,
                     hipStream_t s, const char **kernel_name) {
     const long M = (long)N * D * H * W;
     MI355_REQUIRE(M > 0 && M < (1l << 30), "tconv: %ld voxels out of range", M);
-    static int v3 = -1;
-    if (v3 < 0) { const char *e = getenv("MI355_TCONV_V3"); v3 = (e && e[0] == '0') ? 0 : 1; }
+    const bool v3 = env_switch("MI355_TCONV_V3");
     const long ntiles = (M + 127) / 128;
     // (Cin = 64 only: at Cin = 128 - 128 weight registers, one workgroup per CU - version 3 measured slower than version 2,
     //  3.4 against 3.0 ms for 128 -> 64 @ 8 x 32^3)
@@ -495,8 +494,7 @@ int tconv2_mfma_f16(const TConvWeightsH &w, const _Float16 *in, int N, int D, in
     if (kernel_name) *kernel_name = "tconv2_f16_mfma_v2_kernel";
     const long M = (long)N * D * H * W;
     MI355_REQUIRE(M > 0 && M < (1l << 30), "tconv: %ld voxels out of range", M);
-    static int v3 = -1;
-    if (v3 < 0) { const char *e = getenv("MI355_TCONV_V3"); v3 = (e && e[0] == '0') ? 0 : 1; }
+    const bool v3 = env_switch("MI355_TCONV_V3");
     const long ntiles = (M + 127) / 128;
     if (v3 && (w.cin == 32 || w.cin == 64 || w.cin == 128) && ntiles >= 1024) {
         // persistent: two workgroups per CU and cout block share the 512 resident slots

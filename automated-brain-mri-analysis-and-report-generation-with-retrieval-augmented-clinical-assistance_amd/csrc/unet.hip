@@ -14,7 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "kernels.h"
+#include "conv_plan.h"
 
 namespace mi355 {
 
@@ -292,12 +292,31 @@ struct ProfScope {
     ~ProfScope() { if (on) (void)hipEventRecord(net->prof[idx].b, s); }
 };
 
-static std::string conv_kernel_name(const ConvWeights &w) {
-    if (!w.wp_dev) return "conv3_direct_kernel";
-    char buf[64];
-    if (w.pipe) snprintf(buf, sizeof(buf), "conv3_f32_mfma_pipe_kernel<*, %d>", w.nf);  // MF (4|2) is chosen per launch
-    else snprintf(buf, sizeof(buf), "conv3_f32_mfma_kernel<%d, %d, %d, %d>", w.stride, w.cc, w.stride == 1 ? 2 : 1, w.nf);
-    return buf;
+// The fused operands a conv call may carry besides its first input (plain pointers; the single-op fp16 path converts x1 first).
+namespace {
+struct FusedOps {
+    const void *x1 = nullptr;  // [n,d,h,w,c1] plain NDHWC, or null
+    int c1 = 0;
+    const float *in_scale = nullptr, *in_shift = nullptr;  // [n][cin - c1] device fp32, or null
+    int in_act = ACT_NONE;
+    const float *head_w = nullptr, *head_b = nullptr;  // [ncls][cout], [ncls] device fp32
+    float *head_out = nullptr;                         // [n][ncls][Vo] fp32 logits; the conv output is then not stored
+    int head_ncls = 0;
+    bool any() const { return x1 || c1 || in_scale || in_shift || head_w || head_b || head_out; }
+};
+}  // namespace
+
+// The call struct of one conv: x0 holds the first cin - f.c1 channels, f the fused operands.
+template <typename T>
+static ConvCallT<T> make_call(const void *x0, int cin, int N, int Di, int Hi, int Wi, void *out, double *stats, int act, float slope,
+                              const FusedOps &f = FusedOps()) {
+    ConvCallT<T> c;
+    c.in0 = (const T *)x0; c.C0 = cin - f.c1; c.in1 = (const T *)f.x1; c.C1 = f.c1;
+    c.N = N; c.Di = Di; c.Hi = Hi; c.Wi = Wi; c.out = (T *)out; c.act = act; c.slope = slope;
+    c.stats = stats;
+    c.in_scale = f.in_scale; c.in_shift = f.in_shift; c.in_act = f.in_act;
+    c.head_w = f.head_w; c.head_b = f.head_b; c.head_out = f.head_out; c.head_ncls = f.head_ncls;
+    return c;
 }
 
 // One ConvDropoutNormNonlin / ConvDropoutNonlinNorm block.
@@ -323,35 +342,24 @@ static int run_block(mi355_unet *net, const Plan &pl, const ConvLayer &L, const 
         const double es = f16 ? 2.0 : 4.0;
         const double flops = 2.0 * N * Vo * L.cout * (double)L.cin * 27.0;
         const double bytes = es * ((double)N * Di * Hi * Wi * (C0 + C1) + (double)N * Vo * L.cout + (double)L.cout * L.cin * 27.0);
+        FusedOps f;
+        f.x1 = in1; f.c1 = C1;
+        if (head_logits_out) { f.head_w = net->head.w_dev; f.head_b = net->head.b_dev; f.head_ncls = net->head.ncls; f.head_out = head_logits_out; }
+        if (in_norm) {  // in0 is the previous block's raw conv output: normalise (+ LeakyReLU) while staging (fp32: the F(2x2x2,3x3x3) kernel, in LDS)
+            f.in_scale = (const float *)(pl.arena + pl.scale2_off); f.in_shift = (const float *)(pl.arena + pl.shift2_off);
+            f.in_act = net->nonlin_first ? ACT_NONE : ACT_LRELU;
+        }
+        const char *kname = nullptr;
         if (L.is_stem) {
             ProfScope ps(net, s, f16 ? "conv3_stem_f16_kernel" : "conv3_stem_f32_kernel", flops, bytes);
             MI355_TRY(conv3d_stem(L.stem, in0, N, Di, Hi, Wi, out, stats_arg, act, net->slope, s));
         } else if (f16) {
-            ConvCallH c;
-            c.in0 = (const _Float16 *)in0; c.in1 = (const _Float16 *)in1; c.C0 = C0; c.C1 = C1;
-            c.N = N; c.Di = Di; c.Hi = Hi; c.Wi = Wi; c.out = (_Float16 *)out; c.slope = net->slope;
-            c.act = act; c.stats = stats_arg;
-            if (head_logits_out) { c.head_w = net->head.w_dev; c.head_b = net->head.b_dev; c.head_ncls = net->head.ncls; c.head_out = head_logits_out; }
-            if (in_norm) {  // in0 is the previous block's raw conv output: normalise (+ LeakyReLU) while staging
-                c.in_scale = (const float *)(pl.arena + pl.scale2_off); c.in_shift = (const float *)(pl.arena + pl.shift2_off);
-                c.in_act = net->nonlin_first ? ACT_NONE : ACT_LRELU;
-            }
-            const char *kname = nullptr;
             ProfScope ps(net, s, "conv3_f16", flops, bytes);
-            MI355_TRY(conv3d_mfma_f16(L.wh, c, s, &kname));
+            MI355_TRY(conv3d_mfma_f16(L.wh, make_call<_Float16>(in0, C0 + C1, N, Di, Hi, Wi, out, stats_arg, act, net->slope, f), s, &kname));
             ps.rename(kname);
         } else {
-            ConvCall c;
-            c.in0 = (const float *)in0; c.in1 = (const float *)in1; c.C0 = C0; c.C1 = C1;
-            c.N = N; c.Di = Di; c.Hi = Hi; c.Wi = Wi; c.out = (float *)out; c.slope = net->slope;
-            c.act = act; c.stats = stats_arg;
-            if (head_logits_out) { c.head_w = net->head.w_dev; c.head_b = net->head.b_dev; c.head_ncls = net->head.ncls; c.head_out = head_logits_out; }
-            if (in_norm) {  // in0 is the previous block's raw conv output: the F(2x2x2,3x3x3) kernel normalises (+ LeakyReLU) its brick in LDS
-                c.in_scale = (const float *)(pl.arena + pl.scale2_off); c.in_shift = (const float *)(pl.arena + pl.shift2_off);
-                c.in_act = net->nonlin_first ? ACT_NONE : ACT_LRELU;
-            }
-            const char *kname = nullptr;
-            ProfScope ps(net, s, conv_kernel_name(L.w), flops, bytes);
+            const ConvCall c = make_call<float>(in0, C0 + C1, N, Di, Hi, Wi, out, stats_arg, act, net->slope, f);
+            ProfScope ps(net, s, "conv3_direct_kernel", flops, bytes);  // (renamed to the instantiation the MFMA dispatch picks)
             if (L.w.wp_dev) MI355_TRY(conv3d_mfma_f32(L.w, c, s, &kname));
             else MI355_TRY(conv3d_direct_f32(L.w, c, s));
             ps.rename(kname);
@@ -379,18 +387,13 @@ static int run_block(mi355_unet *net, const Plan &pl, const ConvLayer &L, const 
 // must be a launch of the F(2x2x2,3x3x3) kernel, which normalises its brick in LDS (conv3d_wino3_fuses_input_norm).
 static bool can_defer_norm(const mi355_unet *net, const ConvLayer &L, const ConvLayer &Ln, int N, int Dl, int Hl, int Wl) {
     if (!L.runtime_norm || Ln.stride != 1 || Ln.is_stem || Ln.cin != L.cout) return false;
+    double *const stats = Ln.runtime_norm ? (double *)1 : nullptr;  // (only tested for null)
     if (net->dtype == MI355_F16) {
         if ((!L.is_stem && !L.wh.wp_dev) || !Ln.wh.wp_dev) return false;
-        ConvCallH c;
-        c.C0 = L.cout; c.C1 = 0; c.N = N; c.Di = Dl; c.Hi = Hl; c.Wi = Wl;
-        c.stats = Ln.runtime_norm ? (double *)1 : nullptr;  // (only tested for null)
-        return conv3d_f16_fuses_input_norm(Ln.wh, c);
+        return conv3d_f16_fuses_input_norm(Ln.wh, make_call<_Float16>(nullptr, L.cout, N, Dl, Hl, Wl, nullptr, stats, ACT_NONE, 0.f));
     }
     if (!Ln.w.wp3_dev) return false;
-    ConvCall c;
-    c.C0 = L.cout; c.C1 = 0; c.N = N; c.Di = Dl; c.Hi = Hl; c.Wi = Wl;
-    c.stats = Ln.runtime_norm ? (double *)1 : nullptr;
-    return conv3d_wino3_fuses_input_norm(Ln.w, c);
+    return conv3d_wino3_fuses_input_norm(Ln.w, make_call<float>(nullptr, L.cout, N, Dl, Hl, Wl, nullptr, stats, ACT_NONE, 0.f));
 }
 
 // x0: [N,D,H,W,cin_pad] already in the arena at pl.x0_off.  Returns the last decoder feature map.
@@ -451,12 +454,7 @@ static int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H
         for (size_t i = 0; i < net->dec[u].size(); ++i) {
             const ConvLayer &L = net->dec[u][i];
             void *out = (i & 1) ? freeAB : buf(3, l);
-            static int fuse = -1;
-            if (fuse < 0) {
-                const char *e = getenv("MI355_FUSE_HEAD"), *ci = getenv("MI355_CONV_IMPL");
-                fuse = (e && e[0] == '0') ? 0 : 1;
-                if (f16 && ci && ci[0] == '0') fuse = 0;  // the fp16 fused epilogue exists in the pipelined kernel only
-            }
+            const bool fuse = env_switch("MI355_FUSE_HEAD") && !(f16 && conv_impl() == 0);  // the fp16 fused epilogue exists in the pipelined kernel only
             const bool last = is_logits && (u == np - 1) && (i + 1 == net->dec[u].size());
             const int lnf = f16 ? L.wh.nf : L.w.nf;
             const bool has_pack = f16 ? (L.wh.wp_dev != nullptr) : (L.w.wp_dev != nullptr);
@@ -468,9 +466,7 @@ static int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H
                 *feat = lg; *feat_c = net->head.ncls;
                 return MI355_OK;
             }
-            static int fuse_norm = -1;
-            if (fuse_norm < 0) { const char *e = getenv("MI355_FUSE_NORM"); fuse_norm = (e && e[0] == '0') ? 0 : 1; }
-            const bool to_head = fuse_norm && head_norm && L.runtime_norm && (u == np - 1) && (i + 1 == net->dec[u].size());
+            const bool to_head = env_switch("MI355_FUSE_NORM") && head_norm && L.runtime_norm && (u == np - 1) && (i + 1 == net->dec[u].size());
             const bool defer = to_head || (i + 1 < net->dec[u].size() && can_defer_norm(net, L, net->dec[u][i + 1], N, Dl, Hl, Wl));
             MI355_TRY(run_block(net, pl, L, in0, C0, in1, C1, N, Dl, Hl, Wl, out, s, nullptr, defer, pending_d));
             if (to_head) {
@@ -896,56 +892,58 @@ extern "C" int mi355_sw_predict(const mi355_unet_t *nets, int n_nets, const floa
     return rc;
 }
 
+// The single-op fp16 entry points take and return PLAIN NDHWC tensors (include/mi355_nnunet.h); the kernels work on
+// channel-blocked ones (common.h), so the operands pass through ndhwc_to_b8 / b8_to_ndhwc here.
+namespace {
+struct TmpBuf {
+    void *p = nullptr;
+    ~TmpBuf() { if (p) (void)hipFree(p); }
+};
+// the uploaded weights of a single-op call, freed on every exit
+template <typename W, void (*FREE)(W *)>
+struct TmpWeights {
+    W w;
+    ~TmpWeights() { FREE(&w); }
+};
+}  // namespace
+
+// the network's first-layer kernel instead of the generic dispatch (plain NDHW4 input)
+static bool single_op_stem(int cin, int stride, int impl, int cout, const FusedOps &f) {
+    return cin == 4 && stride == 1 && impl == 0 && cout % 32 == 0 && !f.any();
+}
+// end of a single-op call: wait for the stream and report a kernel that failed asynchronously
+static int synced(int rc, hipStream_t s, const char *what) {
+    hipError_t e = hipStreamSynchronize(s);
+    if (rc == MI355_OK && e != hipSuccess) { set_error("%s kernel failed: %s", what, hipGetErrorString(e)); rc = MI355_ERR_HIP; }
+    return rc;
+}
+
 // `sums` (device, [n][cout][2] doubles, zeroed here) != nullptr: the launch also carries the Instance/GroupNorm statistics
 // epilogue (sum x, sum x^2 of its output per sample and channel) exactly as a run-time-norm block of the network does.
 // `f` (optional): the fused operands of a network conv (ConvCall): the second half of a virtual concat, the producer's
 // normalisation applied while staging, the 1x1x1 head.  They go to the dispatchers unchanged (mi355_conv3d_fused_ndhwc).
-namespace {
-struct FusedOps {
-    const void *x1 = nullptr;  // [n,d,h,w,c1] plain NDHWC, or null
-    int c1 = 0;
-    const float *in_scale = nullptr, *in_shift = nullptr;  // [n][cin - c1] device fp32, or null
-    int in_act = ACT_NONE;
-    const float *head_w = nullptr, *head_b = nullptr;  // [ncls][cout], [ncls] device fp32
-    float *head_out = nullptr;                         // [n][ncls][Vo] fp32 logits; the conv output is then not stored
-    int head_ncls = 0;
-    bool any() const { return x1 || c1 || in_scale || in_shift || head_w || head_b || head_out; }
-};
-}  // namespace
-
 static int conv3d_ndhwc_f32_impl(const float *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
                                  const float *bias_host, int cout, int stride, int act, float slope, int impl, float *y_dev,
                                  double *sums, void *stream, const FusedOps &f = FusedOps()) {
     MI355_TRY(require_device());
     MI355_REQUIRE(act != ACT_LRELU || (slope >= 0.f && slope <= 1.f), "LeakyReLU slope %g outside [0, 1]", (double)slope);
     MI355_REQUIRE(f.c1 >= 0 && f.c1 < cin && (f.c1 == 0) == (f.x1 == nullptr), "bad concat split %d of %d channels", f.c1, cin);
-    if (sums) MI355_HIP(hipMemsetAsync(sums, 0, (size_t)n * cout * 2 * sizeof(double), (hipStream_t)stream));
-    if (cin == 4 && stride == 1 && impl == 0 && cout % 32 == 0 && !f.any()) {  // the network's first-layer kernel
-        StemWeights sw;
-        MI355_TRY(stem_weights_upload(weight_host, bias_host, cin, cout, MI355_F32, &sw));
-        int rc = conv3d_stem(sw, x_dev, n, d, h, w, y_dev, sums, act, slope, (hipStream_t)stream);
+    hipStream_t s = (hipStream_t)stream;
+    if (sums) MI355_HIP(hipMemsetAsync(sums, 0, (size_t)n * cout * 2 * sizeof(double), s));
+    if (single_op_stem(cin, stride, impl, cout, f)) {
+        TmpWeights<StemWeights, stem_weights_free> sw;
+        MI355_TRY(stem_weights_upload(weight_host, bias_host, cin, cout, MI355_F32, &sw.w));
         g_last_conv_kernel = "conv3_stem_f32_kernel";
-        hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-        stem_weights_free(&sw);
-        if (rc == MI355_OK && e != hipSuccess) { set_error("stem conv kernel failed: %s", hipGetErrorString(e)); rc = MI355_ERR_HIP; }
-        return rc;
+        return synced(conv3d_stem(sw.w, x_dev, n, d, h, w, y_dev, sums, act, slope, s), s, "stem conv");
     }
-    ConvWeights cw;
-    MI355_TRY(conv_weights_upload(weight_host, bias_host, cin, cin, cout, stride, impl == 1, &cw));
-    ConvCall c;
-    c.in0 = x_dev; c.C0 = cin - f.c1; c.in1 = (const float *)f.x1; c.C1 = f.c1;
-    c.N = n; c.Di = d; c.Hi = h; c.Wi = w; c.out = y_dev; c.act = act; c.slope = slope;
-    c.stats = sums;
-    c.in_scale = f.in_scale; c.in_shift = f.in_shift; c.in_act = f.in_act;
-    c.head_w = f.head_w; c.head_b = f.head_b; c.head_out = f.head_out; c.head_ncls = f.head_ncls;
+    TmpWeights<ConvWeights, conv_weights_free> cw;
+    MI355_TRY(conv_weights_upload(weight_host, bias_host, cin, cin, cout, stride, impl == 1, &cw.w));
+    const ConvCall c = make_call<float>(x_dev, cin, n, d, h, w, y_dev, sums, act, slope, f);
     MI355_REQUIRE(!sums || impl != 1, "the direct cross-check kernel carries no statistics epilogue");
     const char *kname = "conv3_direct_kernel";
-    int rc = (impl == 1) ? conv3d_direct_f32(cw, c, (hipStream_t)stream) : conv3d_mfma_f32(cw, c, (hipStream_t)stream, &kname);
+    const int rc = (impl == 1) ? conv3d_direct_f32(cw.w, c, s) : conv3d_mfma_f32(cw.w, c, s, &kname);
     g_last_conv_kernel = kname ? kname : "";
-    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    conv_weights_free(&cw);
-    if (rc == MI355_OK && e != hipSuccess) { set_error("conv kernel failed: %s", hipGetErrorString(e)); rc = MI355_ERR_HIP; }
-    return rc;
+    return synced(rc, s, "conv");
 }
 
 extern "C" int mi355_conv3d_ndhwc(const float *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
@@ -957,25 +955,13 @@ extern "C" int mi355_conv3d_ndhwc(const float *x_dev, int n, int d, int h, int w
 extern "C" int mi355_tconv3d_ndhwc(const float *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
                                    int cout, float *y_dev, void *stream) {
     MI355_TRY(require_device());
-    TConvWeights tw;
-    MI355_TRY(tconv_weights_upload(weight_host, cin, cout, &tw));
+    TmpWeights<TConvWeights, tconv_weights_free> tw;
+    MI355_TRY(tconv_weights_upload(weight_host, cin, cout, &tw.w));
     const char *tname = "tconv2_f32_mfma_v2_kernel";
-    int rc = tconv2_mfma_f32(tw, x_dev, n, d, h, w, y_dev, (hipStream_t)stream, &tname);
+    const int rc = tconv2_mfma_f32(tw.w, x_dev, n, d, h, w, y_dev, (hipStream_t)stream, &tname);
     g_last_conv_kernel = tname;
-    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    tconv_weights_free(&tw);
-    if (rc == MI355_OK && e != hipSuccess) { set_error("tconv kernel failed: %s", hipGetErrorString(e)); rc = MI355_ERR_HIP; }
-    return rc;
+    return synced(rc, (hipStream_t)stream, "tconv");
 }
-
-// The single-op fp16 entry points take and return PLAIN NDHWC tensors (include/mi355_nnunet.h); the kernels work on
-// channel-blocked ones (common.h), so the operands pass through ndhwc_to_b8 / b8_to_ndhwc here.
-namespace {
-struct TmpBuf {
-    void *p = nullptr;
-    ~TmpBuf() { if (p) (void)hipFree(p); }
-};
-}  // namespace
 
 static int conv3d_ndhwc_f16_impl(const void *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
                                  const float *bias_host, int cout, int stride, int act, float slope, void *y_dev,
@@ -994,16 +980,13 @@ static int conv3d_ndhwc_f16_impl(const void *x_dev, int n, int d, int h, int w, 
     // all-NaN (0xFFFF) before the launch: a voxel the kernel fails to store cannot pass for a result
     MI355_HIP(hipMemsetAsync(yb.p, 0xFF, (size_t)n * Vo * cout * 2, s));
     int rc;
-    if (cin == 4 && stride == 1 && cout % 32 == 0 && !f.any()) {  // the network's first-layer kernel: plain NDHW4 input
-        StemWeights sw;
-        MI355_TRY(stem_weights_upload(weight_host, bias_host, cin, cout, MI355_F16, &sw));
-        rc = conv3d_stem(sw, x_dev, n, d, h, w, yb.p, sums, act, slope, s);
+    if (single_op_stem(cin, stride, 0, cout, f)) {
+        TmpWeights<StemWeights, stem_weights_free> sw;
+        MI355_TRY(stem_weights_upload(weight_host, bias_host, cin, cout, MI355_F16, &sw.w));
+        rc = conv3d_stem(sw.w, x_dev, n, d, h, w, yb.p, sums, act, slope, s);
         g_last_conv_kernel = "conv3_stem_f16_kernel";
         if (rc == MI355_OK) rc = b8_to_ndhwc((const _Float16 *)yb.p, n, cout, Vo, (_Float16 *)y_dev, s);
-        hipError_t e = hipStreamSynchronize(s);
-        stem_weights_free(&sw);
-        if (rc == MI355_OK && e != hipSuccess) { set_error("stem conv kernel failed: %s", hipGetErrorString(e)); rc = MI355_ERR_HIP; }
-        return rc;
+        return synced(rc, s, "stem conv");
     }
     MI355_REQUIRE(cin % 8 == 0 && f.c1 % 8 == 0, "fp16 conv needs cin %% 8 == 0 on both inputs (got %d, %d)", cin - f.c1, f.c1);
     const int c0 = cin - f.c1;
@@ -1014,22 +997,16 @@ static int conv3d_ndhwc_f16_impl(const void *x_dev, int n, int d, int h, int w, 
         MI355_HIP(hipMalloc(&x1b.p, (size_t)n * Vi * f.c1 * 2));
         MI355_TRY(ndhwc_to_b8((const _Float16 *)f.x1, n, f.c1, Vi, (_Float16 *)x1b.p, s));
     }
-    ConvWeightsH cw;
-    MI355_TRY(conv_weights_upload_f16(weight_host, bias_host, cin, cin, cout, stride, &cw));
-    ConvCallH c;
-    c.in0 = (const _Float16 *)xb.p; c.C0 = c0; c.in1 = (const _Float16 *)x1b.p; c.C1 = f.c1;
-    c.N = n; c.Di = d; c.Hi = h; c.Wi = w; c.out = f.head_out ? nullptr : (_Float16 *)yb.p;  // head mode stores logits only (run_block)
-    c.act = act; c.slope = slope; c.stats = sums;
-    c.in_scale = f.in_scale; c.in_shift = f.in_shift; c.in_act = f.in_act;
-    c.head_w = f.head_w; c.head_b = f.head_b; c.head_out = f.head_out; c.head_ncls = f.head_ncls;
+    TmpWeights<ConvWeightsH, conv_weights_free_f16> cw;
+    MI355_TRY(conv_weights_upload_f16(weight_host, bias_host, cin, cin, cout, stride, &cw.w));
+    FusedOps fb = f;  // (the channel-blocked copy of x1)
+    fb.x1 = x1b.p;
     const char *kname = nullptr;
-    rc = conv3d_mfma_f16(cw, c, s, &kname);
+    // head mode stores logits only (run_block)
+    rc = conv3d_mfma_f16(cw.w, make_call<_Float16>(xb.p, cin, n, d, h, w, f.head_out ? nullptr : yb.p, sums, act, slope, fb), s, &kname);
     g_last_conv_kernel = kname ? kname : "";
     if (rc == MI355_OK && !f.head_out) rc = b8_to_ndhwc((const _Float16 *)yb.p, n, cout, Vo, (_Float16 *)y_dev, s);
-    hipError_t e = hipStreamSynchronize(s);
-    conv_weights_free_f16(&cw);
-    if (rc == MI355_OK && e != hipSuccess) { set_error("conv kernel failed: %s", hipGetErrorString(e)); rc = MI355_ERR_HIP; }
-    return rc;
+    return synced(rc, s, "conv");
 }
 
 extern "C" int mi355_conv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
@@ -1072,6 +1049,76 @@ extern "C" int mi355_conv3d_fused_ndhwc(const void *x0_dev, const void *x1_dev, 
                                  (float *)y_dev, sums_dev, stream, f);
 }
 
+// What mi355_conv3d_fused_ndhwc would do with a call of this shape, without a device: the same route through the stem
+// shortcut, the pack layout and the planner, with stand-in pointers where the planners test for null.
+static int conv3d_plan_impl(int dtype, int n, int d, int h, int w, int c0, int c1, int cout, int stride, int impl, bool stats,
+                            bool in_norm, int head_ncls, mi355_conv_plan *out) {
+    MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_F16, "unknown dtype %d", dtype);
+    MI355_REQUIRE(n > 0 && d > 0 && h > 0 && w > 0 && c0 > 0 && c1 >= 0 && cout > 0 && head_ncls >= 0, "bad conv shape");
+    static float stand_in[2];
+    static _Float16 stand_in_h[2];
+    FusedOps f;
+    f.c1 = c1;
+    if (c1) f.x1 = stand_in;
+    if (in_norm) f.in_scale = f.in_shift = stand_in;
+    if (head_ncls) { f.head_w = f.head_b = stand_in; f.head_out = stand_in; f.head_ncls = head_ncls; }
+    double *const sums = stats ? (double *)stand_in : nullptr;
+    void *const y = head_ncls ? nullptr : (void *)stand_in;
+    const int cin = c0 + c1;
+    const char *name = nullptr;
+    ConvPlan p;
+    FusedOps plain = f;  // the call as can_defer_norm asks about it: without the norm operands
+    plain.in_scale = plain.in_shift = nullptr;
+    if (dtype == MI355_F16) {
+        MI355_REQUIRE(impl == 0, "the fp16 path has no direct kernel");
+        if (single_op_stem(cin, stride, 0, cout, f)) name = "conv3_stem_f16_kernel";
+        else {
+            ConvWeightsH cw;
+            cw.cin = cw.cin_pad = cin; cw.cout = cout; cw.stride = stride;
+            MI355_TRY(conv_pack_layout_f16(cin, cin, cout, stride, &cw.nf));
+            cw.wp_dev = stand_in_h; cw.bias_dev = stand_in;
+            out->fuses_in_norm = conv3d_f16_fuses_input_norm(cw, make_call<_Float16>(stand_in_h, cin, n, d, h, w, y, sums, ACT_NONE, 0.f, plain));
+            MI355_TRY(plan_conv_f16(cw, make_call<_Float16>(stand_in_h, cin, n, d, h, w, y, sums, ACT_NONE, 0.f, f), &p));
+        }
+    } else if (single_op_stem(cin, stride, impl, cout, f)) name = "conv3_stem_f32_kernel";
+    else {
+        ConvPackLayout l;
+        MI355_TRY(conv_pack_layout(cin, cin, cout, stride, &l));
+        ConvWeights cw;
+        cw.cin = cw.cin_pad = cin; cw.cout = cout; cw.stride = stride;
+        cw.cc = l.cc; cw.nf = l.nf; cw.pipe = l.pipe;
+        cw.bias_dev = stand_in;
+        if (l.mfma) cw.wp_dev = stand_in;
+        if (l.c16) cw.wp16_dev = stand_in;
+        if (l.wino2) cw.wpw_dev = stand_in;
+        if (l.wino3) cw.wp3_dev = stand_in;
+        if (impl == 1 || !l.mfma) cw.w_plain_dev = stand_in;
+        const ConvCall c = make_call<float>(stand_in, cin, n, d, h, w, y, sums, ACT_NONE, 0.f, f);
+        out->fuses_in_norm = impl == 0 && cw.wp3_dev && conv3d_wino3_fuses_input_norm(cw, make_call<float>(stand_in, cin, n, d, h, w, y, sums, ACT_NONE, 0.f, plain));
+        MI355_REQUIRE(!sums || impl != 1, "the direct cross-check kernel carries no statistics epilogue");
+        if (impl == 1) { MI355_TRY(plan_conv_direct(cw, c)); name = "conv3_direct_kernel"; }
+        else MI355_TRY(plan_conv_f32(cw, c, &p));
+    }
+    if (p.row) {  // (the stem and direct kernels size their own grids: only the name is reported)
+        name = p.name;
+        out->grid[0] = (int32_t)p.gx; out->grid[1] = (int32_t)p.gy; out->grid[2] = (int32_t)p.gz;
+        out->lds_bytes = (int64_t)p.lds_bytes;
+        out->splitk = p.ksplit;
+        out->tile[0] = 1 << p.g.lz; out->tile[1] = 1 << p.g.ly; out->tile[2] = 1 << p.g.lx;
+    }
+    snprintf(out->kernel, sizeof(out->kernel), "%s", name);
+    return MI355_OK;
+}
+
+extern "C" int mi355_conv3d_plan(int dtype, int n, int d, int h, int w, int c0, int c1, int cout, int stride, int impl, int has_stats,
+                                 int has_in_norm, int head_ncls, mi355_conv_plan *out) {
+    MI355_REQUIRE(out != nullptr, "mi355_conv3d_plan: out is null");
+    memset(out, 0, sizeof(*out));
+    out->splitk = 1;
+    out->rc = conv3d_plan_impl(dtype, n, d, h, w, c0, c1, cout, stride, impl, has_stats != 0, has_in_norm != 0, head_ncls, out);
+    return out->rc;
+}
+
 extern "C" int mi355_tconv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
                                        int cout, void *y_dev, void *stream) {
     MI355_TRY(require_device());
@@ -1081,15 +1128,12 @@ extern "C" int mi355_tconv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, i
     MI355_HIP(hipMalloc(&xb.p, (size_t)n * Vi * cin * 2));
     MI355_HIP(hipMalloc(&yb.p, (size_t)n * Vi * 8 * cout * 2));
     MI355_HIP(hipMemsetAsync(yb.p, 0xFF, (size_t)n * Vi * 8 * cout * 2, s));  // all-NaN: an unstored voxel cannot pass for a result
-    TConvWeightsH tw;
-    MI355_TRY(tconv_weights_upload_f16(weight_host, cin, cout, &tw));
+    TmpWeights<TConvWeightsH, tconv_weights_free_f16> tw;
+    MI355_TRY(tconv_weights_upload_f16(weight_host, cin, cout, &tw.w));
     int rc = ndhwc_to_b8((const _Float16 *)x_dev, n, cin, Vi, (_Float16 *)xb.p, s);
     const char *tname = nullptr;
-    if (rc == MI355_OK) rc = tconv2_mfma_f16(tw, (const _Float16 *)xb.p, n, d, h, w, (_Float16 *)yb.p, s, &tname);
+    if (rc == MI355_OK) rc = tconv2_mfma_f16(tw.w, (const _Float16 *)xb.p, n, d, h, w, (_Float16 *)yb.p, s, &tname);
     g_last_conv_kernel = tname ? tname : "";
     if (rc == MI355_OK) rc = b8_to_ndhwc((const _Float16 *)yb.p, n, cout, Vi * 8, (_Float16 *)y_dev, s);
-    hipError_t e = hipStreamSynchronize(s);
-    tconv_weights_free_f16(&tw);
-    if (rc == MI355_OK && e != hipSuccess) { set_error("tconv kernel failed: %s", hipGetErrorString(e)); rc = MI355_ERR_HIP; }
-    return rc;
+    return synced(rc, s, "tconv");
 }

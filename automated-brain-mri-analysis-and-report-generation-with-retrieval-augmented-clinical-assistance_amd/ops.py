@@ -235,6 +235,19 @@ def conv3d_fused_ndhwc(x0, weight, bias=None, x1=None, in_scale=None, in_shift=N
     return out, sums
 
 
+def conv3d_plan(dtype, shape, c0, cout, c1=0, stride=1, impl="mfma", stats=False, in_norm=False, head_ncls=0):
+    """Dry run of ``conv3d_fused_ndhwc`` (test aid, ``mi355_conv3d_plan``; no GPU needed): the kernel a call of ``shape`` =
+    (N, D, H, W) with C0 (+ C1) input channels would be dispatched to.  dtype: "f32" | "f16".  Returns a dict (rc, kernel, grid,
+    lds_bytes, splitk, tile, fuses_in_norm, error); a refused call has rc < 0 and the dispatcher's message in ``error``."""
+    p = _lib.ConvPlan()
+    n, d, h, w = (int(v) for v in shape)
+    lib = _lib.load()
+    rc = lib.mi355_conv3d_plan({"f32": 0, "f16": 1}[dtype], n, d, h, w, int(c0), int(c1), int(cout), int(stride),
+                               {"mfma": 0, "direct": 1}[impl], int(bool(stats)), int(bool(in_norm)), int(head_ncls), C.byref(p))
+    return {"rc": rc, "kernel": p.kernel.decode(), "grid": tuple(p.grid), "lds_bytes": int(p.lds_bytes), "splitk": int(p.splitk),
+            "tile": tuple(p.tile), "fuses_in_norm": bool(p.fuses_in_norm), "error": (lib.mi355_last_error() or b"").decode() if rc < 0 else ""}
+
+
 def last_conv_kernel() -> str:
     """Kernel instantiation the last ``conv3d_ndhwc`` call of this thread ran on (test aid)."""
     return (_lib.load().mi355_last_conv_kernel() or b"").decode()

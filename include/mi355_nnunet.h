@@ -257,6 +257,23 @@ int mi355_conv3d_fused_ndhwc(const void *x0_dev, const void *x1_dev, int dtype, 
                              int impl, const float *in_scale_dev, const float *in_shift_dev, int in_act,
                              const float *head_w_dev, const float *head_b_dev, int head_ncls, float *head_out_dev,
                              void *y_dev, double *sums_dev, void *stream);
+/* Dry run of mi355_conv3d_fused_ndhwc (test aid; needs no device and launches nothing): which kernel instantiation a call of
+ * this shape is dispatched to, with which grid, dynamic LDS size, split-K slice count and output tile - computed by the same pack
+ * layout and planner code a real call runs, the single-op first-layer shortcut (c0 + c1 = 4) included.  has_stats / has_in_norm:
+ * sums_dev / in_scale_dev would be non-NULL; head_ncls > 0: the fused head with that many classes.  A call the dispatch refuses
+ * returns its error code (also in out->rc) and leaves the reason in mi355_last_error.  For the first-layer and the direct
+ * (impl = 1) kernel only the name is filled.  No reference counterpart. */
+typedef struct mi355_conv_plan {
+    int32_t rc;
+    char kernel[96];  /* as mi355_last_conv_kernel */
+    int32_t grid[3];  /* x, y, z */
+    int64_t lds_bytes;
+    int32_t splitk;   /* slices of a split-K launch, 1 = none */
+    int32_t tile[3];  /* output tile z, y, x */
+    int32_t fuses_in_norm;  /* 1: the network would leave the producer's normalisation to this conv (asked without has_in_norm) */
+} mi355_conv_plan;
+int mi355_conv3d_plan(int dtype, int n, int d, int h, int w, int c0, int c1, int cout, int stride, int impl, int has_stats,
+                      int has_in_norm, int head_ncls, mi355_conv_plan *out);
 /* Name of the kernel instantiation the calling thread's last mi355_conv3d_ndhwc / mi355_conv3d_ndhwc_f16 call dispatched
  * (the names rocprofv3 and mi355_profile_read show).  Test aid: a parity case written for one kernel can assert that it
  * ran on that kernel.  No reference counterpart (torch.nn.Conv3d, generic_UNet.py:56, has one implementation). */
