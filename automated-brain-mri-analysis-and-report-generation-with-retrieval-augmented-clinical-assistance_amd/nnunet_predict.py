@@ -7,6 +7,7 @@ Surface per archived/kaist_original_inference.py:30-32 and scripts/run_inference
     python -m brats_amd.nnunet_predict --ensemble OUT1 OUT2 -o OUT        (probability mean of the npz files)
     python -m brats_amd.nnunet_predict --postprocess FOLDER -o OUT [--threshold 200 --replace_with 2]
            [--label_format nnunet|brats2025|brats2021]                     (kaist_original_inference.py:33-34)
+           [--largest_component CLASS [CLASS ...] [--min_object_size MM3]]  (nnU-Net v1 post-processing, before the threshold)
     python -m brats_amd.nnunet_predict --kaist -i IN -o OUT [-f ...]       (the whole script :26-38 in one process)
 
 IN holds nnU-Net-named files ``<case>_0000..0003.nii.gz``; RESULTS_FOLDER locates the models.
@@ -46,6 +47,11 @@ def main(argv=None):
     ap.add_argument("--replace_with", type=int, default=2)
     ap.add_argument("--label_format", choices=("nnunet", "brats2025", "brats2021"), default=None,
                     help="default: brats2021 for --postprocess / --kaist (the 2018/2019 convention of the KAIST script)")
+    ap.add_argument("--largest_component", nargs="+", type=int, metavar="CLASS", default=None,
+                    help="with --postprocess: per class keep only the largest connected component (nnU-Net v1 "
+                         "remove_all_but_the_largest_connected_component), before the threshold")
+    ap.add_argument("--min_object_size", type=float, default=None, metavar="MM3",
+                    help="with --largest_component: smaller objects of at least this volume are kept too")
     ap.add_argument("--kaist", action="store_true", help="both trainers + probability ensemble + post-processing")
     args = ap.parse_args(argv)
     out = Path(args.output_folder)
@@ -72,6 +78,10 @@ def main(argv=None):
         for fpath in sorted(Path(args.postprocess).glob("*.nii.gz")):
             like = nifti.load(fpath)
             seg = torch.from_numpy(np.ascontiguousarray(like.data.astype(np.uint8))).cuda()
+            if args.largest_component:
+                from . import components
+                seg, _, _ = components.remove_all_but_the_largest_connected_component(
+                    seg, args.largest_component, float(np.prod(like.zooms)), args.min_object_size)
             seg, n3 = evaluate.apply_brats_threshold(seg, args.threshold, args.replace_with)
             seg = evaluate.convert_labels(seg, args.label_format or "brats2021")
             nifti.save_like(out / fpath.name, seg.cpu().numpy(), like)

@@ -134,3 +134,25 @@ def make_volume(seed: int = 1000, shape=(155, 240, 240), dense: bool = False, ch
             hz, hy, hx = int(cz + rs.uniform(-15, 15)), int(cy + rs.uniform(-20, 20)), int(cx + rs.uniform(-20, 20))
             vol[:, max(hz - 2, 0):hz + 2, max(hy - 2, 0):hy + 2, max(hx - 2, 0):hx + 2] = 0.0
     return vol
+
+
+def label_map(seed: int, shape, lesions, fragments: int = 0, enhancing: bool = True, speckle: float = 0.6) -> np.ndarray:
+    """Synthetic uint8 label map ``[d0, d1, d2]`` for the connected-component path: per lesion ``(centre, radius)`` a ball
+    of label 1 (shell), label 2 inside 0.7 radius (core) and, if ``enhancing``, label 3 on a ``speckle`` share of the voxels
+    inside 0.5 radius; then ``fragments`` isolated voxels of a random label 1..3 anywhere in the volume."""
+    rs = np.random.RandomState(seed)
+    seg = np.zeros(tuple(shape), dtype=np.uint8)
+    for centre, radius in lesions:
+        lo = [max(int(np.floor(c - radius)), 0) for c in centre]
+        hi = [min(int(np.ceil(c + radius)) + 1, s) for c, s in zip(centre, shape)]
+        g = np.ogrid[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]]
+        d2 = sum((g[k] - float(centre[k])) ** 2 for k in range(3))
+        box = seg[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]]
+        box[d2 <= radius * radius] = 1
+        box[d2 <= (0.7 * radius) ** 2] = 2
+        if enhancing:
+            box[(d2 <= (0.5 * radius) ** 2) & (rs.random_sample(d2.shape) < speckle)] = 3
+    if fragments:
+        idx = rs.choice(seg.size, fragments, replace=False)
+        seg.reshape(-1)[idx] = rs.randint(1, 4, fragments).astype(np.uint8)
+    return seg

@@ -211,6 +211,28 @@ int mi355_mask_to_float(const uint8_t *mask_dev, float *out_dev, int64_t n, void
  * label is absent; for label 0 only the count is filled).  Labels >= K are ignored.  Synchronous. */
 int mi355_label_stats(const uint8_t *seg_dev, int d0, int d1, int d2, int K, int64_t *stats_host, void *stream);
 
+/* Connected components of a binary volume [d0][d1][d2] (feature_extraction/step3_multiplicity.py:58-59 and :222-223:
+ * scipy.ndimage.label(mask, generate_binary_structure(3, 3)); nnU-Net v1's post-processing labels with scipy's default structure).
+ * Foreground = mask != 0.  connectivity 1 = 6 neighbours, 3 = 26 neighbours, anything else MI355_ERR_INVALID.  labels_dev [d0][d1][d2]
+ * int32: 0 = background, components numbered 1..n in raster (C) order of their first voxel, which is scipy's numbering (the
+ * reference's `id` fields and the tie order of its stable sort by volume, :112, :128, depend on it).  Union-find over voxel indices
+ * in separate launches (csrc/components.hip); volumes of 2^31 voxels or more are refused.  Synchronous (returns n). */
+int mi355_label_components(const uint8_t *mask_dev, int d0, int d1, int d2, int connectivity, int32_t *labels_dev,
+                           int32_t *n_components_host, void *stream);
+/* Per-component integers of a label map as mi355_label_components writes it (step3_multiplicity.py:63-121 and :227-242: what the
+ * reference gets from `labeled_array == comp_id`, np.where and np.mean per component).  stats_host[(c - 1) * 14 + f] for component c:
+ * f = 0 voxel count, 1..3 sum of the coordinates along axis 0..2, 4..6 minimum, 7..9 maximum coordinate, 10..13 number of its voxels
+ * whose seg value is 1, 2, 3, 4 (seg_dev [d0][d1][d2] uint8, may be NULL: those four stay 0).  Exact and independent of arrival order.
+ * n_components <= 65 536 (MI355_ERR_INVALID above, before anything is launched); labels beyond n_components are ignored.
+ * Synchronous. */
+int mi355_component_stats(const int32_t *labels_dev, const uint8_t *seg_dev, int d0, int d1, int d2, int n_components,
+                          int64_t *stats_host, void *stream);
+/* out[i] = keep[labels[i]] ? seg[i] : 0 for labels[i] in 1..n_components, out[i] = seg[i] elsewhere; keep_host has n_components + 1
+ * entries, keep[0] is ignored (nnU-Net v1 remove_all_but_the_largest_connected_component: `image[(lmap == object_id) & mask] = 0`;
+ * no counterpart in the reference tree).  out_dev may be seg_dev.  Asynchronous on `stream`. */
+int mi355_component_filter(const int32_t *labels_dev, const uint8_t *seg_dev, int64_t n, const uint8_t *keep_host, int n_components,
+                           uint8_t *out_dev, void *stream);
+
 /* Per-kernel timing with HIP events on the stream the kernels are launched on (bench.py's
  * roofline). flops / bytes are the ALGORITHMIC work of the recorded launches. */
 typedef struct {
