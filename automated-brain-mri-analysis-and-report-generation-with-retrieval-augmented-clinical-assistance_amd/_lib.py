@@ -31,6 +31,8 @@ EXPORTS = [
     "mi355_sw_partial_folds", "mi355_sw_finish_folds",
     "mi355_resize_axis", "mi355_clip_to_range_of", "mi355_threshold_ge", "mi355_mask_to_float",
     "mi355_label_components", "mi355_component_stats", "mi355_component_filter",
+    "mi355_binary_morphology", "mi355_edt_squared", "mi355_surface_gradient_stats", "mi355_mask_second_moments",
+    "mi355_masked_moments", "mi355_flag_from_labels", "mi355_flag_from_flags",
 ]
 
 
@@ -150,6 +152,13 @@ def load():
     lib.mi355_label_components.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, c_int32_p, vp]
     lib.mi355_component_stats.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), vp]
     lib.mi355_component_filter.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_uint8), C.c_int, vp, vp]
+    lib.mi355_binary_morphology.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.mi355_edt_squared.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.mi355_surface_gradient_stats.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), vp]
+    lib.mi355_mask_second_moments.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), vp]
+    lib.mi355_masked_moments.argtypes = [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_double), vp]
+    lib.mi355_flag_from_labels.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int, vp, C.c_int64, vp]
+    lib.mi355_flag_from_flags.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_int64, vp]
     lib.mi355_profile_enable.argtypes = [vp, C.c_int]
     lib.mi355_profile_read.argtypes = [vp, C.POINTER(ProfEntry), C.c_int]
     _lib = lib

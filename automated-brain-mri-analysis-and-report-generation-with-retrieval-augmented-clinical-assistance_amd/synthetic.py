@@ -156,3 +156,57 @@ def label_map(seed: int, shape, lesions, fragments: int = 0, enhancing: bool = T
         idx = rs.choice(seg.size, fragments, replace=False)
         seg.reshape(-1)[idx] = rs.randint(1, 4, fragments).astype(np.uint8)
     return seg
+
+
+def shapes_map(seed: int, shape, parts) -> np.ndarray:
+    """Synthetic uint8 label map ``[d0, d1, d2]`` painted part by part, later parts over earlier ones (the morphology path:
+    shapes whose sphericity, elongation and contour class are known in advance).  A part is ``["ball", label, centre, radius]``,
+    ``["box", label, lo, hi]`` (hi exclusive) or ``["noise", label, lo, hi, p]`` (each voxel of the box with probability p);
+    everything is clipped to the volume."""
+    rs = np.random.RandomState(seed)
+    seg = np.zeros(tuple(shape), dtype=np.uint8)
+    for part in parts:
+        kind, label = part[0], int(part[1])
+        if kind == "ball":
+            centre, radius = part[2], float(part[3])
+            lo = [max(int(np.floor(c - radius)), 0) for c in centre]
+            hi = [min(int(np.ceil(c + radius)) + 1, s) for c, s in zip(centre, shape)]
+            g = np.ogrid[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]]
+            d2 = sum((g[k] - float(centre[k])) ** 2 for k in range(3))
+            seg[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]][d2 <= radius * radius] = label
+        elif kind in ("box", "noise"):
+            lo = [max(int(v), 0) for v in part[2]]
+            hi = [min(int(v), s) for v, s in zip(part[3], shape)]
+            box = seg[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]]
+            if kind == "box":
+                box[...] = label
+            else:
+                box[rs.random_sample(box.shape) < float(part[4])] = label
+        else:
+            raise ValueError(f"shapes_map: unknown part {kind!r}")
+    return seg
+
+
+def mri_for_label_map(seed: int, seg: np.ndarray, gain: float = 0.0, cystic: float = 0.0, sigma: float = 3.0, brain: bool = True) -> np.ndarray:
+    """Four float32 volumes ``[4, d0, d1, d2]`` (T1, T1ce, T2, FLAIR) on the grid of ``seg`` with integer values below 2^24,
+    as BraTS files hold: a smooth field per channel, zero outside an ellipsoidal 'brain' (``brain``), multiplied by
+    ``1 + gain`` inside the tumour (``seg > 0``), and with a CSF-like signal (T1 and FLAIR dark, T2 bright) on a ``cystic``
+    share of the voxels of label 1."""
+    from scipy.ndimage import gaussian_filter
+
+    rs = np.random.RandomState(seed)
+    shape = seg.shape
+    vols = np.empty((4,) + shape, dtype=np.float32)
+    for c in range(4):
+        smooth = gaussian_filter(rs.standard_normal(shape).astype(np.float32), sigma=sigma, mode="nearest")
+        smooth = (smooth - smooth.min()) / (smooth.max() - smooth.min() + 1e-12)
+        vols[c] = (400.0 + 200.0 * c) + smooth * (1200.0 + 300.0 * c)
+    if brain:
+        g = np.ogrid[0:shape[0], 0:shape[1], 0:shape[2]]
+        inside = sum(((g[k] - (shape[k] - 1) / 2.0) / (0.47 * shape[k])) ** 2 for k in range(3)) <= 1.0
+        vols *= inside[None]
+    vols[:, seg > 0] *= np.float32(1.0 + gain)
+    ncr = seg == 1
+    pick = ncr & (rs.random_sample(shape) < cystic)
+    vols[0][pick], vols[2][pick], vols[3][pick] = 50.0, 6000.0, 60.0
+    return np.rint(vols).astype(np.float32)

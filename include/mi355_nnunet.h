@@ -233,6 +233,52 @@ int mi355_component_stats(const int32_t *labels_dev, const uint8_t *seg_dev, int
 int mi355_component_filter(const int32_t *labels_dev, const uint8_t *seg_dev, int64_t n, const uint8_t *keep_host, int n_components,
                            uint8_t *out_dev, void *stream);
 
+/* ---- binary morphology, distance transform and mask reductions (csrc/morphology.hip): the primitives under
+ * feature_extraction/step4_morphology.py; step2_mass_effect.py:19,373 needs the first one too.  Volumes are [d0][d1][d2]
+ * C-order with fewer than 2^31 voxels (MI355_ERR_INVALID otherwise), uint8 masks are foreground where nonzero, two calls give
+ * bit-equal results, scratch is per stream lane. ---- */
+/* scipy.ndimage.binary_erosion (dilate = 0) / binary_dilation (dilate != 0) with their defaults (step4_morphology.py:42, :149,
+ * :227, :252, :254): the 6-neighbour cross, border_value = 0, `iterations` steps.  out_dev [d0][d1][d2] uint8 holds 0 / 1 and is
+ * bit-equal to scipy's mask for every iterations >= 1.  Refused: iterations < 1 (scipy's "repeat until nothing changes"),
+ * out_dev == mask_dev.  Asynchronous on `stream`. */
+int mi355_binary_morphology(const uint8_t *mask_dev, int d0, int d1, int d2, int dilate, int iterations, uint8_t *out_dev,
+                            void *stream);
+/* Squared Euclidean distance, in voxel units, from every foreground voxel to the nearest background voxel of the volume; 0 on
+ * the background (step4_morphology.py:160-161: scipy.ndimage.distance_transform_edt(mask) without `sampling`).  dist2_dev
+ * [d0][d1][d2] int32 equals rint(distance_transform_edt(mask) ** 2) bit for bit: three separable integer passes, no rounding
+ * anywhere.  Refused before any pass is launched: a volume without a background voxel (one counting launch and a 4-byte
+ * read-back find that out, which makes the call synchronise once); (d0-1)^2 + (d1-1)^2 + (d2-1)^2 >= 2^31; d1 or d2 above
+ * 1024 (a line of axis 1 or 2 must fit the 64 KiB LDS tile; axis 0 is scanned and has no such limit).  The passes themselves are
+ * asynchronous on `stream`. */
+int mi355_edt_squared(const uint8_t *mask_dev, int d0, int d1, int d2, int32_t *dist2_dev, void *stream);
+/* |grad(sqrt(d2_in) - sqrt(d2_out))| at the voxels where surface_dev[i] & select is nonzero (select = 255: any nonzero
+ * value), in fp64 with np.gradient's stencil - central difference / 2 inside, one-sided difference at the first and last index
+ * of an axis (step4_morphology.py:163-181, which differentiates the whole volume and then indexes the surface).
+ * stats_host[0..2] = number of surface voxels, mean, population standard deviation (all 0 when the surface is empty).  The
+ * deviation comes from a second pass about the mean of the first; partial sums are combined in a fixed order.  Refused: an axis
+ * shorter than 2, select outside 1..255.  Synchronous. */
+int mi355_surface_gradient_stats(const int32_t *d2_in_dev, const int32_t *d2_out_dev, const uint8_t *surface_dev, int select,
+                                 int d0, int d1, int d2, double *stats_host, void *stream);
+/* moments_host[0..9] = n, sum c0, sum c1, sum c2, sum c0^2, sum c1^2, sum c2^2, sum c0 c1, sum c0 c2, sum c1 c2 over the
+ * foreground voxels (c_k = index along axis k): what calculate_elongation (step4_morphology.py:78-115) reduces np.where(mask)
+ * to.  Exact int64, independent of arrival order.  Synchronous. */
+int mi355_mask_second_moments(const uint8_t *mask_dev, int d0, int d1, int d2, int64_t *moments_host, void *stream);
+/* vols_dev [C][n] fp32, flags_dev [n] uint8 whose 8 bits mark 8 regions that may overlap.  out_host[(b * C + c) * 3 + 0..2] =
+ * number of voxels with bit b, sum and sum of squares over them of channel c, accumulated in fp64 in a fixed order (the
+ * boolean-mask indexing, .mean() and .std() of step4_morphology.py:231-262 and :324-338).  Sums of integer-valued volumes are
+ * exact while they stay below 2^53.  Refused: C outside 1..8, n outside 1..2^31-1.  Synchronous. */
+int mi355_masked_moments(const float *vols_dev, int C, const uint8_t *flags_dev, int64_t n, double *out_host, void *stream);
+/* Bit `bit` (0..7) of flags_dev[i] = set256_host[labels_dev[i]] != 0; the other bits stay (utils.py:167-178 get_tumor_masks;
+ * with a 0 / 1 mask as the label map and the set {1}: a mask becomes a bit).  Asynchronous on `stream`. */
+int mi355_flag_from_labels(const uint8_t *labels_dev, const uint8_t *set256_host, int bit, uint8_t *flags_dev, int64_t n,
+                           void *stream);
+/* Bit `bit` of flags_dev[i] = every bit of `require` is set, no bit of `forbid` is, and - when x_dev is not NULL -
+ * lo < (double)x_dev[i] < hi; computed from the byte as it was, so `bit` may be among require / forbid.  lo, hi are fp64, +-inf
+ * allowed, NaN refused (the `dilated & ~mask` bands of step4_morphology.py:228, :253-254 and the CSF-like predicate of
+ * :329-333, chained over T1, T2 and FLAIR).  Asynchronous on `stream`. */
+int mi355_flag_from_flags(uint8_t *flags_dev, int bit, int require, int forbid, const float *x_dev, double lo, double hi, int64_t n,
+                          void *stream);
+
 /* Per-kernel timing with HIP events on the stream the kernels are launched on (bench.py's
  * roofline). flops / bytes are the ALGORITHMIC work of the recorded launches. */
 typedef struct {

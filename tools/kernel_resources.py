@@ -17,7 +17,7 @@ def demangle(names):
 
 
 def main():
-    files = sys.argv[1:] or ["conv3d", "conv3d_f16", "conv_stem", "tconv", "elementwise", "extras", "components"]
+    files = sys.argv[1:] or ["conv3d", "conv3d_f16", "conv_stem", "tconv", "elementwise", "extras", "components", "morphology"]
     rows = []
     for f in files:
         res = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-w", "-c", os.path.join(PKG, f + ".hip"),
