@@ -33,6 +33,7 @@ EXPORTS = [
     "mi355_label_components", "mi355_component_stats", "mi355_component_filter",
     "mi355_binary_morphology", "mi355_edt_squared", "mi355_surface_gradient_stats", "mi355_mask_second_moments",
     "mi355_masked_moments", "mi355_flag_from_labels", "mi355_flag_from_flags",
+    "mi355_stage0_plan",
 ]
 
 
@@ -72,6 +73,16 @@ class ProfEntry(C.Structure):
 class ConvPlan(C.Structure):
     _fields_ = [("rc", C.c_int32), ("kernel", C.c_char * 96), ("grid", C.c_int32 * 3), ("lds_bytes", C.c_int64),
                 ("splitk", C.c_int32), ("tile", C.c_int32 * 3), ("fuses_in_norm", C.c_int32)]
+
+
+class Stage0Geom(C.Structure):
+    _fields_ = [("shared", C.c_int32), ("r", C.c_int32), ("n_tiles", C.c_int32), ("n_mirrors", C.c_int32),
+                ("padded", C.c_int32 * 3), ("volume", C.c_int32 * 3), ("slab_thickness", C.c_int32 * 3)]
+
+
+class Stage0Sample(C.Structure):
+    _fields_ = [("tile", C.c_int32), ("mirror", C.c_int32), ("origin", C.c_int32 * 3), ("face", C.c_int32 * 6),
+                ("slab_origin", (C.c_int32 * 3) * 6), ("slab_shape", (C.c_int32 * 3) * 6)]
 
 
 class Mi355Error(RuntimeError):
@@ -140,6 +151,8 @@ def load():
                                              c_float_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, C.c_int, vp, vp,
                                              C.c_int, vp, vp, vp, vp]
     lib.mi355_conv3d_plan.argtypes = [C.c_int] * 13 + [C.POINTER(ConvPlan)]
+    lib.mi355_stage0_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.c_int, C.POINTER(Stage0Geom),
+                                      C.POINTER(Stage0Sample), C.c_int]
     lib.mi355_label_remap.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_uint8), vp]
     lib.mi355_label_confusion.argtypes = [vp, vp, C.c_int64, C.c_int, C.POINTER(C.c_uint64), vp]
     lib.mi355_cosine_topk.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_float_p, vp]

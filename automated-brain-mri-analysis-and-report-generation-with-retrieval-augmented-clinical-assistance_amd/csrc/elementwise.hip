@@ -214,6 +214,107 @@ int extract_tiles(const float *vol, int C, int Z, int Y, int X, int padz, int pa
     return MI355_OK;
 }
 
+// ------------------------------------------------------------------ shared stage 0: tile tensor from whole-volume + slab results
+// One workgroup = one (z, y) row of one sample's tile: whether the row lies in a z or y shell is workgroup-uniform, the x shells
+// are decided per voxel.  Four 16-byte loads in flight per lane before the first store.
+__global__ __launch_bounds__(256) void stage0_gather_kernel(S0GatherArgs a) {
+    const int n = blockIdx.y;
+    const S0Sample sm = a.smp[n];
+    const int z = (int)blockIdx.x / a.P[1], y = (int)blockIdx.x - z * a.P[1];
+    const int r = a.r, C4 = a.C4;
+    // the row's source when a z or y shell holds it: slab base (in quads) of voxel x = 0, and the quads per slab row
+    const f32x4 *row = nullptr;
+    if (sm.slab[0] >= 0 && z < r)
+        row = (const f32x4 *)a.slab[0] + (((int64_t)sm.slab[0] * a.t[0] + z) * a.P[1] + y) * a.P[2] * C4;
+    else if (sm.slab[1] >= 0 && z >= a.P[0] - r)
+        row = (const f32x4 *)a.slab[0] + (((int64_t)sm.slab[1] * a.t[0] + (z - (a.P[0] - a.t[0]))) * a.P[1] + y) * a.P[2] * C4;
+    else if (sm.slab[2] >= 0 && y < r)
+        row = (const f32x4 *)a.slab[1] + (((int64_t)sm.slab[2] * a.P[0] + z) * a.t[1] + y) * a.P[2] * C4;
+    else if (sm.slab[3] >= 0 && y >= a.P[1] - r)
+        row = (const f32x4 *)a.slab[1] + (((int64_t)sm.slab[3] * a.P[0] + z) * a.t[1] + (y - (a.P[1] - a.t[1]))) * a.P[2] * C4;
+    const f32x4 *wrow = (const f32x4 *)a.wv + ((((int64_t)sm.wv * a.Ve[0] + sm.org[0] + z) * a.Ve[1] + sm.org[1] + y) * a.Ve[2] + sm.org[2]) * C4;
+    const f32x4 *xlo = sm.slab[4] < 0 ? nullptr : (const f32x4 *)a.slab[2] + (((int64_t)sm.slab[4] * a.P[0] + z) * a.P[1] + y) * a.t[2] * C4;
+    const f32x4 *xhi = sm.slab[5] < 0 ? nullptr : (const f32x4 *)a.slab[2] + (((int64_t)sm.slab[5] * a.P[0] + z) * a.P[1] + y) * a.t[2] * C4;
+    const int rowq = a.P[2] * C4;
+    f32x4 *dst = (f32x4 *)a.out + ((int64_t)n * a.P[0] * a.P[1] + blockIdx.x) * rowq;
+    constexpr int U = 4;
+    for (int q0 = threadIdx.x; q0 < rowq; q0 += U * 256) {
+        f32x4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int q = q0 + u * 256;
+            if (q >= rowq) continue;
+            const int x = q / C4;
+            const f32x4 *src = wrow + q;
+            if (row) src = row + q;
+            else if (xlo && x < r) src = xlo + q;
+            else if (xhi && x >= a.P[2] - r) src = xhi + (q - (a.P[2] - a.t[2]) * C4);
+            v[u] = *src;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int q = q0 + u * 256;
+            if (q < rowq) dst[q] = v[u];
+        }
+    }
+}
+
+int stage0_gather(const S0GatherArgs &a, int n_samples, hipStream_t s) {
+    MI355_REQUIRE(n_samples > 0 && n_samples <= S0_MAX_SAMPLES, "stage0_gather: %d samples (max %d)", n_samples, S0_MAX_SAMPLES);
+    MI355_REQUIRE(a.C4 > 0 && a.r > 0, "stage0_gather: bad channel count / shell depth");
+    for (int k = 0; k < 3; ++k)
+        MI355_REQUIRE(a.t[k] >= 2 * a.r && a.P[k] >= a.t[k] && a.Ve[k] >= a.P[k], "stage0_gather: axis %d: patch %d, slab %d, volume %d, r %d", k, a.P[k], a.t[k], a.Ve[k], a.r);
+    for (int i = 0; i < n_samples; ++i)
+        for (int k = 0; k < 3; ++k)
+            MI355_REQUIRE(a.smp[i].org[k] >= 0 && a.smp[i].org[k] + a.P[k] <= a.Ve[k], "stage0_gather: sample %d leaves the volume", i);
+    MI355_REQUIRE((int64_t)a.P[0] * a.P[1] < (1ll << 31), "stage0_gather: grid too large");
+    hipLaunchKernelGGL(stage0_gather_kernel, dim3((unsigned)(a.P[0] * a.P[1]), (unsigned)n_samples), dim3(256), 0, s, a);
+    MI355_HIP(hipGetLastError());
+    return MI355_OK;
+}
+
+// Zero outside [0, Zp): the voxels are enumerated as three boxes, z >= Zp0 | z < Zp0, y >= Zp1 | z < Zp0, y < Zp1, x >= Zp2.
+__global__ void stage0_mask_kernel(f32x4 *x, int Ve0, int Ve1, int Ve2, int Zp0, int Zp1, int Zp2, int C4, int64_t nA, int64_t nB, int64_t nC) {
+    const int64_t total = (nA + nB + nC) * C4;
+    f32x4 *xn = x + (int64_t)blockIdx.y * Ve0 * Ve1 * Ve2 * C4;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t w = i / C4;
+        const int c4 = (int)(i - w * C4);
+        int vz, vy, vx;
+        if (w < nA) {
+            vz = Zp0 + (int)(w / ((int64_t)Ve1 * Ve2)); w %= (int64_t)Ve1 * Ve2;
+            vy = (int)(w / Ve2); vx = (int)(w % Ve2);
+        } else if (w < nA + nB) {
+            w -= nA;
+            const int64_t plane = (int64_t)(Ve1 - Zp1) * Ve2;
+            vz = (int)(w / plane); w %= plane;
+            vy = Zp1 + (int)(w / Ve2); vx = (int)(w % Ve2);
+        } else {
+            w -= nA + nB;
+            const int64_t plane = (int64_t)Zp1 * (Ve2 - Zp2);
+            vz = (int)(w / plane); w %= plane;
+            vy = (int)(w / (Ve2 - Zp2)); vx = Zp2 + (int)(w % (Ve2 - Zp2));
+        }
+        xn[(((int64_t)vz * Ve1 + vy) * Ve2 + vx) * C4 + c4] = zero;
+    }
+}
+
+int stage0_mask(float *x, int N, const int Ve[3], const int Zp[3], int C, hipStream_t s) {
+    MI355_REQUIRE(C % 4 == 0 && N > 0 && N <= 65535, "stage0_mask: C = %d, N = %d", C, N);
+    for (int k = 0; k < 3; ++k) MI355_REQUIRE(Zp[k] > 0 && Zp[k] <= Ve[k], "stage0_mask: axis %d: %d of %d", k, Zp[k], Ve[k]);
+    const int64_t nA = (int64_t)(Ve[0] - Zp[0]) * Ve[1] * Ve[2], nB = (int64_t)Zp[0] * (Ve[1] - Zp[1]) * Ve[2],
+                  nC = (int64_t)Zp[0] * Zp[1] * (Ve[2] - Zp[2]);
+    const int64_t total = (nA + nB + nC) * (C / 4);
+    if (total == 0) return MI355_OK;
+    int64_t bx = (total + 255) / 256;
+    if (bx > 4096) bx = 4096;
+    hipLaunchKernelGGL(stage0_mask_kernel, dim3((unsigned)bx, (unsigned)N), dim3(256), 0, s, (f32x4 *)x, Ve[0], Ve[1], Ve[2], Zp[0], Zp[1],
+                       Zp[2], C / 4, nA, nB, nC);
+    MI355_HIP(hipGetLastError());
+    return MI355_OK;
+}
+
 // (fp16 with Cpad % 8 == 0, i.e. a network without the stem kernel: channel-blocked output, common.h; the stem's NDHW4 input
 // is a plain 4-channel tensor in both dtypes)
 template <typename T>

@@ -130,6 +130,27 @@ struct TileDesc {  // one forward sample = one (tile, mirror)
 int extract_tiles(const float *vol, int C, int Z, int Y, int X, int padz, int pady, int padx,
                   const TileDesc *tiles_host, int n_samples, int P0, int P1, int P2, int Cpad, void *x, int dtype,
                   hipStream_t s);
+// Shared stage 0 of the sliding window (unet.hip "shared stage 0"): encoder stage 0 runs once over the whole padded volume and
+// over thin slabs at the tile faces that lie inside the volume; the tile tensor is then gathered from those results.
+constexpr int S0_MAX_SAMPLES = 64;
+struct S0Sample {   // one forward sample = one (tile, mirror), in the coordinates of its (mirrored) pass
+    int wv;         // which whole-volume result (index of the mirror)
+    int org[3];     // tile origin in that volume
+    int slab[6];    // faces z lo, z hi, y lo, y hi, x lo, x hi: index into that axis's slab batch, or -1 (the face is a volume face)
+};
+struct S0GatherArgs {
+    const float *wv;       // [n_mirrors][Ve0][Ve1][Ve2][C]
+    const float *slab[3];  // per axis a: [n_slabs][S0][S1][S2][C], S[a] = t[a], S[k] = P[k] otherwise
+    float *out;            // [n_samples][P0][P1][P2][C]
+    int P[3], Ve[3], t[3];
+    int r;                 // voxel layers taken from a slab at each of its faces
+    int C4;                // C / 4
+    S0Sample smp[S0_MAX_SAMPLES];
+};
+// fp32 NDHWC, 16 bytes per lane.  Where the shells of two or three faces meet the first face in the order above wins.
+int stage0_gather(const S0GatherArgs &a, int n_samples, hipStream_t s);
+// x [N][Ve0][Ve1][Ve2][C] fp32: zero every voxel outside [0, Zp) (C % 4 == 0)
+int stage0_mask(float *x, int N, const int Ve[3], const int Zp[3], int C, hipStream_t s);
 // plain NDHWC <-> channel-blocked [N][C / 8][V][8] fp16 (common.h)
 int ndhwc_to_b8(const _Float16 *x, int N, int C, int64_t V, _Float16 *y, hipStream_t s);
 int b8_to_ndhwc(const _Float16 *x, int N, int C, int64_t V, _Float16 *y, hipStream_t s);

@@ -232,6 +232,8 @@ struct Plan {
     size_t scale2_off = 0, shift2_off = 0;  // second scale / shift pair: a block whose normalisation is applied by its consumer
     size_t stats_bytes = 0;
     char *arena = nullptr;             // the activation arena of the lane (stream) this forward runs on, set by ensure_arena
+    // shared stage 0 (stage0_plan): whole-volume input / intermediate / result and the slab buffers, behind the tile plan
+    struct { size_t wv_in = 0, wv_tmp[2] = {0, 0}, wv_out = 0, slab_in = 0, slab_tmp[2] = {0, 0}, slab_out[3] = {0, 0, 0}; } s0;
 };
 
 static int make_plan(const mi355_unet &net, int N, int D, int H, int W, Plan *pl) {
@@ -403,9 +405,10 @@ static bool can_defer_norm(const mi355_unet *net, const ConvLayer &L, const Conv
 // head_norm (round 3): when non-null and the last decoder block carries a run-time Instance/GroupNorm, that block's
 // normalisation (+ activation) is NOT applied to the returned feature map: *head_norm receives its scale / shift and the
 // caller's head kernel applies them while reading the features (head_logits / head_aggregate take a FeatNorm).
+// after_enc0 (shared stage 0): the level-0 features are already where enc[0]'s last block writes them; the pass starts at level 1.
 static int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W, const void **feat,
                             int *feat_c, hipStream_t s, bool *is_logits = nullptr, float *logits_target = nullptr,
-                            FeatNorm *head_norm = nullptr) {
+                            FeatNorm *head_norm = nullptr, bool after_enc0 = false) {
     const int np = net->num_pool;
     const bool f16 = net->dtype == MI355_F16;
     auto buf = [&](int k, int l) { return (void *)(pl.arena + pl.off[k][l]); };
@@ -417,7 +420,8 @@ static int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H
     for (int l = 0; l <= np; ++l) {
         int Di = D >> l, Hi = H >> l, Wi = W >> l;
         bool pending = false;  // cur holds a raw conv output whose normalisation the next block applies
-        for (size_t i = 0; i < net->enc[l].size(); ++i) {
+        if (l == 0 && after_enc0) { cur = buf((int)((net->enc[0].size() - 1) & 1), 0); curC = net->enc[0].back().cout; }
+        for (size_t i = 0; i < net->enc[l].size() && !(l == 0 && after_enc0); ++i) {
             const ConvLayer &L = net->enc[l][i];
             int inD = Di, inH = Hi, inW = Wi;
             if (L.stride == 2) { inD = Di * 2; inH = Hi * 2; inW = Wi * 2; }
@@ -575,6 +579,179 @@ static int make_geom(const mi355_sw_opts &o, int Z, int Y, int X, SwGeom *g) {
     return MI355_OK;
 }
 
+// ---- shared stage 0.  The tiles of a sliding window overlap (step 0.5: every voxel of a BraTS crop lies in up to 8 tiles), and
+// encoder stage 0 - r stride-1 3x3x3 blocks without run-time statistics, in front of the first stride-2 conv - is translation-
+// equivariant with a (2r + 1)^3 receptive field: a tile's stage-0 output equals the whole padded volume's except within r voxels
+// of a tile face that lies INSIDE the volume, where the tile sees zero padding and the volume real neighbours.  So stage 0 runs
+// once per (net, mirror) over the whole volume and, per batch of tiles, over one thin input slab per interior face (full tile
+// extent on the other two axes, zero padding all around = the tile's own padding; its outer r layers are exact because their
+// receptive field stays inside a slab of thickness >= 2r); stage0_gather_kernel then writes the tile tensor from the two.
+// The decision depends on the network and the geometry of ALL tiles only - not on rank, world, lane or batch size - so that every
+// rank and lane computes a tile's features the same way.
+// For the same reason the slab convs run as launches of exactly S0_SLAB_GROUP slabs (the last one filled up): the kernel the
+// planner picks, and with it the summation order, must not change with the number of tiles a rank or batch happens to hold.
+// Coordinates: a mirrored pass works on the flipped padded volume, where a tile's origin along a flipped axis is Zp - P - origin.
+constexpr int S0_SLAB_GROUP = 8;  // (8 slabs of 4 x 128 x 128: 2048 tiles of the F(2x2x2,3x3x3) kernel, 8 per CU)
+struct S0Geom {
+    bool shared = false;
+    int r = 0;
+    int Ve[3] = {0, 0, 0};         // padded volume extended to whole 4 x 8 x 8 conv tiles
+    int t[3] = {0, 0, 0};          // slab thickness per axis: the smallest multiple of (4, 8, 8) that is >= 2r
+    int max_faces[3] = {0, 0, 0};  // most interior faces any tile has on an axis
+    std::vector<S0Sample> smp;     // [tile][mirror]; slab[f] = 0 where face f needs a slab, -1 where it is a volume face
+};
+
+static void stage0_geometry(const SwGeom &g, int r, S0Geom *o) {
+    static const int unit[3] = {4, 8, 8};
+    *o = S0Geom();
+    o->r = r;
+    bool fits = r >= 1 && g.tiles.size() > 1;
+    for (int a = 0; a < 3; ++a) {
+        o->Ve[a] = ceil_div(g.Zp[a], unit[a]) * unit[a];
+        o->t[a] = ceil_div(std::max(2 * r, 1), unit[a]) * unit[a];
+        fits = fits && g.P[a] >= o->t[a];
+    }
+    if (!fits) return;
+    o->shared = true;
+    for (const TileDesc &td : g.tiles)
+        for (size_t m = 0; m < g.mirrors.size(); ++m) {
+            const int org[3] = {td.z0, td.y0, td.x0};
+            S0Sample sm;
+            sm.wv = (int)m;
+            for (int a = 0; a < 3; ++a) {
+                sm.org[a] = (g.mirrors[m] >> a) & 1 ? g.Zp[a] - g.P[a] - org[a] : org[a];
+                sm.slab[2 * a] = sm.org[a] > 0 ? 0 : -1;
+                sm.slab[2 * a + 1] = sm.org[a] + g.P[a] < g.Zp[a] ? 0 : -1;
+                o->max_faces[a] = std::max(o->max_faces[a], (sm.slab[2 * a] >= 0) + (sm.slab[2 * a + 1] >= 0));
+            }
+            o->smp.push_back(sm);
+        }
+}
+
+// blocks of enc[0] when the network allows the shared stage 0, else 0
+static int stage0_blocks(const mi355_unet &net) {
+    if (!env_switch("MI355_SHARE_STAGE0") || net.dtype != MI355_F32) return 0;
+    for (const ConvLayer &L : net.enc[0])
+        if (L.stride != 1 || L.runtime_norm || L.post_affine || L.cout % 4) return 0;  // (Instance/GroupNorm statistics are per tile; the mask and gather kernels move 16 bytes per lane)
+    return (int)net.enc[0].size();
+}
+
+static void slab_dims(const SwGeom &g, const S0Geom &sg, int a, int S[3]) {
+    for (int k = 0; k < 3; ++k) S[k] = k == a ? sg.t[k] : g.P[k];
+}
+
+// appends the stage-0 regions to the plan of `n_samples` (tile, mirror) samples per forward
+static void stage0_plan(const mi355_unet &net, const SwGeom &g, const S0Geom &sg, int n_samples, Plan *pl) {
+    size_t o = pl->total;
+    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~size_t(255); return r; };
+    int maxc = 0;
+    for (auto &L : net.enc[0]) maxc = std::max(maxc, L.cout);
+    const size_t wv = g.mirrors.size() * (size_t)sg.Ve[0] * sg.Ve[1] * sg.Ve[2];
+    size_t sl = 0, sl_a[3];
+    for (int a = 0; a < 3; ++a) {
+        int S[3];
+        slab_dims(g, sg, a, S);
+        sl_a[a] = (size_t)ceil_div(n_samples * sg.max_faces[a], S0_SLAB_GROUP) * S0_SLAB_GROUP * S[0] * S[1] * S[2];
+        sl = std::max(sl, sl_a[a]);
+    }
+    pl->s0.wv_in = take(wv * net.cin_pad * 4);
+    pl->s0.slab_in = take(sl * net.cin_pad * 4);
+    for (int k = 0; k < 2 && k < sg.r - 1; ++k) {
+        pl->s0.wv_tmp[k] = take(wv * maxc * 4);
+        pl->s0.slab_tmp[k] = take(sl * maxc * 4);
+    }
+    pl->s0.wv_out = take(wv * net.enc[0].back().cout * 4);
+    for (int a = 0; a < 3; ++a) pl->s0.slab_out[a] = take(sl_a[a] * net.enc[0].back().cout * 4);
+    pl->total = o;
+}
+
+// a box of the (mirrored) pass, origin b and size S, as the TileDesc extract_tiles takes: origin in the unflipped padded volume
+static TileDesc pass_box(const SwGeom &g, int mirror, const int b[3], const int S[3]) {
+    int o[3];
+    for (int a = 0; a < 3; ++a) o[a] = (mirror >> a) & 1 ? g.Zp[a] - b[a] - S[a] : b[a];
+    return TileDesc{o[0], o[1], o[2], mirror};
+}
+
+// enc[0] over n boxes of S voxels each, gathered from the volume: `in` receives the input, the last block writes `out`.
+// group > 0: the convs run as launches of exactly `group` boxes each (n is a multiple of it).
+static int stage0_run(mi355_unet *net, const Plan &pl, const float *vol, int Z, int Y, int X, const SwGeom &g, const std::vector<TileDesc> &boxes,
+                      const int S[3], const int *mask_zp, int group, size_t in_off, const size_t tmp_off[2], size_t out_off, hipStream_t s) {
+    const int n = (int)boxes.size();
+    const size_t vox = (size_t)S[0] * S[1] * S[2];
+    for (int b0 = 0; b0 < n; b0 += S0_MAX_SAMPLES) {
+        const int nb = std::min(S0_MAX_SAMPLES, n - b0);
+        ProfScope ps(net, s, "extract_tiles_kernel", 0.0, (double)nb * vox * 4.0 * (net->in_channels + net->cin_pad));
+        MI355_TRY(extract_tiles(vol, net->in_channels, Z, Y, X, g.pad_lo[0], g.pad_lo[1], g.pad_lo[2], boxes.data() + b0, nb, S[0], S[1], S[2],
+                                net->cin_pad, (void *)(pl.arena + in_off + (size_t)b0 * vox * net->cin_pad * 4), net->dtype, s));
+    }
+    const int ng = group > 0 ? group : n;
+    MI355_REQUIRE(n % ng == 0, "shared stage 0: %d boxes in launches of %d", n, ng);
+    for (int g0 = 0; g0 < n; g0 += ng) {
+        const void *cur = pl.arena + in_off + (size_t)g0 * vox * net->cin_pad * 4;
+        int curC = net->cin_pad;
+        for (size_t i = 0; i < net->enc[0].size(); ++i) {
+            const ConvLayer &L = net->enc[0][i];
+            const bool last = i + 1 == net->enc[0].size();
+            void *out = pl.arena + (last ? out_off : tmp_off[i & 1]) + (size_t)g0 * vox * L.cout * 4;
+            MI355_TRY(run_block(net, pl, L, cur, curC, nullptr, 0, ng, S[0], S[1], S[2], out, s));
+            if (!last && mask_zp) {
+                // the next conv must see zero padding outside the padded volume, not act(bias)
+                const double outside = (double)ng * (vox - (double)mask_zp[0] * mask_zp[1] * mask_zp[2]);
+                ProfScope ps(net, s, "stage0_mask_kernel", 0.0, outside * L.cout * 4.0);
+                MI355_TRY(stage0_mask((float *)out, ng, S, mask_zp, L.cout, s));
+            }
+            cur = out; curC = L.cout;
+        }
+    }
+    return MI355_OK;
+}
+
+// whole-volume pass: one box per mirror
+static int stage0_whole(mi355_unet *net, const Plan &pl, const float *vol, int Z, int Y, int X, const SwGeom &g, const S0Geom &sg, hipStream_t s) {
+    std::vector<TileDesc> boxes;
+    const int zero[3] = {0, 0, 0};
+    // (a flipped axis: the flipped volume starts at 0 and its zero extension follows it, as on an unflipped axis)
+    for (int m : g.mirrors) boxes.push_back(pass_box(g, m, zero, sg.Ve));
+    const bool extended = sg.Ve[0] != g.Zp[0] || sg.Ve[1] != g.Zp[1] || sg.Ve[2] != g.Zp[2];
+    return stage0_run(net, pl, vol, Z, Y, X, g, boxes, sg.Ve, extended ? g.Zp : nullptr, 0, pl.s0.wv_in, pl.s0.wv_tmp, pl.s0.wv_out, s);
+}
+
+// the slabs of one batch of samples (indices into sg.smp), then the gather of the batch's tile tensor
+static int stage0_tiles(mi355_unet *net, const Plan &pl, const float *vol, int Z, int Y, int X, const SwGeom &g, const S0Geom &sg,
+                        const std::vector<int> &samples, hipStream_t s) {
+    const int n = (int)samples.size();
+    MI355_REQUIRE(n <= S0_MAX_SAMPLES, "shared stage 0: %d samples per forward (max %d)", n, S0_MAX_SAMPLES);
+    const int C = net->enc[0].back().cout;
+    S0GatherArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    for (int i = 0; i < n; ++i) ga.smp[i] = sg.smp[samples[i]];
+    for (int a = 0; a < 3; ++a) {
+        int S[3];
+        slab_dims(g, sg, a, S);
+        std::vector<TileDesc> boxes;
+        for (int i = 0; i < n; ++i)
+            for (int side = 0; side < 2; ++side) {
+                S0Sample &sm = ga.smp[i];
+                if (sm.slab[2 * a + side] < 0) continue;
+                int b[3] = {sm.org[0], sm.org[1], sm.org[2]};
+                if (side) b[a] += g.P[a] - sg.t[a];
+                sm.slab[2 * a + side] = (int)boxes.size();
+                boxes.push_back(pass_box(g, g.mirrors[sm.wv], b, S));
+            }
+        ga.slab[a] = (const float *)(pl.arena + pl.s0.slab_out[a]);
+        if (boxes.empty()) continue;
+        while (boxes.size() % S0_SLAB_GROUP) boxes.push_back(boxes.back());  // (a whole last launch: its spare results are not read)
+        MI355_TRY(stage0_run(net, pl, vol, Z, Y, X, g, boxes, S, nullptr, S0_SLAB_GROUP, pl.s0.slab_in, pl.s0.slab_tmp, pl.s0.slab_out[a], s));
+    }
+    ga.wv = (const float *)(pl.arena + pl.s0.wv_out);
+    ga.out = (float *)(pl.arena + pl.off[(net->enc[0].size() - 1) & 1][0]);
+    for (int a = 0; a < 3; ++a) { ga.P[a] = g.P[a]; ga.Ve[a] = sg.Ve[a]; ga.t[a] = sg.t[a]; }
+    ga.r = sg.r; ga.C4 = C / 4;
+    const double pv = (double)n * g.P[0] * g.P[1] * g.P[2];
+    ProfScope ps(net, s, "stage0_gather_kernel", 0.0, 2.0 * pv * C * 4.0);
+    return stage0_gather(ga, n, s);
+}
+
 // Evaluates the tiles with (index % world) == rank of one net; adds into agg (and cnt if non-null,
 // for ALL tiles so that every rank holds the full normaliser).
 // `first_item`: index of this net's tile 0 in the caller's work list (fold f of a fold list: f * tiles): the work items
@@ -593,18 +770,26 @@ static int sw_accumulate(mi355_unet *net, const float *vol, int Z, int Y, int X,
     MI355_REQUIRE(nm <= 64, "too many mirrors");
     Plan pl;
     MI355_TRY(make_plan(*net, bt * nm, g.P[0], g.P[1], g.P[2], &pl));
+    S0Geom sg;
+    stage0_geometry(g, stage0_blocks(*net), &sg);
+    if (sg.shared) stage0_plan(*net, g, sg, bt * nm, &pl);
     MI355_TRY(ensure_arena(&pl, s));
     if (mine.empty()) return MI355_OK;
+    if (sg.shared) MI355_TRY(stage0_whole(net, pl, vol, Z, Y, X, g, sg, s));
     for (size_t b0 = 0; b0 < mine.size(); b0 += bt) {
         const int nb = (int)std::min<size_t>(bt, mine.size() - b0);
         std::vector<TileDesc> samples;
+        std::vector<int> sample_ids;  // (tile, mirror) as indexed by S0Geom::smp
         for (int i = 0; i < nb; ++i)
             for (int m = 0; m < nm; ++m) {
                 TileDesc td = g.tiles[mine[b0 + i]];
                 td.mirror = g.mirrors[m];
                 samples.push_back(td);
+                sample_ids.push_back(mine[b0 + i] * nm + m);
             }
-        {
+        if (sg.shared) {
+            MI355_TRY(stage0_tiles(net, pl, vol, Z, Y, X, g, sg, sample_ids, s));
+        } else {
         const double pv = (double)samples.size() * g.P[0] * g.P[1] * g.P[2];
         ProfScope ps(net, s, "extract_tiles_kernel", 0.0, pv * (4.0 * net->in_channels + (net->dtype == MI355_F16 ? 2.0 : 4.0) * net->cin_pad));
         MI355_TRY(extract_tiles(vol, net->in_channels, Z, Y, X, g.pad_lo[0], g.pad_lo[1], g.pad_lo[2], samples.data(),
@@ -613,7 +798,7 @@ static int sw_accumulate(mi355_unet *net, const float *vol, int Z, int Y, int X,
         }
         const void *feat; int fc; bool is_logits = false;
         FeatNorm head_norm;
-        MI355_TRY(forward_features(net, pl, (int)samples.size(), g.P[0], g.P[1], g.P[2], &feat, &fc, s, &is_logits, nullptr, &head_norm));
+        MI355_TRY(forward_features(net, pl, (int)samples.size(), g.P[0], g.P[1], g.P[2], &feat, &fc, s, &is_logits, nullptr, &head_norm, sg.shared));
         MI355_REQUIRE(is_logits || fc == net->head.cin, "head expects %d channels, decoder gives %d", net->head.cin, fc);
         for (int i = 0; i < nb; ++i) {
             const TileDesc &td = g.tiles[mine[b0 + i]];
@@ -1117,6 +1302,40 @@ extern "C" int mi355_conv3d_plan(int dtype, int n, int d, int h, int w, int c0, 
     out->splitk = 1;
     out->rc = conv3d_plan_impl(dtype, n, d, h, w, c0, c1, cout, stride, impl, has_stats != 0, has_in_norm != 0, head_ncls, out);
     return out->rc;
+}
+
+extern "C" int mi355_stage0_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes, int r,
+                                 mi355_stage0_geom *out, mi355_stage0_sample *samples, int max_samples) {
+    MI355_REQUIRE(out && patch && r >= 0 && (samples || max_samples == 0), "mi355_stage0_plan: bad argument");
+    mi355_sw_opts o;
+    memset(&o, 0, sizeof(o));
+    for (int a = 0; a < 3; ++a) o.patch[a] = patch[a];
+    o.step_size = step_size; o.mirror_axes = mirror_axes;
+    SwGeom g;
+    MI355_TRY(make_geom(o, z, y, x, &g));
+    S0Geom sg;
+    stage0_geometry(g, r, &sg);
+    memset(out, 0, sizeof(*out));
+    out->shared = sg.shared; out->r = r;
+    out->n_tiles = (int32_t)g.tiles.size(); out->n_mirrors = (int32_t)g.mirrors.size();
+    for (int a = 0; a < 3; ++a) { out->padded[a] = g.Zp[a]; out->volume[a] = sg.Ve[a]; out->slab_thickness[a] = sg.t[a]; }
+    const int n = sg.shared ? (int)sg.smp.size() : 0;
+    for (int i = 0; i < n && i < max_samples; ++i) {
+        const S0Sample &sm = sg.smp[i];
+        mi355_stage0_sample &d = samples[i];
+        memset(&d, 0, sizeof(d));
+        d.tile = i / (int)g.mirrors.size(); d.mirror = g.mirrors[sm.wv];
+        for (int a = 0; a < 3; ++a) d.origin[a] = sm.org[a];
+        for (int f = 0; f < 6; ++f) {
+            if (sm.slab[f] < 0) continue;
+            d.face[f] = 1;
+            int S[3];
+            slab_dims(g, sg, f >> 1, S);
+            for (int a = 0; a < 3; ++a) { d.slab_origin[f][a] = sm.org[a]; d.slab_shape[f][a] = S[a]; }
+            if (f & 1) d.slab_origin[f][f >> 1] += g.P[f >> 1] - sg.t[f >> 1];
+        }
+    }
+    return n;
 }
 
 extern "C" int mi355_tconv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,

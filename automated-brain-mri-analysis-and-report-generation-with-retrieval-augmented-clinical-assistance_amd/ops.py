@@ -248,6 +248,31 @@ def conv3d_plan(dtype, shape, c0, cout, c1=0, stride=1, impl="mfma", stats=False
             "tile": tuple(p.tile), "fuses_in_norm": bool(p.fuses_in_norm), "error": (lib.mi355_last_error() or b"").decode() if rc < 0 else ""}
 
 
+def stage0_plan(volume, patch, step_size=0.5, mirror_axes=(), r=2):
+    """Dry run of the sliding window's shared stage 0 (``mi355_stage0_plan``; no GPU needed) for a volume (Z, Y, X), a patch and
+    the mirror axes (a subset of (0, 1, 2)); ``r`` = blocks of encoder stage 0 (0: the network does not qualify).  Returns a dict:
+    shared, n_tiles, n_mirrors, padded, volume (the whole-volume pass, padded to whole 4 x 8 x 8 tiles), slab_thickness and
+    samples - one dict per (tile, mirror), tile-major, in the coordinates of its mirrored pass: tile, mirror (tuple of flipped
+    axes), origin, face (six flags: z lo, z hi, y lo, y hi, x lo, x hi) and slabs {face index: (origin, shape)}."""
+    lib = _lib.load()
+    g = _lib.Stage0Geom()
+    p3 = (C.c_int32 * 3)(*(int(v) for v in patch))
+    z, y, x = (int(v) for v in volume)
+    mask = sum(1 << int(a) for a in mirror_axes)
+    n = lib.mi355_stage0_plan(z, y, x, p3, float(step_size), mask, int(r), C.byref(g), None, 0)
+    _lib.check(n, "mi355_stage0_plan")
+    buf = (_lib.Stage0Sample * max(n, 1))()
+    _lib.check(lib.mi355_stage0_plan(z, y, x, p3, float(step_size), mask, int(r), C.byref(g), buf, n), "mi355_stage0_plan")
+    samples = []
+    for i in range(n):
+        s = buf[i]
+        samples.append({"tile": int(s.tile), "mirror": tuple(a for a in range(3) if s.mirror >> a & 1), "origin": tuple(s.origin),
+                        "face": tuple(int(f) for f in s.face),
+                        "slabs": {f: (tuple(s.slab_origin[f]), tuple(s.slab_shape[f])) for f in range(6) if s.face[f]}})
+    return {"shared": bool(g.shared), "n_tiles": int(g.n_tiles), "n_mirrors": int(g.n_mirrors), "padded": tuple(g.padded),
+            "volume": tuple(g.volume), "slab_thickness": tuple(g.slab_thickness), "samples": samples}
+
+
 def last_conv_kernel() -> str:
     """Kernel instantiation the last ``conv3d_ndhwc`` call of this thread ran on (test aid)."""
     return (_lib.load().mi355_last_conv_kernel() or b"").decode()

@@ -342,6 +342,34 @@ typedef struct mi355_conv_plan {
 } mi355_conv_plan;
 int mi355_conv3d_plan(int dtype, int n, int d, int h, int w, int c0, int c1, int cout, int stride, int impl, int has_stats,
                       int has_in_norm, int head_ncls, mi355_conv_plan *out);
+/* Dry run of the shared stage 0 of the sliding window (needs no device and launches nothing; the same code mi355_sw_predict /
+ * mi355_sw_partial[_folds] run).  An fp32 network whose encoder stage 0 is r stride-1 blocks without run-time statistics
+ * (BatchNorm folded or no norm) computes that stage once per mirror over the whole padded volume, and per (tile, mirror) over
+ * one thin input slab at every tile face that lies inside the volume; the tile's level-0 features are gathered from the two
+ * (a voxel within r of such a face from that face's slab - first flagged face in the order below -, every other voxel from
+ * the whole-volume result).  Geometry is given in the coordinates of the (mirrored) pass: the padded volume flipped along the
+ * axes of the mirror mask, where a tile's origin along a flipped axis is padded - patch - origin.
+ * mirror_axes as mi355_sw_opts; r = 0 stands for a network that does not qualify.  `shared` = 0 (one tile, r = 0, or a patch
+ * thinner than a slab): every tile runs stage 0 itself, as with MI355_SHARE_STAGE0=0 (the switch itself is not consulted here).
+ * Returns the number of (tile, mirror) samples, tile-major, written to samples[] (at most max_samples; samples may be NULL),
+ * or a negative error code.  No reference counterpart. */
+typedef struct mi355_stage0_geom {
+    int32_t shared;
+    int32_t r;
+    int32_t n_tiles, n_mirrors;
+    int32_t padded[3];          /* the volume padded to at least one patch (z, y, x) */
+    int32_t volume[3];          /* the whole-volume pass: padded[] zero-extended to whole 4 x 8 x 8 conv tiles */
+    int32_t slab_thickness[3];  /* along the face's axis */
+} mi355_stage0_geom;
+typedef struct mi355_stage0_sample {
+    int32_t tile, mirror;        /* tile index (z outer .. x inner); mirror mask: bit0 flips z, bit1 y, bit2 x */
+    int32_t origin[3];           /* of the tile, in its pass */
+    int32_t face[6];             /* z lo, z hi, y lo, y hi, x lo, x hi: 1 = the face lies inside the volume and gets a slab */
+    int32_t slab_origin[6][3];   /* of the face's slab, in its pass (zeros for an unflagged face) */
+    int32_t slab_shape[6][3];
+} mi355_stage0_sample;
+int mi355_stage0_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes, int r,
+                      mi355_stage0_geom *out, mi355_stage0_sample *samples, int max_samples);
 /* Name of the kernel instantiation the calling thread's last mi355_conv3d_ndhwc / mi355_conv3d_ndhwc_f16 call dispatched
  * (the names rocprofv3 and mi355_profile_read show).  Test aid: a parity case written for one kernel can assert that it
  * ran on that kernel.  No reference counterpart (torch.nn.Conv3d, generic_UNet.py:56, has one implementation). */
