@@ -33,6 +33,7 @@ EXPORTS = [
     "mi355_label_components", "mi355_component_stats", "mi355_component_filter",
     "mi355_binary_morphology", "mi355_edt_squared", "mi355_surface_gradient_stats", "mi355_mask_second_moments",
     "mi355_masked_moments", "mi355_flag_from_labels", "mi355_flag_from_flags",
+    "mi355_masked_percentiles",
     "mi355_stage0_plan",
 ]
 
@@ -172,6 +173,8 @@ def load():
     lib.mi355_masked_moments.argtypes = [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_double), vp]
     lib.mi355_flag_from_labels.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int, vp, C.c_int64, vp]
     lib.mi355_flag_from_flags.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_int64, vp]
+    lib.mi355_masked_percentiles.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_int,
+                                             C.POINTER(C.c_int64), c_float_p, c_float_p, vp]
     lib.mi355_profile_enable.argtypes = [vp, C.c_int]
     lib.mi355_profile_read.argtypes = [vp, C.POINTER(ProfEntry), C.c_int]
     _lib = lib

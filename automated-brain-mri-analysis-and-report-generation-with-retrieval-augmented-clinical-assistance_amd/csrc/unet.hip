@@ -825,7 +825,7 @@ static int sw_accumulate(mi355_unet *net, const float *vol, int Z, int Y, int X,
 // =============================================================================== C ABI
 extern "C" const char *mi355_last_error(void) { return g_last_error.c_str(); }
 extern "C" const char *mi355_last_conv_kernel(void) { return g_last_conv_kernel.c_str(); }
-extern "C" int mi355_version(void) { return 101; }
+extern "C" int mi355_version(void) { return 102; }
 extern "C" int mi355_device_count(void) {
     int n = 0, good = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;

@@ -362,7 +362,10 @@ def region_flags(seg, t1, t2, flair):
     flag_from_labels(binary_dilation(seg, 5), (1,), BAND, flags)         # :227-228
     flag_from_flags(flags, BAND, require=1 << BAND, forbid=1 << WT)
     flag_from_labels(seg, (1,), NCR, flags)                              # utils.py:173
-    t1_hi, t2_lo, flair_hi = csf_thresholds(*(v.cpu().numpy().astype(np.float64) for v in (t1, t2, flair)))
+    from .percentile import masked_percentiles
+    t1_hi = float(masked_percentiles(t1, 10, lo=0)[1][0] * 1.5)          # :317-320 and the factors of :330-332, as csf_thresholds
+    t2_lo = float(masked_percentiles(t2, 85, lo=0)[1][0] * 0.8)
+    flair_hi = float(masked_percentiles(flair, 20, lo=0)[1][0] * 2)
     flag_from_flags(flags, CYSTIC, require=1 << NCR, x=t1, hi=t1_hi)     # :329-333
     flag_from_flags(flags, CYSTIC, require=1 << CYSTIC, x=t2, lo=t2_lo)
     flag_from_flags(flags, CYSTIC, require=1 << CYSTIC, x=flair, hi=flair_hi)
@@ -374,9 +377,9 @@ def tumor_morphology(seg, t1, t1ce, t2, flair, voxel_dims):
     shape -> the dicts ``shape_descriptors``, ``border_regularity``, ``margin_definition``, ``necrosis_pattern`` and
     ``cystic_solid_classification`` of the reference's step 4.
 
-    Everything comes from device results except the three ``np.percentile`` thresholds of :317-320: T1, T2 and FLAIR are
-    copied to the host once and the percentiles are taken there, in numpy on float64, exactly as the reference computes them
-    (three calls on about 1.5 M values each for a BraTS case)."""
+    Everything comes from device results, the three ``np.percentile`` thresholds of :317-320 included: ``masked_percentiles``
+    selects their order statistics on the device and interpolates as numpy does, bit for bit (``csf_thresholds`` is the same
+    on host arrays)."""
     import torch
     from . import components, evaluate
     seg = _check_volume(seg, torch.uint8, "tumor_morphology")

@@ -210,3 +210,34 @@ def mri_for_label_map(seed: int, seg: np.ndarray, gain: float = 0.0, cystic: flo
     pick = ncr & (rs.random_sample(shape) < cystic)
     vols[0][pick], vols[2][pick], vols[3][pick] = 50.0, 6000.0, 60.0
     return np.rint(vols).astype(np.float32)
+
+
+def mri_with_region_gains(seed: int, seg: np.ndarray, gains, et_noise: float = 0.0, zero_channel: Optional[int] = None, sigma: float = 3.0,
+                          brain: bool = True) -> np.ndarray:
+    """Four float32 volumes ``[4, d0, d1, d2]`` (T1, T1ce, T2, FLAIR) on the grid of ``seg`` with integer values below 2^24 (the
+    sequence-findings path: region means in a known ratio to the normal brain's).  Every channel is the same kind of smooth
+    field, 1000..1150, zero outside an ellipsoidal 'brain' (``brain``); ``gains`` holds rows ``[label, g_t1, g_t1ce, g_t2,
+    g_flair]`` and the voxels of ``label`` are multiplied by the row's gain of each channel; T1ce inside the enhancing labels
+    (3 and 4) is further multiplied by ``1 + et_noise * U(-1, 1)`` per voxel; ``zero_channel`` names a channel left all zero."""
+    from scipy.ndimage import gaussian_filter
+
+    rs = np.random.RandomState(seed)
+    shape = seg.shape
+    vols = np.empty((4,) + shape, dtype=np.float64)
+    for c in range(4):
+        smooth = gaussian_filter(rs.standard_normal(shape).astype(np.float32), sigma=sigma, mode="nearest")
+        smooth = (smooth - smooth.min()) / (smooth.max() - smooth.min() + 1e-12)
+        vols[c] = 1000.0 + 150.0 * smooth
+    if brain:
+        g = np.ogrid[0:shape[0], 0:shape[1], 0:shape[2]]
+        inside = sum(((g[k] - (shape[k] - 1) / 2.0) / (0.47 * shape[k])) ** 2 for k in range(3)) <= 1.0
+        vols *= inside[None]
+    for row in gains:
+        where = seg == int(row[0])
+        for c in range(4):
+            vols[c][where] *= float(row[1 + c])
+    et = (seg == 3) | (seg == 4)
+    vols[1][et] *= 1.0 + float(et_noise) * rs.uniform(-1.0, 1.0, int(et.sum()))
+    if zero_channel is not None:
+        vols[int(zero_channel)] = 0.0
+    return np.rint(vols).astype(np.float32)

@@ -279,6 +279,23 @@ int mi355_flag_from_labels(const uint8_t *labels_dev, const uint8_t *set256_host
 int mi355_flag_from_flags(uint8_t *flags_dev, int bit, int require, int forbid, const float *x_dev, double lo, double hi, int64_t n,
                           void *stream);
 
+/* ---- exact masked order statistics (csrc/percentile.hip): what the reference sorts for np.percentile (utils.py:48-49, :57, :67;
+ * step2_mass_effect.py:179; step4_morphology.py:317-320; step5_quality.py:194-212; step6_normal_structures.py:48-50) ---- */
+/* Voxel i of x_dev [n] fp32 takes part when (flags_dev is NULL, or every bit of `require` is set in flags_dev[i] and no bit of
+ * `forbid` is) and lo < (double)x_dev[i] < hi - the selection of mi355_flag_from_flags; lo, hi fp64, +-inf allowed, so
+ * `data[data > 0]` is lo = 0, hi = +inf.  A NaN never passes the comparison.  count_host[0] = m, the number of voxels that take
+ * part; count_host[1] = the number of NaN among the voxels the flag test alone selects (numpy would have returned NaN: the
+ * caller decides).  For each percentile q_host[j] in [0, 100], with v = (m - 1) * (q / 100) in IEEE double as numpy forms it:
+ * below_host[j] = the ascending order statistic of rank floor(v), above_host[j] = the one of rank min(floor(v) + 1, m - 1); both
+ * are fp32 values of the volume, exact (-0.0 counts as and is returned as +0.0).  np.percentile's linear interpolation is host
+ * arithmetic on the two.  m = 0 leaves below_host / above_host untouched and succeeds.  Radix select on the order-preserving
+ * key of the float, four histogram passes over x_dev and flags_dev (5 bytes per voxel each), no sort, no copy of the selected
+ * values; up to 8 percentiles share every pass.  Counters meet in integer atomics: two calls are bit-equal.  Scratch is per
+ * stream lane.  Refused: nq outside 1..8, a q outside [0, 100] or NaN, n outside 1..2^31-1, a NaN bound, require or forbid
+ * outside 0..255 or sharing a bit.  Synchronous. */
+int mi355_masked_percentiles(const float *x_dev, int64_t n, const uint8_t *flags_dev, int require, int forbid, double lo, double hi,
+                             const double *q_host, int nq, int64_t *count_host, float *below_host, float *above_host, void *stream);
+
 /* Per-kernel timing with HIP events on the stream the kernels are launched on (bench.py's
  * roofline). flops / bytes are the ALGORITHMIC work of the recorded launches. */
 typedef struct {

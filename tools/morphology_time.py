@@ -8,7 +8,7 @@ Device times: HIP events around warm calls (one warm-up call first, then the med
 calls); the entry points that return numbers to the host synchronise themselves, which the events include.  The end-to-end
 figure is also taken WITH the upload of the label map and the four volumes.  Host times: the calls step 4 makes - binary
 erosion and dilations, two distance transforms, three whole-volume gradients, np.where + np.cov, the boolean-mask statistics
-and the three percentiles - threads capped at 16 as tests/conftest.py does.  --profile: a short device-only run, for
+and the three percentiles (which the device path takes with masked_percentiles) - threads capped at 16 as tests/conftest.py does.  --profile: a short device-only run, for
 `rocprofv3 --kernel-trace --stats -- python tools/morphology_time.py --profile`.
 """
 import argparse
@@ -123,7 +123,7 @@ def main():
         "surface_gradient_stats": device_ms(lambda: mo.surface_gradient_stats(d2_in, d2_out, flags, 1 << mo.INNER), repeats),
         "second_moments": device_ms(lambda: mo.second_moments(dseg), repeats),
         "masked_moments_4_channels": device_ms(lambda: mo.masked_moments(dvols, flags), repeats),
-        "region_flags_with_host_percentiles": device_ms(lambda: mo.region_flags(dseg, dvols[mo.T1], dvols[mo.T2], dvols[mo.FLAIR]), repeats),
+        "region_flags_with_device_percentiles": device_ms(lambda: mo.region_flags(dseg, dvols[mo.T1], dvols[mo.T2], dvols[mo.FLAIR]), repeats),
         "tumor_morphology": device_ms(lambda: mo.tumor_morphology(dseg, *dvols, dims), repeats),
     }
     state = {}
