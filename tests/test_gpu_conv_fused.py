@@ -14,6 +14,14 @@ rounding of the output - the error budget of the plain-input gates of test_gpu_o
   head logits   |l - l_ref| <= sum_c |hw[k,c]| * (G * max(1, max|a_ref|) + eps * |a_ref[n,c,v]|), eps = 2^-11 on fp16 (the
                 kernel rounds the activation to fp16 before the head), 0 on fp32: the conv gate carried through the head's
                 linear map plus one fp16 ulp per activation.
+The fp16 cases without a head add the rounding gate of f16_rounding_util.py on y: the stored bits are RNE16 of the fp64
+reference except at a rate of at most max(0.5 %, 4 x the rate of the same composition in torch float32), no element off by
+more than one fp16 ulp.  That needs the staging model to be bit-faithful, not merely close: _f16 rounds a double ONCE, as
+v_pk_fma_f16 / v_pk_mul_f16 round their exact result (torch's double -> half conversion goes through float32 and rounds
+twice), and the output slope is the float32 the kernel is handed.
+LeakyReLU slopes: the 2e-3-of-range gate cannot tell a slope of 0.01 - the network's own - from a zero slope, so the fp16
+cases written for it run at 0.2.  The rounding gate can: the cases with the suffix _s01 repeat four of them at 0.01, and
+their zero-slope mutants (M4in, M4out) are judged by it.
 The CPU tests (no gpu mark) check that these gates can see the defects they are for: every mutated reference that applies
 to a case (padding before the norm, one sample's scale for all, in_act toggled, negative slope 0, a channel taking its
 neighbour's scale, concat halves swapped or straddled, head bias / activation / class order, statistics before the
@@ -26,6 +34,8 @@ import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+import f16_rounding_util as ru
 
 G32, G16 = 2e-5, 2e-3           # conv output gates (test_gpu_ops.py)
 SUMS_GATE = 1e-4                # statistics gates (test_conv3d_norm_sums_match_reference)
@@ -43,7 +53,7 @@ Case = namedtuple("Case", "name dtype shape c0 c1 cout act slope norm head stats
 
 def _c(name, dtype, shape, c0, c1, cout, act=1, slope=None, norm=None, head=0, stats=False, impl="mfma", kernel=None):
     if slope is None:
-        slope = 0.2 if dtype == "f16" else 0.01  # fp16: at 0.01 a zero slope stays under the fp16 gate (module docstring)
+        slope = 0.2 if dtype == "f16" else 0.01  # fp16: G16 cannot see a zero slope at 0.01; the _s01 cases can (module docstring)
     return Case(name, dtype, shape, c0, c1, cout, act, slope, norm, head, stats, impl, kernel)
 
 
@@ -97,6 +107,11 @@ CASES = [
     _c("pipe4_head", "f16", (2, 20, 64, 128), 32, 0, 32, head=4, kernel="conv3_f16_mfma_pipe_kernel<4, 1, true, false, 1, true>"),
     _c("pipe4_head_ragged", "f16", (2, 19, 64, 120), 32, 0, 32, head=2, kernel="conv3_f16_mfma_pipe_kernel<4, 1, true, false, 1, false>"),
     _c("splitk_cat_f16", "f16", (2, 4, 4, 4), 160, 160, 320, kernel="conv3_f16_mfma_kernel<1, 2, 2> split-K"),
+    # ---- fp16 at the network's own slope 0.01 (output activation; producer activation on the three staging paths)
+    _c("c32_cat_s01", "f16", (8, 32, 32, 32), 16, 16, 32, slope=0.01, kernel="conv3_f16_c32_kernel<false, false, false>"),
+    _c("c32_norm_lrelu_s01", "f16", (8, 32, 32, 32), 32, 0, 32, act=1, slope=0.01, norm=1, kernel="conv3_f16_c32_kernel<false, true, false>"),
+    _c("dma_norm_lrelu_stats_s01", "f16", (8, 32, 32, 32), 64, 0, 64, act=0, slope=0.01, norm=1, stats=True, kernel="conv3_f16_dma_kernel<true, true>"),
+    _c("pipe2_norm32_s01", "f16", (2, 16, 16, 32), 32, 0, 32, act=1, slope=0.01, norm=1, kernel="conv3_f16_mfma_pipe_kernel<2, 1, false, true, 1, true>"),
 ]
 EXPECT_KERNEL = {c.name: c.kernel for c in CASES if c.kernel}
 
@@ -157,7 +172,8 @@ def _t64(a):
 
 
 def _f16(t):
-    return t.to(torch.float16).to(torch.float64)
+    """a double rounded to fp16 ONCE (numpy; t.to(torch.float16) goes through float32 and rounds twice)"""
+    return torch.from_numpy(t.contiguous().numpy().astype(np.float16).astype(np.float64))
 
 
 def _lrelu(t, slope):
@@ -192,11 +208,12 @@ def _straddled(x0, x1):
     return out.reshape(n, d, h, w, c0 + c1)
 
 
-def _reference(case, inp, mut=(), crop=None):
+def _reference(case, inp, mut=(), crop=None, dtype=torch.float64):
     """fp64 reference of one case, optionally with one mutation (see _mutations).  Returns y = act(conv) [N,Cout,D,H,W],
     z (the conv + bias before the activation), sums [N,Cout,2] when the case has statistics, and logits [N,K,D,H,W] plus the
     activation `a` the head reads when it has a head.  crop = k: only the outputs [:k, :k, :k] of the corner, computed
-    exactly from the (padded) inputs they depend on."""
+    exactly from the (padded) inputs they depend on.  dtype = torch.float32: the same staged operands (exact in fp16, so in
+    float32), conv + bias + LeakyReLU in torch's float32 - the independent fp32 implementation of the rounding gate."""
     f16 = case.dtype == "f16"
     pad = lambda t: F.pad(t, (1, 1, 1, 1, 1, 1))  # noqa: E731
     ncdhw = lambda a: _t64(a).permute(0, 4, 1, 2, 3)  # noqa: E731
@@ -225,8 +242,8 @@ def _reference(case, inp, mut=(), crop=None):
         xin = torch.cat(parts, 1)
     if crop is not None:
         xin = xin[:, :, :crop + 2, :crop + 2, :crop + 2]
-    z = F.conv3d(xin, _t64(inp["w"]), _t64(inp["b"]))
-    slope = 0.0 if ("M4out" in mut or "M4head" in mut) else case.slope
+    z = F.conv3d(xin.to(dtype), _t64(inp["w"]).to(dtype), _t64(inp["b"]).to(dtype))
+    slope = 0.0 if ("M4out" in mut or "M4head" in mut) else float(np.float32(case.slope))  # (the C ABI takes a float)
     y = _lrelu(z, slope) if case.act and "M7act" not in mut else z
     res = {"y": y, "z": z}
     if case.stats:
@@ -279,6 +296,20 @@ def _gate(case):
     return G16 if case.dtype == "f16" else G32
 
 
+def _rounding_gated(case):
+    """fp16 cases whose output is the fp16 y (the head cases store fp32 logits)"""
+    return case.dtype == "f16" and not case.head
+
+
+def _by_rounding_gate(case, m):
+    """the zero-slope mutants of the slope-0.01 cases: below G16 (module docstring), judged by the rounding gate"""
+    return case.name.endswith("_s01") and m in ("M4in", "M4out")
+
+
+def _nchw16(t):
+    return t.contiguous().numpy().astype(np.float16)
+
+
 def _out_ratio(case, ref, got, crop=None):
     """max over elements of |got - ref| / gate; `got` is y [N,Cout,...] or logits [N,K,...] (fp64, NCDHW), compared with the
     [:crop]^3 corner of the full reference `ref` (whose maximum sets the gate)"""
@@ -325,20 +356,31 @@ def test_required_kernels_are_in_the_expectation_table():
 def test_reference_mutations_exceed_the_gates(case):
     """Every mutated reference that applies to the case misses the case's gate by >= 4x at some element.  Mutants of the
     output are evaluated on the 8^3 corner (which holds three of the six borders): an element there that misses the gate
-    is one of the full output."""
+    is one of the full output.  M4in and M4out of the _s01 cases are judged by the rounding gate instead: the mutant's y,
+    rounded to fp16 once, mismatches the reference's bits on that corner at >= 3x the cap the corner's references set."""
     inp = _inputs_cache(case)
     ref = _reference(case, inp)
-    ratios = {}
+    ratios, rates = {}, {}
     for m in _mutations(case):
         if m == "M8":  # statistics of the conv before its activation: the sums gate
             ratios[m] = _sums_ratio(ref["y"], _sums(ref["z"]))
             continue
         mut = _reference(case, inp, (m,), crop=CROP)
+        if _by_rounding_gate(case, m):
+            ref64 = _reference(case, inp, crop=CROP)["y"].numpy()
+            cap, _ = ru.gate(_reference(case, inp, crop=CROP, dtype=torch.float32)["y"].numpy(), ref64)
+            rates[m] = ru.rounding_report(_nchw16(mut["y"]), ref64)[0] / cap
+            continue
         ratios[m] = _out_ratio(case, ref, mut["logits"] if case.head else mut["y"], crop=CROP)
-    print(f"MUTANTS {case.name}: " + " ".join(f"{m}={r:.3g}" for m, r in ratios.items()))
-    assert ratios, "no mutation applies"
+    print(f"MUTANTS {case.name}: " + " ".join(f"{m}={r:.3g}" for m, r in ratios.items())
+          + "".join(f" {m}={r:.3g} x the mismatch cap" for m, r in rates.items()))
+    assert ratios or rates, "no mutation applies"
     weak = {m: r for m, r in ratios.items() if not r >= MUTANT_MARGIN}
     assert not weak, f"mutants within {MUTANT_MARGIN}x of the gate: {weak}"
+    weak = {m: r for m, r in rates.items() if not r >= ru.MUTANT_FACTOR}
+    assert not weak, f"mutants within {ru.MUTANT_FACTOR}x of the mismatch cap: {weak}"
+    if case.name.endswith("_s01"):
+        assert rates, "a slope-0.01 case without a zero-slope mutant"
 
 
 # ------------------------------------------------------------------ GPU: every fused instantiation against the reference
@@ -388,6 +430,11 @@ def test_fused_conv_matches_reference(amd, gpu, case):
         assert r_sums <= 1.0, f"statistics error {r_sums:.3g} x the gate ({ran})"
     if case.kernel and not _switched(case):
         assert ran == case.kernel, ran
+    if _rounding_gated(case):
+        ref32 = _reference(case, inp, dtype=torch.float32)["y"].numpy()
+        mismatch, cap, worst, worst_cap = ru.check(f"{case.name} [{ran}]", out.cpu().permute(0, 4, 1, 2, 3).contiguous().numpy(), ref32, ref["y"].numpy())
+        assert mismatch <= cap, f"{mismatch:.3e} of the outputs are not RNE16 of the fp64 reference, cap {cap:.3e} ({ran})"
+        assert worst <= worst_cap, f"an output is {worst:.3f} fp16 ulps from the fp64 reference ({ran})"
 
 
 # ------------------------------------------------------------------ GPU: refused combinations

@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import f16_rounding_util as ru
+
 pytestmark = pytest.mark.gpu
 
 
@@ -195,6 +197,30 @@ def test_compute_steps_table(amd):
 
 
 # --------------------------------------------------------------------------- fp16 storage kernels
+# "fp16 parity" of one launch (f16_rounding_util.py; its power is proved in test_f16_rounding_cpu.py): the stored fp16 bits
+# are RNE16 of the fp64 result on the same fp16-rounded operands, except at a rate of at most max(0.5 %, 4 x the rate of
+# torch's own fp32 conv on the CPU), and no element is off by more than one fp16 ulp.  It follows each test's older gate
+# (2e-3 of the output range), which stays.
+def _ref_conv64(x_ndhwc, w, b, stride, act, slope):
+    """_ref_conv in float64 (x, w: the fp16-rounded operands; the slope is the float32 the kernel is handed)"""
+    x = torch.from_numpy(x_ndhwc.astype(np.float64)).permute(0, 4, 1, 2, 3).contiguous()
+    y = F.conv3d(x, torch.from_numpy(w.astype(np.float64)), None if b is None else torch.from_numpy(b.astype(np.float64)), stride=stride, padding=1)
+    if act:
+        y = torch.maximum(y, y * float(np.float32(slope)))
+    return y.permute(0, 2, 3, 4, 1).contiguous().numpy()
+
+
+def _ref_tconv64(x_ndhwc, w):
+    ref = F.conv_transpose3d(torch.from_numpy(x_ndhwc.astype(np.float64)).permute(0, 4, 1, 2, 3), torch.from_numpy(w.astype(np.float64)), None, stride=2)
+    return ref.permute(0, 2, 3, 4, 1).contiguous().numpy()
+
+
+def _assert_f16_rounding(case, ran, y16, ref32, ref64):
+    mismatch, cap, worst, worst_cap = ru.check(f"{case} [{ran}]", y16, ref32, ref64)
+    assert mismatch <= cap, f"{mismatch:.3e} of the outputs are not RNE16 of the fp64 result, cap {cap:.3e} ({ran})"
+    assert worst <= worst_cap, f"an output is {worst:.3f} fp16 ulps from the fp64 result ({ran})"
+
+
 F16_CONV_CASES = [
     (1, 8, 8, 32, 32, 32, 1, 0),
     (2, 8, 12, 40, 16, 64, 1, 1),
@@ -254,13 +280,15 @@ def test_conv3d_f16_matches_torch(amd, gpu, case):
     ref = _ref_conv(x.astype(np.float32), wt.astype(np.float32), b, stride, act, 0.01)
     y = amd.ops.conv3d_ndhwc(torch.from_numpy(x).to(gpu), wt.astype(np.float32), b, stride=stride, act=act, slope=0.01)
     ran = amd.ops.last_conv_kernel()
-    y = y.float().cpu().numpy()
+    y16 = y.cpu().numpy()
+    y = y16.astype(np.float32)
     assert y.shape == ref.shape
     err = np.abs(y - ref).max()
     assert err <= 2e-3 * max(1.0, np.abs(ref).max()), f"max abs err {err} ({ran})"
     import os
     if case in F16_EXPECT_KERNEL and not any(k in os.environ for k in ("MI355_CONV_IMPL", "MI355_F16_DMA", "MI355_F16_C32", "MI355_F16_S2", "MI355_S2_DMA", "MI355_SPLITK")):
         assert ran == F16_EXPECT_KERNEL[case], ran
+    _assert_f16_rounding(case, ran, y16, ref, _ref_conv64(x, wt, b, stride, act, 0.01))
 
 
 # Norm statistics epilogue (sum y, sum y^2 per sample and channel: what InstanceNorm / GroupNorm reduce the conv output to,
@@ -313,10 +341,12 @@ def test_conv3d_norm_sums_match_reference(amd, gpu, case):
     b = _rand(rs, cout)
     if dt == "f16":
         x = x.astype(np.float16); wt = wt.astype(np.float16).astype(np.float32)
-    ref = _ref_conv(x.astype(np.float32), wt, b, stride, act, 0.01).astype(np.float64)
+    ref32 = _ref_conv(x.astype(np.float32), wt, b, stride, act, 0.01)
+    ref = ref32.astype(np.float64)
     y, sums = amd.ops.conv3d_sums_ndhwc(torch.from_numpy(x).to(gpu), wt, b, stride=stride, act=act, slope=0.01)
     ran = amd.ops.last_conv_kernel()
-    y = y.float().cpu().numpy(); sums = sums.cpu().numpy()
+    y_stored = y.cpu().numpy()
+    y = y_stored.astype(np.float32); sums = sums.cpu().numpy()
     assert np.abs(y - ref).max() <= (2e-3 if dt == "f16" else 2e-5) * max(1.0, np.abs(ref).max()), ran
     V = ref.shape[1] * ref.shape[2] * ref.shape[3]
     mean_ref = ref.sum(axis=(1, 2, 3)) / V
@@ -328,6 +358,8 @@ def test_conv3d_norm_sums_match_reference(amd, gpu, case):
     import os
     if case in SUMS_EXPECT_KERNEL and not any(k in os.environ for k in ("MI355_CONV_IMPL", "MI355_F16_DMA", "MI355_F16_C32", "MI355_F16_S2", "MI355_S2_DMA", "MI355_WINOGRAD", "MI355_WINO3")):
         assert ran == SUMS_EXPECT_KERNEL[case], ran
+    if dt == "f16":  # the y of the statistics instantiations (an epilogue of their own)
+        _assert_f16_rounding(case, ran, y_stored, ref32, _ref_conv64(x, wt, b, stride, act, 0.01))
 
 
 def test_conv3d_f16_identity_asymmetric(amd, gpu):
@@ -343,7 +375,7 @@ def test_conv3d_f16_identity_asymmetric(amd, gpu):
     assert np.array_equal(y, ref)
 
 
-@pytest.mark.parametrize("case", [(1, 4, 4, 4, 32, 32), (2, 3, 5, 6, 64, 32), (1, 2, 2, 2, 256, 512)])
+@pytest.mark.parametrize("case", [(1, 4, 4, 4, 32, 32), (2, 3, 5, 6, 64, 32), (1, 2, 2, 2, 256, 512), (1, 8, 8, 8, 320, 320)])
 def test_tconv_f16_matches_torch(amd, gpu, case):
     n, d, h, w, cin, cout = case
     rs = np.random.RandomState(5)
@@ -352,9 +384,12 @@ def test_tconv_f16_matches_torch(amd, gpu, case):
     ref = F.conv_transpose3d(torch.from_numpy(x.astype(np.float32)).permute(0, 4, 1, 2, 3),
                              torch.from_numpy(wt.astype(np.float32)), None, stride=2)
     ref = ref.permute(0, 2, 3, 4, 1).contiguous().numpy()
-    y = amd.ops.tconv3d_ndhwc(torch.from_numpy(x).to(gpu), wt.astype(np.float32)).float().cpu().numpy()
+    y16 = amd.ops.tconv3d_ndhwc(torch.from_numpy(x).to(gpu), wt.astype(np.float32)).cpu().numpy()
+    ran = amd.ops.last_conv_kernel()
+    y = y16.astype(np.float32)
     assert y.shape == ref.shape
     assert np.abs(y - ref).max() <= 2e-3 * max(1.0, np.abs(ref).max())
+    _assert_f16_rounding(case, ran, y16, ref, _ref_tconv64(x, wt))
 
 
 @pytest.mark.parametrize("case", [(1, 33, 63, 65, 32, 32), (2, 32, 32, 64, 64, 32), (1, 32, 64, 64, 128, 64)])
@@ -370,10 +405,13 @@ def test_tconv_f16_persistent_kernel_matches_torch(amd, gpu, case):
     ref = F.conv_transpose3d(torch.from_numpy(x.astype(np.float32)).permute(0, 4, 1, 2, 3),
                              torch.from_numpy(wt.astype(np.float32)), None, stride=2)
     ref = ref.permute(0, 2, 3, 4, 1).contiguous().numpy()
-    y = amd.ops.tconv3d_ndhwc(torch.from_numpy(x).to(gpu), wt.astype(np.float32)).float().cpu().numpy()
-    assert amd.ops.last_conv_kernel().startswith("tconv2_f16_mfma_v3_kernel<"), amd.ops.last_conv_kernel()
+    y16 = amd.ops.tconv3d_ndhwc(torch.from_numpy(x).to(gpu), wt.astype(np.float32)).cpu().numpy()
+    ran = amd.ops.last_conv_kernel()
+    y = y16.astype(np.float32)
+    assert ran.startswith("tconv2_f16_mfma_v3_kernel<"), ran
     assert y.shape == ref.shape
     assert np.abs(y - ref).max() <= 2e-3 * max(1.0, np.abs(ref).max())
+    _assert_f16_rounding(case, ran, y16, ref, _ref_tconv64(x, wt))
 
 
 @pytest.mark.parametrize("shape,seed", [((155, 240, 240), 1000), ((40, 56, 48), 5), ((33, 17, 29), 6)])
@@ -404,11 +442,16 @@ def test_crop_mask_matches_scipy_fill_holes(amd, gpu, shape, seed):
 
 
 _SWITCH_SCRIPT = r"""
-import sys, numpy as np, torch
+import os, sys, numpy as np, torch
 sys.path.insert(0, sys.argv[1])
+sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
 import brats_amd as amd
+import f16_rounding_util as ru
 import torch.nn.functional as F
 rs = np.random.RandomState(3)
+def conv_on_f16_operands(x16, w16, b, stride, dtype):
+    y = F.conv3d(torch.from_numpy(x16).to(dtype).permute(0, 4, 1, 2, 3), torch.from_numpy(w16).to(dtype), torch.from_numpy(b).to(dtype), stride=stride, padding=1)
+    return torch.maximum(y, y * float(np.float32(0.01))).permute(0, 2, 3, 4, 1).contiguous().numpy()
 worst = 0.0
 for (n, d, h, w, cin, cout, stride) in [(1, 64, 64, 64, 32, 64, 1), (2, 64, 64, 128, 32, 64, 2), (8, 8, 8, 8, 320, 320, 1)]:
     x = rs.standard_normal((n, d, h, w, cin)).astype(np.float32)
@@ -421,11 +464,18 @@ for (n, d, h, w, cin, cout, stride) in [(1, 64, 64, 64, 32, 64, 1), (2, 64, 64, 
             y = amd.ops.conv3d_ndhwc(torch.from_numpy(x).cuda(), wt, b, stride=stride, act=1, slope=0.01, impl="mfma").cpu().numpy()
             tol = 2e-5
         else:
-            y = amd.ops.conv3d_ndhwc(torch.from_numpy(x.astype(np.float16)).cuda(), wt, b, stride=stride, act=1, slope=0.01).float().cpu().numpy()
+            x16, w16 = x.astype(np.float16), wt.astype(np.float16)
+            y16 = amd.ops.conv3d_ndhwc(torch.from_numpy(x16).cuda(), wt, b, stride=stride, act=1, slope=0.01).cpu().numpy()
+            ran = amd.ops.last_conv_kernel()
+            y = y16.astype(np.float32)
             tol = 6e-3
         err = float(np.abs(y - ref).max() / max(1.0, np.abs(ref).max()))
         assert err <= tol, (dt, n, d, cin, cout, stride, err)
         worst = max(worst, err)
+        if dt == "f16":  # the rounding gate of the single-op tests, on the fp16-rounded operands the kernel computes with
+            mismatch, cap, ulps, ulps_cap = ru.check(f"{(n, d, h, w, cin, cout, stride, 1)} [{ran}]", y16,
+                                                     conv_on_f16_operands(x16, w16, b, stride, torch.float32), conv_on_f16_operands(x16, w16, b, stride, torch.float64))
+            assert mismatch <= cap and ulps <= ulps_cap, (ran, n, d, cin, cout, stride, mismatch, cap, ulps)
 print("OK", worst)
 """
 
@@ -441,4 +491,5 @@ def test_conv_dispatch_switches_keep_working(amd, gpu, env):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = subprocess.run([sys.executable, "-c", _SWITCH_SCRIPT, root], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
+    print("".join(line + "\n" for line in res.stdout.splitlines() if line.startswith("ROUNDING")), end="")
     assert res.returncode == 0 and "OK" in res.stdout, res.stdout[-1500:] + res.stderr[-1500:]
