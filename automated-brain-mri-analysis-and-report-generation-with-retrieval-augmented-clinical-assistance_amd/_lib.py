@@ -35,6 +35,8 @@ EXPORTS = [
     "mi355_masked_moments", "mi355_flag_from_labels", "mi355_flag_from_flags",
     "mi355_masked_percentiles",
     "mi355_stage0_plan",
+    "mi355_norm_finalize", "mi355_norm_apply", "mi355_extract_tiles", "mi355_head_logits", "mi355_head_aggregate",
+    "mi355_logits_aggregate", "mi355_cnt_add_tile", "mi355_stage0_gather", "mi355_stage0_mask",
 ]
 
 
@@ -84,6 +86,16 @@ class Stage0Geom(C.Structure):
 class Stage0Sample(C.Structure):
     _fields_ = [("tile", C.c_int32), ("mirror", C.c_int32), ("origin", C.c_int32 * 3), ("face", C.c_int32 * 6),
                 ("slab_origin", (C.c_int32 * 3) * 6), ("slab_shape", (C.c_int32 * 3) * 6)]
+
+
+class Stage0GatherSample(C.Structure):
+    _fields_ = [("wv", C.c_int32), ("origin", C.c_int32 * 3), ("slab", C.c_int32 * 6)]
+
+
+class Stage0GatherArgs(C.Structure):
+    _fields_ = [("wv_dev", C.c_void_p), ("slab_dev", C.c_void_p * 3), ("out_dev", C.c_void_p),
+                ("patch", C.c_int32 * 3), ("volume", C.c_int32 * 3), ("slab_thickness", C.c_int32 * 3),
+                ("r", C.c_int32), ("channels", C.c_int32), ("n_samples", C.c_int32), ("samples", Stage0GatherSample * 64)]
 
 
 class Mi355Error(RuntimeError):
@@ -175,6 +187,18 @@ def load():
     lib.mi355_flag_from_flags.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_int64, vp]
     lib.mi355_masked_percentiles.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_int,
                                              C.POINTER(C.c_int64), c_float_p, c_float_p, vp]
+    lib.mi355_norm_finalize.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]
+    lib.mi355_norm_apply.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int, vp, vp, C.c_int, C.c_float, vp]
+    lib.mi355_extract_tiles.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p, C.c_int, c_int32_p, C.c_int, vp,
+                                        C.c_int, vp]
+    lib.mi355_head_logits.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int, c_float_p, c_float_p, C.c_int, vp, vp, C.c_float, vp, vp]
+    lib.mi355_head_aggregate.argtypes = [vp, C.c_int, C.c_int, c_float_p, c_float_p, C.c_int, vp, vp, C.c_float, C.c_int, c_int32_p,
+                                         C.c_int, c_int32_p, C.c_int, vp, vp, vp, c_int32_p, c_int32_p, vp]
+    lib.mi355_logits_aggregate.argtypes = [vp, C.c_int, C.c_int, c_int32_p, C.c_int, c_int32_p, C.c_int, vp, vp, vp, c_int32_p,
+                                           c_int32_p, vp]
+    lib.mi355_cnt_add_tile.argtypes = [vp, c_int32_p, vp, c_int32_p, c_int32_p, vp]
+    lib.mi355_stage0_gather.argtypes = [C.POINTER(Stage0GatherArgs), vp]
+    lib.mi355_stage0_mask.argtypes = [vp, C.c_int, c_int32_p, c_int32_p, C.c_int, vp]
     lib.mi355_profile_enable.argtypes = [vp, C.c_int]
     lib.mi355_profile_read.argtypes = [vp, C.POINTER(ProfEntry), C.c_int]
     _lib = lib

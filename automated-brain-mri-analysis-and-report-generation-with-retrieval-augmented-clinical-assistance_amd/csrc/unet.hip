@@ -1356,3 +1356,134 @@ extern "C" int mi355_tconv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, i
     if (rc == MI355_OK) rc = b8_to_ndhwc((const _Float16 *)yb.p, n, cout, Vi * 8, (_Float16 *)y_dev, s);
     return synced(rc, s, "tconv");
 }
+
+// ---- single-op entry points of the kernels around the convolutions (csrc/elementwise.hip): each binds the device, calls the
+// launcher the network calls and waits for the stream.  Test aids; tensors are taken in the layout the launcher takes.
+static bool tile_in_grid(const int32_t patch[3], const int32_t padded[3], const int32_t origin[3]) {
+    for (int a = 0; a < 3; ++a)
+        if (patch[a] <= 0 || origin[a] < 0 || origin[a] + patch[a] > padded[a]) return false;
+    return true;
+}
+
+extern "C" int mi355_norm_finalize(const double *stats_dev, int n, int c, int64_t count, int kind, int groups, float eps,
+                                   const float *gamma_dev, const float *beta_dev, float *scale_dev, float *shift_dev, void *stream) {
+    MI355_REQUIRE(stats_dev && scale_dev && shift_dev && n > 0 && c > 0 && count > 0, "mi355_norm_finalize: bad argument");
+    MI355_REQUIRE(kind == MI355_NORM_INSTANCE || kind == MI355_NORM_GROUP, "mi355_norm_finalize: norm kind %d has no run-time statistics", kind);
+    MI355_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    return synced(norm_finalize(stats_dev, n, c, count, kind, groups, eps, gamma_dev, beta_dev, scale_dev, shift_dev, s), s, "norm_finalize");
+}
+
+extern "C" int mi355_norm_apply(void *x_dev, int dtype, int n, int64_t v, int c, const float *scale_dev, const float *shift_dev, int act,
+                                float slope, void *stream) {
+    MI355_REQUIRE(x_dev && scale_dev && shift_dev && n > 0 && v > 0 && c > 0, "mi355_norm_apply: bad argument");
+    MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_F16, "unknown dtype %d", dtype);
+    MI355_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    return synced(norm_apply(x_dev, dtype, n, v, c, scale_dev, shift_dev, act, slope, s), s, "norm_apply");
+}
+
+extern "C" int mi355_extract_tiles(const float *vol_dev, int c, int z, int y, int x, const int32_t pad[3], const int32_t *tiles_host,
+                                   int n_samples, const int32_t patch[3], int cpad, void *x_dev, int dtype, void *stream) {
+    MI355_REQUIRE(vol_dev && pad && tiles_host && patch && x_dev && c > 0 && z > 0 && y > 0 && x > 0, "mi355_extract_tiles: bad argument");
+    MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_F16, "unknown dtype %d", dtype);
+    MI355_REQUIRE(patch[0] > 0 && patch[1] > 0 && patch[2] > 0 && cpad >= c, "mi355_extract_tiles: patch %d x %d x %d, %d of %d channels", patch[0],
+                  patch[1], patch[2], c, cpad);
+    MI355_REQUIRE(n_samples > 0 && n_samples <= S0_MAX_SAMPLES, "mi355_extract_tiles: %d samples", n_samples);
+    MI355_TRY(require_device());
+    std::vector<TileDesc> tiles(n_samples);
+    for (int i = 0; i < n_samples; ++i) tiles[i] = TileDesc{tiles_host[4 * i], tiles_host[4 * i + 1], tiles_host[4 * i + 2], tiles_host[4 * i + 3]};
+    hipStream_t s = (hipStream_t)stream;
+    return synced(extract_tiles(vol_dev, c, z, y, x, pad[0], pad[1], pad[2], tiles.data(), n_samples, patch[0], patch[1], patch[2], cpad, x_dev, dtype, s),
+                  s, "extract_tiles");
+}
+
+static FeatNorm feat_norm(const float *scale_dev, const float *shift_dev, float slope) {
+    FeatNorm fn;
+    fn.scale = scale_dev; fn.shift = shift_dev; fn.slope = slope;
+    return fn;
+}
+
+extern "C" int mi355_head_logits(const void *feat_dev, int dtype, int n, int64_t v, int cin, const float *weight_host, const float *bias_host,
+                                 int ncls, const float *scale_dev, const float *shift_dev, float slope, float *logits_dev, void *stream) {
+    MI355_REQUIRE(feat_dev && weight_host && logits_dev && v > 0, "mi355_head_logits: bad argument");
+    MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_F16, "unknown dtype %d", dtype);
+    MI355_REQUIRE(!scale_dev == !shift_dev, "scale and shift come together");
+    MI355_TRY(require_device());
+    TmpWeights<HeadWeights, head_weights_free> hw;
+    MI355_TRY(head_weights_upload(weight_host, bias_host, cin, ncls, &hw.w));
+    hipStream_t s = (hipStream_t)stream;
+    return synced(head_logits(hw.w, feat_dev, dtype, n, v, logits_dev, s, feat_norm(scale_dev, shift_dev, slope)), s, "head_logits");
+}
+
+extern "C" int mi355_head_aggregate(const void *feat_dev, int dtype, int cin, const float *weight_host, const float *bias_host, int ncls,
+                                    const float *scale_dev, const float *shift_dev, float slope, int first_sample, const int32_t *mirrors_host,
+                                    int n_mirrors, const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *cnt_dev,
+                                    const int32_t padded[3], const int32_t origin[3], void *stream) {
+    MI355_REQUIRE(feat_dev && weight_host && mirrors_host && patch && agg_dev && padded && origin && first_sample >= 0, "mi355_head_aggregate: bad argument");
+    MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_F16, "unknown dtype %d", dtype);
+    MI355_REQUIRE(!scale_dev == !shift_dev, "scale and shift come together");
+    MI355_REQUIRE(tile_in_grid(patch, padded, origin), "mi355_head_aggregate: the tile leaves the padded grid");
+    MI355_TRY(require_device());
+    TmpWeights<HeadWeights, head_weights_free> hw;
+    MI355_TRY(head_weights_upload(weight_host, bias_host, cin, ncls, &hw.w));
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> mirrors(mirrors_host, mirrors_host + std::max(n_mirrors, 0));
+    return synced(head_aggregate(hw.w, feat_dev, dtype, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev, agg_dev,
+                                 cnt_dev, padded[0], padded[1], padded[2], origin[0], origin[1], origin[2], s, feat_norm(scale_dev, shift_dev, slope)),
+                  s, "head_aggregate");
+}
+
+extern "C" int mi355_logits_aggregate(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
+                                      const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *cnt_dev,
+                                      const int32_t padded[3], const int32_t origin[3], void *stream) {
+    MI355_REQUIRE(logits_dev && mirrors_host && patch && agg_dev && padded && origin && first_sample >= 0, "mi355_logits_aggregate: bad argument");
+    MI355_REQUIRE(tile_in_grid(patch, padded, origin), "mi355_logits_aggregate: the tile leaves the padded grid");
+    MI355_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> mirrors(mirrors_host, mirrors_host + std::max(n_mirrors, 0));
+    return synced(logits_aggregate(logits_dev, ncls, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev, agg_dev,
+                                   cnt_dev, padded[0], padded[1], padded[2], origin[0], origin[1], origin[2], s),
+                  s, "logits_aggregate");
+}
+
+extern "C" int mi355_cnt_add_tile(const float *gauss_dev, const int32_t patch[3], float *cnt_dev, const int32_t padded[3],
+                                  const int32_t origin[3], void *stream) {
+    MI355_REQUIRE(patch && cnt_dev && padded && origin, "mi355_cnt_add_tile: bad argument");
+    MI355_REQUIRE(tile_in_grid(patch, padded, origin), "mi355_cnt_add_tile: the tile leaves the padded grid");
+    MI355_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    return synced(cnt_add_tile(gauss_dev, patch[0], patch[1], patch[2], cnt_dev, padded[1], padded[2], origin[0], origin[1], origin[2], s), s,
+                  "cnt_add_tile");
+}
+
+extern "C" int mi355_stage0_gather(const mi355_stage0_gather_args *a, void *stream) {
+    MI355_REQUIRE(a && a->wv_dev && a->out_dev && a->channels > 0 && a->channels % 4 == 0, "mi355_stage0_gather: bad argument");
+    MI355_REQUIRE(a->n_samples > 0 && a->n_samples <= S0_MAX_SAMPLES, "mi355_stage0_gather: %d samples (max %d)", a->n_samples, S0_MAX_SAMPLES);
+    MI355_TRY(require_device());
+    S0GatherArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.wv = a->wv_dev; ga.out = a->out_dev;
+    for (int k = 0; k < 3; ++k) { ga.slab[k] = a->slab_dev[k]; ga.P[k] = a->patch[k]; ga.Ve[k] = a->volume[k]; ga.t[k] = a->slab_thickness[k]; }
+    ga.r = a->r; ga.C4 = a->channels / 4;
+    for (int i = 0; i < a->n_samples; ++i) {
+        S0Sample &sm = ga.smp[i];
+        sm.wv = a->samples[i].wv;
+        MI355_REQUIRE(sm.wv >= 0, "mi355_stage0_gather: sample %d: whole-volume index %d", i, sm.wv);
+        for (int k = 0; k < 3; ++k) sm.org[k] = a->samples[i].origin[k];
+        for (int f = 0; f < 6; ++f) {
+            sm.slab[f] = a->samples[i].slab[f];
+            MI355_REQUIRE(sm.slab[f] < 0 || a->slab_dev[f >> 1], "mi355_stage0_gather: sample %d: face %d without a slab tensor", i, f);
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    return synced(stage0_gather(ga, a->n_samples, s), s, "stage0_gather");
+}
+
+extern "C" int mi355_stage0_mask(float *x_dev, int n, const int32_t volume[3], const int32_t keep[3], int c, void *stream) {
+    MI355_REQUIRE(x_dev && volume && keep, "mi355_stage0_mask: bad argument");
+    MI355_TRY(require_device());
+    const int ve[3] = {volume[0], volume[1], volume[2]}, zp[3] = {keep[0], keep[1], keep[2]};
+    hipStream_t s = (hipStream_t)stream;
+    return synced(stage0_mask(x_dev, n, ve, zp, c, s), s, "stage0_mask");
+}

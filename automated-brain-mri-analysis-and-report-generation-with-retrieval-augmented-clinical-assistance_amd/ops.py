@@ -305,3 +305,230 @@ def compute_steps(patch, image, step_size):
     n = _lib.load().mi355_compute_steps(int(patch), int(image), float(step_size), buf, 256)
     _lib.check(n, "mi355_compute_steps")
     return [int(buf[i]) for i in range(n)]
+
+
+# ---- the kernels around the convolutions, one launch each (test entry points; every call waits for the stream).  fp32 tensors
+# are plain NDHWC, fp16 tensors channel-blocked [N, C / 8, V, 8], passed as they are.
+def _i3(v):
+    v = [int(k) for k in v]
+    if len(v) != 3:
+        raise ValueError(f"expected three extents, got {v}")
+    return (C.c_int32 * 3)(*v)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _f32(t, name, numel=None):
+    import torch
+    if t is None:
+        return None
+    t = _require_cuda(t, torch.float32, name)
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"{name}: {t.numel()} elements, expected {numel}")
+    return t
+
+
+def norm_finalize(stats, count, kind="instance", groups=1, eps=1e-5, gamma=None, beta=None):
+    """``mi355_norm_finalize``: stats CUDA fp64 [N, C, 2] (sum, sum of squares over ``count`` voxels) -> (scale, shift) CUDA fp32
+    [N, C]; gamma / beta CUDA fp32 [C] or None."""
+    import torch
+    stats = _require_cuda(stats, torch.float64, "stats")
+    n, c, two = stats.shape
+    if two != 2:
+        raise ValueError("stats must be [N, C, 2]")
+    gamma, beta = _f32(gamma, "gamma", c), _f32(beta, "beta", c)
+    scale = torch.full((n, c), float("nan"), dtype=torch.float32, device=stats.device)
+    shift = torch.full((n, c), float("nan"), dtype=torch.float32, device=stats.device)
+    _lib.check(_lib.load().mi355_norm_finalize(stats.data_ptr(), n, c, int(count), {"instance": _lib.NORM_INSTANCE, "group": _lib.NORM_GROUP}[kind],
+                                               int(groups), float(eps), _ptr(gamma), _ptr(beta), scale.data_ptr(), shift.data_ptr(),
+                                               _stream(stats)), "mi355_norm_finalize")
+    return scale, shift
+
+
+def norm_apply_(x, scale, shift, act=0, slope=0.01):
+    """``mi355_norm_apply``, in place.  x: contiguous CUDA fp32 [N, V, C] or fp16 channel-blocked [N, C / 8, V, 8]; scale / shift
+    CUDA fp32 [N, C]."""
+    import torch
+    if not (x.is_cuda and x.is_contiguous() and x.dtype in (torch.float32, torch.float16)):
+        raise ValueError("norm_apply_: x must be a contiguous CUDA fp32 / fp16 tensor")
+    if x.dtype == torch.float16:
+        n, cb, v, eight = x.shape
+        if eight != 8:
+            raise ValueError("norm_apply_: fp16 tensors are [N, C / 8, V, 8]")
+        c = cb * 8
+    else:
+        n, v, c = x.shape
+    scale, shift = _f32(scale, "scale", n * c), _f32(shift, "shift", n * c)
+    _lib.check(_lib.load().mi355_norm_apply(x.data_ptr(), int(x.dtype == torch.float16), n, v, c, scale.data_ptr(), shift.data_ptr(), int(act),
+                                            float(slope), _stream(x)), "mi355_norm_apply")
+    return x
+
+
+def extract_tiles(vol, pad, tiles, patch, cpad, dtype="f32"):
+    """``mi355_extract_tiles``.  vol: CUDA fp32 [C, Z, Y, X]; pad: its offset (z, y, x) in the padded volume; tiles: (z0, y0, x0,
+    mirror mask) per sample.  Returns [n, PV, cpad] (fp32, and fp16 when cpad % 8 != 0) or the blocked [n, cpad / 8, PV, 8] fp16."""
+    import torch
+    vol = _require_cuda(vol, torch.float32, "vol")
+    c, z, y, x = vol.shape
+    tiles = [tuple(int(k) for k in t) for t in tiles]
+    if not tiles or any(len(t) != 4 for t in tiles):
+        raise ValueError("extract_tiles: tiles are (z0, y0, x0, mirror)")
+    n, cpad = len(tiles), int(cpad)
+    pv = int(np.prod([int(p) for p in patch]))
+    f16 = {"f32": False, "f16": True}[dtype]
+    shape = (n, cpad // 8, pv, 8) if f16 and cpad % 8 == 0 else (n, pv, cpad)
+    out = torch.full(shape, float("nan"), dtype=torch.float16 if f16 else torch.float32, device=vol.device)
+    flat = (C.c_int32 * (4 * n))(*[k for t in tiles for k in t])
+    _lib.check(_lib.load().mi355_extract_tiles(vol.data_ptr(), c, z, y, x, _i3(pad), flat, n, _i3(patch), cpad, out.data_ptr(), int(f16),
+                                               _stream(vol)), "mi355_extract_tiles")
+    return out
+
+
+def _feat_dims(feat):
+    """(f16, samples, voxels, channels) of a feature tensor in the network's layout."""
+    import torch
+    if not (feat.is_cuda and feat.is_contiguous() and feat.dtype in (torch.float32, torch.float16)):
+        raise ValueError("feat must be a contiguous CUDA fp32 / fp16 tensor")
+    if feat.dtype == torch.float16:
+        n, cb, v, eight = feat.shape
+        if eight != 8:
+            raise ValueError("fp16 features are [N, C / 8, V, 8]")
+        return True, n, v, cb * 8
+    n, v, c = feat.shape
+    return False, n, v, c
+
+
+def _head_operands(weight, bias, cin):
+    weight = np.ascontiguousarray(weight, dtype=np.float32)
+    if weight.ndim != 2 or weight.shape[1] != cin:
+        raise ValueError(f"head weight must be [ncls, {cin}]")
+    bias = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+    if bias is not None and bias.shape != (weight.shape[0],):
+        raise ValueError("head bias must be [ncls]")
+    return weight, bias
+
+
+def head_logits(feat, weight, bias=None, scale=None, shift=None, slope=1.0):
+    """``mi355_head_logits``.  feat: CUDA fp32 [N, V, C] or fp16 blocked [N, C / 8, V, 8]; weight numpy [ncls, C]; scale / shift CUDA
+    fp32 [N, C] or None.  Returns logits CUDA fp32 [N, ncls, V]."""
+    import torch
+    f16, n, v, c = _feat_dims(feat)
+    weight, bias = _head_operands(weight, bias, c)
+    scale, shift = _f32(scale, "scale", n * c), _f32(shift, "shift", n * c)
+    ncls = weight.shape[0]
+    out = torch.full((n, ncls, v), float("nan"), dtype=torch.float32, device=feat.device)
+    _lib.check(_lib.load().mi355_head_logits(feat.data_ptr(), int(f16), n, v, c, _lib.fptr(weight), _lib.fptr(bias), ncls, _ptr(scale),
+                                             _ptr(shift), float(slope), out.data_ptr(), _stream(feat)), "mi355_head_logits")
+    return out
+
+
+def _tile_operands(agg, cnt, gauss, ncls, patch, origin, name):
+    import torch
+    agg = _require_cuda(agg, torch.float32, "agg")
+    if not agg.is_contiguous() or agg.dim() != 4 or agg.shape[0] != ncls:
+        raise ValueError(f"{name}: agg must be a contiguous [ncls, Zp, Yp, Xp]")
+    padded = tuple(int(k) for k in agg.shape[1:])
+    if cnt is not None and (not cnt.is_cuda or cnt.dtype != torch.float32 or not cnt.is_contiguous() or tuple(cnt.shape) != padded):
+        raise ValueError(f"{name}: cnt must be a contiguous CUDA fp32 [Zp, Yp, Xp]")
+    pv = int(np.prod([int(p) for p in patch]))
+    gauss = _f32(gauss, "gauss", pv)
+    if any(int(o) < 0 or int(o) + int(p) > q for o, p, q in zip(origin, patch, padded)):
+        raise ValueError(f"{name}: the tile leaves the padded grid")
+    return gauss, padded, pv
+
+
+def head_aggregate_(feat, weight, bias, mirrors, patch, nonlin, agg, cnt, origin, gauss=None, first_sample=0, scale=None, shift=None,
+                    slope=1.0):
+    """``mi355_head_aggregate``: one tile into agg [ncls, Zp, Yp, Xp] / cnt [Zp, Yp, Xp] (CUDA fp32, in place; cnt may be None).
+    feat: every sample of the forward ([S, PV, C] fp32 or blocked fp16), of which first_sample .. + len(mirrors) - 1 are this tile's;
+    mirrors: masks, bit0 z; nonlin "identity" | "sigmoid" | "softmax"; gauss CUDA fp32 [patch] or None."""
+    f16, n, v, c = _feat_dims(feat)
+    weight, bias = _head_operands(weight, bias, c)
+    mirrors = [int(m) for m in mirrors]
+    gauss, padded, pv = _tile_operands(agg, cnt, gauss, weight.shape[0], patch, origin, "head_aggregate_")
+    if v != pv or first_sample < 0 or first_sample + len(mirrors) > n:
+        raise ValueError("head_aggregate_: feat does not hold the tile's samples")
+    scale, shift = _f32(scale, "scale", n * c), _f32(shift, "shift", n * c)
+    from .predictor import NONLIN
+    _lib.check(_lib.load().mi355_head_aggregate(feat.data_ptr(), int(f16), c, _lib.fptr(weight), _lib.fptr(bias), weight.shape[0], _ptr(scale),
+                                                _ptr(shift), float(slope), int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
+                                                len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss), agg.data_ptr(), _ptr(cnt), _i3(padded),
+                                                _i3(origin), _stream(feat)), "mi355_head_aggregate")
+
+
+def logits_aggregate_(logits, mirrors, patch, nonlin, agg, cnt, origin, gauss=None, first_sample=0):
+    """``mi355_logits_aggregate``: as ``head_aggregate_`` from logits CUDA fp32 [S, ncls, PV]."""
+    import torch
+    logits = _require_cuda(logits, torch.float32, "logits")
+    n, ncls, v = logits.shape
+    mirrors = [int(m) for m in mirrors]
+    gauss, padded, pv = _tile_operands(agg, cnt, gauss, ncls, patch, origin, "logits_aggregate_")
+    if v != pv or first_sample < 0 or first_sample + len(mirrors) > n:
+        raise ValueError("logits_aggregate_: logits do not hold the tile's samples")
+    from .predictor import NONLIN
+    _lib.check(_lib.load().mi355_logits_aggregate(logits.data_ptr(), ncls, int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
+                                                  len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss), agg.data_ptr(), _ptr(cnt), _i3(padded),
+                                                  _i3(origin), _stream(logits)), "mi355_logits_aggregate")
+
+
+def cnt_add_tile_(cnt, patch, origin, gauss=None):
+    """``mi355_cnt_add_tile``: cnt [Zp, Yp, Xp] (CUDA fp32, in place) += gauss [patch] (None: 1) at origin."""
+    gauss, padded, _ = _tile_operands(cnt[None], cnt, gauss, 1, patch, origin, "cnt_add_tile_")
+    _lib.check(_lib.load().mi355_cnt_add_tile(_ptr(gauss), _i3(patch), cnt.data_ptr(), _i3(padded), _i3(origin), _stream(cnt)),
+               "mi355_cnt_add_tile")
+
+
+def stage0_gather(wv, slabs, samples, patch, r):
+    """``mi355_stage0_gather``.  wv: CUDA fp32 [mirrors, Ve0, Ve1, Ve2, C]; slabs: per axis a CUDA fp32 [n, S0, S1, S2, C] (S[a] = the
+    slab thickness, S[k] = patch[k] otherwise) or None; samples: dicts {wv, origin, slab: six indices or -1}.  Returns
+    [len(samples), P0, P1, P2, C].  Slab and whole-volume indices are checked against the tensors here."""
+    import torch
+    wv = _require_cuda(wv, torch.float32, "wv")
+    nwv, c = int(wv.shape[0]), int(wv.shape[4])
+    patch = [int(p) for p in patch]
+    a = _lib.Stage0GatherArgs()
+    a.wv_dev = wv.data_ptr()
+    keep = [wv]
+    for k in range(3):
+        a.patch[k], a.volume[k] = patch[k], int(wv.shape[1 + k])
+        a.slab_thickness[k] = 2 * int(r)
+    for k, sl in enumerate(slabs):
+        if sl is None:
+            continue
+        sl = _require_cuda(sl, torch.float32, f"slabs[{k}]")
+        keep.append(sl)
+        want = [int(sl.shape[1 + j]) if j == k else patch[j] for j in range(3)]
+        if sl.dim() != 5 or list(sl.shape[1:4]) != want or sl.shape[4] != c:
+            raise ValueError(f"slabs[{k}]: shape {tuple(sl.shape)}")
+        a.slab_dev[k] = sl.data_ptr()
+        a.slab_thickness[k] = int(sl.shape[1 + k])
+    if len(samples) > 64:
+        raise ValueError("stage0_gather: more than 64 samples")
+    for i, sm in enumerate(samples):
+        if not 0 <= int(sm["wv"]) < nwv:
+            raise ValueError(f"stage0_gather: sample {i}: whole-volume index")
+        a.samples[i].wv = int(sm["wv"])
+        for k in range(3):
+            a.samples[i].origin[k] = int(sm["origin"][k])
+        for f in range(6):
+            idx = int(sm["slab"][f])
+            if idx >= 0 and (slabs[f >> 1] is None or idx >= slabs[f >> 1].shape[0]):
+                raise ValueError(f"stage0_gather: sample {i}: face {f} has no slab {idx}")
+            a.samples[i].slab[f] = idx
+    a.r, a.channels, a.n_samples = int(r), c, len(samples)
+    out = torch.full((max(len(samples), 1), patch[0], patch[1], patch[2], c), float("nan"), dtype=torch.float32, device=wv.device)
+    a.out_dev = out.data_ptr()
+    _lib.check(_lib.load().mi355_stage0_gather(C.byref(a), _stream(wv)), "mi355_stage0_gather")
+    return out
+
+
+def stage0_mask_(x, keep):
+    """``mi355_stage0_mask``, in place: x CUDA fp32 [N, Ve0, Ve1, Ve2, C], zero outside [0, keep)."""
+    import torch
+    if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 5):
+        raise ValueError("stage0_mask_: x must be a contiguous CUDA fp32 [N, Ve0, Ve1, Ve2, C]")
+    _lib.check(_lib.load().mi355_stage0_mask(x.data_ptr(), int(x.shape[0]), _i3(x.shape[1:4]), _i3(keep), int(x.shape[4]), _stream(x)),
+               "mi355_stage0_mask")
+    return x

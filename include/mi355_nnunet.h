@@ -387,6 +387,68 @@ typedef struct mi355_stage0_sample {
 } mi355_stage0_sample;
 int mi355_stage0_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes, int r,
                       mi355_stage0_geom *out, mi355_stage0_sample *samples, int max_samples);
+/* ---- the kernels around the convolutions, one launch each (test aids; no reference counterpart beyond the one named at the
+ * kernel in csrc/elementwise.hip).  Each call runs the launcher the network runs and waits for `stream`.  Tensors are taken in
+ * the layout the network holds them in: fp32 plain NDHWC ([N][V][C]), fp16 channel-blocked ([N][C / 8][V][8]), AS IS. ---- */
+/* stats_dev [n][c][2] fp64 (sum, sum of squares over `count` voxels) -> scale_dev / shift_dev [n][c] fp32 with
+ * norm(x) = x * scale + shift: biased variance (clamped at 0), eps inside the root.  kind = MI355_NORM_INSTANCE, or
+ * MI355_NORM_GROUP with `groups` groups of c / groups consecutive channels (c % groups != 0 is refused).  gamma_dev / beta_dev
+ * [c] fp32 or NULL (1 / 0). */
+int mi355_norm_finalize(const double *stats_dev, int n, int c, int64_t count, int kind, int groups, float eps,
+                        const float *gamma_dev, const float *beta_dev, float *scale_dev, float *shift_dev, void *stream);
+/* In place: x = act(x * scale[n][c] + shift[n][c]) over n samples of v voxels; act 1 = LeakyReLU(slope).  c % 4 == 0 (fp32),
+ * c % 8 == 0 (fp16). */
+int mi355_norm_apply(void *x_dev, int dtype, int n, int64_t v, int c, const float *scale_dev, const float *shift_dev, int act,
+                     float slope, void *stream);
+/* vol_dev [c][z][y][x] fp32 sits at offset pad[] (z, y, x) in a zero volume; sample i is the patch[]-sized box at
+ * tiles_host[4 i .. 4 i + 2] (z, y, x) of that volume, flipped along the axes of the mask tiles_host[4 i + 3] (bit0 z, bit1 y,
+ * bit2 x), written to x_dev [n_samples][patch voxels][cpad] of dtype (fp16 with cpad % 8 == 0: channel-blocked); channels
+ * >= c are zero.  At most 64 samples. */
+int mi355_extract_tiles(const float *vol_dev, int c, int z, int y, int x, const int32_t pad[3], const int32_t *tiles_host,
+                        int n_samples, const int32_t patch[3], int cpad, void *x_dev, int dtype, void *stream);
+/* 1x1x1 head: feat_dev [n][v][cin] of dtype -> logits_dev [n][ncls][v] fp32, weight_host [ncls][cin], bias_host [ncls] or NULL
+ * (uploaded inside the call; cin % 8 == 0, ncls <= 8).  scale_dev / shift_dev [n][cin] fp32 or both NULL: the features are a
+ * conv's raw output and the head reads max(y, slope * y) of y = x * scale + shift (slope 1: no activation). */
+int mi355_head_logits(const void *feat_dev, int dtype, int n, int64_t v, int cin, const float *weight_host, const float *bias_host,
+                      int ncls, const float *scale_dev, const float *shift_dev, float slope, float *logits_dev, void *stream);
+/* One tile of the sliding window: samples first_sample .. first_sample + n_mirrors - 1 of feat_dev are the forwards of the
+ * tile flipped by mirrors_host[] (masks as above); result = sum over them, in list order, of (1 / n_mirrors) *
+ * flip_back(nonlin(head(features))); agg_dev [ncls][padded] += result * gauss_dev [patch] (NULL: 1) at origin[], cnt_dev
+ * [padded] += gauss (cnt_dev may be NULL).  scale_dev / shift_dev are indexed by the sample as feat_dev is.  A tile that
+ * leaves the padded grid is refused. */
+int mi355_head_aggregate(const void *feat_dev, int dtype, int cin, const float *weight_host, const float *bias_host, int ncls,
+                         const float *scale_dev, const float *shift_dev, float slope, int first_sample, const int32_t *mirrors_host,
+                         int n_mirrors, const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *cnt_dev,
+                         const int32_t padded[3], const int32_t origin[3], void *stream);
+/* The same from logits_dev [samples][ncls][patch voxels] fp32 (a last conv with the fused head). */
+int mi355_logits_aggregate(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
+                           const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *cnt_dev,
+                           const int32_t padded[3], const int32_t origin[3], void *stream);
+/* cnt_dev [padded] += gauss_dev [patch] (NULL: 1) at origin[]: the normaliser of a tile another rank evaluates. */
+int mi355_cnt_add_tile(const float *gauss_dev, const int32_t patch[3], float *cnt_dev, const int32_t padded[3],
+                       const int32_t origin[3], void *stream);
+/* The gather of the shared stage 0 (mi355_stage0_plan): out_dev [n_samples][patch][channels] fp32 from the whole-volume results
+ * wv_dev [mirrors][volume][channels] and, per axis a, the slab results slab_dev[a] [slabs][S][channels] with S[a] =
+ * slab_thickness[a], S[k] = patch[k] otherwise.  Sample i is the box at samples[i].origin of whole-volume result samples[i].wv;
+ * slab[f] (faces z lo, z hi, y lo, y hi, x lo, x hi) = index of that face's slab in its axis's tensor, or -1: a voxel within r
+ * of a face with a slab comes from that slab (the first such face in that order), every other voxel from the whole volume.
+ * A hi-face slab covers the last slab_thickness layers of the tile.  Refused: a sample that leaves the volume,
+ * slab_thickness < 2 r, patch < slab_thickness, channels % 4 != 0, more than 64 samples. */
+typedef struct mi355_stage0_gather_args {
+    const float *wv_dev;
+    const float *slab_dev[3];
+    float *out_dev;
+    int32_t patch[3], volume[3], slab_thickness[3];
+    int32_t r, channels, n_samples;
+    struct {
+        int32_t wv;
+        int32_t origin[3];
+        int32_t slab[6];
+    } samples[64];
+} mi355_stage0_gather_args;
+int mi355_stage0_gather(const mi355_stage0_gather_args *args, void *stream);
+/* x_dev [n][volume][c] fp32: zero every voxel outside [0, keep) (c % 4 == 0, 0 < keep <= volume); the rest is not written. */
+int mi355_stage0_mask(float *x_dev, int n, const int32_t volume[3], const int32_t keep[3], int c, void *stream);
 /* Name of the kernel instantiation the calling thread's last mi355_conv3d_ndhwc / mi355_conv3d_ndhwc_f16 call dispatched
  * (the names rocprofv3 and mi355_profile_read show).  Test aid: a parity case written for one kernel can assert that it
  * ran on that kernel.  No reference counterpart (torch.nn.Conv3d, generic_UNet.py:56, has one implementation). */
