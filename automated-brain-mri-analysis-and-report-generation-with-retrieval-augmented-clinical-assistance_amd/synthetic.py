@@ -241,3 +241,63 @@ def mri_with_region_gains(seed: int, seg: np.ndarray, gains, et_noise: float = 0
     if zero_channel is not None:
         vols[int(zero_channel)] = 0.0
     return np.rint(vols).astype(np.float32)
+
+
+def mri_for_quality(seed: int, seg: np.ndarray, levels=None, brain_axes: Optional[float] = 0.47, radial_gain: float = 0.0, plateau=(), ghost=(),
+                    dropout=(), spikes=(), edge_noise=None, zero_channel: Optional[int] = None, sigma: float = 3.0) -> np.ndarray:
+    """Four float32 volumes ``[4, d0, d1, d2]`` (T1, T1ce, T2, FLAIR) on the grid of ``seg`` with integer values below 2^15 (the
+    quality-control path: every artefact the reference's step 5 looks for can be switched on by itself).  Channel ``c`` is a
+    smooth field ``levels[c] = [base, amplitude]`` (default 1000, 150), zero outside a centred ellipsoidal 'brain' whose
+    semi-axes are ``brain_axes`` times the shape (None: no skull strip), then in this order:
+    ``radial_gain``  every channel times ``1 + radial_gain * r``, r = 0 at the centre and 1 on the ellipsoid (a bias field);
+    ``plateau``      rows ``[channel, fraction]``: the lowest ``fraction`` of the channel's positive voxels take its smallest
+                     positive value (a tie at the minimum: the 5th / 10th percentile then IS the minimum);
+    ``dropout``      rows ``[channel, lo, hi]``: the box set to zero (missing data);
+    ``spikes``       rows ``[channel, p_high, high, p_low, low]``: a share of the voxels inside the ellipsoid set to ``high`` / ``low``;
+    ``edge_noise``   ``[p, value]``: T1 plus ``value`` on a share ``p`` of the voxels within two steps of the tumour surface;
+    ``ghost``        rows ``[channel, level, kind]``: noise on the zero voxels outside the ellipsoid, ``"exp"`` = 1 + an exponential
+                     of mean ``level`` (coefficient of variation near 1), ``"flat"`` = ``level`` .. ``1.1 level`` uniform;
+    ``zero_channel`` names a channel left all zero."""
+    from scipy.ndimage import binary_dilation, binary_erosion, gaussian_filter
+
+    rs = np.random.RandomState(seed)
+    shape = seg.shape
+    levels = [[1000.0, 150.0]] * 4 if levels is None else levels
+    vols = np.empty((4,) + shape, dtype=np.float64)
+    for c in range(4):
+        smooth = gaussian_filter(rs.standard_normal(shape).astype(np.float32), sigma=sigma, mode="nearest")
+        smooth = (smooth - smooth.min()) / (smooth.max() - smooth.min() + 1e-12)
+        vols[c] = float(levels[c][0]) + float(levels[c][1]) * smooth
+    g = np.ogrid[0:shape[0], 0:shape[1], 0:shape[2]]
+    if brain_axes is None:
+        r = np.sqrt(sum(((g[k] - (shape[k] - 1) / 2.0) / (0.5 * shape[k])) ** 2 for k in range(3)))
+        inside = np.ones(shape, dtype=bool)
+    else:
+        r = np.sqrt(sum(((g[k] - (shape[k] - 1) / 2.0) / (float(brain_axes) * shape[k])) ** 2 for k in range(3)))
+        inside = r <= 1.0
+        vols *= inside[None]
+    vols *= (1.0 + float(radial_gain) * r)[None]
+    vols = np.rint(vols)
+    for c, fraction in plateau:
+        v = vols[int(c)]
+        pos = v[v > 0]
+        v[(v > 0) & (v <= np.percentile(pos, 100.0 * float(fraction)))] = pos.min()
+    for c, lo, hi in dropout:
+        vols[int(c)][tuple(slice(int(a), int(b)) for a, b in zip(lo, hi))] = 0.0
+    for c, p_high, high, p_low, low in spikes:
+        u = rs.random_sample(shape)
+        vols[int(c)][inside & (u < float(p_high))] = float(high)
+        vols[int(c)][inside & (u > 1.0 - float(p_low))] = float(low)
+    if edge_noise is not None and seg.any():
+        wt = seg > 0
+        near = binary_dilation(wt, iterations=2) & ~binary_erosion(wt, iterations=3)
+        vols[0][near & (rs.random_sample(shape) < float(edge_noise[0]))] += float(edge_noise[1])
+    for c, level, kind in ghost:
+        outside = ~inside & (vols[int(c)] == 0)
+        n = int(outside.sum())
+        noise = 1.0 + rs.exponential(float(level), n) if kind == "exp" else float(level) * (1.0 + 0.1 * rs.random_sample(n))
+        vols[int(c)][outside] = np.minimum(np.rint(noise), 30000.0)
+    if zero_channel is not None:
+        vols[int(zero_channel)] = 0.0
+    assert vols.max() < 2 ** 15 and vols.min() >= 0
+    return vols.astype(np.float32)

@@ -234,7 +234,8 @@ int mi355_component_filter(const int32_t *labels_dev, const uint8_t *seg_dev, in
                            uint8_t *out_dev, void *stream);
 
 /* ---- binary morphology, distance transform and mask reductions (csrc/morphology.hip): the primitives under
- * feature_extraction/step4_morphology.py; step2_mass_effect.py:19,373 needs the first one too.  Volumes are [d0][d1][d2]
+ * feature_extraction/step4_morphology.py; step2_mass_effect.py:19,373 needs the first one too, step1_sequence_findings.py the
+ * dilation, flag bits and moments, step5_quality.py (:408, :179-241, :283, :322-327) the erosion, flag bits, moments and centroid.  Volumes are [d0][d1][d2]
  * C-order with fewer than 2^31 voxels (MI355_ERR_INVALID otherwise), uint8 masks are foreground where nonzero, two calls give
  * bit-equal results, scratch is per stream lane. ---- */
 /* scipy.ndimage.binary_erosion (dilate = 0) / binary_dilation (dilate != 0) with their defaults (step4_morphology.py:42, :149,
@@ -280,7 +281,8 @@ int mi355_flag_from_flags(uint8_t *flags_dev, int bit, int require, int forbid, 
                           void *stream);
 
 /* ---- exact masked order statistics (csrc/percentile.hip): what the reference sorts for np.percentile (utils.py:48-49, :57, :67;
- * step2_mass_effect.py:179; step4_morphology.py:317-320; step5_quality.py:194-212; step6_normal_structures.py:48-50) ---- */
+ * step2_mass_effect.py:179; step4_morphology.py:317-320; step5_quality.py:194-212; step6_normal_structures.py:48-50).  On the device so far: steps 1, 4 and
+ * 5 (brats_amd.sequence_findings, .morphology, .quality) ---- */
 /* Voxel i of x_dev [n] fp32 takes part when (flags_dev is NULL, or every bit of `require` is set in flags_dev[i] and no bit of
  * `forbid` is) and lo < (double)x_dev[i] < hi - the selection of mi355_flag_from_flags; lo, hi fp64, +-inf allowed, so
  * `data[data > 0]` is lo = 0, hi = +inf.  A NaN never passes the comparison.  count_host[0] = m, the number of voxels that take
@@ -295,6 +297,40 @@ int mi355_flag_from_flags(uint8_t *flags_dev, int bit, int require, int forbid, 
  * outside 0..255 or sharing a bit.  Synchronous. */
 int mi355_masked_percentiles(const float *x_dev, int64_t n, const uint8_t *flags_dev, int require, int forbid, double lo, double hi,
                              const double *q_host, int nq, int64_t *count_host, float *below_host, float *above_host, void *stream);
+
+/* ---- hole filling, Sobel gradient statistics, radial shells and face slabs (csrc/quality.hip): the primitives under
+ * feature_extraction/step5_quality.py that the entries above do not cover.  Conventions as for csrc/morphology.hip: volumes are
+ * [d0][d1][d2] C-order with fewer than 2^31 voxels (MI355_ERR_INVALID otherwise), uint8 masks are foreground where nonzero, two
+ * calls give bit-equal results (fp64 sums are combined in a fixed order, integers meet in integer atomics), scratch is per
+ * stream lane. ---- */
+/* scipy.ndimage.binary_fill_holes(mask) with its default structure (step5_quality.py:103): a background voxel stays background
+ * exactly when a path of 6-neighbour steps through background voxels joins it to a voxel on one of the six faces of the volume.
+ * out_dev [d0][d1][d2] uint8 holds 0 / 1 and is bit-equal to scipy's result; *filled_host = the number of voxels added.  The
+ * complement is labelled by mi355_label_components at connectivity 1 (one union-find labelling, no sweep that repeats until
+ * nothing changes), the components that own a face voxel are marked, and the others are filled.  Refused: out_dev == mask_dev.
+ * Synchronous. */
+int mi355_binary_fill_holes(const uint8_t *mask_dev, int d0, int d1, int d2, uint8_t *out_dev, int64_t *filled_host, void *stream);
+/* sqrt(gx^2 + gy^2 + gz^2) in fp64 at the voxels where flags_dev[i] & select is nonzero, g_axis being
+ * scipy.ndimage.sobel(x.astype(float), axis) with scipy's defaults (step5_quality.py:413-416, which differentiates the whole
+ * volume and then indexes the tumour edge): [-1, 0, 1] along the axis, [1, 2, 1] along each of the other two, boundary mode
+ * `reflect` (index -1 reads index 0, index n reads index n - 1; an axis of length 1 reads itself).  A 27-point gather at the
+ * selected voxels only.  stats_host[0..2] = number of selected voxels, mean, population standard deviation (all 0 when nothing
+ * is selected); the deviation comes from a second pass about the mean of the first.  For integer-valued x below 2^15 every
+ * magnitude is the correctly rounded root of an exact integer, bit-equal to scipy's.  Refused: select outside 1..255.
+ * Synchronous. */
+int mi355_sobel_magnitude_stats(const float *x_dev, const uint8_t *flags_dev, int select, int d0, int d1, int d2, double *stats_host,
+                                void *stream);
+/* Over the voxels whose flag byte has every bit of `require` (step5_quality.py:280-300): out_host[0] = max_dist, the maximum of
+ * sqrt((c0 - centre[0])**2 + (c1 - centre[1])**2 + (c2 - centre[2])**2) evaluated in fp64 in that order, every square rounded
+ * before the additions (no fused multiply-add); out_host[1], [2] = the number and the fp64 sum of x over the voxels with
+ * dist < max_dist * inner_frac; out_host[3], [4] = the same over the voxels with dist > max_dist * outer_frac.  An empty
+ * selection gives all zeros and succeeds.  Refused: require outside 0..255, a NaN centre or fraction.  Synchronous. */
+int mi355_radial_shell_moments(const float *x_dev, const uint8_t *flags_dev, int require, int d0, int d1, int d2, const double centre[3],
+                               double inner_frac, double outer_frac, double *out_host, void *stream);
+/* counts_host[2 a], counts_host[2 a + 1] = the number of voxels with x > 0 among the first `margin` and among the last `margin`
+ * indices of axis a (step5_quality.py:385-390: `t1_data[:5].max() > 0` is counts_host[0] > 0); a margin at or above the axis
+ * length means the whole axis.  A NaN is not counted.  Refused: margin < 1.  Synchronous. */
+int mi355_face_slab_counts(const float *x_dev, int d0, int d1, int d2, int margin, int64_t *counts_host, void *stream);
 
 /* Per-kernel timing with HIP events on the stream the kernels are launched on (bench.py's
  * roofline). flops / bytes are the ALGORITHMIC work of the recorded launches. */
