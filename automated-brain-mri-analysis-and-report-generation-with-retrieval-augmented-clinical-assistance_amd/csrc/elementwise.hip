@@ -850,10 +850,10 @@ extern "C" int mi355_regions_to_labels(const float *probs_dev, int C, int Z, int
 
 extern "C" int mi355_label_ensemble(const uint8_t *a_dev, const uint8_t *b_dev, uint8_t *out_dev, int64_t n,
                                     void *stream) {
+    MI355_REQUIRE(a_dev && b_dev && out_dev && n >= 1, "label_ensemble: bad argument");
     MI355_TRY(bind_device());
     int64_t blocks = (n + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(label_ensemble_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a_dev,
                        b_dev, out_dev, n);
     MI355_HIP(hipGetLastError());
@@ -861,10 +861,10 @@ extern "C" int mi355_label_ensemble(const uint8_t *a_dev, const uint8_t *b_dev, 
 }
 
 extern "C" int mi355_prob_mean(const float *a_dev, const float *b_dev, float *out_dev, int64_t n, void *stream) {
+    MI355_REQUIRE(a_dev && b_dev && out_dev && n >= 1, "prob_mean: bad argument");
     MI355_TRY(bind_device());
     int64_t blocks = (n + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(prob_mean_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a_dev, b_dev,
                        out_dev, n);
     MI355_HIP(hipGetLastError());
@@ -873,10 +873,10 @@ extern "C" int mi355_prob_mean(const float *a_dev, const float *b_dev, float *ou
 
 extern "C" int mi355_zscore_masked(float *vol_dev, const uint8_t *mask_dev, int C, int64_t voxels, void *stream) {
     MI355_REQUIRE(C >= 1 && C <= 64, "zscore: %d channels", C);
+    MI355_REQUIRE(vol_dev && mask_dev && voxels >= 1, "zscore: bad argument");
     hipStream_t s = (hipStream_t)stream;
     int64_t blocks = (voxels + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
     // persistent scratch, ONE slot of its own: [sums 64 x 3 | partial C x blocks x 3] doubles; asynchronous on `stream`.  The sums
     // used to sit in SCR_SMALL, which mi355_label_confusion / mi355_label_stats also use: a caller following INTEGRATION.md's
     // two-stream exception (preprocess the next case beside a prediction / evaluation) would have corrupted mean and std.
