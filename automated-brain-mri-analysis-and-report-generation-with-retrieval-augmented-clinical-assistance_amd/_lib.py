@@ -35,6 +35,7 @@ EXPORTS = [
     "mi355_masked_moments", "mi355_flag_from_labels", "mi355_flag_from_flags",
     "mi355_masked_percentiles",
     "mi355_binary_fill_holes", "mi355_sobel_magnitude_stats", "mi355_radial_shell_moments", "mi355_face_slab_counts",
+    "mi355_axis_counts", "mi355_box_counts", "mi355_select_ranked", "mi355_min_pair_dist2", "mi355_masked_min_i32",
     "mi355_stage0_plan",
     "mi355_norm_finalize", "mi355_norm_apply", "mi355_extract_tiles", "mi355_head_logits", "mi355_head_aggregate",
     "mi355_logits_aggregate", "mi355_cnt_add_tile", "mi355_stage0_gather", "mi355_stage0_mask",
@@ -193,6 +194,11 @@ def load():
     lib.mi355_radial_shell_moments.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double,
                                                C.POINTER(C.c_double), vp]
     lib.mi355_face_slab_counts.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), vp]
+    lib.mi355_axis_counts.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), vp]
+    lib.mi355_box_counts.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, C.c_int, C.POINTER(C.c_int64), vp]
+    lib.mi355_select_ranked.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.c_int, vp, C.POINTER(C.c_int64), vp]
+    lib.mi355_min_pair_dist2.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), vp]
+    lib.mi355_masked_min_i32.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int64, c_int32_p, C.POINTER(C.c_int64), vp]
     lib.mi355_norm_finalize.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]
     lib.mi355_norm_apply.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int, vp, vp, C.c_int, C.c_float, vp]
     lib.mi355_extract_tiles.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p, C.c_int, c_int32_p, C.c_int, vp,

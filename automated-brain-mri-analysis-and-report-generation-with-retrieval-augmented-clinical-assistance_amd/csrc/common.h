@@ -24,7 +24,7 @@ int bind_device();
 // `zeroed` buffers are cleared when (re)allocated.  Work that uses a slot is ordered by the stream it was asked for
 // ("Stream semantics").
 enum ScratchSlot { SCR_ARENA = 0, SCR_SW_AGG, SCR_SPLITK_F32, SCR_SPLITK_F16, SCR_ZEROS, SCR_ZERO_BIAS, SCR_SMALL, SCR_TOPK,
-                   SCR_CROP, SCR_ZSCORE, SCR_RESAMPLE, SCR_RESAMPLE_MM, SCR_COMPONENTS, SCR_MORPHOLOGY, SCR_QUALITY, SCR_COUNT };
+                   SCR_CROP, SCR_ZSCORE, SCR_RESAMPLE, SCR_RESAMPLE_MM, SCR_COMPONENTS, SCR_MORPHOLOGY, SCR_QUALITY, SCR_MASS_EFFECT, SCR_COUNT };
 int device_scratch(int slot, hipStream_t stream, size_t bytes, void **out, bool zeroed = false);
 
 #define MI355_HIP(expr)                                                                    \

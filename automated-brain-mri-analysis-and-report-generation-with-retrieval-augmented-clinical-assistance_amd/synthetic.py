@@ -301,3 +301,41 @@ def mri_for_quality(seed: int, seg: np.ndarray, levels=None, brain_axes: Optiona
         vols[int(zero_channel)] = 0.0
     assert vols.max() < 2 ** 15 and vols.min() >= 0
     return vols.astype(np.float32)
+
+
+def mri_for_mass_effect(seed: int, seg: np.ndarray, brain_axes: float = 0.47, cuts=(), dark=(), noise: float = 0.0, peri_scale: float = 1.0,
+                        zero: bool = False, sigma: float = 3.0) -> np.ndarray:
+    """One float32 T1 volume ``[d0, d1, d2]`` on the grid of ``seg`` with integer values below 2^15 (the mass-effect path: the
+    hemispheric asymmetry of the brain mask, the sides of the CSF-like voxels and the intensity spread around the tumour can be
+    steered one by one).  A smooth field 1000..1150 plus white noise of standard deviation ``noise``, zero outside a centred
+    ellipsoidal 'brain' whose semi-axes are ``brain_axes`` times the shape, then in this order:
+    ``peri_scale``  within ten dilations of the tumour (the tumour excluded) the deviation from 1075 is multiplied by it (below
+                    1: the sulci around the tumour are effaced);
+    ``dark``        rows ``[lo, hi, factor]``: the box multiplied by ``factor`` (CSF-like signal: with enough of it the 5th and
+                    15th percentile fall inside these boxes, and their sizes decide the left / right CSF volumes);
+    ``cuts``        rows ``[lo, hi]``: the box set to zero (tissue missing on one side: the two halves of the brain mask lose
+                    their symmetry about the middle of its extent);
+    ``zero``        all zero (no brain)."""
+    from scipy.ndimage import binary_dilation, gaussian_filter
+
+    rs = np.random.RandomState(seed)
+    shape = seg.shape
+    smooth = gaussian_filter(rs.standard_normal(shape).astype(np.float32), sigma=sigma, mode="nearest")
+    smooth = (smooth - smooth.min()) / (smooth.max() - smooth.min() + 1e-12)
+    t1 = 1000.0 + 150.0 * smooth.astype(np.float64) + float(noise) * rs.standard_normal(shape)
+    g = np.ogrid[0:shape[0], 0:shape[1], 0:shape[2]]
+    inside = sum(((g[k] - (shape[k] - 1) / 2.0) / (float(brain_axes) * shape[k])) ** 2 for k in range(3)) <= 1.0
+    if peri_scale != 1.0 and seg.any():
+        wt = seg > 0
+        zone = binary_dilation(wt, iterations=10) & ~wt
+        t1[zone] = 1075.0 + float(peri_scale) * (t1[zone] - 1075.0)
+    t1 = np.maximum(t1, 1.0) * inside
+    for lo, hi, factor in dark:
+        t1[tuple(slice(int(a), int(b)) for a, b in zip(lo, hi))] *= float(factor)
+    for lo, hi in cuts:
+        t1[tuple(slice(int(a), int(b)) for a, b in zip(lo, hi))] = 0.0
+    if zero:
+        t1[...] = 0.0
+    t1 = np.rint(t1)
+    assert t1.max() < 2 ** 15 and t1.min() >= 0
+    return t1.astype(np.float32)

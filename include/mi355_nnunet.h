@@ -281,8 +281,8 @@ int mi355_flag_from_flags(uint8_t *flags_dev, int bit, int require, int forbid, 
                           void *stream);
 
 /* ---- exact masked order statistics (csrc/percentile.hip): what the reference sorts for np.percentile (utils.py:48-49, :57, :67;
- * step2_mass_effect.py:179; step4_morphology.py:317-320; step5_quality.py:194-212; step6_normal_structures.py:48-50).  On the device so far: steps 1, 4 and
- * 5 (brats_amd.sequence_findings, .morphology, .quality) ---- */
+ * step2_mass_effect.py:179; step4_morphology.py:317-320; step5_quality.py:194-212; step6_normal_structures.py:48-50).  On the device so far: steps 1, 2, 4 and
+ * 5 (brats_amd.sequence_findings, .mass_effect, .morphology, .quality) ---- */
 /* Voxel i of x_dev [n] fp32 takes part when (flags_dev is NULL, or every bit of `require` is set in flags_dev[i] and no bit of
  * `forbid` is) and lo < (double)x_dev[i] < hi - the selection of mi355_flag_from_flags; lo, hi fp64, +-inf allowed, so
  * `data[data > 0]` is lo = 0, hi = +inf.  A NaN never passes the comparison.  count_host[0] = m, the number of voxels that take
@@ -331,6 +331,49 @@ int mi355_radial_shell_moments(const float *x_dev, const uint8_t *flags_dev, int
  * indices of axis a (step5_quality.py:385-390: `t1_data[:5].max() > 0` is counts_host[0] > 0); a margin at or above the axis
  * length means the whole axis.  A NaN is not counted.  Refused: margin < 1.  Synchronous. */
 int mi355_face_slab_counts(const float *x_dev, int d0, int d1, int d2, int margin, int64_t *counts_host, void *stream);
+
+/* ---- axis profiles, box counts, ranked picks, point-set distance and a masked minimum (csrc/mass_effect.hip): the primitives under
+ * feature_extraction/step2_mass_effect.py that the entries above do not cover.  Conventions as for csrc/morphology.hip and
+ * csrc/quality.hip: volumes are [d0][d1][d2] C-order with fewer than 2^31 voxels (MI355_ERR_INVALID otherwise); a voxel is
+ * SELECTED when every bit of `require` is set in flags_dev[i] and no bit of `forbid` is (both in 0..255, sharing no bit - the
+ * selection of mi355_flag_from_flags); two calls give bit-equal results (integers meet in integer atomics, there is no float
+ * anywhere); scratch is per stream lane; null pointers and sizes out of range are refused before anything is launched. ---- */
+#define MI355_AXIS_COUNTS_MAX 4096  /* longest axis of mi355_axis_counts: its d0 + d1 + d2 32-bit counters must fit 48 KiB of LDS */
+#define MI355_MAX_BOXES 16
+#define MI355_MAX_POINTS 65536
+/* counts_host[0 .. d0), [d0 .. d0 + d1), [d0 + d1 .. d0 + d1 + d2) = the number of selected voxels at each index of axis 0, 1, 2.
+ * Host arithmetic gets from them what step2_mass_effect.py takes from np.where(mask): `brain_coords[0].min() / .max()` (:66-67),
+ * `tumor_coords[0].mean()` (:73; an exact integer sum divided once), `left_half.sum()`, `right_half.sum()` and
+ * `ndimage.center_of_mass(half)[0]` (:84-93), the CSF halves (:186-193), `tumor_mask[:k].sum()` (:447-448), utils.get_centroid and
+ * utils.get_bounding_box (:441-442).  Refused: an axis longer than MI355_AXIS_COUNTS_MAX.  Synchronous. */
+int mi355_axis_counts(const uint8_t *flags_dev, int require, int forbid, int d0, int d1, int d2, int64_t *counts_host, void *stream);
+/* counts_host[b] = the number of selected voxels with lo_k <= c_k < hi_k on every axis k, for the nb (1..MI355_MAX_BOXES) boxes
+ * boxes_host[b * 6 + 0..5] = lo0, hi0, lo1, hi1, lo2, hi2: `(tumor_mask & lobe_mask).sum()` of step2_mass_effect.py:472-518, whose
+ * lobe masks are slices (the temporal lobe is two boxes).  Boxes may overlap; a box with lo >= hi on an axis counts 0.  Refused:
+ * lo < 0 or hi > the axis length.  Synchronous. */
+int mi355_box_counts(const uint8_t *flags_dev, int require, int forbid, int d0, int d1, int d2, const int32_t *boxes_host, int nb,
+                     int64_t *counts_host, void *stream);
+/* count_host[0] = m, the number of selected voxels among flags_dev[0 .. n); index_dev[j] = the linear index of the selected voxel
+ * whose 0-based rank among the selected voxels in C order is ranks_host[j], i.e. np.flatnonzero(selected)[ranks] - what
+ * `tumor_coords[k][sample_idx]` and `csf_points[csf_sample_idx]` of step2_mass_effect.py:215-225 index, without np.where.  Ranks
+ * come in any order and may repeat; 1 <= k <= MI355_MAX_POINTS; n in 1..2^31-1.  One count per 4096-voxel block, a two-level
+ * scan of the counts, then one wave per rank finds the owning block by bisection and the voxel by popcounts and a wave scan.
+ * A rank outside [0, m) fails the call with nothing written to index_dev; count_host is filled all the same.  Synchronous. */
+int mi355_select_ranked(const uint8_t *flags_dev, int require, int forbid, int64_t n, const int64_t *ranks_host, int k,
+                        int64_t *index_dev, int64_t *count_host, void *stream);
+/* min_host[0] = the smallest squared Euclidean distance, in voxel units, between a voxel of a_index_dev [ka] and one of
+ * b_index_dev [kb] (linear C-order indices into [d0][d1][d2], as mi355_select_ranked writes them; ka, kb in
+ * 1..MI355_MAX_POINTS): the double loop of step2_mass_effect.py:227-232.  An exact integer; sqrt is monotone and correctly
+ * rounded, so sqrt(min d^2) is the reference's min(sqrt(d^2)) bit for bit.  Refused after the launch, with min_host untouched: an
+ * index outside the volume (the kernel reads the two lists and nothing else).  Synchronous. */
+int mi355_min_pair_dist2(const int64_t *a_index_dev, int ka, const int64_t *b_index_dev, int kb, int d0, int d1, int d2,
+                         int64_t *min_host, void *stream);
+/* min_host[0] = the minimum of values_dev [n] int32 over the selected voxels, count_host[0] = their number; an empty selection
+ * leaves min_host untouched and succeeds with count 0.  With mi355_edt_squared of the complement of a mask as the values this is
+ * the exact squared distance from the selection to that mask: the minimum over ALL pairs of what step2_mass_effect.py:214-232
+ * samples.  n in 1..2^31-1.  Synchronous. */
+int mi355_masked_min_i32(const int32_t *values_dev, const uint8_t *flags_dev, int require, int forbid, int64_t n, int32_t *min_host,
+                         int64_t *count_host, void *stream);
 
 /* Per-kernel timing with HIP events on the stream the kernels are launched on (bench.py's
  * roofline). flops / bytes are the ALGORITHMIC work of the recorded launches. */
