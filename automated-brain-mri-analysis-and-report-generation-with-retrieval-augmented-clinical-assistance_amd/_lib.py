@@ -36,7 +36,7 @@ EXPORTS = [
     "mi355_masked_percentiles",
     "mi355_binary_fill_holes", "mi355_sobel_magnitude_stats", "mi355_radial_shell_moments", "mi355_face_slab_counts",
     "mi355_axis_counts", "mi355_box_counts", "mi355_select_ranked", "mi355_min_pair_dist2", "mi355_masked_min_i32",
-    "mi355_stage0_plan",
+    "mi355_stage0_plan", "mi355_skip_share_plan", "mi355_conv3d_wino3_ndhwc",
     "mi355_norm_finalize", "mi355_norm_apply", "mi355_extract_tiles", "mi355_head_logits", "mi355_head_aggregate",
     "mi355_logits_aggregate", "mi355_cnt_add_tile", "mi355_stage0_gather", "mi355_stage0_mask",
 ]
@@ -83,6 +83,17 @@ class ConvPlan(C.Structure):
 class Stage0Geom(C.Structure):
     _fields_ = [("shared", C.c_int32), ("r", C.c_int32), ("n_tiles", C.c_int32), ("n_mirrors", C.c_int32),
                 ("padded", C.c_int32 * 3), ("volume", C.c_int32 * 3), ("slab_thickness", C.c_int32 * 3)]
+
+
+class SkipShareNet(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("norm", C.c_int32), ("nonlin_first", C.c_int32), ("enc0_blocks", C.c_int32),
+                ("stride", C.c_int32), ("skip_is_enc0", C.c_int32), ("c_up", C.c_int32), ("c_skip", C.c_int32), ("cout", C.c_int32),
+                ("head_ncls", C.c_int32)]
+
+
+class SkipShareGeom(C.Structure):
+    _fields_ = [("stage0_shared", C.c_int32), ("skip_shared", C.c_int32), ("r", C.c_int32), ("skip_shell", C.c_int32),
+                ("n_tiles", C.c_int32), ("n_mirrors", C.c_int32), ("volume", C.c_int32 * 3), ("slab_thickness", C.c_int32 * 3)]
 
 
 class Stage0Sample(C.Structure):
@@ -168,6 +179,10 @@ def load():
     lib.mi355_conv3d_plan.argtypes = [C.c_int] * 13 + [C.POINTER(ConvPlan)]
     lib.mi355_stage0_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.c_int, C.POINTER(Stage0Geom),
                                       C.POINTER(Stage0Sample), C.c_int]
+    lib.mi355_skip_share_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.POINTER(SkipShareNet), C.c_int,
+                                          C.c_int, C.c_int, C.POINTER(SkipShareGeom)]
+    lib.mi355_conv3d_wino3_ndhwc.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
+                                             C.c_int, C.c_int, C.c_float, vp, vp, vp]
     lib.mi355_label_remap.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_uint8), vp]
     lib.mi355_label_confusion.argtypes = [vp, vp, C.c_int64, C.c_int, C.POINTER(C.c_uint64), vp]
     lib.mi355_cosine_topk.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_float_p, vp]

@@ -1465,6 +1465,7 @@ int plan_conv_f32(const ConvWeights &w, const ConvCall &c, ConvPlan *p) {
     const int gy_nf = w.cout / (32 * w.nf);  // cout blocks when a workgroup takes all w.nf fragments
     p->nf = w.nf;
     if (plan_wino3(w, c, p)) return MI355_OK;
+    MI355_REQUIRE(!c.addend, "conv %d->%d: an addend reached a kernel that cannot add it", w.cin, w.cout);
     MI355_REQUIRE(!c.in_scale, "conv %d->%d: a pending input normalisation reached a kernel that cannot apply it", w.cin, w.cout);
     // the 16-channel-chunk kernels below pick in0 or in1 once per chunk: a concat split that is a multiple of 8 only (w.cc of
     // the pipelined build) would make a chunk straddle the two halves; such calls go to the 8-channel kernels
@@ -1623,6 +1624,7 @@ int plan_conv_direct(const ConvWeights &w, const ConvCall &c) {
     MI355_REQUIRE(c.C0 + c.C1 == w.cin_pad, "conv input channels %d+%d != %d", c.C0, c.C1, w.cin_pad);
     // (the statistics epilogue is here; the fused head and the fused input normalisation are not)
     MI355_REQUIRE(!c.head_out && !c.in_scale, "conv %d->%d: the direct kernel has no fused head or input normalisation", w.cin, w.cout);
+    MI355_REQUIRE(!c.addend, "conv %d->%d: the direct kernel has no addend epilogue", w.cin, w.cout);
     MI355_REQUIRE(c.out != nullptr, "conv %d->%d: no output tensor", w.cin, w.cout);
     return MI355_OK;
 }

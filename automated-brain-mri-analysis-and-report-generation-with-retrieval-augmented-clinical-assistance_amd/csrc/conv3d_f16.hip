@@ -1319,6 +1319,7 @@ int plan_conv_f16(const ConvWeightsH &w, const ConvCallH &c, ConvPlan *p) {
     MI355_REQUIRE(c.C0 + c.C1 == w.cin_pad, "conv input channels %d+%d != %d", c.C0, c.C1, w.cin_pad);
     MI355_REQUIRE(c.C0 % 16 == 0 && c.C1 % 16 == 0, "fp16 concat split %d/%d not a multiple of 16", c.C0, c.C1);
     MI355_REQUIRE(c.C1 == 0 || c.in1 != nullptr, "second conv input missing");
+    MI355_REQUIRE(!c.addend, "conv %d->%d: the fp16 kernels have no addend epilogue", w.cin, w.cout);
     const int st = w.stride;
     const bool pipe = conv_impl() != 0;  // MI355_CONV_IMPL=0: the one-tile-per-workgroup kernels only
     MI355_REQUIRE(!c.head_out || (st == 1 && pipe && w.cout == 32 * w.nf && !c.stats && c.head_ncls >= 1 && c.head_ncls <= 4 && c.head_w && c.head_b),

@@ -54,6 +54,8 @@ struct Wino3Args {
     // INAFF: in0 is the RAW output of the previous block; act(x * in_scale[n][c] + in_shift[n][c]) is applied to the brick in LDS
     const float *in_scale, *in_shift;
     float in_slope;  // LeakyReLU slope of that activation, 1 = none
+    // EPI 3: [N][D][H][W][Cout] added to the conv sum in front of bias and activation (the other half of a split concat conv), or null
+    const float *addend;
 };
 
 constexpr int W3_IZ = 6, W3_IY = 10, W3_IX = 10, W3_BV = W3_IZ * W3_IY * W3_IX;  // 600 brick voxels
@@ -66,7 +68,8 @@ constexpr int W3_JUNK = 64 * 4;                 // INAFF: where the in-place wri
 constexpr size_t W3_LDS_BYTES = (size_t)(2 * W3_BUF + W3_STAGE + 4 * 32 * 2 + W3_JUNK) * sizeof(float);
 static_assert(W3_LDS_BYTES <= 160 * 1024, "LDS budget");
 
-// EPI: 0 = bias + LeakyReLU + store, 1 = fused 1x1x1 segmentation head (the network's last conv, Cout = 32: only the logits are
+// EPI: 0 = bias + LeakyReLU + store, 3 = as 0 with an addend in front of the bias (a separate instantiation: the plain one carries
+// no branch or register for it), 1 = fused 1x1x1 segmentation head (the network's last conv, Cout = 32: only the logits are
 // written), 2 = as 0 + Instance/GroupNorm statistics (sum x, sum x^2 per sample and cout)
 // INAFF (round 4): the producer's Instance/GroupNorm (+ LeakyReLU) is applied by THIS conv (generic_UNet.py:62-72 is one expression,
 // lrelu(instnorm(conv(x)))): every lane normalises, in place in LDS, the ten 16-byte pieces it fetched itself - no other lane has
@@ -546,6 +549,24 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino3_kernel(Wino3Args p) {
         int lane_e;  // rebuilt from the hardware lane id: a tile-loop invariant would be hoisted to the kernel entry and spilled
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
         float *wr = stage + wave * (4 * W3_IMG) + (lane_e & 31) * W3_PITCH + 4 * (lane_e >> 5);
+        // Addend (EPI 3): the eight 16-byte pieces this lane adds in phase 2, from the addresses of its own stores in the other
+        // tensor.  Issued here, in every wave alike, so that phase 1 hides their latency; the vmcnt(0) in front of phase 2 (the next
+        // tile's first weights) retires them.  (The build's ISA gate, H2, fails if hipcc places a copy of a piece behind its load
+        // while it may be in flight.)
+        f32x4 ad[8];
+        if constexpr (EPI == 3) {
+            {
+                const int srow_a = lane_e >> 3;
+                const size_t row_a = (size_t)p.W * p.Cout;
+                const float *abase = p.addend + (((size_t)cur.n * p.D + cur.oz0) * p.H + cur.oy0 + (wave >> 1)) * row_a + (int)blockIdx.y * 32;
+                const unsigned aoff = (unsigned)(((2 * (srow_a >> 2)) * p.W + cur.ox0 + 2 * (srow_a & 3) + (wave & 1)) * p.Cout + (lane_e & 7) * 4);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {  // k = 2 t + oz, as phase 2 walks its rows
+                    const float *ap = abase + ((size_t)(2 * (k >> 2) + (k & 1)) * p.H + 4 * ((k >> 1) & 1)) * row_a + aoff;
+                    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(ad[k]) : "v"(ap) : "memory");
+                }
+            }
+        }
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
             // The accumulators are "redefined" by an empty asm at the top of every register pair: the 32 v_accvgpr_read of pair r
@@ -577,6 +598,10 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino3_kernel(Wino3Args p) {
         // and stores of a wave may complete out of order with each other, a count-based wait taken behind the stores could not
         // tell them apart.  The next tile's first step then starts without any wait.
         { auto &u0 = uq[0]; W3_UWAIT(u0, 0); }
+        if constexpr (EPI == 3) {
+            // ("redefined" behind the wait that retired the loads: nothing reads the pieces in front of it)
+            asm volatile("" : "+v"(ad[0]), "+v"(ad[1]), "+v"(ad[2]), "+v"(ad[3]), "+v"(ad[4]), "+v"(ad[5]), "+v"(ad[6]), "+v"(ad[7]));
+        }
 
         // ---- phase 2: wave (oy, ox) adds the four xi_z partials (A^T along z), bias, LeakyReLU, whole-line stores.
         // Lane = (block row srow + 8 t, 4 couts `piece`): 8 lanes hold the 32 couts = the 128-B line of one voxel.
@@ -636,6 +661,10 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino3_kernel(Wino3Args p) {
                     x1 = pk_sub(pk_sub(f32x2{pz[1][2], pz[1][3]}, f32x2{pz[2][2], pz[2][3]}), f32x2{pz[3][2], pz[3][3]});
                 }
                 f32x4 val;
+                if constexpr (EPI == 3) {
+                    x0 = pk_add(x0, f32x2{ad[2 * t + oz][0], ad[2 * t + oz][1]});
+                    x1 = pk_add(x1, f32x2{ad[2 * t + oz][2], ad[2 * t + oz][3]});
+                }
                 asm("v_pk_add_f32 %0, %1, %2" : "=v"(x0) : "v"(x0), "v"(b01));
                 asm("v_pk_add_f32 %0, %1, %2" : "=v"(x1) : "v"(x1), "v"(b23));
                 asm("v_pk_mul_f32 %0, %1, %2" : "=v"(y0) : "v"(x0), "v"(slope2));
@@ -787,8 +816,10 @@ bool conv3d_wino3_enabled() { return env_switch("MI355_WINO3"); }
 // Does the F(2x2x2, 3x3x3) kernel take this call?  Stride 1, whole 4 x 8 x 8 tiles, 16-channel chunks on both halves of a virtual
 // concat, enough tiles to fill the chip; the fused head needs Cout = 32; the fused input norm (INAFF) a single input tensor and
 // the statistics instantiation (its consumer is a block of the same Instance/GroupNorm stage).
-static bool wino3_fits(const ConvWeights &w, const ConvCall &c) {
+// `force`: without the fill-the-chip rule (the single-op test entry of the addend epilogue runs shapes of a few tiles).
+static bool wino3_fits(const ConvWeights &w, const ConvCall &c, bool force = false) {
     if (!conv3d_wino3_enabled() || !w.wp3_dev || w.stride != 1) return false;
+    if (c.addend && (c.stats || c.head_out || c.in_scale)) return false;  // the addend goes with the plain epilogue only (EPI 3)
     if (c.head_out && (w.cout != 32 || c.stats || c.head_ncls < 1 || c.head_ncls > 4 || !c.head_w || !c.head_b)) return false;
     if (c.head_out && (long)c.head_ncls * c.Di * c.Hi * c.Wi >= (1l << 30)) return false;  // the head's lane offset is 32 bits
     if (c.in_scale && (c.C1 != 0 || !c.stats || c.head_out || !c.in_shift)) return false;
@@ -798,7 +829,7 @@ static bool wino3_fits(const ConvWeights &w, const ConvCall &c) {
     // each), enough chunks per unit that one tile per workgroup on 160 of the 256 CUs still beats the direct split-K kernel, which
     // executes 27/8 of the multiplies at 0.57 of the pipe (round 4: 0.26 -> 0.11 ms per launch).
     const long units = tiles * (w.cout / 32);
-    if ((units < 1024 && !(units >= 96 && w.cin_pad >= 128)) || tiles >= (1l << 30)) return false;
+    if ((!force && units < 1024 && !(units >= 96 && w.cin_pad >= 128)) || tiles >= (1l << 30)) return false;
     if ((long)c.Di * c.Hi * c.Wi * (c.C0 > c.C1 ? c.C0 : c.C1) >= (1l << 31)) return false;  // the per-lane part of a DMA address fits 32 bits
     if ((long)c.N * c.Di * c.Hi * c.Wi >= (1l << 30)) return false;  // the brick corner's voxel index is a 32-bit scalar (adv4)
     return true;
@@ -818,14 +849,15 @@ static KernelRow wino3_rows[] = {
     MI355_KERNEL_ROW(conv3_f32_wino3_kernel<1, false>),
     MI355_KERNEL_ROW(conv3_f32_wino3_kernel<2, false>),
     MI355_KERNEL_ROW(conv3_f32_wino3_kernel<2, true>),
+    MI355_KERNEL_ROW(conv3_f32_wino3_kernel<3, false>),
 };
 
-bool plan_wino3(const ConvWeights &w, const ConvCall &c, ConvPlan *p) {
-    if (!wino3_fits(w, c)) return false;
+bool plan_wino3(const ConvWeights &w, const ConvCall &c, ConvPlan *p, bool force) {
+    if (!wino3_fits(w, c, force)) return false;
     const TileGeom g = fixed_tile(c.Di, c.Hi, c.Wi, 2, 3, 3, W3_IZ, W3_IY, W3_IX);
     const long tiles = g.tiles_per_n() * c.N;
     const int gy = w.cout / 32;  // one persistent workgroup per CU
-    plan_set(p, find_row(wino3_rows, "conv3_f32_wino3_kernel<%d, %s>", c.in_scale ? 2 : (c.head_out ? 1 : (c.stats ? 2 : 0)), tf(c.in_scale != nullptr)),
+    plan_set(p, find_row(wino3_rows, "conv3_f32_wino3_kernel<%d, %s>", c.in_scale ? 2 : (c.head_out ? 1 : (c.stats ? 2 : (c.addend ? 3 : 0))), tf(c.in_scale != nullptr)),
              FAM_WINO3, g, tiles, persistent_grid_x(256, gy, tiles), gy, W3_LDS_BYTES);
     p->pack = PACK_WINO3; p->nf = 1;
     return true;
@@ -841,6 +873,7 @@ int launch_wino3(const ConvWeights &w, const ConvCall &c, const ConvPlan &p, hip
     a.order = make_tile_order(p.g.tiles_x, p.g.tiles_y, p.g.tiles_z);
     a.head_w = c.head_w; a.head_b = c.head_b; a.head_out = c.head_out; a.head_ncls = c.head_ncls;
     a.in_scale = c.in_scale; a.in_shift = c.in_shift; a.in_slope = c.in_act == ACT_LRELU ? c.slope : 1.0f;
+    a.addend = c.addend;
     float *zeros = nullptr;
     MI355_TRY(device_scratch(SCR_ZEROS, s, 256, (void **)&zeros, true));
     a.zeros = zeros;

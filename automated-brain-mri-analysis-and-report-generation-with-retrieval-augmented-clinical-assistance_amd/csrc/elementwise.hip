@@ -215,60 +215,91 @@ int extract_tiles(const float *vol, int C, int Z, int Y, int X, int padz, int pa
 }
 
 // ------------------------------------------------------------------ shared stage 0: tile tensor from whole-volume + slab results
-// One workgroup = one (z, y) row of one sample's tile: whether the row lies in a z or y shell is workgroup-uniform, the x shells
-// are decided per voxel.  Four 16-byte loads in flight per lane before the first store.
-__global__ __launch_bounds__(256) void stage0_gather_kernel(S0GatherArgs a) {
-    const int n = blockIdx.y;
-    const S0Sample sm = a.smp[n];
-    const int z = (int)blockIdx.x / a.P[1], y = (int)blockIdx.x - z * a.P[1];
-    const int r = a.r, C4 = a.C4;
-    // the row's source when a z or y shell holds it: slab base (in quads) of voxel x = 0, and the quads per slab row
-    const f32x4 *row = nullptr;
-    if (sm.slab[0] >= 0 && z < r)
-        row = (const f32x4 *)a.slab[0] + (((int64_t)sm.slab[0] * a.t[0] + z) * a.P[1] + y) * a.P[2] * C4;
-    else if (sm.slab[1] >= 0 && z >= a.P[0] - r)
-        row = (const f32x4 *)a.slab[0] + (((int64_t)sm.slab[1] * a.t[0] + (z - (a.P[0] - a.t[0]))) * a.P[1] + y) * a.P[2] * C4;
-    else if (sm.slab[2] >= 0 && y < r)
-        row = (const f32x4 *)a.slab[1] + (((int64_t)sm.slab[2] * a.P[0] + z) * a.t[1] + y) * a.P[2] * C4;
-    else if (sm.slab[3] >= 0 && y >= a.P[1] - r)
-        row = (const f32x4 *)a.slab[1] + (((int64_t)sm.slab[3] * a.P[0] + z) * a.t[1] + (y - (a.P[1] - a.t[1]))) * a.P[2] * C4;
-    const f32x4 *wrow = (const f32x4 *)a.wv + ((((int64_t)sm.wv * a.Ve[0] + sm.org[0] + z) * a.Ve[1] + sm.org[1] + y) * a.Ve[2] + sm.org[2]) * C4;
-    const f32x4 *xlo = sm.slab[4] < 0 ? nullptr : (const f32x4 *)a.slab[2] + (((int64_t)sm.slab[4] * a.P[0] + z) * a.P[1] + y) * a.t[2] * C4;
-    const f32x4 *xhi = sm.slab[5] < 0 ? nullptr : (const f32x4 *)a.slab[2] + (((int64_t)sm.slab[5] * a.P[0] + z) * a.P[1] + y) * a.t[2] * C4;
-    const int rowq = a.P[2] * C4;
-    f32x4 *dst = (f32x4 *)a.out + ((int64_t)n * a.P[0] * a.P[1] + blockIdx.x) * rowq;
+// One workgroup = one (z, y) row of one whole-volume result: the row is read ONCE and written to every sample (tile) of that result
+// that holds it - walking the tiles instead re-read each volume row from HBM once per tile, 4.7 times per voxel at step 0.5.  Whether
+// a tile's row lies in a z or y shell is workgroup-uniform (the whole row then comes from that slab), the x shells are decided per
+// voxel.  Four 16-byte loads in flight per lane before the first store.
+// One tensor of the gather: the sources, the destination, the shell depth and the channel quads per voxel.
+struct S0GatherSet {
+    const float *wv, *slab[3];
+    float *out;
+    int r, C4;
+};
+static __device__ __forceinline__ void stage0_gather_row(const S0GatherArgs &a, const S0GatherSet &t, int m, int Z, int Y) {
+    const int r = t.r, C4 = t.C4;
+    const f32x4 *wrow = (const f32x4 *)t.wv + (((int64_t)m * a.Ve[0] + Z) * a.Ve[1] + Y) * a.Ve[2] * C4;
+    const int volq = a.Ve[2] * C4, rowq = a.P[2] * C4;
     constexpr int U = 4;
-    for (int q0 = threadIdx.x; q0 < rowq; q0 += U * 256) {
+    for (int q0 = threadIdx.x; q0 < volq; q0 += U * 256) {
         f32x4 v[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int q = q0 + u * 256;
-            if (q >= rowq) continue;
-            const int x = q / C4;
-            const f32x4 *src = wrow + q;
-            if (row) src = row + q;
-            else if (xlo && x < r) src = xlo + q;
-            else if (xhi && x >= a.P[2] - r) src = xhi + (q - (a.P[2] - a.t[2]) * C4);
-            v[u] = *src;
-        }
+        for (int u = 0; u < U; ++u)
+            if (q0 + u * 256 < volq) v[u] = wrow[q0 + u * 256];
+        for (int n = 0; n < a.n; ++n) {
+            const S0Sample &sm = a.smp[n];
+            const int z = Z - sm.org[0], y = Y - sm.org[1];
+            if (sm.wv != m || (unsigned)z >= (unsigned)a.P[0] || (unsigned)y >= (unsigned)a.P[1]) continue;
+            // the row's source when a z or y shell holds it: slab base (in quads) of voxel x = 0
+            const f32x4 *row = nullptr;
+            if (sm.slab[0] >= 0 && z < r)
+                row = (const f32x4 *)t.slab[0] + (((int64_t)sm.slab[0] * a.t[0] + z) * a.P[1] + y) * a.P[2] * C4;
+            else if (sm.slab[1] >= 0 && z >= a.P[0] - r)
+                row = (const f32x4 *)t.slab[0] + (((int64_t)sm.slab[1] * a.t[0] + (z - (a.P[0] - a.t[0]))) * a.P[1] + y) * a.P[2] * C4;
+            else if (sm.slab[2] >= 0 && y < r)
+                row = (const f32x4 *)t.slab[1] + (((int64_t)sm.slab[2] * a.P[0] + z) * a.t[1] + y) * a.P[2] * C4;
+            else if (sm.slab[3] >= 0 && y >= a.P[1] - r)
+                row = (const f32x4 *)t.slab[1] + (((int64_t)sm.slab[3] * a.P[0] + z) * a.t[1] + (y - (a.P[1] - a.t[1]))) * a.P[2] * C4;
+            const f32x4 *xlo = sm.slab[4] < 0 ? nullptr : (const f32x4 *)t.slab[2] + (((int64_t)sm.slab[4] * a.P[0] + z) * a.P[1] + y) * a.t[2] * C4;
+            const f32x4 *xhi = sm.slab[5] < 0 ? nullptr : (const f32x4 *)t.slab[2] + (((int64_t)sm.slab[5] * a.P[0] + z) * a.P[1] + y) * a.t[2] * C4;
+            f32x4 *dst = (f32x4 *)t.out + (((int64_t)n * a.P[0] + z) * a.P[1] + y) * rowq;
+            const int qorg = sm.org[2] * C4;
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int q = q0 + u * 256;
-            if (q < rowq) dst[q] = v[u];
+            for (int u = 0; u < U; ++u) {
+                const int q = q0 + u * 256 - qorg;  // quad of the tile's row
+                if (q0 + u * 256 >= volq || (unsigned)q >= (unsigned)rowq) continue;
+                const int x = q / C4;
+                f32x4 val = v[u];
+                if (row) val = row[q];
+                else if (xlo && x < r) val = xlo[q];
+                else if (xhi && x >= a.P[2] - r) val = xhi[q - (a.P[2] - a.t[2]) * C4];
+                dst[q] = val;
+            }
         }
+    }
+}
+
+// A second tensor may ride along (the shared skip half of the last decoder stage's concat conv, unet.hip): same samples, same
+// slab indices, its own sources, channel count and shell depth.
+__global__ __launch_bounds__(256) void stage0_gather_kernel(S0GatherArgs a) {
+    const int m = blockIdx.y;
+    const int Z = (int)blockIdx.x / a.Ve[1], Y = (int)blockIdx.x - Z * a.Ve[1];
+    const S0GatherSet t0 = {a.wv, {a.slab[0], a.slab[1], a.slab[2]}, a.out, a.r, a.C4};
+    stage0_gather_row(a, t0, m, Z, Y);
+    if (a.out2) {
+        const S0GatherSet t1 = {a.wv2, {a.slab2[0], a.slab2[1], a.slab2[2]}, a.out2, a.r2, a.C42};
+        stage0_gather_row(a, t1, m, Z, Y);
     }
 }
 
 int stage0_gather(const S0GatherArgs &a, int n_samples, hipStream_t s) {
     MI355_REQUIRE(n_samples > 0 && n_samples <= S0_MAX_SAMPLES, "stage0_gather: %d samples (max %d)", n_samples, S0_MAX_SAMPLES);
     MI355_REQUIRE(a.C4 > 0 && a.r > 0, "stage0_gather: bad channel count / shell depth");
+    MI355_REQUIRE(!a.out2 || (a.wv2 && a.C42 > 0 && a.r2 >= a.r), "stage0_gather: bad second tensor");
+    const int rmax = a.out2 ? a.r2 : a.r;
     for (int k = 0; k < 3; ++k)
-        MI355_REQUIRE(a.t[k] >= 2 * a.r && a.P[k] >= a.t[k] && a.Ve[k] >= a.P[k], "stage0_gather: axis %d: patch %d, slab %d, volume %d, r %d", k, a.P[k], a.t[k], a.Ve[k], a.r);
+        MI355_REQUIRE(a.t[k] >= 2 * rmax && a.P[k] >= a.t[k] && a.Ve[k] >= a.P[k], "stage0_gather: axis %d: patch %d, slab %d, volume %d, r %d", k, a.P[k], a.t[k], a.Ve[k], rmax);
     for (int i = 0; i < n_samples; ++i)
         for (int k = 0; k < 3; ++k)
             MI355_REQUIRE(a.smp[i].org[k] >= 0 && a.smp[i].org[k] + a.P[k] <= a.Ve[k], "stage0_gather: sample %d leaves the volume", i);
-    MI355_REQUIRE((int64_t)a.P[0] * a.P[1] < (1ll << 31), "stage0_gather: grid too large");
-    hipLaunchKernelGGL(stage0_gather_kernel, dim3((unsigned)(a.P[0] * a.P[1]), (unsigned)n_samples), dim3(256), 0, s, a);
+    int n_wv = 0;
+    for (int i = 0; i < n_samples; ++i) {
+        MI355_REQUIRE(a.smp[i].wv >= 0 && a.smp[i].wv < 65535, "stage0_gather: sample %d: whole-volume index %d", i, a.smp[i].wv);
+        n_wv = a.smp[i].wv + 1 > n_wv ? a.smp[i].wv + 1 : n_wv;
+    }
+    MI355_REQUIRE((int64_t)a.Ve[0] * a.Ve[1] < (1ll << 31), "stage0_gather: grid too large");
+    S0GatherArgs k = a;
+    k.n = n_samples;
+    hipLaunchKernelGGL(stage0_gather_kernel, dim3((unsigned)(a.Ve[0] * a.Ve[1]), (unsigned)n_wv), dim3(256), 0, s, k);
     MI355_HIP(hipGetLastError());
     return MI355_OK;
 }

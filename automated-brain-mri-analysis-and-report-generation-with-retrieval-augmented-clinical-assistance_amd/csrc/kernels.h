@@ -58,6 +58,9 @@ struct ConvCallT {
     // normalises its brick in LDS, the fp16 kernels while staging)
     const float *in_scale = nullptr, *in_shift = nullptr;
     int in_act = ACT_NONE;
+    // [N,Do,Ho,Wo,Cout] added to the conv sum in front of bias and activation: out = act(bias + conv(in) + addend).  The shared
+    // skip half of a split concat conv (unet.hip "shared skip half"); conv3_f32_wino3_kernel<3, false> only (the plain epilogue's twin), refused elsewhere.
+    const T *addend = nullptr;
 };
 typedef ConvCallT<float> ConvCall;
 typedef ConvCallT<_Float16> ConvCallH;
@@ -145,6 +148,13 @@ struct S0GatherArgs {
     int P[3], Ve[3], t[3];
     int r;                 // voxel layers taken from a slab at each of its faces
     int C4;                // C / 4
+    // optional second tensor gathered for the same samples (out2 == nullptr: none): the shared skip half of the last decoder
+    // stage's concat conv, C42 * 4 channels, taken r2 >= r layers deep from the slabs (t >= 2 r2)
+    const float *wv2;
+    const float *slab2[3];
+    float *out2;
+    int r2, C42;
+    int n;                 // samples (set by stage0_gather)
     S0Sample smp[S0_MAX_SAMPLES];
 };
 // fp32 NDHWC, 16 bytes per lane.  Where the shells of two or three faces meet the first face in the order above wins.

@@ -39,6 +39,10 @@ struct ConvLayer {
     bool runtime_norm = false;                        // statistics needed at run time (IN / GN)
     bool post_affine = false;                         // BN that could not be folded (nonlin_first)
     int cin = 0, cout = 0, stride = 1;
+    // shared skip half (fp32, first block of the last decoder stage): the block's weights split at the concat boundary,
+    // w_up = W[:, :split_c0] with the block's bias, w_skip = W[:, split_c0:] with zero bias; split_c0 = 0: not split
+    ConvWeights w_up, w_skip;
+    int split_c0 = 0;
 };
 
 }  // namespace mi355
@@ -156,7 +160,33 @@ static int upload(const float *host, size_t n, float **dev) {
     return MI355_OK;
 }
 
-static int build_conv(const mi355_unet &net, const mi355_conv_desc &d, int cin_phys, ConvLayer *out, bool stem = false) {
+// The network side of the shared skip half ("shared skip half" below): what is known of the first block of the last decoder stage
+// when the network is created, when a sliding window decides, and in the dry run - one description, one predicate.
+struct SkipShareNet {
+    int dtype = MI355_F32;
+    int r = 0;                     // stage0_blocks
+    int stride = 1;                // of the last decoder stage's first block
+    bool runtime_norm = false, post_affine = false;
+    bool skip_is_enc0 = true;      // its second input is enc[0]'s output
+    int c_up = 0, c_skip = 0, cout = 0;
+    int head_ncls = 0;             // > 0: the block is also the stage's only one, i.e. the net's last conv, which may carry the fused head
+};
+static SkipShareNet skip_share_net_of(int dtype, int r, int stride, int norm, int nonlin_first, int c_up, int c_skip, int cout, int head_ncls) {
+    SkipShareNet d;
+    d.dtype = dtype; d.r = r; d.stride = stride;
+    d.runtime_norm = norm == MI355_NORM_INSTANCE || norm == MI355_NORM_GROUP;
+    d.post_affine = norm == MI355_NORM_BATCH && nonlin_first;
+    d.c_up = c_up; d.c_skip = c_skip; d.cout = cout; d.head_ncls = head_ncls;
+    return d;
+}
+static bool skip_share_network_ok(const SkipShareNet &d);
+static int stage0_blocks(const mi355_unet &net);
+
+// half != nullptr (the first block of the last decoder stage, which reads the virtual concat (upsampled, skip)): when the network
+// qualifies for the shared skip half (skip_share_network_ok, the predicate the sliding window decides by) the block also gets the
+// packs of its two halves, each through conv_weights_upload and so through conv_pack_layout like any layer: the same fp64
+// Winograd transform, rounded once.
+static int build_conv(const mi355_unet &net, const mi355_conv_desc &d, int cin_phys, ConvLayer *out, bool stem = false, const SkipShareNet *half = nullptr) {
     MI355_REQUIRE(d.weight != nullptr, "conv %d->%d: null weight", d.cin, d.cout);
     MI355_REQUIRE(d.cin > 0 && d.cout > 0 && cin_phys >= d.cin, "conv: bad channel counts %d->%d (phys %d)", d.cin, d.cout, cin_phys);
     ConvLayer L;
@@ -198,12 +228,28 @@ static int build_conv(const mi355_unet &net, const mi355_conv_desc &d, int cin_p
     if (stem) { L.is_stem = true; MI355_TRY(stem_weights_upload(w.data(), b.data(), d.cin, d.cout, net.dtype, &L.stem)); }
     else if (net.dtype == MI355_F16) MI355_TRY(conv_weights_upload_f16(w.data(), b.data(), d.cin, cin_phys, d.cout, d.stride, &L.wh));
     else MI355_TRY(conv_weights_upload(w.data(), b.data(), d.cin, cin_phys, d.cout, d.stride, false, &L.w));
+    if (half && !stem && cin_phys == d.cin && half->c_up + half->c_skip == d.cin && skip_share_network_ok(*half)) {
+        const int split_c0 = half->c_up, c_skip = half->c_skip;
+        {
+            std::vector<float> wu((size_t)d.cout * split_c0 * 27), ws((size_t)d.cout * c_skip * 27);
+            for (int co = 0; co < d.cout; ++co) {
+                const float *src = &w[(size_t)co * d.cin * 27];
+                std::copy(src, src + (size_t)split_c0 * 27, &wu[(size_t)co * split_c0 * 27]);
+                std::copy(src + (size_t)split_c0 * 27, src + (size_t)d.cin * 27, &ws[(size_t)co * c_skip * 27]);
+            }
+            MI355_TRY(conv_weights_upload(wu.data(), b.data(), split_c0, split_c0, d.cout, 1, false, &L.w_up));
+            MI355_TRY(conv_weights_upload(ws.data(), nullptr, c_skip, c_skip, d.cout, 1, false, &L.w_skip));
+            L.split_c0 = split_c0;
+        }
+    }
     *out = L;
     return MI355_OK;
 }
 
 static void free_conv(ConvLayer *L) {
     conv_weights_free(&L->w);
+    conv_weights_free(&L->w_up);
+    conv_weights_free(&L->w_skip);
     conv_weights_free_f16(&L->wh);
     stem_weights_free(&L->stem);
     if (L->gamma_dev) (void)hipFree(L->gamma_dev);
@@ -233,7 +279,8 @@ struct Plan {
     size_t stats_bytes = 0;
     char *arena = nullptr;             // the activation arena of the lane (stream) this forward runs on, set by ensure_arena
     // shared stage 0 (stage0_plan): whole-volume input / intermediate / result and the slab buffers, behind the tile plan
-    struct { size_t wv_in = 0, wv_tmp[2] = {0, 0}, wv_out = 0, slab_in = 0, slab_tmp[2] = {0, 0}, slab_out[3] = {0, 0, 0}; } s0;
+    struct { size_t wv_in = 0, wv_tmp[2] = {0, 0}, wv_out = 0, slab_in = 0, slab_tmp[2] = {0, 0}, slab_out[3] = {0, 0, 0};
+             size_t wv_skip = 0, slab_skip[3] = {0, 0, 0}; } s0;  // (shared skip half: S over the whole volume and over the slabs)
 };
 
 static int make_plan(const mi355_unet &net, int N, int D, int H, int W, Plan *pl) {
@@ -290,7 +337,7 @@ struct ProfScope {
         idx = net->prof.size();
         net->prof.push_back(r);
     }
-    void rename(const char *name) { if (on && name) net->prof[idx].name = name; }
+    void rename(const char *name, const char *suffix = "") { if (on && name) net->prof[idx].name = std::string(name) + suffix; }
     ~ProfScope() { if (on) (void)hipEventRecord(net->prof[idx].b, s); }
 };
 
@@ -326,8 +373,12 @@ static ConvCallT<T> make_call(const void *x0, int cin, int N, int Di, int Hi, in
 // to the plan's second pair and the NEXT block applies them while staging its input (`in_norm` of that call).
 static int run_block(mi355_unet *net, const Plan &pl, const ConvLayer &L, const void *in0, int C0,
                      const void *in1, int C1, int N, int Di, int Hi, int Wi, void *out, hipStream_t s,
-                     float *head_logits_out = nullptr, bool defer_norm = false, bool in_norm = false) {
+                     float *head_logits_out = nullptr, bool defer_norm = false, bool in_norm = false,
+                     const ConvWeights *half = nullptr, const float *addend = nullptr, const char *half_name = "") {
+    // `half` (fp32, shared skip half): the launch runs with these weights instead of L's - one half of L's input channels, C0 + C1
+    // of them - and `addend` [N][Vo][cout] is added in front of bias and activation; reported under the kernel's name + half_name
     const bool f16 = net->dtype == MI355_F16;
+    MI355_REQUIRE(!half || (!f16 && !L.is_stem && !L.runtime_norm && !L.post_affine && half->cin == C0 + C1), "conv %d->%d: bad half launch", L.cin, L.cout);
     double *stats = (double *)(pl.arena + pl.stats_off);
     float *scale = (float *)(pl.arena + (defer_norm ? pl.scale2_off : pl.scale_off)), *shift = (float *)(pl.arena + (defer_norm ? pl.shift2_off : pl.shift_off));
     int act = ACT_LRELU;
@@ -342,8 +393,9 @@ static int run_block(mi355_unet *net, const Plan &pl, const ConvLayer &L, const 
     {
         // algorithmic work of this launch: 2*MAC over the LOGICAL cin; input read once + output written once + weights
         const double es = f16 ? 2.0 : 4.0;
-        const double flops = 2.0 * N * Vo * L.cout * (double)L.cin * 27.0;
-        const double bytes = es * ((double)N * Di * Hi * Wi * (C0 + C1) + (double)N * Vo * L.cout + (double)L.cout * L.cin * 27.0);
+        const int cin = half ? half->cin : L.cin;
+        const double flops = 2.0 * N * Vo * L.cout * (double)cin * 27.0;
+        const double bytes = es * ((double)N * Di * Hi * Wi * (C0 + C1) + (addend ? 2.0 : 1.0) * N * Vo * L.cout + (double)L.cout * cin * 27.0);
         FusedOps f;
         f.x1 = in1; f.c1 = C1;
         if (head_logits_out) { f.head_w = net->head.w_dev; f.head_b = net->head.b_dev; f.head_ncls = net->head.ncls; f.head_out = head_logits_out; }
@@ -360,13 +412,16 @@ static int run_block(mi355_unet *net, const Plan &pl, const ConvLayer &L, const 
             MI355_TRY(conv3d_mfma_f16(L.wh, make_call<_Float16>(in0, C0 + C1, N, Di, Hi, Wi, out, stats_arg, act, net->slope, f), s, &kname));
             ps.rename(kname);
         } else {
-            const ConvCall c = make_call<float>(in0, C0 + C1, N, Di, Hi, Wi, out, stats_arg, act, net->slope, f);
+            ConvCall c = make_call<float>(in0, C0 + C1, N, Di, Hi, Wi, out, stats_arg, half && !addend ? ACT_NONE : act, net->slope, f);
+            c.addend = addend;
+            const ConvWeights &W = half ? *half : L.w;
             ProfScope ps(net, s, "conv3_direct_kernel", flops, bytes);  // (renamed to the instantiation the MFMA dispatch picks)
-            if (L.w.wp_dev) MI355_TRY(conv3d_mfma_f32(L.w, c, s, &kname));
-            else MI355_TRY(conv3d_direct_f32(L.w, c, s));
-            ps.rename(kname);
+            if (W.wp_dev) MI355_TRY(conv3d_mfma_f32(W, c, s, &kname));
+            else MI355_TRY(conv3d_direct_f32(W, c, s));
+            ps.rename(kname, half_name);
         }
     }
+    if (half) return MI355_OK;
     const double es = f16 ? 2.0 : 4.0;
     if (L.runtime_norm) {
         MI355_TRY(norm_finalize(stats, N, L.cout, Vo, net->norm, net->num_groups, net->eps, L.gamma_dev, L.beta_dev,
@@ -406,9 +461,11 @@ static bool can_defer_norm(const mi355_unet *net, const ConvLayer &L, const Conv
 // normalisation (+ activation) is NOT applied to the returned feature map: *head_norm receives its scale / shift and the
 // caller's head kernel applies them while reading the features (head_logits / head_aggregate take a FeatNorm).
 // after_enc0 (shared stage 0): the level-0 features are already where enc[0]'s last block writes them; the pass starts at level 1.
+// skip_half (shared skip half): [N][V][cout] = the skip half of the last decoder stage's first conv, already gathered into the
+// level-0 buffer that stage leaves free; that block then runs over the upsampled tensor alone and adds it in its epilogue.
 static int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W, const void **feat,
                             int *feat_c, hipStream_t s, bool *is_logits = nullptr, float *logits_target = nullptr,
-                            FeatNorm *head_norm = nullptr, bool after_enc0 = false) {
+                            FeatNorm *head_norm = nullptr, bool after_enc0 = false, const float *skip_half = nullptr) {
     const int np = net->num_pool;
     const bool f16 = net->dtype == MI355_F16;
     auto buf = [&](int k, int l) { return (void *)(pl.arena + pl.off[k][l]); };
@@ -469,6 +526,12 @@ static int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H
                 *is_logits = true;
                 *feat = lg; *feat_c = net->head.ncls;
                 return MI355_OK;
+            }
+            if (skip_half && u == np - 1 && i == 0) {
+                MI355_REQUIRE(L.split_c0 == C0 && (const void *)skip_half == freeAB, "shared skip half: the block was not split at %d channels", C0);
+                MI355_TRY(run_block(net, pl, L, in0, C0, nullptr, 0, N, Dl, Hl, Wl, out, s, nullptr, false, false, &L.w_up, skip_half, " up-half"));
+                in0 = out; C0 = L.cout; in1 = nullptr; C1 = 0;
+                continue;
             }
             const bool to_head = env_switch("MI355_FUSE_NORM") && head_norm && L.runtime_norm && (u == np - 1) && (i + 1 == net->dec[u].size());
             const bool defer = to_head || (i + 1 < net->dec[u].size() && can_defer_norm(net, L, net->dec[u][i + 1], N, Dl, Hl, Wl));
@@ -595,20 +658,21 @@ constexpr int S0_SLAB_GROUP = 8;  // (8 slabs of 4 x 128 x 128: 2048 tiles of th
 struct S0Geom {
     bool shared = false;
     int r = 0;
+    int rs = 0;                    // depth of the slab chain: r, or r + 1 with the shared skip half (one more conv behind stage 0)
     int Ve[3] = {0, 0, 0};         // padded volume extended to whole 4 x 8 x 8 conv tiles
-    int t[3] = {0, 0, 0};          // slab thickness per axis: the smallest multiple of (4, 8, 8) that is >= 2r
+    int t[3] = {0, 0, 0};          // slab thickness per axis: the smallest multiple of (4, 8, 8) that is >= 2 rs
     int max_faces[3] = {0, 0, 0};  // most interior faces any tile has on an axis
     std::vector<S0Sample> smp;     // [tile][mirror]; slab[f] = 0 where face f needs a slab, -1 where it is a volume face
 };
 
-static void stage0_geometry(const SwGeom &g, int r, S0Geom *o) {
+static void stage0_geometry(const SwGeom &g, int r, S0Geom *o, int extra = 0) {
     static const int unit[3] = {4, 8, 8};
     *o = S0Geom();
-    o->r = r;
+    o->r = r; o->rs = r + extra;
     bool fits = r >= 1 && g.tiles.size() > 1;
     for (int a = 0; a < 3; ++a) {
         o->Ve[a] = ceil_div(g.Zp[a], unit[a]) * unit[a];
-        o->t[a] = ceil_div(std::max(2 * r, 1), unit[a]) * unit[a];
+        o->t[a] = ceil_div(std::max(2 * o->rs, 1), unit[a]) * unit[a];
         fits = fits && g.P[a] >= o->t[a];
     }
     if (!fits) return;
@@ -634,6 +698,55 @@ static int stage0_blocks(const mi355_unet &net) {
     for (const ConvLayer &L : net.enc[0])
         if (L.stride != 1 || L.runtime_norm || L.post_affine || L.cout % 4) return 0;  // (Instance/GroupNorm statistics are per tile; the mask and gather kernels move 16 bytes per lane)
     return (int)net.enc[0].size();
+}
+
+// ---- shared skip half.  The first block of the last decoder stage reads the virtual concat (upsampled, skip) and is linear in
+// front of its bias and activation: out = act(bias + conv(W_up, up) + conv(W_skip, skip)).  Its skip is the output of the shared
+// stage 0, so S = conv(W_skip, skip) is one more translation-equivariant layer behind it: computed once per (net, mirror) over the
+// whole volume and over the slabs - whose chain is then r + 1 layers deep: thickness >= 2 (r + 1), shell r + 1 for S, r for the skip
+// as before -, gathered per tile next to the skip, and added by the per-tile launch, which runs over the upsampled half alone
+// (half the MFMAs of the largest launch of a forward), in its epilogue (Wino3Args::addend).
+// What the decision may depend on is what stage 0's may: the network and the geometry of all tiles, never rank, lane or batch.
+// The network's part: also what decides, at mi355_unet_create, whether the block gets the packs of its two halves.  A last stage
+// of one block is left alone: its conv is the net's last and may carry the fused head, which has no addend.
+static bool skip_share_network_ok(const SkipShareNet &d) {
+    if (!env_switch("MI355_SHARE_SKIP_CONV")) return false;
+    if (d.dtype != MI355_F32 || d.r < 1 || d.stride != 1 || d.runtime_norm || d.post_affine || !d.skip_is_enc0 || d.head_ncls > 0) return false;
+    if (d.c_up <= 0 || d.c_skip <= 0 || d.c_up % 4 || d.c_skip % 4 || d.cout % 4) return false;
+    ConvPackLayout lu, ls;
+    if (conv_pack_layout(d.c_up, d.c_up, d.cout, 1, &lu) != MI355_OK || conv_pack_layout(d.c_skip, d.c_skip, d.cout, 1, &ls) != MI355_OK) return false;
+    return lu.wino3 && ls.mfma;
+}
+static bool skip_share_decide(const SkipShareNet &d, const SwGeom &g) {
+    if (!skip_share_network_ok(d)) return false;
+    S0Geom sg;
+    stage0_geometry(g, d.r, &sg, 1);
+    if (!sg.shared) return false;  // (one tile, or a patch thinner than a slab of the deeper chain)
+    // the per-tile launch over the upsampled half must be the kernel that has the addend epilogue.  Asked for ONE sample of the
+    // tile shape: more samples never send a call away from that kernel, and the answer must not depend on the batch.
+    // (plan_wino3 is the first step of plan_conv_f32 and, unlike it, answers without leaving an error text behind)
+    ConvPackLayout lu;
+    (void)conv_pack_layout(d.c_up, d.c_up, d.cout, 1, &lu);
+    static float stand_in[2];
+    ConvWeights cw;
+    cw.cin = cw.cin_pad = d.c_up; cw.cout = d.cout; cw.stride = 1;
+    cw.cc = lu.cc; cw.nf = lu.nf; cw.pipe = lu.pipe;
+    cw.bias_dev = cw.wp_dev = cw.wp16_dev = cw.wpw_dev = cw.wp3_dev = stand_in;  // (lu.wino3 implies the other packs)
+    ConvCall c = make_call<float>(stand_in, d.c_up, 1, g.P[0], g.P[1], g.P[2], stand_in, nullptr, ACT_LRELU, 0.01f);
+    c.addend = stand_in;
+    ConvPlan p;
+    if (!plan_wino3(cw, c, &p) || strcmp(p.name, "conv3_f32_wino3_kernel<3, false>") != 0) return false;
+    c.addend = nullptr;  // (and the same call without the addend is a launch of the plain instantiation)
+    return plan_wino3(cw, c, &p) && strcmp(p.name, "conv3_f32_wino3_kernel<0, false>") == 0;
+}
+static SkipShareNet skip_share_net(const mi355_unet &net) {
+    const std::vector<ConvLayer> &st = net.dec.back();
+    const ConvLayer &L = st[0];
+    const int c_skip = net.enc[0].back().cout;
+    SkipShareNet d = skip_share_net_of(net.dtype, stage0_blocks(net), L.stride, net.norm, net.nonlin_first, L.cin - c_skip, c_skip, L.cout,
+                                       st.size() == 1 ? net.head.ncls : 0);
+    d.skip_is_enc0 = L.split_c0 == d.c_up;  // (Generic_UNet: the last stage's skip is enc[0]'s; the packs of the two halves were made)
+    return d;
 }
 
 static void slab_dims(const SwGeom &g, const S0Geom &sg, int a, int S[3]) {
@@ -662,6 +775,10 @@ static void stage0_plan(const mi355_unet &net, const SwGeom &g, const S0Geom &sg
     }
     pl->s0.wv_out = take(wv * net.enc[0].back().cout * 4);
     for (int a = 0; a < 3; ++a) pl->s0.slab_out[a] = take(sl_a[a] * net.enc[0].back().cout * 4);
+    if (sg.rs > sg.r) {  // shared skip half: S for the whole volume per mirror and for the slabs (its tile tensor lives in the level-0 buffer the last decoder stage leaves free)
+        pl->s0.wv_skip = take(wv * net.dec.back()[0].cout * 4);
+        for (int a = 0; a < 3; ++a) pl->s0.slab_skip[a] = take(sl_a[a] * net.dec.back()[0].cout * 4);
+    }
     pl->total = o;
 }
 
@@ -674,8 +791,10 @@ static TileDesc pass_box(const SwGeom &g, int mirror, const int b[3], const int 
 
 // enc[0] over n boxes of S voxels each, gathered from the volume: `in` receives the input, the last block writes `out`.
 // group > 0: the convs run as launches of exactly `group` boxes each (n is a multiple of it).
+// skip_off != 0 (shared skip half): one more launch behind the last block - the skip half of the last decoder stage's first conv,
+// zero bias, no activation - writes S there.
 static int stage0_run(mi355_unet *net, const Plan &pl, const float *vol, int Z, int Y, int X, const SwGeom &g, const std::vector<TileDesc> &boxes,
-                      const int S[3], const int *mask_zp, int group, size_t in_off, const size_t tmp_off[2], size_t out_off, hipStream_t s) {
+                      const int S[3], const int *mask_zp, int group, size_t in_off, const size_t tmp_off[2], size_t out_off, size_t skip_off, hipStream_t s) {
     const int n = (int)boxes.size();
     const size_t vox = (size_t)S[0] * S[1] * S[2];
     for (int b0 = 0; b0 < n; b0 += S0_MAX_SAMPLES) {
@@ -694,13 +813,18 @@ static int stage0_run(mi355_unet *net, const Plan &pl, const float *vol, int Z, 
             const bool last = i + 1 == net->enc[0].size();
             void *out = pl.arena + (last ? out_off : tmp_off[i & 1]) + (size_t)g0 * vox * L.cout * 4;
             MI355_TRY(run_block(net, pl, L, cur, curC, nullptr, 0, ng, S[0], S[1], S[2], out, s));
-            if (!last && mask_zp) {
+            if ((!last || skip_off) && mask_zp) {
                 // the next conv must see zero padding outside the padded volume, not act(bias)
                 const double outside = (double)ng * (vox - (double)mask_zp[0] * mask_zp[1] * mask_zp[2]);
                 ProfScope ps(net, s, "stage0_mask_kernel", 0.0, outside * L.cout * 4.0);
                 MI355_TRY(stage0_mask((float *)out, ng, S, mask_zp, L.cout, s));
             }
             cur = out; curC = L.cout;
+        }
+        if (skip_off) {
+            const ConvLayer &Ld = net->dec.back()[0];
+            MI355_TRY(run_block(net, pl, Ld, cur, curC, nullptr, 0, ng, S[0], S[1], S[2], pl.arena + skip_off + (size_t)g0 * vox * Ld.cout * 4, s,
+                                nullptr, false, false, &Ld.w_skip, nullptr, " skip-half"));
         }
     }
     return MI355_OK;
@@ -713,7 +837,7 @@ static int stage0_whole(mi355_unet *net, const Plan &pl, const float *vol, int Z
     // (a flipped axis: the flipped volume starts at 0 and its zero extension follows it, as on an unflipped axis)
     for (int m : g.mirrors) boxes.push_back(pass_box(g, m, zero, sg.Ve));
     const bool extended = sg.Ve[0] != g.Zp[0] || sg.Ve[1] != g.Zp[1] || sg.Ve[2] != g.Zp[2];
-    return stage0_run(net, pl, vol, Z, Y, X, g, boxes, sg.Ve, extended ? g.Zp : nullptr, 0, pl.s0.wv_in, pl.s0.wv_tmp, pl.s0.wv_out, s);
+    return stage0_run(net, pl, vol, Z, Y, X, g, boxes, sg.Ve, extended ? g.Zp : nullptr, 0, pl.s0.wv_in, pl.s0.wv_tmp, pl.s0.wv_out, pl.s0.wv_skip, s);
 }
 
 // the slabs of one batch of samples (indices into sg.smp), then the gather of the batch's tile tensor
@@ -741,14 +865,23 @@ static int stage0_tiles(mi355_unet *net, const Plan &pl, const float *vol, int Z
         ga.slab[a] = (const float *)(pl.arena + pl.s0.slab_out[a]);
         if (boxes.empty()) continue;
         while (boxes.size() % S0_SLAB_GROUP) boxes.push_back(boxes.back());  // (a whole last launch: its spare results are not read)
-        MI355_TRY(stage0_run(net, pl, vol, Z, Y, X, g, boxes, S, nullptr, S0_SLAB_GROUP, pl.s0.slab_in, pl.s0.slab_tmp, pl.s0.slab_out[a], s));
+        MI355_TRY(stage0_run(net, pl, vol, Z, Y, X, g, boxes, S, nullptr, S0_SLAB_GROUP, pl.s0.slab_in, pl.s0.slab_tmp, pl.s0.slab_out[a], pl.s0.slab_skip[a], s));
+        ga.slab2[a] = (const float *)(pl.arena + pl.s0.slab_skip[a]);
     }
     ga.wv = (const float *)(pl.arena + pl.s0.wv_out);
     ga.out = (float *)(pl.arena + pl.off[(net->enc[0].size() - 1) & 1][0]);
     for (int a = 0; a < 3; ++a) { ga.P[a] = g.P[a]; ga.Ve[a] = sg.Ve[a]; ga.t[a] = sg.t[a]; }
     ga.r = sg.r; ga.C4 = C / 4;
+    int C2 = 0;
+    if (sg.rs > sg.r) {  // shared skip half: S rides along, into the level-0 buffer that is not the skip's
+        C2 = net->dec.back()[0].cout;
+        ga.wv2 = (const float *)(pl.arena + pl.s0.wv_skip);
+        ga.out2 = (float *)(pl.arena + pl.off[((net->enc[0].size() - 1) & 1) ^ 1][0]);
+        ga.r2 = sg.rs; ga.C42 = C2 / 4;
+    } else
+        for (int a = 0; a < 3; ++a) ga.slab2[a] = nullptr;
     const double pv = (double)n * g.P[0] * g.P[1] * g.P[2];
-    ProfScope ps(net, s, "stage0_gather_kernel", 0.0, 2.0 * pv * C * 4.0);
+    ProfScope ps(net, s, "stage0_gather_kernel", 0.0, 2.0 * pv * (C + C2) * 4.0);
     return stage0_gather(ga, n, s);
 }
 
@@ -771,7 +904,8 @@ static int sw_accumulate(mi355_unet *net, const float *vol, int Z, int Y, int X,
     Plan pl;
     MI355_TRY(make_plan(*net, bt * nm, g.P[0], g.P[1], g.P[2], &pl));
     S0Geom sg;
-    stage0_geometry(g, stage0_blocks(*net), &sg);
+    const bool share_skip = skip_share_decide(skip_share_net(*net), g);
+    stage0_geometry(g, stage0_blocks(*net), &sg, share_skip ? 1 : 0);
     if (sg.shared) stage0_plan(*net, g, sg, bt * nm, &pl);
     MI355_TRY(ensure_arena(&pl, s));
     if (mine.empty()) return MI355_OK;
@@ -798,7 +932,8 @@ static int sw_accumulate(mi355_unet *net, const float *vol, int Z, int Y, int X,
         }
         const void *feat; int fc; bool is_logits = false;
         FeatNorm head_norm;
-        MI355_TRY(forward_features(net, pl, (int)samples.size(), g.P[0], g.P[1], g.P[2], &feat, &fc, s, &is_logits, nullptr, &head_norm, sg.shared));
+        MI355_TRY(forward_features(net, pl, (int)samples.size(), g.P[0], g.P[1], g.P[2], &feat, &fc, s, &is_logits, nullptr, &head_norm, sg.shared,
+                                   share_skip ? (const float *)(pl.arena + pl.off[((net->enc[0].size() - 1) & 1) ^ 1][0]) : nullptr));
         MI355_REQUIRE(is_logits || fc == net->head.cin, "head expects %d channels, decoder gives %d", net->head.cin, fc);
         for (int i = 0; i < nb; ++i) {
             const TileDesc &td = g.tiles[mine[b0 + i]];
@@ -891,7 +1026,9 @@ extern "C" int mi355_unet_create(const mi355_unet_desc *d, mi355_unet_t *out) {
             const mi355_conv_desc &cd = d->convs[ci++];
             if (cd.stride != 1 || cd.cin != inC) { set_error("decoder conv %d.%d: cin %d stride %d, expected %d / 1", u, i, cd.cin, cd.stride, inC); return fail(MI355_ERR_INVALID); }
             ConvLayer L;
-            rc = build_conv(*net, cd, inC, &L);
+            const SkipShareNet half = skip_share_net_of(d->dtype, stage0_blocks(*net), cd.stride, d->norm, d->nonlin_first, td.cout, skipC[l], cd.cout,
+                                                         d->dec_convs[u] == 1 ? d->num_classes : 0);
+            rc = build_conv(*net, cd, inC, &L, false, (u == d->num_pool - 1 && i == 0) ? &half : nullptr);
             if (rc != MI355_OK) return fail(rc);
             net->dec[u].push_back(L);
             inC = cd.cout;
@@ -1336,6 +1473,55 @@ extern "C" int mi355_stage0_plan(int z, int y, int x, const int32_t patch[3], fl
         }
     }
     return n;
+}
+
+extern "C" int mi355_skip_share_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes,
+                                     const mi355_skip_share_net *nd, int batch_tiles, int rank, int world, mi355_skip_share_geom *out) {
+    MI355_REQUIRE(out && patch && nd && batch_tiles >= 0 && world >= 1 && rank >= 0 && rank < world, "mi355_skip_share_plan: bad argument");
+    mi355_sw_opts o;
+    memset(&o, 0, sizeof(o));
+    for (int a = 0; a < 3; ++a) o.patch[a] = patch[a];
+    o.step_size = step_size; o.mirror_axes = mirror_axes;
+    SwGeom g;
+    MI355_TRY(make_geom(o, z, y, x, &g));
+    // stage0_blocks' rule, from the description: fp32, enc[0] = stride-1 blocks without run-time statistics or a BN left unfolded
+    const bool folded = nd->norm == MI355_NORM_NONE || (nd->norm == MI355_NORM_BATCH && !nd->nonlin_first);
+    const int r0 = (nd->dtype == MI355_F32 && folded && nd->c_skip % 4 == 0) ? nd->enc0_blocks : 0;
+    SkipShareNet d = skip_share_net_of(nd->dtype, r0, nd->stride, nd->norm, nd->nonlin_first, nd->c_up, nd->c_skip, nd->cout, nd->head_ncls);
+    d.skip_is_enc0 = nd->skip_is_enc0 != 0;
+    // (rank, world, batch_tiles: taken so that a caller can see that nothing below reads them - the invariant of the shared stage 0)
+    (void)batch_tiles; (void)rank; (void)world;
+    const bool on = skip_share_decide(d, g);
+    S0Geom sg;
+    stage0_geometry(g, d.r, &sg, on ? 1 : 0);
+    memset(out, 0, sizeof(*out));
+    out->stage0_shared = sg.shared; out->skip_shared = on;
+    out->r = sg.r; out->skip_shell = on ? sg.rs : 0;
+    out->n_tiles = (int32_t)g.tiles.size(); out->n_mirrors = (int32_t)g.mirrors.size();
+    for (int a = 0; a < 3; ++a) { out->volume[a] = sg.Ve[a]; out->slab_thickness[a] = sg.t[a]; }
+    return MI355_OK;
+}
+
+extern "C" int mi355_conv3d_wino3_ndhwc(const float *x0_dev, const float *x1_dev, int n, int d, int h, int w, int c0, int c1,
+                                        const float *weight_host, const float *bias_host, int cout, int act, float slope,
+                                        const float *addend_dev, float *y_dev, void *stream) {
+    MI355_REQUIRE(x0_dev && y_dev && weight_host && c0 > 0 && c1 >= 0 && (c1 == 0) == (x1_dev == nullptr), "mi355_conv3d_wino3_ndhwc: bad argument");
+    MI355_REQUIRE(act != ACT_LRELU || (slope >= 0.f && slope <= 1.f), "LeakyReLU slope %g outside [0, 1]", (double)slope);
+    MI355_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    TmpWeights<ConvWeights, conv_weights_free> cw;
+    MI355_TRY(conv_weights_upload(weight_host, bias_host, c0 + c1, c0 + c1, cout, 1, false, &cw.w));
+    FusedOps f;
+    f.x1 = x1_dev; f.c1 = c1;
+    ConvCall c = make_call<float>(x0_dev, c0 + c1, n, d, h, w, y_dev, nullptr, act, slope, f);
+    c.addend = addend_dev;
+    ConvPlan p;
+    if (!plan_wino3(cw.w, c, &p, true)) {
+        set_error("mi355_conv3d_wino3_ndhwc: %dx%dx%dx%d, %d+%d -> %d is not a call of the F(2x2x2,3x3x3) kernel", n, d, h, w, c0, c1, cout);
+        return MI355_ERR_UNSUPPORTED;
+    }
+    g_last_conv_kernel = p.name;
+    return synced(launch_wino3(cw.w, c, p, s), s, "conv");
 }
 
 extern "C" int mi355_tconv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,

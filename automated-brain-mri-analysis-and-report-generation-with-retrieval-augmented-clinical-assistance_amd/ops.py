@@ -273,6 +273,53 @@ def stage0_plan(volume, patch, step_size=0.5, mirror_axes=(), r=2):
             "volume": tuple(g.volume), "slab_thickness": tuple(g.slab_thickness), "samples": samples}
 
 
+def skip_share_plan(volume, patch, step_size=0.5, mirror_axes=(), dtype="f32", norm="batch", nonlin_first=False, enc0_blocks=2,
+                    stride=1, skip_is_enc0=True, c_up=32, c_skip=32, cout=32, head_ncls=0, batch_tiles=0, rank=0, world=1):
+    """Dry run of the shared skip half (``mi355_skip_share_plan``; no GPU needed): whether the last decoder stage's first conv takes
+    its skip half from the shared stage-0 pass, for a volume (Z, Y, X), a patch, the mirror axes and a description of the network
+    (defaults: model A).  Returns a dict: stage0_shared, skip_shared, r, skip_shell (r + 1 when on, else 0), n_tiles, n_mirrors,
+    volume and slab_thickness.  batch_tiles, rank and world are passed through; the result does not depend on them."""
+    nd = _lib.SkipShareNet({"f32": 0, "f16": 1}[dtype], {"none": 0, "batch": 1, "instance": 2, "group": 3}[norm], int(bool(nonlin_first)),
+                           int(enc0_blocks), int(stride), int(bool(skip_is_enc0)), int(c_up), int(c_skip), int(cout), int(head_ncls))
+    g = _lib.SkipShareGeom()
+    z, y, x = (int(v) for v in volume)
+    mask = sum(1 << int(a) for a in mirror_axes)
+    _lib.check(_lib.load().mi355_skip_share_plan(z, y, x, _i3(patch), float(step_size), mask, C.byref(nd), int(batch_tiles), int(rank),
+                                                 int(world), C.byref(g)), "mi355_skip_share_plan")
+    return {"stage0_shared": bool(g.stage0_shared), "skip_shared": bool(g.skip_shared), "r": int(g.r), "skip_shell": int(g.skip_shell),
+            "n_tiles": int(g.n_tiles), "n_mirrors": int(g.n_mirrors), "volume": tuple(g.volume), "slab_thickness": tuple(g.slab_thickness)}
+
+
+def conv3d_wino3_ndhwc(x0, weight, bias=None, x1=None, addend=None, act=0, slope=0.01):
+    """One stride-1 conv on ``conv3_f32_wino3_kernel<0, false>`` whatever the size (test entry point, ``mi355_conv3d_wino3_ndhwc``):
+    act(bias + conv(cat(x0, x1)) + addend).  x0 / x1: CUDA fp32 [N,D,H,W,C]; addend: CUDA fp32 [N,D,H,W,Cout] or None; weight:
+    numpy [Cout,C0+C1,3,3,3]."""
+    import torch
+    x0 = _require_cuda(x0, torch.float32, "x0")
+    n, d, h, w, c0 = x0.shape
+    c1 = 0
+    if x1 is not None:
+        x1 = _require_cuda(x1, torch.float32, "x1")
+        if tuple(x1.shape[:4]) != (n, d, h, w):
+            raise ValueError("conv3d_wino3_ndhwc: x1 must cover the same voxels as x0")
+        c1 = int(x1.shape[4])
+    weight = np.ascontiguousarray(weight, dtype=np.float32)
+    cout = weight.shape[0]
+    if weight.shape[1] != c0 + c1:
+        raise ValueError(f"conv3d_wino3_ndhwc: weight takes {weight.shape[1]} channels, the inputs hold {c0} + {c1}")
+    if addend is not None:
+        addend = _require_cuda(addend, torch.float32, "addend")
+        if tuple(addend.shape) != (n, d, h, w, cout):
+            raise ValueError("conv3d_wino3_ndhwc: addend must be [N,D,H,W,Cout]")
+    b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+    y = torch.full((n, d, h, w, cout), float("nan"), dtype=torch.float32, device=x0.device)
+    _lib.check(_lib.load().mi355_conv3d_wino3_ndhwc(x0.data_ptr(), None if x1 is None else x1.data_ptr(), n, d, h, w, c0, c1,
+                                                    _lib.fptr(weight), _lib.fptr(b), cout, act, slope,
+                                                    None if addend is None else addend.data_ptr(), y.data_ptr(), _stream(x0)),
+               "mi355_conv3d_wino3_ndhwc")
+    return y
+
+
 def last_conv_kernel() -> str:
     """Kernel instantiation the last ``conv3d_ndhwc`` call of this thread ran on (test aid)."""
     return (_lib.load().mi355_last_conv_kernel() or b"").decode()

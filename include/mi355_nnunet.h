@@ -466,6 +466,42 @@ typedef struct mi355_stage0_sample {
 } mi355_stage0_sample;
 int mi355_stage0_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes, int r,
                       mi355_stage0_geom *out, mi355_stage0_sample *samples, int max_samples);
+/* Dry run of the shared skip half (needs no device and launches nothing; the decision code mi355_sw_predict /
+ * mi355_sw_partial[_folds] run).  The first block of the last decoder stage reads the concat (upsampled, skip) and is linear in
+ * front of its bias and activation; where its skip is the output of a shared stage 0, the skip half of that conv is one more
+ * layer of the shared pass - computed once per mirror over the whole volume and over the slabs, whose chain is then r + 1 deep -
+ * and every tile runs the upsampled half alone, adding the gathered skip half in its epilogue.  On when: fp32; the shared stage 0
+ * is on (r >= 1, more than one tile, patch >= slab of the deeper chain); the block has stride 1, no run-time norm and no unfolded
+ * BatchNorm; its skip is enc[0]'s output; the stage has a second block (head_ncls = 0); one sample of the patch shape with c_up channels goes to conv3_f32_wino3_kernel<0, false>
+ * (whose twin with the addend epilogue, <3, false>, then runs it);
+ * and MI355_SHARE_SKIP_CONV is not 0.  batch_tiles, rank and world are accepted and, by construction, not consulted: every rank
+ * and lane computes a tile the same way.  No reference counterpart. */
+typedef struct mi355_skip_share_net {
+    int32_t dtype;          /* MI355_F32 / MI355_F16 */
+    int32_t norm;           /* MI355_NORM_* of the network */
+    int32_t nonlin_first;
+    int32_t enc0_blocks;    /* blocks of encoder stage 0 */
+    int32_t stride;         /* of the last decoder stage's first block */
+    int32_t skip_is_enc0;
+    int32_t c_up, c_skip, cout;
+    int32_t head_ncls;      /* > 0: that block is the stage's only one - the network's last conv, which may carry the fused head */
+} mi355_skip_share_net;
+typedef struct mi355_skip_share_geom {
+    int32_t stage0_shared, skip_shared;
+    int32_t r;                  /* shell depth of the skip (stage-0 blocks) */
+    int32_t skip_shell;         /* shell depth of the skip half: r + 1, or 0 when off */
+    int32_t n_tiles, n_mirrors;
+    int32_t volume[3];
+    int32_t slab_thickness[3];  /* smallest multiple of (4, 8, 8) >= 2 (r + 1) when on, >= 2 r otherwise */
+} mi355_skip_share_geom;
+int mi355_skip_share_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes,
+                          const mi355_skip_share_net *net, int batch_tiles, int rank, int world, mi355_skip_share_geom *out);
+/* One stride-1 conv on conv3_f32_wino3_kernel<0, false> - with an addend its twin <3, false> - whatever the size (test aid: the dispatch sends launches of a few tiles
+ * elsewhere): y = act(bias + conv(cat(x0, x1)) + addend), x1_dev / addend_dev may be NULL; d % 4 == h % 8 == w % 8 == 0,
+ * c0 % 16 == c1 % 16 == 0, cout % 32 == 0; addend_dev [n,d,h,w,cout].  Refused (MI355_ERR_UNSUPPORTED) otherwise. */
+int mi355_conv3d_wino3_ndhwc(const float *x0_dev, const float *x1_dev, int n, int d, int h, int w, int c0, int c1,
+                             const float *weight_host, const float *bias_host, int cout, int act, float slope,
+                             const float *addend_dev, float *y_dev, void *stream);
 /* ---- the kernels around the convolutions, one launch each (test aids; no reference counterpart beyond the one named at the
  * kernel in csrc/elementwise.hip).  Each call runs the launcher the network runs and waits for `stream`.  Tensors are taken in
  * the layout the network holds them in: fp32 plain NDHWC ([N][V][C]), fp16 channel-blocked ([N][C / 8][V][8]), AS IS. ---- */
