@@ -50,6 +50,19 @@ def label_components(mask, connectivity=1):
     return labels, int(n.value)
 
 
+def label_components_neighbours(mask, neighbours):
+    """``label_components`` with the neighbourhood named by its size: 6, 18 (faces and edges, ``generate_binary_structure(3, 2)``:
+    what ``feature_extraction/step6_normal_structures.py:66-67`` labels with) or 26."""
+    import torch
+    mask = _check_volume(mask, torch.uint8, "label_components_neighbours")
+    labels = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
+    n = C.c_int32(0)
+    stream = torch.cuda.current_stream(mask.device).cuda_stream
+    _lib.check(_lib.load().mi355_label_components_nb(mask.data_ptr(), mask.shape[0], mask.shape[1], mask.shape[2], int(neighbours),
+                                                     labels.data_ptr(), C.byref(n), stream), "mi355_label_components_nb")
+    return labels, int(n.value)
+
+
 def component_stats(labels, n, seg=None):
     """labels: the map of ``label_components``, n its component count, seg: optional CUDA uint8 map of the same shape.
     Returns int64 [n, 14]: count, coordinate sums (3), minima (3), maxima (3), voxels with seg value 1, 2, 3, 4."""

@@ -8,7 +8,7 @@
 // order - which is how scipy numbers components, so ranking the roots by index gives scipy's labels.
 //
 //   1 local    a workgroup labels one 4 x 8 x 64 brick in LDS (union over the backward half of the neighbourhood: 3 of 6,
-//              13 of 26) and writes the GLOBAL index of every voxel's brick-local root; it writes inside its brick only
+//              9 of 18, 13 of 26) and writes the GLOBAL index of every voxel's brick-local root; it writes inside its brick only
 //   2 seam     threads over the voxels with a backward neighbour in another brick unite the two trees in the global array
 //   3 flatten  parent[i] = root(i), and the number of roots (parent[i] == i) per 2048-voxel chunk
 //   4 scan     exclusive prefix sum of the chunk counts (one workgroup), total = number of components
@@ -72,10 +72,11 @@ __device__ void unite_local(int *par, int a, int b) {
     }
 }
 
-// is (dz, dy, dx) a backward neighbour (before the voxel in raster order) of the chosen connectivity?
+// is (dz, dy, dx) a backward neighbour (before the voxel in raster order) of the chosen connectivity (the rank of scipy's
+// generate_binary_structure(3, conn))?
 __device__ __forceinline__ bool backward(int dz, int dy, int dx, int conn) {
     if (dz == 0 && (dy > 0 || (dy == 0 && dx >= 0))) return false;
-    return conn != 1 || (dz != 0) + (dy != 0) + (dx != 0) == 1;
+    return (dz != 0) + (dy != 0) + (dx != 0) <= conn;  // conn 1: faces (6), 2: faces and edges (18), 3: corners too (26)
 }
 
 __global__ __launch_bounds__(256) void ccl_local_kernel(const uint8_t *mask, int d0, int d1, int d2, int nbx, int nby, int conn,
@@ -325,10 +326,9 @@ using namespace mi355;
 
 // scratch slot SCR_COMPONENTS: [statistics table, TABLE_BYTES | work area]; the work area holds, for a labelling,
 // [total i32, pad to 256 B | chunk counts i32 | parent i32 V] and, for a filter, the keep table.
-extern "C" int mi355_label_components(const uint8_t *mask_dev, int d0, int d1, int d2, int connectivity, int32_t *labels_dev,
-                                      int32_t *n_components_host, void *stream) {
+static int label_components(const uint8_t *mask_dev, int d0, int d1, int d2, int connectivity, int32_t *labels_dev, int32_t *n_components_host,
+                            void *stream) {
     MI355_REQUIRE(mask_dev && labels_dev && n_components_host && d0 >= 1 && d1 >= 1 && d2 >= 1, "label_components: bad argument");
-    MI355_REQUIRE(connectivity == 1 || connectivity == 3, "label_components: connectivity %d (1 = 6 neighbours, 3 = 26 neighbours)", connectivity);
     const int64_t V = (int64_t)d0 * d1 * d2;
     MI355_REQUIRE(V < (1ll << 31), "label_components: %dx%dx%d has 2^31 voxels or more (parents are int32 voxel indices)", d0, d1, d2);
     hipStream_t s = (hipStream_t)stream;
@@ -352,6 +352,19 @@ extern "C" int mi355_label_components(const uint8_t *mask_dev, int d0, int d1, i
     MI355_HIP(e);
     *n_components_host = n;
     return MI355_OK;
+}
+
+extern "C" int mi355_label_components(const uint8_t *mask_dev, int d0, int d1, int d2, int connectivity, int32_t *labels_dev,
+                                      int32_t *n_components_host, void *stream) {
+    MI355_REQUIRE(connectivity == 1 || connectivity == 3, "label_components: connectivity %d (1 = 6 neighbours, 3 = 26 neighbours)", connectivity);
+    return label_components(mask_dev, d0, d1, d2, connectivity, labels_dev, n_components_host, stream);
+}
+
+// the same labelling named by the size of the neighbourhood, 18 (faces and edges) included
+extern "C" int mi355_label_components_nb(const uint8_t *mask_dev, int d0, int d1, int d2, int neighbours, int32_t *labels_dev,
+                                         int32_t *n_components_host, void *stream) {
+    MI355_REQUIRE(neighbours == 6 || neighbours == 18 || neighbours == 26, "label_components_nb: %d neighbours (6, 18 or 26)", neighbours);
+    return label_components(mask_dev, d0, d1, d2, neighbours == 6 ? 1 : (neighbours == 18 ? 2 : 3), labels_dev, n_components_host, stream);
 }
 
 extern "C" int mi355_component_stats(const int32_t *labels_dev, const uint8_t *seg_dev, int d0, int d1, int d2, int n_components,

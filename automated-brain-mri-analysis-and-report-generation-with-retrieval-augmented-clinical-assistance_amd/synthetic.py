@@ -339,3 +339,88 @@ def mri_for_mass_effect(seed: int, seg: np.ndarray, brain_axes: float = 0.47, cu
     t1 = np.rint(t1)
     assert t1.max() < 2 ** 15 and t1.min() >= 0
     return t1.astype(np.float32)
+
+
+def painted_mask(shape, parts) -> np.ndarray:
+    """Boolean mask ``[d0, d1, d2]``, the union of ``["box", lo, hi]`` (hi exclusive) and ``["obox", lo, hi]`` parts, clipped to the
+    volume.  An ``obox`` is the box without its twelve edges: what an erosion and a dilation with the 6-neighbour cross leave of a
+    box, so a union of them passes such an opening unchanged, and two of them can touch across an edge or a corner only."""
+    mask = np.zeros(tuple(shape), dtype=bool)
+    for kind, lo, hi in parts:
+        lo = [max(int(v), 0) for v in lo]
+        hi = [min(int(v), s) for v, s in zip(hi, shape)]
+        box = np.ones([max(b - a, 0) for a, b in zip(lo, hi)], dtype=bool)
+        if kind == "obox":
+            ends = [np.isin(np.arange(n), (0, n - 1)).astype(int) for n in box.shape]  # 1 on the two end planes of an axis
+            box &= (ends[0][:, None, None] + ends[1][None, :, None] + ends[2][None, None, :]) < 2
+        elif kind != "box":
+            raise ValueError(f"painted_mask: unknown part {kind!r}")
+        mask[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]] |= box
+    return mask
+
+
+def mri_for_normal_structures(seed: int, seg: np.ndarray, ventricles=(), brain_axes: float = 0.47, outside: float = 60.0, contrast: float = 0.0,
+                              pv_gain: float = 0.0, voids: Optional[str] = None, enhancement: float = 1.0, cuts=(), zero: bool = False,
+                              sigma: float = 3.0) -> np.ndarray:
+    """Four float32 volumes ``[4, d0, d1, d2]`` (T1, T1ce, T2, FLAIR) on the grid of ``seg`` with integer values below 2^15 (the
+    normal-structures path: the size, side and neighbourhood of the ventricles, the deep / cortical T1 contrast, the
+    periventricular FLAIR signal, the flow voids and the enhancement around the tumour can be steered one by one).  T1 is a smooth
+    field 1000..1150 and T2 is 1.5 times the same field, so no voxel of the background is dark on T1 and bright on T2 at once;
+    T1ce and FLAIR are fields of their own.  Inside a centred ellipsoidal 'brain' whose semi-axes are ``brain_axes`` times the
+    shape, in this order:
+    ``contrast``     T1 and T2 times ``1 + contrast * (1 - r)``, r = 0 at the centre and 1 on the ellipsoid (bright deep tissue);
+    ``ventricles``   parts of ``painted_mask``: CSF-like signal there (T1 300, T2 3000, FLAIR 200);
+    ``pv_gain``      FLAIR times ``1 + pv_gain`` within ten dilations of the painted ventricles, themselves excluded;
+    ``voids``        the darkest T1 voxels of the brain's inferior third ``[:, :, :d2 // 3]`` outside the ventricles: ``"tie"`` = the
+                     lowest 6 % all take one value (nothing lies below their 5th percentile), ``"step"`` = the lowest 3 % take
+                     150 and the next 4 % one value (3 % lie below), ``"ramp"`` = the lowest 5.5 % take distinct values;
+    ``enhancement``  T1ce times it within ten dilations of the tumour, the tumour excluded.
+    Outside the ellipsoid every channel is ``outside`` (more than 5 % of the positive voxels, all tied: the brain mask ``t1 > P5``
+    is the ellipsoid); ``cuts`` are rows ``[lo, hi]`` of boxes set to ``outside`` too (no brain there); ``zero`` = all zero."""
+    from scipy.ndimage import binary_dilation, gaussian_filter
+
+    rs = np.random.RandomState(seed)
+    shape = seg.shape
+    fields = []
+    for _ in range(3):
+        smooth = gaussian_filter(rs.standard_normal(shape).astype(np.float32), sigma=sigma, mode="nearest").astype(np.float64)
+        fields.append(1000.0 + 150.0 * (smooth - smooth.min()) / (smooth.max() - smooth.min() + 1e-12))
+    g = np.ogrid[0:shape[0], 0:shape[1], 0:shape[2]]
+    r = np.sqrt(sum(((g[k] - (shape[k] - 1) / 2.0) / (float(brain_axes) * shape[k])) ** 2 for k in range(3)))
+    inside = r <= 1.0
+    base = fields[0] * (1.0 + float(contrast) * (1.0 - np.minimum(r, 1.0)))
+    t1, t1ce, t2, flair = np.rint(base), np.rint(fields[1]), np.rint(1.5 * base), np.rint(fields[2])
+    vent = painted_mask(shape, ventricles) & inside
+    t1[vent], t2[vent], flair[vent] = 300.0, 3000.0, 200.0
+    if pv_gain and vent.any():
+        zone = binary_dilation(vent, iterations=10) & ~vent
+        flair[zone] = np.rint(flair[zone] * (1.0 + float(pv_gain)))
+    if voids is not None:
+        region = inside & ~vent
+        region[:, :, shape[2] // 3:] = False
+        idx = np.flatnonzero(region.ravel())
+        idx = idx[np.argsort(t1.ravel()[idx], kind="stable")]
+        flat = t1.reshape(-1)
+        if voids == "tie":
+            flat[idx[:int(0.06 * idx.size)]] = 850.0
+        elif voids == "step":
+            flat[idx[:int(0.07 * idx.size)]] = 850.0
+            flat[idx[:int(0.03 * idx.size)]] = 150.0
+        elif voids == "ramp":
+            k = int(0.055 * idx.size)
+            assert k <= 650  # (below the darkest background value)
+            flat[idx[:k]] = 200.0 + np.arange(k)
+        else:
+            raise ValueError(f"mri_for_normal_structures: unknown voids {voids!r}")
+    if enhancement != 1.0 and seg.any():
+        wt = seg > 0
+        zone = binary_dilation(wt, iterations=10) & ~wt
+        t1ce[zone] = np.rint(t1ce[zone] * float(enhancement))
+    vols = np.stack([t1, t1ce, t2, flair])
+    vols[:, ~inside] = float(outside)
+    for lo, hi in cuts:
+        vols[(slice(None),) + tuple(slice(int(a), int(b)) for a, b in zip(lo, hi))] = float(outside)
+    if zero:
+        vols[...] = 0.0
+    assert vols.max() < 2 ** 15 and vols.min() >= 0
+    return vols.astype(np.float32)

@@ -232,6 +232,11 @@ int mi355_component_stats(const int32_t *labels_dev, const uint8_t *seg_dev, int
  * no counterpart in the reference tree).  out_dev may be seg_dev.  Asynchronous on `stream`. */
 int mi355_component_filter(const int32_t *labels_dev, const uint8_t *seg_dev, int64_t n, const uint8_t *keep_host, int n_components,
                            uint8_t *out_dev, void *stream);
+/* mi355_label_components with the neighbourhood named by its size: 6 (faces), 18 (faces and edges: scipy's
+ * generate_binary_structure(3, 2), which step6_normal_structures.py:66-67 labels the CSF mask with) or 26 (corners too); anything
+ * else MI355_ERR_INVALID.  Labels, numbering, limits and synchronisation as there. */
+int mi355_label_components_nb(const uint8_t *mask_dev, int d0, int d1, int d2, int neighbours, int32_t *labels_dev,
+                              int32_t *n_components_host, void *stream);
 
 /* ---- binary morphology, distance transform and mask reductions (csrc/morphology.hip): the primitives under
  * feature_extraction/step4_morphology.py; step2_mass_effect.py:19,373 needs the first one too, step1_sequence_findings.py the
@@ -281,8 +286,8 @@ int mi355_flag_from_flags(uint8_t *flags_dev, int bit, int require, int forbid, 
                           void *stream);
 
 /* ---- exact masked order statistics (csrc/percentile.hip): what the reference sorts for np.percentile (utils.py:48-49, :57, :67;
- * step2_mass_effect.py:179; step4_morphology.py:317-320; step5_quality.py:194-212; step6_normal_structures.py:48-50).  On the device so far: steps 1, 2, 4 and
- * 5 (brats_amd.sequence_findings, .mass_effect, .morphology, .quality) ---- */
+ * step2_mass_effect.py:179; step4_morphology.py:317-320; step5_quality.py:194-212; step6_normal_structures.py:48-50, :129, :313).  On the device: steps 1, 2, 4, 5
+ * and 6 (brats_amd.sequence_findings, .mass_effect, .morphology, .quality, .normal_structures) ---- */
 /* Voxel i of x_dev [n] fp32 takes part when (flags_dev is NULL, or every bit of `require` is set in flags_dev[i] and no bit of
  * `forbid` is) and lo < (double)x_dev[i] < hi - the selection of mi355_flag_from_flags; lo, hi fp64, +-inf allowed, so
  * `data[data > 0]` is lo = 0, hi = +inf.  A NaN never passes the comparison.  count_host[0] = m, the number of voxels that take
@@ -374,6 +379,50 @@ int mi355_min_pair_dist2(const int64_t *a_index_dev, int ka, const int64_t *b_in
  * samples.  n in 1..2^31-1.  Synchronous. */
 int mi355_masked_min_i32(const int32_t *values_dev, const uint8_t *flags_dev, int require, int forbid, int64_t n, int32_t *min_host,
                          int64_t *count_host, void *stream);
+
+/* ---- city-block distance, integer flag predicates, int32 order statistics and a column-count maximum
+ * (csrc/normal_structures.hip): the primitives under feature_extraction/step6_normal_structures.py that the entries above do not
+ * cover.  Conventions as for csrc/morphology.hip and csrc/mass_effect.hip: volumes are [d0][d1][d2] C-order with fewer than 2^31
+ * voxels (MI355_ERR_INVALID otherwise), uint8 masks are foreground where nonzero, two calls give bit-equal results (there is no
+ * float anywhere: a voxel has one writer, reductions meet in integer atomics), scratch is per stream lane. ---- */
+#define MI355_CITYBLOCK_FAR 1073741824u  /* 2^30: the distance mi355_cityblock_distance writes where there is nothing to measure to */
+/* The exact city-block (L1, taxicab) distance transform: what scipy.ndimage.binary_dilation / binary_erosion with their default
+ * cross reach in `iterations` steps, for every number of steps at once (step6_normal_structures.py:152 dilates the tumour 5 steps,
+ * :345 the same mask 10 steps, :215 the ventricles 10 steps; :62-63 and :272 erode).  dist_dev [d0][d1][d2] int32:
+ *   to_foreground != 0: the distance to the nearest nonzero voxel of the mask, 0 on it, MI355_CITYBLOCK_FAR everywhere when the
+ *     mask is empty; `dist <= n` is bit-equal to binary_dilation(mask, iterations=n) for every n >= 1;
+ *   to_foreground == 0: the distance to the nearest zero voxel, every position outside the volume counting as zero (scipy's
+ *     border_value = 0), so a volume without a zero voxel holds its distances to the faces; `dist > n` is bit-equal to
+ *     binary_erosion(mask, iterations=n).
+ * Three separable passes in place, each a forward and a backward running minimum along its axis.  Refused: d0 + d1 + d2 above
+ * 2^30, d2 above 16383 (a line of axis 2 must fit the 64 KiB LDS tile).  Asynchronous on `stream`. */
+int mi355_cityblock_distance(const uint8_t *mask_dev, int d0, int d1, int d2, int to_foreground, int32_t *dist_dev, void *stream);
+/* Bit `bit` (0..7) of flags_dev[i] = every bit of `require` is set, no bit of `forbid` is, and lo <= values_dev[i] <= hi (both
+ * ends included); computed from the byte as it was.  The integer twin of mi355_flag_from_flags: `dist <= 5` on a city-block map
+ * (step6_normal_structures.py:152-153, :215-216, :345-346) and `brain_dist > threshold` / `< threshold` on the squared distance
+ * map of mi355_edt_squared, the float threshold turned into an integer bound on d^2 by the caller (:210, :224).  Asynchronous on
+ * `stream`. */
+int mi355_flag_from_i32(uint8_t *flags_dev, int bit, int require, int forbid, const int32_t *values_dev, int32_t lo, int32_t hi, int64_t n,
+                        void *stream);
+/* Bit `bit` of flags_dev[i] = every bit of `require` is set, no bit of `forbid` is, and the voxel lies inside the half-open index
+ * box box_host[0..5] = lo0, hi0, lo1, hi1, lo2, hi2, which is clipped to the volume (lo >= hi on an axis: nowhere):
+ * `inferior_brain[:, :, inferior_third:] = False` of step6_normal_structures.py:306-308 is the box [0, d0) x [0, d1) x [0, d2 / 3).
+ * Asynchronous on `stream`. */
+int mi355_flag_from_box(uint8_t *flags_dev, int bit, int require, int forbid, int d0, int d1, int d2, const int32_t *box_host, void *stream);
+/* mi355_masked_percentiles for an int32 map with values in [0, 2^31): count_host[0] = m, the number of voxels whose flag byte has
+ * every bit of `require` and no bit of `forbid` (flags_dev NULL: all n), and per percentile q_host[j] the two exact order
+ * statistics of rank floor(v) and min(floor(v) + 1, m - 1), v = (m - 1) * (q / 100), in below_host[j] / above_host[j] (untouched
+ * when m = 0).  step6_normal_structures.py:207 and :224 take np.percentile(brain_dist[brain_mask], 60) and the 40th of
+ * distance_transform_edt, the root of exact integers: the root is monotone, so the host takes np.sqrt of the two order statistics
+ * of mi355_edt_squared's map and interpolates as numpy does.  The radix select of csrc/percentile.hip on the value as its own key.
+ * Refused: a negative selected value, nq outside 1..8, a q outside [0, 100] or NaN, n outside 1..2^31-1, require or forbid
+ * outside 0..255 or sharing a bit.  Synchronous. */
+int mi355_masked_order_stats_i32(const int32_t *values_dev, int64_t n, const uint8_t *flags_dev, int require, int forbid, const double *q_host,
+                                 int nq, int64_t *count_host, int32_t *below_host, int32_t *above_host, void *stream);
+/* out_host[0] = np.max(np.sum(selected[:, i1_from:, :], axis=0)) (step6_normal_structures.py:130-131: the widest run of ventricle
+ * voxels along axis 0 in front of `frontal_y`), selected as for mi355_axis_counts; 0 when i1_from >= d1 or nothing is selected
+ * there.  Refused: i1_from < 0.  Synchronous. */
+int mi355_column_count_max(const uint8_t *flags_dev, int require, int forbid, int d0, int d1, int d2, int i1_from, int64_t *out_host, void *stream);
 
 /* Per-kernel timing with HIP events on the stream the kernels are launched on (bench.py's
  * roofline). flops / bytes are the ALGORITHMIC work of the recorded launches. */
