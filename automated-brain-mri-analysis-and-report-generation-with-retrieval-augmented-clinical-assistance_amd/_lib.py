@@ -41,6 +41,7 @@ EXPORTS = [
     "mi355_stage0_plan", "mi355_skip_share_plan", "mi355_conv3d_wino3_ndhwc",
     "mi355_norm_finalize", "mi355_norm_apply", "mi355_extract_tiles", "mi355_head_logits", "mi355_head_aggregate",
     "mi355_logits_aggregate", "mi355_cnt_add_tile", "mi355_stage0_gather", "mi355_stage0_mask",
+    "mi355_stage0_view_plan", "mi355_conv3d_s2dma_view_ndhwc", "mi355_conv3d_wino3_view_ndhwc", "mi355_stage0_gather_shells",
 ]
 
 
@@ -111,6 +112,24 @@ class Stage0GatherArgs(C.Structure):
     _fields_ = [("wv_dev", C.c_void_p), ("slab_dev", C.c_void_p * 3), ("out_dev", C.c_void_p),
                 ("patch", C.c_int32 * 3), ("volume", C.c_int32 * 3), ("slab_thickness", C.c_int32 * 3),
                 ("r", C.c_int32), ("channels", C.c_int32), ("n_samples", C.c_int32), ("samples", Stage0GatherSample * 64)]
+
+
+class Stage0ViewGeom(C.Structure):
+    _fields_ = [("enc0_viewed", C.c_int32), ("half_viewed", C.c_int32), ("depth", C.c_int32 * 2), ("n_tiles", C.c_int32),
+                ("n_mirrors", C.c_int32), ("volume", C.c_int32 * 3)]
+
+
+class Stage0ViewSample(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("faces", C.c_int32), ("pad_", C.c_int32), ("shell_voxels", C.c_int64 * 2)]
+
+
+class Stage0ViewItem(C.Structure):
+    _fields_ = [("wv", C.c_int32), ("origin", C.c_int32 * 3), ("faces", C.c_int32)]
+
+
+class Stage0View(C.Structure):
+    _fields_ = [("src_dev", C.c_void_p), ("n_wv", C.c_int32), ("volume", C.c_int32 * 3), ("depth", C.c_int32), ("n_samples", C.c_int32),
+                ("samples", Stage0ViewItem * 64)]
 
 
 class Mi355Error(RuntimeError):
@@ -235,6 +254,13 @@ def load():
     lib.mi355_cnt_add_tile.argtypes = [vp, c_int32_p, vp, c_int32_p, c_int32_p, vp]
     lib.mi355_stage0_gather.argtypes = [C.POINTER(Stage0GatherArgs), vp]
     lib.mi355_stage0_mask.argtypes = [vp, C.c_int, c_int32_p, c_int32_p, C.c_int, vp]
+    lib.mi355_stage0_gather_shells.argtypes = [C.POINTER(Stage0GatherArgs), vp]
+    lib.mi355_stage0_view_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.POINTER(SkipShareNet), C.c_int, C.c_int,
+                                           C.POINTER(Stage0ViewGeom), C.POINTER(Stage0ViewSample), C.c_int]
+    lib.mi355_conv3d_s2dma_view_ndhwc.argtypes = [vp, C.POINTER(Stage0View), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
+                                                  C.c_int, C.c_int, C.c_float, C.c_int, vp, vp]
+    lib.mi355_conv3d_wino3_view_ndhwc.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, C.c_int, C.c_int,
+                                                  C.c_float, vp, C.POINTER(Stage0View), vp, vp]
     lib.mi355_profile_enable.argtypes = [vp, C.c_int]
     lib.mi355_profile_read.argtypes = [vp, C.POINTER(ProfEntry), C.c_int]
     _lib = lib

@@ -1134,172 +1134,16 @@ struct S2Geom {
     static constexpr size_t LDS_BYTES = (size_t)(2 * BUF_FLOATS + 2 * WSLOT_FLOATS + 4 * 64 * 2) * sizeof(float);
 };
 
-template <int TXL>
-__global__ __launch_bounds__(256, 1) void conv3_f32_s2dma_kernel(Wino2Args pa) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const ConvArgs &p = pa.c;
-    typedef S2Geom<TXL> GM;
-    constexpr int IX = GM::IX, IY = GM::IY, BV = GM::BV;
-    constexpr int S2_BUF_FLOATS = GM::BUF_FLOATS, S2_WSLOT_FLOATS = GM::WSLOT_FLOATS, S2_RSTRIDE = GM::RSTRIDE;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int half = lane >> 5;
-    const int l31 = lane & 31;
-    float *wring = lds + 2 * S2_BUF_FLOATS;
-
-    const int xcd = (int)blockIdx.x & 7, li = (int)blockIdx.x >> 3;
-    const int nl = ((int)gridDim.x - xcd + 7) >> 3;
-    const int q8 = pa.total_tiles >> 3, r8 = pa.total_tiles & 7;
-    const int lo = xcd * q8 + (xcd < r8 ? xcd : r8);
-    const int hi = lo + q8 + (xcd < r8 ? 1 : 0);
-    int tile = lo + li;
-    if (tile >= hi) return;
-
-    struct TileCoord { int n, oz0, oy0, ox0; };
-    auto decode = [&](int t) {
-        TileCoord tc;
-        tc.n = (int)fdiv((uint32_t)t, p.div_tiles_per_n);
-        const int tt = t - tc.n * (int)p.div_tiles_per_n.d;
-        int tile_x, tile_y, tile_z;
-        tile_from_id(tt, pa.order, tile_x, tile_y, tile_z);
-        tc.oz0 = tile_z << 1; tc.oy0 = tile_y * GM::TY; tc.ox0 = tile_x << TXL;
-        return tc;
-    };
-
-    // brick DMA: 7 ranges per wave, both quads of a range back to back.  Range r = voxels [59r, 59r + 64) of a quad
-    // plane; overlaps carry identical data, the tail of range 27 runs into the next plane (or the padding).
-    unsigned dma_pk[7];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-        int bv = (wave + 4 * k) * S2_RSTRIDE + lane;
-        const int over = bv >= BV ? 1 : 0;
-        bv -= over * BV;
-        const int rr = bv / IX, bx = bv - rr * IX;
-        const int rz = rr / IY, ry = rr - rz * IY;
-        dma_pk[k] = (unsigned)(rz | (ry << 4) | (bx << 8) | (over << 16));
-    }
-    auto dma_brick = [&](const TileCoord &tc, int ch, int k, float *buf) {
-        const int rng = wave + 4 * k;
-        const int cglob = ch * 8;
-        const float *src; int Csrc, coff;
-        if (cglob < p.C0) { src = p.in0; Csrc = p.C0; coff = cglob; }
-        else { src = p.in1; Csrc = p.C1; coff = cglob - p.C0; }
-        src += ((((size_t)tc.n * p.Di + (2 * tc.oz0 - 1)) * p.Hi + (2 * tc.oy0 - 1)) * p.Wi + (2 * tc.ox0 - 1)) * (long)Csrc + coff;
-        const unsigned pk = dma_pk[k];
-        const int rz = pk & 15, ry = (pk >> 4) & 15, bx = (pk >> 8) & 255, over = pk >> 16;
-        const bool in_vol = ((unsigned)(2 * tc.oz0 - 1 + rz) < (unsigned)p.Di) && ((unsigned)(2 * tc.oy0 - 1 + ry) < (unsigned)p.Hi) &&
-                            ((unsigned)(2 * tc.ox0 - 1 + bx) < (unsigned)p.Wi);
-        const int voff = ((rz * p.Hi + ry) * p.Wi + bx) * Csrc + over * 4;
-        const float *g0 = in_vol ? src + voff : pa.zeros;
-        const float *g1 = (in_vol && over == 0) ? src + voff : pa.zeros;  // quad 1's overrun lanes fill padding
-        asm volatile("" : "+v"(g0), "+v"(g1));
-        float *dst = buf + rng * S2_RSTRIDE * 4;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g0,
-                                         (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g1,
-                                         (__attribute__((address_space(3))) void *)(dst + BV * 4 - 4), 16, 16, 0);
-    };
-    // weight DMA: dz plane `dz` of chunk `ch` = 18 KiB contiguous in the pack; KiB i goes to wave i & 3
-    const float *wblk = p.wp + (size_t)blockIdx.y * p.nchunks * (27 * 2 * 256);
-    auto dma_weights = [&](int ch, int dz, float *slot, int i_lo = 0, int i_hi = 5) {
-        const float *wsrc = wblk + ((size_t)ch * 27 + dz * 9) * (2 * 256) + lane * 4;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            if (i < i_lo || i >= i_hi) continue;  // (compile-time at the call sites)
-            // (no branch: KiB 18 and 19 do not exist - waves 2 and 3 fetch KiB 16 and 17 a second time in the last round,
-            //  the same bytes into the same slot as waves 0 and 1)
-            const int kib = wave + 4 * i < 18 ? wave + 4 * i : wave + 4 * i - 2;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(wsrc + kib * 256),
-                                             (__attribute__((address_space(3))) void *)(slot + kib * 256), 16, 0, 0);
-        }
-    };
-
-    // wave w = z plane w >> 1, y rows (w & 1) * TY/2 ..; lane = (y row, x); floats: input voxel (2z, 2y, 2x) at tap 0, quad `half`
-    const int ay = (wave & 1) * (GM::TY / 2) + (l31 >> TXL), ax = l31 & (GM::TX - 1);
-    const int a_base = half * BV * 4 + (((wave >> 1) * 2 * IY + ay * 2) * IX + 2 * ax) * 4;
-
-    TileCoord cur = decode(tile);
-#pragma unroll
-    for (int k = 0; k < 7; ++k) dma_brick(cur, 0, k, lds);
-    dma_weights(0, 0, wring);
-    __syncthreads();
-
-    int buf = 0, wslot = 0;
-    for (; tile < hi; tile += nl) {
-        f32x16 acc[1][2];
-#pragma unroll
-        for (int nf = 0; nf < 2; ++nf)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[0][nf][r] = 0.f;
-        const int ntile = tile + nl;
-        const TileCoord nxt_tile = ntile < hi ? decode(ntile) : cur;
-
-        for (int ch = 0; ch < p.nchunks; ++ch) {
-            const bool last_ch = ch == p.nchunks - 1;
-            const bool have_next = !last_ch || ntile < hi;
-            // (without a next chunk the fetches re-stage the current one into the idle buffers: no branch in the MFMA stream)
-            const TileCoord nxt = last_ch ? nxt_tile : cur;   // (nxt_tile = cur past the last tile)
-            const int nch = have_next ? (last_ch ? 0 : ch + 1) : ch;
-            const float *bufc = lds + buf * S2_BUF_FLOATS;
-            float *bufn = lds + (buf ^ 1) * S2_BUF_FLOATS;
-#pragma unroll
-            for (int dz = 0; dz < 3; ++dz) {
-                // fetches of the step: the next weight plane and a third of the next chunk's brick - issued from inside the tap loop
-                // (round 4: in front of it, their ~11 DMAs and address arithmetic ran with the matrix pipe idle, once per step)
-                auto step_fetch = [&](int piece) {
-                    if (piece < 2) {  // the weight plane's 18 KiB: rounds 0-1, then 2-4
-                        const int lo = piece == 0 ? 0 : 2, hi = piece == 0 ? 2 : 5;
-                        if (dz < 2) dma_weights(ch, dz + 1, wring + (wslot ^ 1) * S2_WSLOT_FLOATS, lo, hi);
-                        else dma_weights(nch, 0, wring + (wslot ^ 1) * S2_WSLOT_FLOATS, lo, hi);
-                    } else {
-                        const int q = piece - 1;
-                        const int k = dz == 0 ? q - 1 : (dz == 1 ? 2 + q : 4 + q);   // dz 0: ranges 0 1 2, dz 1: 3 4, dz 2: 5 6
-                        if (q <= (dz == 0 ? 3 : 2)) dma_brick(nxt, nch, k, bufn);
-                    }
-                };
-                const float *wcur = wring + wslot * S2_WSLOT_FLOATS + lane * 4;
-                f32x4 a_cur, a_nxt, b_cur[2], b_nxt[2];
-                a_cur = *(const f32x4 *)(bufc + a_base + dz * IY * IX * 4);
-                b_cur[0] = *(const f32x4 *)(wcur);
-                b_cur[1] = *(const f32x4 *)(wcur + 256);
-                // The next tap's fragments are read BEHIND the first two MFMAs of this tap (round 4).  With an LDS-DMA in flight hipcc
-                // does not count LDS reads (every wait is lgkmcnt(0)): read at the top of the tap, as before, the three reads
-                // were waited for on the spot - their latency exposed nine times a step, which is what kept this kernel's matrix
-                // pipe at 0.72.  Now the wait comes in front of the NEXT tap's first MFMA, six MFMAs later.
-#pragma unroll
-                for (int t = 0; t < 9; ++t) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-#pragma unroll
-                        for (int nf = 0; nf < 2; ++nf) {
-                            acc[0][nf] = __builtin_amdgcn_mfma_f32_32x32x2f32(b_cur[nf][j], a_cur[j], acc[0][nf], 0, 0, 0);
-                            if (j == 0 && nf == 1) {
-                                __builtin_amdgcn_sched_barrier(0);
-                                if (t + 1 < 9) {
-                                    const int dy = (t + 1) / 3, dx = (t + 1) - dy * 3;
-                                    a_nxt = *(const f32x4 *)(bufc + a_base + ((dz * IY + dy) * IX + dx) * 4);
-                                    b_nxt[0] = *(const f32x4 *)(wcur + (t + 1) * 512);
-                                    b_nxt[1] = *(const f32x4 *)(wcur + (t + 1) * 512 + 256);
-                                }
-                                if (t < 5) step_fetch(t);
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-                        }
-                    a_cur = a_nxt; b_cur[0] = b_nxt[0]; b_cur[1] = b_nxt[1];
-                }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // explicit: a ds_read is ordered behind an LDS-DMA only by the issuer's vmcnt + a barrier
-                __syncthreads();  // retires the step's DMAs (vmcnt(0)); the other weight slot / brick buffer may be read now
-                wslot ^= 1;
-            }
-            buf ^= 1;
-        }
-        ConvArgs q = p;
-        q.lx = TXL; q.ly = 6 - TXL; q.lz = 1;  // voxel v = wave * 32 + lane: x = v & (TX-1), y = (v >> TXL) & (TY-1), z = v >> 6
-        conv_epilogue<1, 2>(acc, q, cur.n, cur.oz0, cur.oy0, cur.ox0, (int)blockIdx.y * 64);
-        cur = nxt_tile;
-    }
-}
+struct S2ViewArgs {  // conv3_f32_s2dma_kernel_view: the plain kernel's arguments + the view
+    Wino2Args w;
+    S0View v;
+};
+#define S2DMA_VIEW 0
+#include "conv3d_s2dma_body.h"
+#undef S2DMA_VIEW
+#define S2DMA_VIEW 1
+#include "conv3d_s2dma_body.h"
+#undef S2DMA_VIEW
 
 // MI355_WINOGRAD: 0 = direct kernels only; anything else (default) = F(2x2,3x3) over (z, y)
 static bool winograd_enabled() { return env_switch("MI355_WINOGRAD"); }
@@ -1434,6 +1278,8 @@ static KernelRow f32_rows[] = {
     MI355_KERNEL_ROW(conv3_f32_wino2_kernel<2>),
     MI355_KERNEL_ROW(conv3_f32_s2dma_kernel<5>),
     MI355_KERNEL_ROW(conv3_f32_s2dma_kernel<4>),
+    MI355_KERNEL_ROW(conv3_f32_s2dma_kernel_view<5>),
+    MI355_KERNEL_ROW(conv3_f32_s2dma_kernel_view<4>),
     MI355_KERNEL_ROW(conv3_f32_mfma_pipe_kernel<4, 1>),
     MI355_KERNEL_ROW(conv3_f32_mfma_pipe_kernel<2, 2>),
     MI355_KERNEL_ROW(conv3_f32_mfma_pipe_kernel<2, 1>),
@@ -1451,6 +1297,25 @@ static KernelRow f32_rows[] = {
 
 // Which kernel an fp32 call goes to, with which tile, grid, LDS size and weight pack.  No side effects: the error text is set
 // only when the call is refused.
+// Does conv3_f32_s2dma_kernel take this call?  Stride 2, 8-channel chunks, 64 couts per workgroup, no fused head, enough tiles.
+// `force`: without the fill-the-chip rule (the single-op test entry of the view instantiation runs shapes of a few tiles).
+bool plan_s2dma(const ConvWeights &w, const ConvCall &c, ConvPlan *p, bool force) {
+    if (!(w.stride == 2 && w.wp_dev && w.cc == 8 && w.nf == 2 && !c.head_out)) return false;
+    const int Do = (c.Di - 1) / 2 + 1, Ho = (c.Hi - 1) / 2 + 1, Wo = (c.Wi - 1) / 2 + 1;
+    const bool in_fits_32bit = (long)c.Di * c.Hi * c.Wi * (c.C0 > c.C1 ? c.C0 : c.C1) < (1l << 31);
+    const int txl = Wo >= 24 ? 5 : 4;  // 2 x 2 x 32 tiles, or 2 x 4 x 16 on narrow volumes
+    const int TX = 1 << txl, TY = 64 >> txl;
+    const TileGeom g = fixed_tile(Do, Ho, Wo, 1, 6 - txl, txl, 5, 2 * TY + 1, 2 * TX + 1);
+    const long tiles = g.tiles_per_n() * c.N;
+    const int gy = w.cout / 64;
+    // persistent workgroups need a few tiles each, and the fixed tiles waste lanes on very small volumes
+    if (!(env_switch("MI355_S2_DMA") && (force || tiles * gy >= 768) && tiles < (1l << 30) && Wo >= 12 && Ho >= 3 && in_fits_32bit)) return false;
+    plan_set(p, find_row(f32_rows, "conv3_f32_s2dma_kernel<%d>", txl), FAM_S2DMA, g, tiles, persistent_grid_x(256, gy, tiles), gy,
+             txl == 5 ? S2Geom<5>::LDS_BYTES : S2Geom<4>::LDS_BYTES);
+    p->nf = w.nf;
+    return true;
+}
+
 int plan_conv_f32(const ConvWeights &w, const ConvCall &c, ConvPlan *p) {
     *p = ConvPlan();
     MI355_REQUIRE(w.wp_dev != nullptr, "conv %d->%d has no MFMA weight pack", w.cin, w.cout);
@@ -1537,19 +1402,7 @@ int plan_conv_f32(const ConvWeights &w, const ConvCall &c, ConvPlan *p) {
         p->nf = NF;
         return MI355_OK;
     }
-    if (st == 2 && w.cc == 8 && w.nf == 2 && !c.head_out) {
-        const int txl = Wo >= 24 ? 5 : 4;  // 2 x 2 x 32 tiles, or 2 x 4 x 16 on narrow volumes
-        const int TX = 1 << txl, TY = 64 >> txl;
-        const TileGeom g = fixed_tile(Do, Ho, Wo, 1, 6 - txl, txl, 5, 2 * TY + 1, 2 * TX + 1);
-        const long tiles = g.tiles_per_n() * c.N;
-        const int gy = w.cout / 64;
-        // persistent workgroups need a few tiles each, and the fixed tiles waste lanes on very small volumes
-        if (env_switch("MI355_S2_DMA") && tiles * gy >= 768 && tiles < (1l << 30) && Wo >= 12 && Ho >= 3 && in_fits_32bit) {
-            plan_set(p, find_row(f32_rows, "conv3_f32_s2dma_kernel<%d>", txl), FAM_S2DMA, g, tiles, persistent_grid_x(256, gy, tiles), gy,
-                     txl == 5 ? S2Geom<5>::LDS_BYTES : S2Geom<4>::LDS_BYTES);
-            return MI355_OK;
-        }
-    }
+    if (plan_s2dma(w, c, p, false)) return MI355_OK;
     int MF = (st == 1) ? 4 : 1;
     TileGeom g = chosen_tile(Do, Ho, Wo, st, 128 * MF);
     if (st == 1 && (g.tiles_per_n() * c.N * gy_nf < 512 || (size_t)g.brickvox() * w.cc * 4 > 80 * 1024 || (w.cc == 8 && w.nf == 2))) {
@@ -1570,10 +1423,30 @@ int plan_conv_f32(const ConvWeights &w, const ConvCall &c, ConvPlan *p) {
     return MI355_OK;
 }
 
+static int launch_conv_f32(const ConvWeights &w, const ConvCall &c, const ConvPlan &p, hipStream_t s, const char **kernel_name);
 int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, const char **kernel_name) {
     ConvPlan p;
     MI355_TRY(plan_conv_f32(w, c, &p));
+    return launch_conv_f32(w, c, p, s, kernel_name);
+}
+
+int conv3d_s2dma_f32(const ConvWeights &w, const ConvCall &c, bool force, hipStream_t s, const char **kernel_name) {
+    ConvPlan p;
+    MI355_REQUIRE(c.C0 + c.C1 == w.cin_pad && c.C0 % 8 == 0 && c.C1 % 8 == 0 && (c.C1 == 0 || c.in1) && !c.addend && !c.in_scale && !c.stats,
+                  "conv %d->%d: not a call of the stride-2 LDS-DMA kernel", w.cin, w.cout);
+    if (!plan_s2dma(w, c, &p, force)) {
+        set_error("conv %dx%dx%dx%d, %d -> %d: not a call of conv3_f32_s2dma_kernel", c.N, c.Di, c.Hi, c.Wi, w.cin, w.cout);
+        return MI355_ERR_UNSUPPORTED;
+    }
+    return launch_conv_f32(w, c, p, s, kernel_name);
+}
+
+static int launch_conv_f32(const ConvWeights &w, const ConvCall &c, const ConvPlan &p, hipStream_t s, const char **kernel_name) {
     if (kernel_name) *kernel_name = p.name;
+    // a view is attached to the plan the call has without it; a kernel that cannot read through one must never be handed one
+    MI355_REQUIRE(!c.in0_view || (p.family == FAM_S2DMA && c.C1 == 0 && c.in0_view->src && c.N <= S0_VIEW_MAX_SAMPLES),
+                  "conv %d->%d: an input view reached %s, which cannot read through it", w.cin, w.cout, p.name);
+    MI355_REQUIRE(!c.addend_view || p.family == FAM_WINO3, "conv %d->%d: an addend view reached %s, which cannot read through it", w.cin, w.cout, p.name);
     if (p.family == FAM_WINO3) return launch_wino3(w, c, p, s);
     ConvArgs a;
     a.in0 = c.in0; a.in1 = c.in1; a.C0 = c.C0; a.C1 = c.C1;
@@ -1594,6 +1467,14 @@ int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, cons
         Wino2Args wa;
         wa.c = a; wa.total_tiles = (int)p.tiles; wa.zeros = zeros;
         wa.order = make_tile_order(p.g.tiles_x, p.g.tiles_y, p.g.tiles_z);
+        if (c.in0_view) {  // the same plan on the instantiation that reads through the view
+            KernelRow *row = find_row(f32_rows, "conv3_f32_s2dma_kernel_view<%d>", p.g.lx);
+            MI355_REQUIRE(row != nullptr, "no view instantiation of %s", p.name);
+            S2ViewArgs va;
+            va.w = wa; va.v = *c.in0_view;
+            if (kernel_name) *kernel_name = row->name;
+            return launch_row(*row, grid, p.lds_bytes, s, &va);
+        }
         return launch_row(*p.row, grid, p.lds_bytes, s, &wa);
     }
     if (p.family == FAM_PIPE) {

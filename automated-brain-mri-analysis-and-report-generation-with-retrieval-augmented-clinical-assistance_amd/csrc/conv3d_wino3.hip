@@ -56,6 +56,10 @@ struct Wino3Args {
     float in_slope;  // LeakyReLU slope of that activation, 1 = none
     // EPI 3: [N][D][H][W][Cout] added to the conv sum in front of bias and activation (the other half of a split concat conv), or null
     const float *addend;
+    // EPI 3, stage-0 views (kernels.h S0View): `addend` holds only the shells of its samples, every other piece is read in place from
+    // the view's tensor.  Always filled: without a view the launcher hands over one in which every voxel is a shell voxel.  Last
+    // member: the other instantiations never touch it, and the offsets of everything they read are what they were.
+    S0View aview;
 };
 
 constexpr int W3_IZ = 6, W3_IY = 10, W3_IX = 10, W3_BV = W3_IZ * W3_IY * W3_IX;  // 600 brick voxels
@@ -434,10 +438,17 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino3_kernel(Wino3Args p) {
     double stat_acc = 0.0;  // EPI 2, wave 0: this workgroup's quantised statistics of sample stat_n (lane = cout, statistic)
     int stat_n = -1;
     int buf = 0;
+    // EPI 3: the view words of the current tile's sample.  The next tile's are fetched at the top of its predecessor (a scalar load:
+    // its lgkmcnt(0) falls into the first LDS wait of the chunk loop, which comes anyway) - fetched in the epilogue, in front of the
+    // addend loads that need them, their latency would be exposed once per tile.
+    S0ViewSample av_cur = {0u, 0u};
+    if constexpr (EPI == 3) av_cur = p.aview.smp[cur.n & (S0_VIEW_MAX_SAMPLES - 1)];
     for (; tile < hi; tile += nl) {
         f32x16 acc[16];
         const int ntile = tile + nl;
         const TileCoord nxt_tile = ntile < hi ? decode(ntile) : cur;
+        S0ViewSample av_nxt = av_cur;
+        if constexpr (EPI == 3) av_nxt = p.aview.smp[nxt_tile.n & (S0_VIEW_MAX_SAMPLES - 1)];  // (host: N <= S0_VIEW_MAX_SAMPLES with a view; the index never leaves the arguments)
         // Two bodies (round 5): a second copy of the chunk body for a tile's chunk 0 whose first MFMAs take the constant 0 as C
         // saves the 256 v_accvgpr_write of the accumulator clear (1 - 3 % per launch, profiles/r05_wino3_two_body.txt).  Round 4
         // abandoned it after "a memory access fault on every shape".  The cause, from that build's listing: with the second body
@@ -560,9 +571,33 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino3_kernel(Wino3Args p) {
                 const size_t row_a = (size_t)p.W * p.Cout;
                 const float *abase = p.addend + (((size_t)cur.n * p.D + cur.oz0) * p.H + cur.oy0 + (wave >> 1)) * row_a + (int)blockIdx.y * 32;
                 const unsigned aoff = (unsigned)(((2 * (srow_a >> 2)) * p.W + cur.ox0 + 2 * (srow_a & 3) + (wave & 1)) * p.Cout + (lane_e & 7) * 4);
+                // The same piece in the view's tensor (strides sy, sz in place of W, H * W), and which of the two holds it: the dense
+                // tensor inside a shell - the tile's planes (scalar, per piece) and its rows / columns (bits of two scalar masks, per
+                // lane) within `depth` of a face whose bit is set -, the view elsewhere.  Branch-free: eight loads per lane either way.
+                const S0View &av = p.aview;
+                const int dpt = av.depth;
+                auto shell_bits = [](int c0, int n, int lo, int hi) {  // planes c0 .. c0 + n - 1 below lo or at / above hi, as bits
+                    int a = lo - c0, b = hi - c0;
+                    a = a < 0 ? 0 : (a > n ? n : a);
+                    b = b < 0 ? 0 : (b > n ? n : b);
+                    return ((1u << a) - 1u) | (((1u << n) - 1u) & ~((1u << b) - 1u));
+                };
+                const unsigned fc = av_cur.faces;
+                const unsigned mz = shell_bits(cur.oz0, 4, (fc & 1u) ? dpt : 0, (fc & 2u) ? p.D - dpt : p.D);
+                const unsigned my = shell_bits(cur.oy0, 8, (fc & 4u) ? dpt : 0, (fc & 8u) ? p.H - dpt : p.H);
+                const unsigned mx = shell_bits(cur.ox0, 8, (fc & 16u) ? dpt : 0, (fc & 32u) ? p.W - dpt : p.W);
+                const int yb = (wave >> 1) + 2 * (srow_a >> 2), xb = 2 * (srow_a & 3) + (wave & 1);
+                const bool sh_x = (mx >> xb) & 1u;
+                const bool sh_lane[2] = {sh_x || ((my >> yb) & 1u), sh_x || ((my >> (yb + 4)) & 1u)};
+                const size_t vrow = (size_t)av.sy * p.Cout;
+                const float *vbase = av.src + ((size_t)av_cur.off + (size_t)cur.oz0 * av.sz) * p.Cout + (size_t)(cur.oy0 + (wave >> 1)) * vrow + (int)blockIdx.y * 32;
+                const unsigned voff = (unsigned)(((2 * (srow_a >> 2)) * av.sy + cur.ox0 + 2 * (srow_a & 3) + (wave & 1)) * p.Cout + (lane_e & 7) * 4);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {  // k = 2 t + oz, as phase 2 walks its rows
                     const float *ap = abase + ((size_t)(2 * (k >> 2) + (k & 1)) * p.H + 4 * ((k >> 1) & 1)) * row_a + aoff;
+                    const float *vp = vbase + ((size_t)(2 * (k >> 2) + (k & 1)) * av.sz * p.Cout + 4 * ((k >> 1) & 1) * vrow) + voff;
+                    const bool shell = ((mz >> (2 * (k >> 2) + (k & 1))) & 1u) || sh_lane[(k >> 1) & 1];
+                    ap = shell ? ap : vp;
                     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(ad[k]) : "v"(ap) : "memory");
                 }
             }
@@ -750,6 +785,7 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino3_kernel(Wino3Args p) {
             }
         }
         cur = nxt_tile;
+        av_cur = av_nxt;
     }
     if constexpr (EPI == 2) {
         if (wave == 0 && stat_n >= 0)
@@ -874,6 +910,14 @@ int launch_wino3(const ConvWeights &w, const ConvCall &c, const ConvPlan &p, hip
     a.head_w = c.head_w; a.head_b = c.head_b; a.head_out = c.head_out; a.head_ncls = c.head_ncls;
     a.in_scale = c.in_scale; a.in_shift = c.in_shift; a.in_slope = c.in_act == ACT_LRELU ? c.slope : 1.0f;
     a.addend = c.addend;
+    MI355_REQUIRE(!c.addend_view || (c.addend && c.addend_view->src && c.N <= S0_VIEW_MAX_SAMPLES), "conv %d->%d: an addend view without an addend", w.cin, w.cout);
+    if (c.addend_view) a.aview = *c.addend_view;
+    else if (c.addend) {
+        // dense only: every face set and a shell deeper than any tile - each piece comes from `addend`, the view is never read
+        a.aview = S0View();
+        a.aview.src = c.addend; a.aview.depth = 1 << 24;
+        for (S0ViewSample &sm : a.aview.smp) { sm.off = 0; sm.faces = 63u; }
+    }
     float *zeros = nullptr;
     MI355_TRY(device_scratch(SCR_ZEROS, s, 256, (void **)&zeros, true));
     a.zeros = zeros;

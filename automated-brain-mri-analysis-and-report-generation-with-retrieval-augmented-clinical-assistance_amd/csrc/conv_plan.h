@@ -166,6 +166,7 @@ int plan_conv_f32(const ConvWeights &w, const ConvCall &c, ConvPlan *p);
 int plan_conv_f16(const ConvWeightsH &w, const ConvCallH &c, ConvPlan *p);
 // steps of the planners that live beside their kernels: true = the call fits and *p is its plan
 bool plan_wino3(const ConvWeights &w, const ConvCall &c, ConvPlan *p, bool force = false);  // conv3d_wino3.hip
+bool plan_s2dma(const ConvWeights &w, const ConvCall &c, ConvPlan *p, bool force = false);  // conv3d.hip
 bool plan_f16_s2dma(const ConvWeightsH &w, const ConvCallH &c, ConvPlan *p);  // conv3d_f16_s2.hip
 int launch_wino3(const ConvWeights &w, const ConvCall &c, const ConvPlan &p, hipStream_t s);
 int launch_f16_s2dma(const ConvWeightsH &w, const ConvCallH &c, const ConvPlan &p, hipStream_t s);

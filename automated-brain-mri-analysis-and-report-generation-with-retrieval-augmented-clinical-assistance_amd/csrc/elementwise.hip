@@ -281,7 +281,93 @@ __global__ __launch_bounds__(256) void stage0_gather_kernel(S0GatherArgs a) {
     }
 }
 
+static int stage0_gather_check(const S0GatherArgs &a, int n_samples, int *n_wv);
 int stage0_gather(const S0GatherArgs &a, int n_samples, hipStream_t s) {
+    int n_wv = 0;
+    MI355_TRY(stage0_gather_check(a, n_samples, &n_wv));
+    MI355_REQUIRE((int64_t)a.Ve[0] * a.Ve[1] < (1ll << 31), "stage0_gather: grid too large");
+    S0GatherArgs k = a;
+    k.n = n_samples;
+    hipLaunchKernelGGL(stage0_gather_kernel, dim3((unsigned)(a.Ve[0] * a.Ve[1]), (unsigned)n_wv), dim3(256), 0, s, k);
+    MI355_HIP(hipGetLastError());
+    return MI355_OK;
+}
+
+// ---- the same for a tensor whose reader takes a stage-0 view (kernels.h S0View): the shells alone.  Per sample the shell voxels are
+// enumerated as three boxes - A: the planes within r of a z face that has a slab, whole; B: of the other planes the rows within r
+// of such a y face; C: of the other rows the voxels within r of such an x face - so the grid covers what is written and nothing
+// else, and consecutive lanes write consecutive 16-byte pieces.  Sources and precedence are stage0_gather_row's.
+struct S0ShellDims {
+    int lo[3], hi[3];   // axis a: [0, lo) and [hi, P) lie in a shell
+    unsigned nA, nB, nC;  // voxels per box
+};
+static __host__ __device__ inline S0ShellDims s0_shell_dims(const int P[3], int r, const int faces[6]) {
+    S0ShellDims d;
+    for (int a = 0; a < 3; ++a) { d.lo[a] = faces[2 * a] >= 0 ? r : 0; d.hi[a] = faces[2 * a + 1] >= 0 ? P[a] - r : P[a]; }
+    const unsigned nz = (unsigned)(d.lo[0] + P[0] - d.hi[0]), ny = (unsigned)(d.lo[1] + P[1] - d.hi[1]), nx = (unsigned)(d.lo[2] + P[2] - d.hi[2]);
+    d.nA = nz * (unsigned)P[1] * (unsigned)P[2];
+    d.nB = ((unsigned)P[0] - nz) * ny * (unsigned)P[2];
+    d.nC = ((unsigned)P[0] - nz) * ((unsigned)P[1] - ny) * nx;
+    return d;
+}
+int64_t stage0_shell_voxels(const int P[3], int r, const int faces[6]) {
+    const S0ShellDims d = s0_shell_dims(P, r, faces);
+    return (int64_t)d.nA + d.nB + d.nC;
+}
+
+__global__ __launch_bounds__(256) void stage0_gather_shell_kernel(S0GatherArgs a, int which) {
+    const S0GatherSet t = which ? S0GatherSet{a.wv2, {a.slab2[0], a.slab2[1], a.slab2[2]}, a.out2, a.r2, a.C42}
+                                : S0GatherSet{a.wv, {a.slab[0], a.slab[1], a.slab[2]}, a.out, a.r, a.C4};
+    const int n = blockIdx.y, r = t.r;
+    const unsigned C4 = (unsigned)t.C4;
+    const S0Sample &sm = a.smp[n];
+    const S0ShellDims d = s0_shell_dims(a.P, r, sm.slab);
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;   // (host: voxels of a tile * C4 < 2^31)
+    if (i >= (d.nA + d.nB + d.nC) * C4) return;
+    unsigned w = i / C4;
+    const unsigned c4 = i - w * C4;
+    auto shell_at = [](unsigned k, int lo, int hi) { return (int)k < lo ? (int)k : hi + ((int)k - lo); };  // k-th shell plane of an axis
+    int z, y, x;
+    if (w < d.nA) {
+        const unsigned plane = (unsigned)a.P[1] * (unsigned)a.P[2];
+        const unsigned kz = w / plane; w -= kz * plane;
+        z = shell_at(kz, d.lo[0], d.hi[0]);
+        y = (int)(w / (unsigned)a.P[2]); x = (int)(w - (unsigned)y * (unsigned)a.P[2]);
+    } else if (w < d.nA + d.nB) {
+        w -= d.nA;
+        const unsigned ny = (unsigned)(d.lo[1] + a.P[1] - d.hi[1]), plane = ny * (unsigned)a.P[2];
+        const unsigned kz = w / plane; w -= kz * plane;
+        z = d.lo[0] + (int)kz;
+        const unsigned ky = w / (unsigned)a.P[2];
+        y = shell_at(ky, d.lo[1], d.hi[1]); x = (int)(w - ky * (unsigned)a.P[2]);
+    } else {
+        w -= d.nA + d.nB;
+        const unsigned ny = (unsigned)(d.lo[1] + a.P[1] - d.hi[1]), nx = (unsigned)(d.lo[2] + a.P[2] - d.hi[2]);
+        const unsigned plane = ((unsigned)a.P[1] - ny) * nx;
+        const unsigned kz = w / plane; w -= kz * plane;
+        z = d.lo[0] + (int)kz;
+        const unsigned ky = w / nx;
+        y = d.lo[1] + (int)ky; x = shell_at(w - ky * nx, d.lo[2], d.hi[2]);
+    }
+    const f32x4 *src;
+    if (sm.slab[0] >= 0 && z < r)
+        src = (const f32x4 *)t.slab[0] + ((((int64_t)sm.slab[0] * a.t[0] + z) * a.P[1] + y) * a.P[2] + x) * C4;
+    else if (sm.slab[1] >= 0 && z >= a.P[0] - r)
+        src = (const f32x4 *)t.slab[0] + ((((int64_t)sm.slab[1] * a.t[0] + (z - (a.P[0] - a.t[0]))) * a.P[1] + y) * a.P[2] + x) * C4;
+    else if (sm.slab[2] >= 0 && y < r)
+        src = (const f32x4 *)t.slab[1] + ((((int64_t)sm.slab[2] * a.P[0] + z) * a.t[1] + y) * a.P[2] + x) * C4;
+    else if (sm.slab[3] >= 0 && y >= a.P[1] - r)
+        src = (const f32x4 *)t.slab[1] + ((((int64_t)sm.slab[3] * a.P[0] + z) * a.t[1] + (y - (a.P[1] - a.t[1]))) * a.P[2] + x) * C4;
+    else if (sm.slab[4] >= 0 && x < r)
+        src = (const f32x4 *)t.slab[2] + ((((int64_t)sm.slab[4] * a.P[0] + z) * a.P[1] + y) * a.t[2] + x) * C4;
+    else if (sm.slab[5] >= 0 && x >= a.P[2] - r)
+        src = (const f32x4 *)t.slab[2] + ((((int64_t)sm.slab[5] * a.P[0] + z) * a.P[1] + y) * a.t[2] + (x - (a.P[2] - a.t[2]))) * C4;
+    else   // (not reached: every enumerated voxel lies in a shell)
+        src = (const f32x4 *)t.wv + ((((int64_t)sm.wv * a.Ve[0] + sm.org[0] + z) * a.Ve[1] + sm.org[1] + y) * a.Ve[2] + sm.org[2] + x) * C4;
+    ((f32x4 *)t.out)[((((int64_t)n * a.P[0] + z) * a.P[1] + y) * a.P[2] + x) * C4 + c4] = src[c4];
+}
+
+static int stage0_gather_check(const S0GatherArgs &a, int n_samples, int *n_wv) {
     MI355_REQUIRE(n_samples > 0 && n_samples <= S0_MAX_SAMPLES, "stage0_gather: %d samples (max %d)", n_samples, S0_MAX_SAMPLES);
     MI355_REQUIRE(a.C4 > 0 && a.r > 0, "stage0_gather: bad channel count / shell depth");
     MI355_REQUIRE(!a.out2 || (a.wv2 && a.C42 > 0 && a.r2 >= a.r), "stage0_gather: bad second tensor");
@@ -291,16 +377,52 @@ int stage0_gather(const S0GatherArgs &a, int n_samples, hipStream_t s) {
     for (int i = 0; i < n_samples; ++i)
         for (int k = 0; k < 3; ++k)
             MI355_REQUIRE(a.smp[i].org[k] >= 0 && a.smp[i].org[k] + a.P[k] <= a.Ve[k], "stage0_gather: sample %d leaves the volume", i);
-    int n_wv = 0;
+    *n_wv = 0;
     for (int i = 0; i < n_samples; ++i) {
         MI355_REQUIRE(a.smp[i].wv >= 0 && a.smp[i].wv < 65535, "stage0_gather: sample %d: whole-volume index %d", i, a.smp[i].wv);
-        n_wv = a.smp[i].wv + 1 > n_wv ? a.smp[i].wv + 1 : n_wv;
+        *n_wv = a.smp[i].wv + 1 > *n_wv ? a.smp[i].wv + 1 : *n_wv;
     }
-    MI355_REQUIRE((int64_t)a.Ve[0] * a.Ve[1] < (1ll << 31), "stage0_gather: grid too large");
+    return MI355_OK;
+}
+
+int stage0_gather_shells(const S0GatherArgs &a, int n_samples, int which, hipStream_t s) {
+    int n_wv = 0;
+    MI355_TRY(stage0_gather_check(a, n_samples, &n_wv));
+    MI355_REQUIRE(which == 0 || (which == 1 && a.out2), "stage0_gather_shells: tensor %d", which);
+    const int C4 = which ? a.C42 : a.C4, r = which ? a.r2 : a.r;
+    MI355_REQUIRE((int64_t)a.P[0] * a.P[1] * a.P[2] * C4 < (1ll << 31), "stage0_gather_shells: tile too large");
+    int64_t most = 0;
+    for (int i = 0; i < n_samples; ++i) most = std::max(most, stage0_shell_voxels(a.P, r, a.smp[i].slab));
+    if (most == 0) return MI355_OK;  // no sample has a face inside the volume
     S0GatherArgs k = a;
     k.n = n_samples;
-    hipLaunchKernelGGL(stage0_gather_kernel, dim3((unsigned)(a.Ve[0] * a.Ve[1]), (unsigned)n_wv), dim3(256), 0, s, k);
+    hipLaunchKernelGGL(stage0_gather_shell_kernel, dim3((unsigned)((most * C4 + 255) / 256), (unsigned)n_samples), dim3(256), 0, s, k, which);
     MI355_HIP(hipGetLastError());
+    return MI355_OK;
+}
+
+// The view of n samples into a whole-volume tensor (kernels.h): pure host code.
+int stage0_view_make(const float *src, int n_wv, const int Ve[3], const int P[3], int C, int depth, const S0Sample *smp, int n, S0View *out) {
+    *out = S0View();
+    MI355_REQUIRE(src && n_wv > 0 && C > 0 && depth > 0 && smp, "stage-0 view: bad argument");
+    MI355_REQUIRE(n > 0 && n <= S0_VIEW_MAX_SAMPLES, "stage-0 view: %d samples (max %d)", n, S0_VIEW_MAX_SAMPLES);
+    for (int k = 0; k < 3; ++k) MI355_REQUIRE(P[k] > 0 && Ve[k] >= P[k] && 2 * depth <= P[k], "stage-0 view: axis %d: tile %d, volume %d, shell %d", k, P[k], Ve[k], depth);
+    // what a reader forms in 32 bits: a sample's origin as a voxel index (unsigned), and per lane the element offset of a piece from
+    // its brick's or tile's corner - at most 5 planes + 9 rows + 65 voxels (stride-2 brick), 2 rows + 8 voxels (addend)
+    MI355_REQUIRE((int64_t)n_wv * Ve[0] * Ve[1] * Ve[2] < (1ll << 32) && 8ll * Ve[1] * Ve[2] * C < (1ll << 31),
+                  "stage-0 view: a tensor of %d x %d x %d x %d voxels x %d channels exceeds the 32-bit offsets", n_wv, Ve[0], Ve[1], Ve[2], C);
+    S0View v;
+    for (int i = 0; i < n; ++i) {
+        MI355_REQUIRE(smp[i].wv >= 0 && smp[i].wv < n_wv, "stage-0 view: sample %d: whole-volume index %d of %d", i, smp[i].wv, n_wv);
+        for (int k = 0; k < 3; ++k)
+            MI355_REQUIRE(smp[i].org[k] >= 0 && smp[i].org[k] + P[k] <= Ve[k], "stage-0 view: sample %d leaves its tensor on axis %d (%d + %d > %d)", i, k, smp[i].org[k], P[k], Ve[k]);
+        v.smp[i].off = (unsigned)((((int64_t)smp[i].wv * Ve[0] + smp[i].org[0]) * Ve[1] + smp[i].org[1]) * Ve[2] + smp[i].org[2]);
+        v.smp[i].faces = 0;
+        for (int f = 0; f < 6; ++f) v.smp[i].faces |= smp[i].slab[f] >= 0 ? 1u << f : 0u;
+    }
+    for (int i = n; i < S0_VIEW_MAX_SAMPLES; ++i) v.smp[i] = v.smp[0];  // (never indexed; a defined value all the same)
+    v.src = src; v.sy = Ve[2]; v.sz = Ve[1] * Ve[2]; v.depth = depth;
+    *out = v;
     return MI355_OK;
 }
 

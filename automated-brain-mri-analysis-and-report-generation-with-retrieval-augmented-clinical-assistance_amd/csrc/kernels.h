@@ -37,6 +37,24 @@ int conv_weights_upload(const float *w_host, const float *bias_host, int cin, in
                         int stride, bool keep_plain, ConvWeights *out);
 void conv_weights_free(ConvWeights *w);
 
+// A per-sample view into a whole-volume tensor of the shared stage 0 (unet.hip "stage-0 views"): the tile tensor [N][D][H][W][C] a
+// conv reads is written only inside the shells - within `depth` voxels of a tile face whose bit is set - and every other voxel of
+// sample n is read in place from `src` at smp[n].off + (z * sz + y * sy + x) voxels.  Voxel (z, y, x) of sample n comes from the tile
+// tensor iff z < depth with face bit 0, z >= D - depth with bit 1, the same for y (bits 2, 3) and x (bits 4, 5); the reader's
+// out-of-tile test comes first, so halo pieces beyond a tile face stay zero although the view has neighbours there.
+// Passed by value inside the kernel arguments.  Built by stage0_view_make (below), which refuses a view that leaves its tensor.
+constexpr int S0_VIEW_MAX_SAMPLES = 64;  // = S0_MAX_SAMPLES
+struct S0ViewSample {
+    unsigned off;    // voxel index of the tile's origin in src: (wv * Ve0 + org0) * Ve1 * Ve2 + org1 * Ve2 + org2
+    unsigned faces;  // bit f = face f (z lo, z hi, y lo, y hi, x lo, x hi) lies inside the volume: its shell comes from the tile tensor
+};
+struct S0View {
+    const float *src = nullptr;  // [n_wv][Ve0][Ve1][Ve2][C], C = the reader's channel count; null = no view
+    int sy = 0, sz = 0;          // row and plane strides in voxels: Ve2, Ve1 * Ve2
+    int depth = 0;               // shell depth
+    S0ViewSample smp[S0_VIEW_MAX_SAMPLES];
+};
+
 // One 3x3x3 conv call; T = the element type of the activations (ConvCall = fp32 NDHWC, ConvCallH = fp16 channel-blocked).
 template <typename T>
 struct ConvCallT {
@@ -61,10 +79,17 @@ struct ConvCallT {
     // [N,Do,Ho,Wo,Cout] added to the conv sum in front of bias and activation: out = act(bias + conv(in) + addend).  The shared
     // skip half of a split concat conv (unet.hip "shared skip half"); conv3_f32_wino3_kernel<3, false> only (the plain epilogue's twin), refused elsewhere.
     const T *addend = nullptr;
+    // Stage-0 views (fp32): in0 / addend hold their shells only, the rest is read through the view.  The planner never looks at
+    // them - a view must not change which kernel runs -; the launcher refuses a view on a kernel that cannot read through one
+    // (in0_view: conv3_f32_s2dma_kernel_view, C1 == 0; addend_view: conv3_f32_wino3_kernel<3, false>).
+    const S0View *in0_view = nullptr, *addend_view = nullptr;
 };
 typedef ConvCallT<float> ConvCall;
 typedef ConvCallT<_Float16> ConvCallH;
 int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, const char **kernel_name = nullptr);
+// conv3_f32_s2dma_kernel (or, with c.in0_view, its view instantiation) whatever the planner would pick; `force`: also below the
+// fill-the-chip rule.  Test aid of the stage-0 views.
+int conv3d_s2dma_f32(const ConvWeights &w, const ConvCall &c, bool force, hipStream_t s, const char **kernel_name = nullptr);
 // F(2x2x2, 3x3x3) kernel (conv3d_wino3.hip)
 void pack_conv_weights_wino3(const float *w, int cin, int cin_pad, int cout, std::vector<float> &out);
 bool conv3d_wino3_enabled();
@@ -159,6 +184,17 @@ struct S0GatherArgs {
 };
 // fp32 NDHWC, 16 bytes per lane.  Where the shells of two or three faces meet the first face in the order above wins.
 int stage0_gather(const S0GatherArgs &a, int n_samples, hipStream_t s);
+// The same for a tensor whose reader takes a stage-0 view (S0View): only the voxels within r of a face that has a slab are written,
+// from the sources and with the precedence of stage0_gather; the rest of the tile tensor is left as it is.  which = 0: the first
+// tensor of `a` (out, depth r), 1: the second (out2, depth r2).
+int stage0_gather_shells(const S0GatherArgs &a, int n_samples, int which, hipStream_t s);
+// voxels of a P0 x P1 x P2 tile within r of a face f with faces[f] >= 0 (host; what stage0_gather_shells writes per sample)
+int64_t stage0_shell_voxels(const int P[3], int r, const int faces[6]);
+// The view of n samples (wv, org and faces as in S0Sample: slab[f] >= 0 sets face bit f) of P0 x P1 x P2 voxels into src
+// [n_wv][Ve0][Ve1][Ve2][C], shell depth `depth`.  Pure host code.  Refused (MI355_ERR_INVALID, *out left without a source): a
+// sample that leaves its tensor (wv >= n_wv, org + P > Ve), a shell deeper than half a tile, more than S0_VIEW_MAX_SAMPLES
+// samples, or a tensor so large that an offset a kernel forms in 32 bits would not fit (n_wv * Ve0 * Ve1 * Ve2 * C >= 2^31).
+int stage0_view_make(const float *src, int n_wv, const int Ve[3], const int P[3], int C, int depth, const S0Sample *smp, int n, S0View *out);
 // x [N][Ve0][Ve1][Ve2][C] fp32: zero every voxel outside [0, Zp) (C % 4 == 0)
 int stage0_mask(float *x, int N, const int Ve[3], const int Zp[3], int C, hipStream_t s);
 // plain NDHWC <-> channel-blocked [N][C / 8][V][8] fp16 (common.h)

@@ -374,11 +374,13 @@ static ConvCallT<T> make_call(const void *x0, int cin, int N, int Di, int Hi, in
 static int run_block(mi355_unet *net, const Plan &pl, const ConvLayer &L, const void *in0, int C0,
                      const void *in1, int C1, int N, int Di, int Hi, int Wi, void *out, hipStream_t s,
                      float *head_logits_out = nullptr, bool defer_norm = false, bool in_norm = false,
-                     const ConvWeights *half = nullptr, const float *addend = nullptr, const char *half_name = "") {
+                     const ConvWeights *half = nullptr, const float *addend = nullptr, const char *half_name = "",
+                     const S0View *in0_view = nullptr, const S0View *addend_view = nullptr) {
     // `half` (fp32, shared skip half): the launch runs with these weights instead of L's - one half of L's input channels, C0 + C1
     // of them - and `addend` [N][Vo][cout] is added in front of bias and activation; reported under the kernel's name + half_name
     const bool f16 = net->dtype == MI355_F16;
     MI355_REQUIRE(!half || (!f16 && !L.is_stem && !L.runtime_norm && !L.post_affine && half->cin == C0 + C1), "conv %d->%d: bad half launch", L.cin, L.cout);
+    MI355_REQUIRE((!in0_view && !addend_view) || (!f16 && !L.is_stem), "conv %d->%d: a stage-0 view on a launch that cannot take one", L.cin, L.cout);
     double *stats = (double *)(pl.arena + pl.stats_off);
     float *scale = (float *)(pl.arena + (defer_norm ? pl.scale2_off : pl.scale_off)), *shift = (float *)(pl.arena + (defer_norm ? pl.shift2_off : pl.shift_off));
     int act = ACT_LRELU;
@@ -414,6 +416,7 @@ static int run_block(mi355_unet *net, const Plan &pl, const ConvLayer &L, const 
         } else {
             ConvCall c = make_call<float>(in0, C0 + C1, N, Di, Hi, Wi, out, stats_arg, half && !addend ? ACT_NONE : act, net->slope, f);
             c.addend = addend;
+            c.in0_view = in0_view; c.addend_view = addend_view;  // (stage-0 views: the caller asked the planner first)
             const ConvWeights &W = half ? *half : L.w;
             ProfScope ps(net, s, "conv3_direct_kernel", flops, bytes);  // (renamed to the instantiation the MFMA dispatch picks)
             if (W.wp_dev) MI355_TRY(conv3d_mfma_f32(W, c, s, &kname));
@@ -463,9 +466,12 @@ static bool can_defer_norm(const mi355_unet *net, const ConvLayer &L, const Conv
 // after_enc0 (shared stage 0): the level-0 features are already where enc[0]'s last block writes them; the pass starts at level 1.
 // skip_half (shared skip half): [N][V][cout] = the skip half of the last decoder stage's first conv, already gathered into the
 // level-0 buffer that stage leaves free; that block then runs over the upsampled tensor alone and adds it in its epilogue.
+// enc0_view / skip_half_view (stage-0 views): the level-0 features / the skip half hold their shells only; their one reader - the
+// first block of level 1 / that epilogue - takes the rest through the view.
 static int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W, const void **feat,
                             int *feat_c, hipStream_t s, bool *is_logits = nullptr, float *logits_target = nullptr,
-                            FeatNorm *head_norm = nullptr, bool after_enc0 = false, const float *skip_half = nullptr) {
+                            FeatNorm *head_norm = nullptr, bool after_enc0 = false, const float *skip_half = nullptr,
+                            const S0View *enc0_view = nullptr, const S0View *skip_half_view = nullptr) {
     const int np = net->num_pool;
     const bool f16 = net->dtype == MI355_F16;
     auto buf = [&](int k, int l) { return (void *)(pl.arena + pl.off[k][l]); };
@@ -484,12 +490,14 @@ static int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H
             if (L.stride == 2) { inD = Di * 2; inH = Hi * 2; inW = Wi * 2; }
             void *out = buf((int)(i & 1), l);
             const bool defer = i + 1 < net->enc[l].size() && can_defer_norm(net, L, net->enc[l][i + 1], N, Di, Hi, Wi);
-            MI355_TRY(run_block(net, pl, L, cur, curC, nullptr, 0, N, inD, inH, inW, out, s, nullptr, defer, pending));
+            const S0View *view = (l == 1 && i == 0 && after_enc0) ? enc0_view : nullptr;
+            MI355_TRY(run_block(net, pl, L, cur, curC, nullptr, 0, N, inD, inH, inW, out, s, nullptr, defer, pending, nullptr, nullptr, "", view));
             pending = defer;
             cur = out; curC = L.cout;
         }
         if (l < np) { skip[l] = cur; skipC[l] = curC; }
     }
+    MI355_REQUIRE(!enc0_view || (skip_half && np >= 1), "stage-0 view of the level-0 features while the decoder reads them whole");
     // decoder
     for (int u = 0; u < np; ++u) {
         const int l = np - 1 - u;
@@ -529,7 +537,7 @@ static int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H
             }
             if (skip_half && u == np - 1 && i == 0) {
                 MI355_REQUIRE(L.split_c0 == C0 && (const void *)skip_half == freeAB, "shared skip half: the block was not split at %d channels", C0);
-                MI355_TRY(run_block(net, pl, L, in0, C0, nullptr, 0, N, Dl, Hl, Wl, out, s, nullptr, false, false, &L.w_up, skip_half, " up-half"));
+                MI355_TRY(run_block(net, pl, L, in0, C0, nullptr, 0, N, Dl, Hl, Wl, out, s, nullptr, false, false, &L.w_up, skip_half, " up-half", nullptr, skip_half_view));
                 in0 = out; C0 = L.cout; in1 = nullptr; C1 = 0;
                 continue;
             }
@@ -840,9 +848,43 @@ static int stage0_whole(mi355_unet *net, const Plan &pl, const float *vol, int Z
     return stage0_run(net, pl, vol, Z, Y, X, g, boxes, sg.Ve, extended ? g.Zp : nullptr, 0, pl.s0.wv_in, pl.s0.wv_tmp, pl.s0.wv_out, pl.s0.wv_skip, s);
 }
 
-// the slabs of one batch of samples (indices into sg.smp), then the gather of the batch's tile tensor
+// ---- stage-0 views (MI355_STAGE0_VIEWS).  The gather above copies, per tile, mostly values that already lie in the whole-volume
+// tensors: a tile's copy differs from them only inside the shells.  Each of the two tile tensors has one reader - the level-0
+// features the first stride-2 conv (enc[1][0]), the skip half S the addend epilogue of the up-half launch -, so where that reader
+// can take a per-sample view (kernels.h S0View) it reads the whole-volume tensor in place and only shell voxels from the tile
+// tensor, and the gather writes the shells alone (stage0_gather_shells).  The tile tensors stay where they are, with their dense
+// strides; outside the shells they then hold stale values nobody reads.
+// Views change where bytes are read, never which kernel runs or in which order anything is summed: results are bit-identical, and
+// unlike stage0_plan this decision may depend on the batch.  Per tensor and per forward:
+//   * the level-0 features: the shared skip half is on (otherwise the concat conv reads them whole, as in1), and the planner - asked
+//     first, for exactly this call - sends enc[1][0] to conv3_f32_s2dma_kernel; the launch then runs conv3_f32_s2dma_kernel_view;
+//   * S: the shared skip half is on (its reader is then always conv3_f32_wino3_kernel<3, false>).
+// A view that cannot be built (stage0_view_make: offsets beyond 32 bits) falls back to the full gather for that tensor.
+struct S0ViewChoice { bool enc0 = false, half = false; };
+// w1: the weights (or, for a dry run, the pack layout with stand-in pointers) of the first block of level 1, null = none that
+// qualifies; c0 its input channels; w1_stats: it carries run-time statistics
+static S0ViewChoice stage0_views_choose(const S0Geom &sg, bool share_skip, int n_samples, const int P[3], const ConvWeights *w1, int c0, bool w1_stats) {
+    S0ViewChoice v;
+    if (!env_switch("MI355_STAGE0_VIEWS") || !sg.shared || !share_skip || n_samples < 1 || n_samples > S0_VIEW_MAX_SAMPLES) return v;
+    v.half = true;
+    if (!w1 || !w1->wp_dev || w1->stride != 2) return v;
+    static float stand_in[2];
+    ConvCall c = make_call<float>(stand_in, c0, n_samples, P[0], P[1], P[2], stand_in, w1_stats ? (double *)stand_in : nullptr, ACT_LRELU, 0.01f);
+    ConvPlan p;
+    v.enc0 = plan_conv_f32(*w1, c, &p) == MI355_OK && p.family == FAM_S2DMA;
+    return v;
+}
+static S0ViewChoice stage0_views_decide(const mi355_unet &net, const S0Geom &sg, bool share_skip, int n_samples, const int P[3]) {
+    if (net.dtype != MI355_F32 || net.num_pool < 1 || net.enc[1].empty()) return S0ViewChoice();
+    const ConvLayer &L = net.enc[1][0];
+    return stage0_views_choose(sg, share_skip, n_samples, P, L.is_stem ? nullptr : &L.w, net.enc[0].back().cout, L.runtime_norm);
+}
+
+// the slabs of one batch of samples (indices into sg.smp), then the gather of the batch's tile tensor.  want: which tensors'
+// readers will take a view; *enc0_view / *half_view receive the views that were built (src = null: none, the tensor is dense).
 static int stage0_tiles(mi355_unet *net, const Plan &pl, const float *vol, int Z, int Y, int X, const SwGeom &g, const S0Geom &sg,
-                        const std::vector<int> &samples, hipStream_t s) {
+                        const std::vector<int> &samples, hipStream_t s, S0ViewChoice want = S0ViewChoice(), S0View *enc0_view = nullptr,
+                        S0View *half_view = nullptr) {
     const int n = (int)samples.size();
     MI355_REQUIRE(n <= S0_MAX_SAMPLES, "shared stage 0: %d samples per forward (max %d)", n, S0_MAX_SAMPLES);
     const int C = net->enc[0].back().cout;
@@ -881,14 +923,46 @@ static int stage0_tiles(mi355_unet *net, const Plan &pl, const float *vol, int Z
     } else
         for (int a = 0; a < 3; ++a) ga.slab2[a] = nullptr;
     const double pv = (double)n * g.P[0] * g.P[1] * g.P[2];
-    ProfScope ps(net, s, "stage0_gather_kernel", 0.0, 2.0 * pv * (C + C2) * 4.0);
-    return stage0_gather(ga, n, s);
+    // stage-0 views: a view that cannot be built leaves its tensor to the full gather
+    const int n_wv = (int)g.mirrors.size();
+    bool v0 = want.enc0 && enc0_view && stage0_view_make(ga.wv, n_wv, ga.Ve, ga.P, C, ga.r, ga.smp, n, enc0_view) == MI355_OK;
+    bool v1 = want.half && half_view && C2 && stage0_view_make(ga.wv2, n_wv, ga.Ve, ga.P, C2, ga.r2, ga.smp, n, half_view) == MI355_OK;
+    double shell0 = 0.0, shell1 = 0.0;
+    for (int i = 0; i < n; ++i) {
+        shell0 += (double)stage0_shell_voxels(ga.P, ga.r, ga.smp[i].slab);
+        if (C2) shell1 += (double)stage0_shell_voxels(ga.P, ga.r2, ga.smp[i].slab);
+    }
+    // (one profile entry, as before; its bytes are what is moved: read + written)
+    ProfScope ps(net, s, "stage0_gather_kernel", 0.0, 2.0 * 4.0 * ((v0 ? shell0 : pv) * C + (v1 ? shell1 : pv) * C2));
+    if (!v0 && !v1) return stage0_gather(ga, n, s);
+    if (v0) MI355_TRY(stage0_gather_shells(ga, n, 0, s));
+    else {  // the level-0 features whole, alone
+        S0GatherArgs g0 = ga;
+        g0.out2 = nullptr; g0.wv2 = nullptr;
+        MI355_TRY(stage0_gather(g0, n, s));
+    }
+    if (!C2) return MI355_OK;
+    if (v1) return stage0_gather_shells(ga, n, 1, s);
+    S0GatherArgs g1 = ga;  // S whole, alone: as the first tensor of a gather
+    g1.wv = ga.wv2; g1.out = ga.out2; g1.r = ga.r2; g1.C4 = ga.C42;
+    for (int a = 0; a < 3; ++a) g1.slab[a] = ga.slab2[a];
+    g1.out2 = nullptr; g1.wv2 = nullptr;
+    return stage0_gather(g1, n, s);
 }
 
 // Evaluates the tiles with (index % world) == rank of one net; adds into agg (and cnt if non-null,
 // for ALL tiles so that every rank holds the full normaliser).
 // `first_item`: index of this net's tile 0 in the caller's work list (fold f of a fold list: f * tiles): the work items
 // (fold, tile) are dealt round-robin over the ranks as ONE list, so 5 folds x 8 tiles on 3 ranks still balance.
+// tiles per forward (each with its nm mirrors): 16 samples (fp32) / 32 (fp16: half the bytes per sample; config 3 fp16 297 -> 293 ms
+// per volume with 32, the deep levels' launches fill the chip better), 64 at the most - the arena is sized for 288 GB of HBM, not
+// for a few GB.  One helper for sw_accumulate and the dry run mi355_stage0_view_plan, so that the two cannot drift.
+static int sw_batch_tiles(int dtype, int batch_tiles, int nm) {
+    int bt = batch_tiles > 0 ? batch_tiles : std::max(1, (dtype == MI355_F16 ? 32 : 16) / nm);
+    if (bt * nm > 64) bt = std::max(1, 64 / nm);
+    return bt;
+}
+
 static int sw_accumulate(mi355_unet *net, const float *vol, int Z, int Y, int X, const mi355_sw_opts &o,
                          const SwGeom &g, int rank, int world, float *agg, float *cnt, hipStream_t s, long first_item = 0) {
     const int nm = (int)g.mirrors.size();
@@ -896,10 +970,7 @@ static int sw_accumulate(mi355_unet *net, const float *vol, int Z, int Y, int X,
     if (use_gauss) MI355_TRY(ensure_gaussian(net, g.P));
     std::vector<int> mine;
     for (size_t t = 0; t < g.tiles.size(); ++t) if ((int)((first_item + (long)t) % world) == rank) mine.push_back((int)t);
-    // samples per forward: 16 (fp32) / 32 (fp16: half the bytes per sample; config 3 fp16 297 -> 293 ms per volume with 32, the
-    // deep levels' launches fill the chip better) - the arena is sized for 288 GB of HBM, not for a few GB
-    int bt = o.batch_tiles > 0 ? o.batch_tiles : std::max(1, (net->dtype == MI355_F16 ? 32 : 16) / nm);
-    if (bt * nm > 64) bt = std::max(1, 64 / nm);
+    const int bt = sw_batch_tiles(net->dtype, o.batch_tiles, nm);
     MI355_REQUIRE(nm <= 64, "too many mirrors");
     Plan pl;
     MI355_TRY(make_plan(*net, bt * nm, g.P[0], g.P[1], g.P[2], &pl));
@@ -921,8 +992,10 @@ static int sw_accumulate(mi355_unet *net, const float *vol, int Z, int Y, int X,
                 samples.push_back(td);
                 sample_ids.push_back(mine[b0 + i] * nm + m);
             }
+        S0View enc0_view, half_view;
         if (sg.shared) {
-            MI355_TRY(stage0_tiles(net, pl, vol, Z, Y, X, g, sg, sample_ids, s));
+            const S0ViewChoice want = stage0_views_decide(*net, sg, share_skip, (int)samples.size(), g.P);
+            MI355_TRY(stage0_tiles(net, pl, vol, Z, Y, X, g, sg, sample_ids, s, want, &enc0_view, &half_view));
         } else {
         const double pv = (double)samples.size() * g.P[0] * g.P[1] * g.P[2];
         ProfScope ps(net, s, "extract_tiles_kernel", 0.0, pv * (4.0 * net->in_channels + (net->dtype == MI355_F16 ? 2.0 : 4.0) * net->cin_pad));
@@ -933,7 +1006,8 @@ static int sw_accumulate(mi355_unet *net, const float *vol, int Z, int Y, int X,
         const void *feat; int fc; bool is_logits = false;
         FeatNorm head_norm;
         MI355_TRY(forward_features(net, pl, (int)samples.size(), g.P[0], g.P[1], g.P[2], &feat, &fc, s, &is_logits, nullptr, &head_norm, sg.shared,
-                                   share_skip ? (const float *)(pl.arena + pl.off[((net->enc[0].size() - 1) & 1) ^ 1][0]) : nullptr));
+                                   share_skip ? (const float *)(pl.arena + pl.off[((net->enc[0].size() - 1) & 1) ^ 1][0]) : nullptr,
+                                   enc0_view.src ? &enc0_view : nullptr, half_view.src ? &half_view : nullptr));
         MI355_REQUIRE(is_logits || fc == net->head.cin, "head expects %d channels, decoder gives %d", net->head.cin, fc);
         for (int i = 0; i < nb; ++i) {
             const TileDesc &td = g.tiles[mine[b0 + i]];
@@ -1524,6 +1598,112 @@ extern "C" int mi355_conv3d_wino3_ndhwc(const float *x0_dev, const float *x1_dev
     return synced(launch_wino3(cw.w, c, p, s), s, "conv");
 }
 
+// ---- stage-0 views: dry run and single-op entries
+extern "C" int mi355_stage0_view_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes,
+                                      const mi355_skip_share_net *nd, int c_level1, int batch_samples, mi355_stage0_view_geom *out,
+                                      mi355_stage0_view_sample *samples, int max_samples) {
+    MI355_REQUIRE(out && patch && nd && c_level1 > 0 && batch_samples >= 0 && (samples || max_samples == 0), "mi355_stage0_view_plan: bad argument");
+    mi355_sw_opts o;
+    memset(&o, 0, sizeof(o));
+    for (int a = 0; a < 3; ++a) o.patch[a] = patch[a];
+    o.step_size = step_size; o.mirror_axes = mirror_axes;
+    SwGeom g;
+    MI355_TRY(make_geom(o, z, y, x, &g));
+    const bool folded = nd->norm == MI355_NORM_NONE || (nd->norm == MI355_NORM_BATCH && !nd->nonlin_first);
+    const int r0 = (nd->dtype == MI355_F32 && folded && nd->c_skip % 4 == 0) ? nd->enc0_blocks : 0;
+    SkipShareNet d = skip_share_net_of(nd->dtype, r0, nd->stride, nd->norm, nd->nonlin_first, nd->c_up, nd->c_skip, nd->cout, nd->head_ncls);
+    d.skip_is_enc0 = nd->skip_is_enc0 != 0;
+    const bool on = skip_share_decide(d, g);
+    S0Geom sg;
+    stage0_geometry(g, d.r, &sg, on ? 1 : 0);
+    // the first block of level 1 as the network would hold it: c_skip -> c_level1, stride 2
+    static float stand_in[2];
+    ConvPackLayout l;
+    ConvWeights cw;
+    const bool have_w1 = nd->dtype == MI355_F32 && conv_pack_layout(nd->c_skip, nd->c_skip, c_level1, 2, &l) == MI355_OK && l.mfma;
+    if (have_w1) {
+        cw.cin = cw.cin_pad = nd->c_skip; cw.cout = c_level1; cw.stride = 2;
+        cw.cc = l.cc; cw.nf = l.nf; cw.pipe = l.pipe;
+        cw.bias_dev = cw.wp_dev = stand_in;
+    }
+    const int nm = (int)g.mirrors.size();
+    // a full batch of one rank; a short last batch, or the tiles one rank of several gets, is asked for with batch_samples
+    const int per_forward = batch_samples > 0 ? batch_samples : sw_batch_tiles(nd->dtype, 0, nm) * nm;
+    const S0ViewChoice v = stage0_views_choose(sg, on, std::min(per_forward, (int)g.tiles.size() * nm), g.P, have_w1 ? &cw : nullptr, nd->c_skip, !folded);
+    memset(out, 0, sizeof(*out));
+    out->enc0_viewed = v.enc0; out->half_viewed = v.half;
+    out->depth[0] = sg.r; out->depth[1] = on ? sg.rs : 0;
+    out->n_tiles = (int32_t)g.tiles.size(); out->n_mirrors = nm;
+    for (int a = 0; a < 3; ++a) out->volume[a] = sg.Ve[a];
+    const int n = sg.shared ? (int)sg.smp.size() : 0;
+    for (int i = 0; i < n && i < max_samples; ++i) {
+        const S0Sample &sm = sg.smp[i];
+        mi355_stage0_view_sample &q = samples[i];
+        memset(&q, 0, sizeof(q));
+        q.offset = (((int64_t)sm.wv * sg.Ve[0] + sm.org[0]) * sg.Ve[1] + sm.org[1]) * sg.Ve[2] + sm.org[2];
+        for (int f = 0; f < 6; ++f) q.faces |= sm.slab[f] >= 0 ? 1 << f : 0;
+        q.shell_voxels[0] = stage0_shell_voxels(g.P, sg.r, sm.slab);
+        q.shell_voxels[1] = on ? stage0_shell_voxels(g.P, sg.rs, sm.slab) : 0;
+    }
+    return n;
+}
+
+// the C-ABI description of a view -> S0View (refused where stage0_view_make refuses)
+static int view_from_abi(const mi355_stage0_view *v, int n, int d, int h, int w, int c, S0View *out) {
+    MI355_REQUIRE(v->src_dev && v->n_samples == n, "stage-0 view: %d samples for a call of %d", v->n_samples, n);
+    MI355_REQUIRE(n > 0 && n <= S0_VIEW_MAX_SAMPLES, "stage-0 view: %d samples (max %d)", n, S0_VIEW_MAX_SAMPLES);
+    std::vector<S0Sample> smp(n);
+    for (int i = 0; i < n; ++i) {
+        smp[i].wv = v->samples[i].wv;
+        for (int k = 0; k < 3; ++k) smp[i].org[k] = v->samples[i].origin[k];
+        for (int f = 0; f < 6; ++f) smp[i].slab[f] = (v->samples[i].faces >> f) & 1 ? 0 : -1;
+    }
+    const int Ve[3] = {v->volume[0], v->volume[1], v->volume[2]}, P[3] = {d, h, w};
+    return stage0_view_make(v->src_dev, v->n_wv, Ve, P, c, v->depth, smp.data(), n, out);
+}
+
+extern "C" int mi355_conv3d_s2dma_view_ndhwc(const float *x_dev, const mi355_stage0_view *view, int n, int d, int h, int w, int cin,
+                                             const float *weight_host, const float *bias_host, int cout, int act, float slope, int force,
+                                             float *y_dev, void *stream) {
+    MI355_REQUIRE(x_dev && y_dev && weight_host && cin > 0 && cout > 0, "mi355_conv3d_s2dma_view_ndhwc: bad argument");
+    MI355_REQUIRE(act != ACT_LRELU || (slope >= 0.f && slope <= 1.f), "LeakyReLU slope %g outside [0, 1]", (double)slope);
+    S0View sv;
+    if (view) MI355_TRY(view_from_abi(view, n, d, h, w, cin, &sv));  // (before anything touches the device: a bad view launches nothing)
+    MI355_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    TmpWeights<ConvWeights, conv_weights_free> cw;
+    MI355_TRY(conv_weights_upload(weight_host, bias_host, cin, cin, cout, 2, false, &cw.w));
+    ConvCall c = make_call<float>(x_dev, cin, n, d, h, w, y_dev, nullptr, act, slope);
+    if (view) c.in0_view = &sv;
+    const char *kname = nullptr;
+    const int rc = conv3d_s2dma_f32(cw.w, c, force != 0, s, &kname);
+    g_last_conv_kernel = kname ? kname : "";
+    return synced(rc, s, "conv");
+}
+
+extern "C" int mi355_conv3d_wino3_view_ndhwc(const float *x0_dev, int n, int d, int h, int w, int c0, const float *weight_host,
+                                             const float *bias_host, int cout, int act, float slope, const float *addend_dev,
+                                             const mi355_stage0_view *view, float *y_dev, void *stream) {
+    MI355_REQUIRE(x0_dev && y_dev && weight_host && addend_dev && c0 > 0 && cout > 0, "mi355_conv3d_wino3_view_ndhwc: bad argument");
+    MI355_REQUIRE(act != ACT_LRELU || (slope >= 0.f && slope <= 1.f), "LeakyReLU slope %g outside [0, 1]", (double)slope);
+    S0View sv;
+    if (view) MI355_TRY(view_from_abi(view, n, d, h, w, cout, &sv));
+    MI355_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    TmpWeights<ConvWeights, conv_weights_free> cw;
+    MI355_TRY(conv_weights_upload(weight_host, bias_host, c0, c0, cout, 1, false, &cw.w));
+    ConvCall c = make_call<float>(x0_dev, c0, n, d, h, w, y_dev, nullptr, act, slope);
+    c.addend = addend_dev;
+    if (view) c.addend_view = &sv;
+    ConvPlan p;
+    if (!plan_wino3(cw.w, c, &p, true)) {
+        set_error("mi355_conv3d_wino3_view_ndhwc: %dx%dx%dx%d, %d -> %d is not a call of the F(2x2x2,3x3x3) kernel", n, d, h, w, c0, cout);
+        return MI355_ERR_UNSUPPORTED;
+    }
+    g_last_conv_kernel = p.name;
+    return synced(launch_wino3(cw.w, c, p, s), s, "conv");
+}
+
 extern "C" int mi355_tconv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
                                        int cout, void *y_dev, void *stream) {
     MI355_TRY(require_device());
@@ -1643,7 +1823,7 @@ extern "C" int mi355_cnt_add_tile(const float *gauss_dev, const int32_t patch[3]
                   "cnt_add_tile");
 }
 
-extern "C" int mi355_stage0_gather(const mi355_stage0_gather_args *a, void *stream) {
+static int stage0_gather_abi(const mi355_stage0_gather_args *a, void *stream, bool shells_only) {
     MI355_REQUIRE(a && a->wv_dev && a->out_dev && a->channels > 0 && a->channels % 4 == 0, "mi355_stage0_gather: bad argument");
     MI355_REQUIRE(a->n_samples > 0 && a->n_samples <= S0_MAX_SAMPLES, "mi355_stage0_gather: %d samples (max %d)", a->n_samples, S0_MAX_SAMPLES);
     MI355_TRY(require_device());
@@ -1663,8 +1843,11 @@ extern "C" int mi355_stage0_gather(const mi355_stage0_gather_args *a, void *stre
         }
     }
     hipStream_t s = (hipStream_t)stream;
+    if (shells_only) return synced(stage0_gather_shells(ga, a->n_samples, 0, s), s, "stage0_gather_shells");
     return synced(stage0_gather(ga, a->n_samples, s), s, "stage0_gather");
 }
+extern "C" int mi355_stage0_gather(const mi355_stage0_gather_args *a, void *stream) { return stage0_gather_abi(a, stream, false); }
+extern "C" int mi355_stage0_gather_shells(const mi355_stage0_gather_args *a, void *stream) { return stage0_gather_abi(a, stream, true); }
 
 extern "C" int mi355_stage0_mask(float *x_dev, int n, const int32_t volume[3], const int32_t keep[3], int c, void *stream) {
     MI355_REQUIRE(x_dev && volume && keep, "mi355_stage0_mask: bad argument");

@@ -320,6 +320,92 @@ def conv3d_wino3_ndhwc(x0, weight, bias=None, x1=None, addend=None, act=0, slope
     return y
 
 
+def stage0_view_plan(volume, patch, step_size=0.5, mirror_axes=(), dtype="f32", norm="batch", nonlin_first=False, enc0_blocks=2,
+                     stride=1, skip_is_enc0=True, c_up=32, c_skip=32, cout=32, head_ncls=0, c_level1=64, batch_samples=0):
+    """Dry run of the stage-0 views (``mi355_stage0_view_plan``; no GPU needed) for a volume (Z, Y, X), a patch, the mirror axes and
+    a description of the network (defaults: model A; ``c_level1`` = output channels of the first stride-2 conv, ``batch_samples`` =
+    (tile, mirror) samples per forward, 0 = the default).  Returns a dict: enc0_viewed, half_viewed (which tile tensor is read
+    through a view), depth (shell depths of the two), n_tiles, n_mirrors, volume and samples - one dict per (tile, mirror), tile-major
+    as ``stage0_plan`` lists them: offset (voxel index of the tile's origin in the whole-volume tensor), faces (six flags) and
+    shell_voxels (what the gather still writes, per tensor)."""
+    nd = _lib.SkipShareNet({"f32": 0, "f16": 1}[dtype], {"none": 0, "batch": 1, "instance": 2, "group": 3}[norm], int(bool(nonlin_first)),
+                           int(enc0_blocks), int(stride), int(bool(skip_is_enc0)), int(c_up), int(c_skip), int(cout), int(head_ncls))
+    lib = _lib.load()
+    g = _lib.Stage0ViewGeom()
+    z, y, x = (int(v) for v in volume)
+    mask = sum(1 << int(a) for a in mirror_axes)
+    args = (z, y, x, _i3(patch), float(step_size), mask, C.byref(nd), int(c_level1), int(batch_samples), C.byref(g))
+    n = lib.mi355_stage0_view_plan(*args, None, 0)
+    _lib.check(n, "mi355_stage0_view_plan")
+    buf = (_lib.Stage0ViewSample * max(n, 1))()
+    _lib.check(lib.mi355_stage0_view_plan(*args, buf, n), "mi355_stage0_view_plan")
+    samples = [{"offset": int(buf[i].offset), "faces": tuple(buf[i].faces >> f & 1 for f in range(6)),
+                "shell_voxels": tuple(int(v) for v in buf[i].shell_voxels)} for i in range(n)]
+    return {"enc0_viewed": bool(g.enc0_viewed), "half_viewed": bool(g.half_viewed), "depth": tuple(g.depth), "n_tiles": int(g.n_tiles),
+            "n_mirrors": int(g.n_mirrors), "volume": tuple(g.volume), "samples": samples}
+
+
+def _stage0_view(src, samples, depth):
+    """src: CUDA fp32 [n_wv, Ve0, Ve1, Ve2, C]; samples: dicts {wv, origin, faces: six flags} -> (Stage0View, keep-alive)"""
+    import torch
+    src = _require_cuda(src, torch.float32, "view source")
+    if src.dim() != 5 or len(samples) > 64:
+        raise ValueError("stage-0 view: source must be [n_wv, Ve0, Ve1, Ve2, C], at most 64 samples")
+    v = _lib.Stage0View()
+    v.src_dev, v.n_wv, v.depth, v.n_samples = src.data_ptr(), int(src.shape[0]), int(depth), len(samples)
+    for k in range(3):
+        v.volume[k] = int(src.shape[1 + k])
+    for i, sm in enumerate(samples):
+        v.samples[i].wv = int(sm["wv"])
+        for k in range(3):
+            v.samples[i].origin[k] = int(sm["origin"][k])
+        v.samples[i].faces = sum(1 << f for f in range(6) if sm["faces"][f])
+    return v, src
+
+
+def conv3d_s2dma_view_ndhwc(x, weight, bias=None, view=None, act=0, slope=0.01, force=True):
+    """One stride-2 conv on ``conv3_f32_s2dma_kernel`` or, with ``view`` = (src, samples, depth), on its view twin (test entry point,
+    ``mi355_conv3d_s2dma_view_ndhwc``).  x: CUDA fp32 [N,D,H,W,Cin], the dense tile tensor - with a view only its shell voxels are
+    read; src: CUDA fp32 [n_wv,Ve0,Ve1,Ve2,Cin]; samples: one dict {wv, origin, faces} per sample of x; weight: numpy [Cout,Cin,3,3,3]."""
+    import torch
+    x = _require_cuda(x, torch.float32, "x")
+    n, d, h, w, cin = x.shape
+    weight = np.ascontiguousarray(weight, dtype=np.float32)
+    cout = weight.shape[0]
+    b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+    v, keep = (None, None) if view is None else _stage0_view(view[0], view[1], view[2])
+    if keep is not None and keep.shape[4] != cin:
+        raise ValueError("conv3d_s2dma_view_ndhwc: the view's source must have the input's channels")
+    y = torch.full((n, (d - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1, cout), float("nan"), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().mi355_conv3d_s2dma_view_ndhwc(x.data_ptr(), None if v is None else C.byref(v), n, d, h, w, cin, _lib.fptr(weight),
+                                                         _lib.fptr(b), cout, act, slope, int(bool(force)), y.data_ptr(), _stream(x)),
+               "mi355_conv3d_s2dma_view_ndhwc")
+    return y
+
+
+def conv3d_wino3_view_ndhwc(x0, weight, bias, addend, view=None, act=0, slope=0.01):
+    """``conv3d_wino3_ndhwc`` with an addend that is read through ``view`` = (src, samples, depth) (test entry point,
+    ``mi355_conv3d_wino3_view_ndhwc``): addend CUDA fp32 [N,D,H,W,Cout], the dense tile tensor - with a view only its shell voxels
+    are read; src: CUDA fp32 [n_wv,Ve0,Ve1,Ve2,Cout]."""
+    import torch
+    x0 = _require_cuda(x0, torch.float32, "x0")
+    n, d, h, w, c0 = x0.shape
+    weight = np.ascontiguousarray(weight, dtype=np.float32)
+    cout = weight.shape[0]
+    addend = _require_cuda(addend, torch.float32, "addend")
+    if tuple(addend.shape) != (n, d, h, w, cout):
+        raise ValueError("conv3d_wino3_view_ndhwc: addend must be [N,D,H,W,Cout]")
+    b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+    v, keep = (None, None) if view is None else _stage0_view(view[0], view[1], view[2])
+    if keep is not None and keep.shape[4] != cout:
+        raise ValueError("conv3d_wino3_view_ndhwc: the view's source must have the addend's channels")
+    y = torch.full((n, d, h, w, cout), float("nan"), dtype=torch.float32, device=x0.device)
+    _lib.check(_lib.load().mi355_conv3d_wino3_view_ndhwc(x0.data_ptr(), n, d, h, w, c0, _lib.fptr(weight), _lib.fptr(b), cout, act, slope,
+                                                         addend.data_ptr(), None if v is None else C.byref(v), y.data_ptr(), _stream(x0)),
+               "mi355_conv3d_wino3_view_ndhwc")
+    return y
+
+
 def last_conv_kernel() -> str:
     """Kernel instantiation the last ``conv3d_ndhwc`` call of this thread ran on (test aid)."""
     return (_lib.load().mi355_last_conv_kernel() or b"").decode()
@@ -527,10 +613,12 @@ def cnt_add_tile_(cnt, patch, origin, gauss=None):
                "mi355_cnt_add_tile")
 
 
-def stage0_gather(wv, slabs, samples, patch, r):
+def stage0_gather(wv, slabs, samples, patch, r, shells_only=False, out=None):
     """``mi355_stage0_gather``.  wv: CUDA fp32 [mirrors, Ve0, Ve1, Ve2, C]; slabs: per axis a CUDA fp32 [n, S0, S1, S2, C] (S[a] = the
     slab thickness, S[k] = patch[k] otherwise) or None; samples: dicts {wv, origin, slab: six indices or -1}.  Returns
-    [len(samples), P0, P1, P2, C].  Slab and whole-volume indices are checked against the tensors here."""
+    [len(samples), P0, P1, P2, C].  Slab and whole-volume indices are checked against the tensors here.
+    shells_only: ``mi355_stage0_gather_shells`` - only the voxels within r of a face with a slab are written, into ``out`` (CUDA fp32
+    of the result's shape, otherwise left as it is) when given."""
     import torch
     wv = _require_cuda(wv, torch.float32, "wv")
     nwv, c = int(wv.shape[0]), int(wv.shape[4])
@@ -565,9 +653,16 @@ def stage0_gather(wv, slabs, samples, patch, r):
                 raise ValueError(f"stage0_gather: sample {i}: face {f} has no slab {idx}")
             a.samples[i].slab[f] = idx
     a.r, a.channels, a.n_samples = int(r), c, len(samples)
-    out = torch.full((max(len(samples), 1), patch[0], patch[1], patch[2], c), float("nan"), dtype=torch.float32, device=wv.device)
+    shape = (max(len(samples), 1), patch[0], patch[1], patch[2], c)
+    if out is None:
+        out = torch.full(shape, float("nan"), dtype=torch.float32, device=wv.device)
+    elif not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape):
+        raise ValueError(f"stage0_gather: out must be a contiguous CUDA fp32 {shape}")
     a.out_dev = out.data_ptr()
-    _lib.check(_lib.load().mi355_stage0_gather(C.byref(a), _stream(wv)), "mi355_stage0_gather")
+    if shells_only:
+        _lib.check(_lib.load().mi355_stage0_gather_shells(C.byref(a), _stream(wv)), "mi355_stage0_gather_shells")
+    else:
+        _lib.check(_lib.load().mi355_stage0_gather(C.byref(a), _stream(wv)), "mi355_stage0_gather")
     return out
 
 

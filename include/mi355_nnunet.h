@@ -551,6 +551,58 @@ int mi355_skip_share_plan(int z, int y, int x, const int32_t patch[3], float ste
 int mi355_conv3d_wino3_ndhwc(const float *x0_dev, const float *x1_dev, int n, int d, int h, int w, int c0, int c1,
                              const float *weight_host, const float *bias_host, int cout, int act, float slope,
                              const float *addend_dev, float *y_dev, void *stream);
+/* ---- stage-0 views (MI355_STAGE0_VIEWS; csrc/unet.hip "stage-0 views").  With the shared stage 0 and the shared skip half on, the
+ * two tile tensors a forward gathers - the level-0 features and the skip half S - differ from the whole-volume tensors only inside
+ * the shells (within r, for S r + 1, voxels of a tile face that lies inside the volume), and each has one reader: the first
+ * stride-2 conv, the addend epilogue of the up-half launch.  Where the reader can, it reads the whole-volume tensor in place
+ * through a per-sample view and only shell voxels from the tile tensor, and the gather writes the shells alone.  Results are
+ * bit-identical either way. ---- */
+/* Dry run (needs no device and launches nothing; the decision code mi355_sw_predict / mi355_sw_partial[_folds] run).  net as for
+ * mi355_skip_share_plan; c_level1 = output channels of the first block of level 1 (c_skip -> c_level1, stride 2); batch_samples =
+ * (tile, mirror) samples per forward, 0 = a full batch of one rank with batch_tiles = 0 (the same helper sizes the real call's
+ * batches); the real call decides per forward, so a short last batch, or the share of the tiles one rank of several gets, is
+ * asked for with its own sample count.  half_viewed: the shared skip half is on; enc0_viewed: also, a forward
+ * of that many samples sends that block to conv3_f32_s2dma_kernel.  Returns the number of (tile, mirror) samples, tile-major as
+ * mi355_stage0_plan lists them, written to samples[] (at most max_samples; may be NULL), or a negative error code. */
+typedef struct mi355_stage0_view_geom {
+    int32_t enc0_viewed, half_viewed;
+    int32_t depth[2];           /* shell depth of the level-0 features (r) and of S (r + 1, 0 when the skip half is not shared) */
+    int32_t n_tiles, n_mirrors;
+    int32_t volume[3];          /* of one whole-volume result */
+} mi355_stage0_view_geom;
+typedef struct mi355_stage0_view_sample {
+    int64_t offset;             /* of the tile's origin voxel in the whole-volume tensor, in voxels: (mirror index * volume + origin) */
+    int32_t faces;              /* bit f: face f (z lo, z hi, y lo, y hi, x lo, x hi) lies inside the volume */
+    int32_t pad_;
+    int64_t shell_voxels[2];    /* voxels of the tile the gather still writes, per tensor */
+} mi355_stage0_view_sample;
+int mi355_stage0_view_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes,
+                           const mi355_skip_share_net *net, int c_level1, int batch_samples, mi355_stage0_view_geom *out,
+                           mi355_stage0_view_sample *samples, int max_samples);
+/* A view as the single-op entries below take it: sample i of the call is the box at samples[i].origin of volume samples[i].wv of
+ * src_dev [n_wv][volume][channels] (channels = those of the tensor the view stands in for); a voxel within `depth` of a face whose
+ * bit is set in samples[i].faces is read from the dense tensor, every other voxel from src_dev.  Refused (MI355_ERR_INVALID,
+ * nothing is launched): a sample that leaves its tensor, n_samples other than the call's, a shell deeper than half a tile. */
+typedef struct mi355_stage0_view {
+    const float *src_dev;
+    int32_t n_wv, volume[3], depth, n_samples;
+    struct {
+        int32_t wv;
+        int32_t origin[3];
+        int32_t faces;
+    } samples[64];
+} mi355_stage0_view;
+/* One stride-2 conv on conv3_f32_s2dma_kernel - with a view its twin conv3_f32_s2dma_kernel_view - (test aid; force: also below
+ * the size the dispatch sends there): y = act(bias + conv(x)), x_dev [n,d,h,w,cin] the dense tile tensor, cin % 8 == 0,
+ * cout % 64 == 0.  Refused (MI355_ERR_UNSUPPORTED) where the kernel does not take the shape. */
+int mi355_conv3d_s2dma_view_ndhwc(const float *x_dev, const mi355_stage0_view *view, int n, int d, int h, int w, int cin,
+                                  const float *weight_host, const float *bias_host, int cout, int act, float slope, int force,
+                                  float *y_dev, void *stream);
+/* mi355_conv3d_wino3_ndhwc with an addend (conv3_f32_wino3_kernel<3, false>) that is read through a view: addend_dev [n,d,h,w,cout]
+ * the dense tile tensor; view (channels = cout) may be NULL. */
+int mi355_conv3d_wino3_view_ndhwc(const float *x0_dev, int n, int d, int h, int w, int c0, const float *weight_host,
+                                  const float *bias_host, int cout, int act, float slope, const float *addend_dev,
+                                  const mi355_stage0_view *view, float *y_dev, void *stream);
 /* ---- the kernels around the convolutions, one launch each (test aids; no reference counterpart beyond the one named at the
  * kernel in csrc/elementwise.hip).  Each call runs the launcher the network runs and waits for `stream`.  Tensors are taken in
  * the layout the network holds them in: fp32 plain NDHWC ([N][V][C]), fp16 channel-blocked ([N][C / 8][V][8]), AS IS. ---- */
@@ -611,6 +663,9 @@ typedef struct mi355_stage0_gather_args {
     } samples[64];
 } mi355_stage0_gather_args;
 int mi355_stage0_gather(const mi355_stage0_gather_args *args, void *stream);
+/* The same for a tensor whose reader takes a stage-0 view: only the voxels within r of a face with a slab are written (from that
+ * slab, same precedence); every other element of out_dev is left as it is. */
+int mi355_stage0_gather_shells(const mi355_stage0_gather_args *args, void *stream);
 /* x_dev [n][volume][c] fp32: zero every voxel outside [0, keep) (c % 4 == 0, 0 < keep <= volume); the rest is not written. */
 int mi355_stage0_mask(float *x_dev, int n, const int32_t volume[3], const int32_t keep[3], int c, void *stream);
 /* Name of the kernel instantiation the calling thread's last mi355_conv3d_ndhwc / mi355_conv3d_ndhwc_f16 call dispatched
