@@ -27,7 +27,7 @@ EXPORTS = [
     "mi355_profile_read", "mi355_conv3d_ndhwc_f16", "mi355_tconv3d_ndhwc_f16",
     "mi355_label_remap", "mi355_label_confusion", "mi355_cosine_topk", "mi355_crop_mask", "mi355_label_stats",
     "mi355_last_conv_kernel",
-    "mi355_conv3d_sums_ndhwc", "mi355_conv3d_fused_ndhwc", "mi355_conv3d_plan",
+    "mi355_conv3d_sums_ndhwc", "mi355_conv3d_fused_ndhwc", "mi355_conv3d_plan", "mi355_conv_kernel_names",
     "mi355_sw_partial_folds", "mi355_sw_finish_folds",
     "mi355_resize_axis", "mi355_clip_to_range_of", "mi355_threshold_ge", "mi355_mask_to_float",
     "mi355_label_components", "mi355_component_stats", "mi355_component_filter",
@@ -198,6 +198,8 @@ def load():
                                              c_float_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, C.c_int, vp, vp,
                                              C.c_int, vp, vp, vp, vp]
     lib.mi355_conv3d_plan.argtypes = [C.c_int] * 13 + [C.POINTER(ConvPlan)]
+    lib.mi355_conv_kernel_names.argtypes = [C.c_char_p, C.c_int64]
+    lib.mi355_conv_kernel_names.restype = C.c_int64
     lib.mi355_stage0_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.c_int, C.POINTER(Stage0Geom),
                                       C.POINTER(Stage0Sample), C.c_int]
     lib.mi355_skip_share_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.POINTER(SkipShareNet), C.c_int,

@@ -1294,6 +1294,7 @@ static KernelRow f32_rows[] = {
     MI355_KERNEL_ROW(conv3_f32_mfma_kernel<2, 8, 1, 1>),
     MI355_KERNEL_ROW(conv3_f32_mfma_kernel<2, 8, 1, 2>),
 };
+void list_f32_rows(std::string *out) { list_rows("f32_rows", f32_rows, out); }
 
 // Which kernel an fp32 call goes to, with which tile, grid, LDS size and weight pack.  No side effects: the error text is set
 // only when the call is refused.

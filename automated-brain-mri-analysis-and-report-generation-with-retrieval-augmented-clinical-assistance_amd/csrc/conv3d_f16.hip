@@ -1297,6 +1297,7 @@ static KernelRow f16_rows[] = {
     MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<2, 2, false, false, 1, false>),
     MI355_KERNEL_ROW(conv3_f16_mfma_pipe_kernel<1, 2, false, false, 2, false>),
 };
+void list_f16_rows(std::string *out) { list_rows("f16_rows", f16_rows, out); }
 
 // Can conv `w` apply the producer's normalisation to the input of call `c` (N, Di, Hi, Wi, C0, stats and head set as it will be
 // called)?  Then plan_conv_f16 accepts the call with in_scale set: on the pipelined stride-1 kernel (which normalises while staging

@@ -332,6 +332,7 @@ static KernelRow s2h_rows[] = {
     MI355_KERNEL_ROW(conv3_f16_s2dma_kernel<true, 64>),
     MI355_KERNEL_ROW(conv3_f16_s2dma_kernel<false, 64>),
 };
+void list_s2h_rows(std::string *out) { list_rows("s2h_rows", s2h_rows, out); }
 
 // Does the kernel above take this call (otherwise the older stride-2 kernels do)?  One input tensor, whole 4 x 4 x 8 output tiles,
 // Cout % 64 == 0 and enough tiles for one persistent workgroup per CU.

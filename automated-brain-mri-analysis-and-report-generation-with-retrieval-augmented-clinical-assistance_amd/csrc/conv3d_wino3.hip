@@ -887,6 +887,7 @@ static KernelRow wino3_rows[] = {
     MI355_KERNEL_ROW(conv3_f32_wino3_kernel<2, true>),
     MI355_KERNEL_ROW(conv3_f32_wino3_kernel<3, false>),
 };
+void list_wino3_rows(std::string *out) { list_rows("wino3_rows", wino3_rows, out); }
 
 bool plan_wino3(const ConvWeights &w, const ConvCall &c, ConvPlan *p, bool force) {
     if (!wino3_fits(w, c, force)) return false;

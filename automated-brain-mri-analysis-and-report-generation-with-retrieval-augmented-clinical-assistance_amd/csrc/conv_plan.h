@@ -118,6 +118,16 @@ inline KernelRow *find_row(KernelRow (&rows)[N], const char *fmt, ...) {
         if (strcmp(r.name, name) == 0) return &r;
     return nullptr;
 }
+// `table | name` lines of a table's rows, and the four tables' own listings (mi355_conv_kernel_names): what ships, whether or not
+// a planner ever selects it
+template <size_t N>
+inline void list_rows(const char *table, KernelRow (&rows)[N], std::string *out) {
+    for (KernelRow &r : rows) *out += std::string(table) + " | " + r.name + "\n";
+}
+void list_f32_rows(std::string *out);    // conv3d.hip
+void list_wino3_rows(std::string *out);  // conv3d_wino3.hip
+void list_f16_rows(std::string *out);    // conv3d_f16.hip
+void list_s2h_rows(std::string *out);    // conv3d_f16_s2.hip
 inline const char *tf(bool b) { return b ? "true" : "false"; }
 // launch `r` with 256 threads per workgroup; `args` = the kernel's one argument struct
 inline int launch_row(KernelRow &r, dim3 grid, size_t lds_bytes, hipStream_t s, void *args) {

@@ -1314,6 +1314,30 @@ static int synced(int rc, hipStream_t s, const char *what) {
     return rc;
 }
 
+// Guard bands of the single-op fp16 entry points.  The fp16 kernels store into a channel-blocked buffer these entry points own,
+// not into the caller's tensor, so a caller cannot see a store that misses it.  The buffer therefore sits between two bands of
+// GUARD_BYTE - a sample's worth each, at most 4 MiB - that are read back after the launch: a byte changed there fails the call.
+constexpr unsigned char GUARD_BYTE = 0xA5;
+static size_t guard_bytes(size_t sample_bytes) {
+    const size_t g = sample_bytes < 4096 ? 4096 : (sample_bytes > (4u << 20) ? (4u << 20) : sample_bytes);
+    return (g + 255) / 256 * 256;  // (the buffer between the bands keeps hipMalloc's alignment to 256 B)
+}
+static int guards_intact(const void *buf, size_t guard, size_t bytes, const char *kernel) {
+    std::vector<unsigned char> host(2 * guard);
+    MI355_HIP(hipMemcpy(host.data(), buf, guard, hipMemcpyDeviceToHost));
+    MI355_HIP(hipMemcpy(host.data() + guard, (const char *)buf + guard + bytes, guard, hipMemcpyDeviceToHost));
+    size_t front = 0, behind = 0, first_behind = 0;
+    for (size_t i = 0; i < guard; ++i) front += host[i] != GUARD_BYTE;
+    for (size_t i = guard; i-- > 0;)
+        if (host[guard + i] != GUARD_BYTE) { ++behind; first_behind = i; }
+    if (front || behind) {
+        set_error("%s stored outside its %zu-byte output: %zu bytes changed in front of it, %zu behind (first at +%zu)", kernel, bytes, front,
+                  behind, first_behind);
+        return MI355_ERR_HIP;
+    }
+    return MI355_OK;
+}
+
 // `sums` (device, [n][cout][2] doubles, zeroed here) != nullptr: the launch also carries the Instance/GroupNorm statistics
 // epilogue (sum x, sum x^2 of its output per sample and channel) exactly as a run-time-norm block of the network does.
 // `f` (optional): the fused operands of a network conv (ConvCall): the second half of a virtual concat, the producer's
@@ -1371,10 +1395,13 @@ static int conv3d_ndhwc_f16_impl(const void *x_dev, int n, int d, int h, int w, 
     const int64_t Vi = (int64_t)d * h * w;
     const int64_t Vo = (int64_t)((d - 1) / stride + 1) * ((h - 1) / stride + 1) * ((w - 1) / stride + 1);
     MI355_REQUIRE(cout % 8 == 0, "fp16 conv needs cout %% 8 == 0 (got %d)", cout);
-    TmpBuf yb;
-    MI355_HIP(hipMalloc(&yb.p, (size_t)n * Vo * cout * 2));
+    const size_t ybytes = (size_t)n * Vo * cout * 2, guard = guard_bytes((size_t)Vo * cout * 2);
+    TmpBuf ybuf;  // guard band, the kernel's output, guard band (guards_intact)
+    MI355_HIP(hipMalloc(&ybuf.p, ybytes + 2 * guard));
+    struct { void *p; } yb = {(char *)ybuf.p + guard};
+    MI355_HIP(hipMemsetAsync(ybuf.p, GUARD_BYTE, ybytes + 2 * guard, s));
     // all-NaN (0xFFFF) before the launch: a voxel the kernel fails to store cannot pass for a result
-    MI355_HIP(hipMemsetAsync(yb.p, 0xFF, (size_t)n * Vo * cout * 2, s));
+    MI355_HIP(hipMemsetAsync(yb.p, 0xFF, ybytes, s));
     int rc;
     if (single_op_stem(cin, stride, 0, cout, f)) {
         TmpWeights<StemWeights, stem_weights_free> sw;
@@ -1382,7 +1409,8 @@ static int conv3d_ndhwc_f16_impl(const void *x_dev, int n, int d, int h, int w, 
         rc = conv3d_stem(sw.w, x_dev, n, d, h, w, yb.p, sums, act, slope, s);
         g_last_conv_kernel = "conv3_stem_f16_kernel";
         if (rc == MI355_OK) rc = b8_to_ndhwc((const _Float16 *)yb.p, n, cout, Vo, (_Float16 *)y_dev, s);
-        return synced(rc, s, "stem conv");
+        rc = synced(rc, s, "stem conv");
+        return rc == MI355_OK ? guards_intact(ybuf.p, guard, ybytes, g_last_conv_kernel.c_str()) : rc;
     }
     MI355_REQUIRE(cin % 8 == 0 && f.c1 % 8 == 0, "fp16 conv needs cin %% 8 == 0 on both inputs (got %d, %d)", cin - f.c1, f.c1);
     const int c0 = cin - f.c1;
@@ -1402,7 +1430,8 @@ static int conv3d_ndhwc_f16_impl(const void *x_dev, int n, int d, int h, int w, 
     rc = conv3d_mfma_f16(cw.w, make_call<_Float16>(xb.p, cin, n, d, h, w, f.head_out ? nullptr : yb.p, sums, act, slope, fb), s, &kname);
     g_last_conv_kernel = kname ? kname : "";
     if (rc == MI355_OK && !f.head_out) rc = b8_to_ndhwc((const _Float16 *)yb.p, n, cout, Vo, (_Float16 *)y_dev, s);
-    return synced(rc, s, "conv");
+    rc = synced(rc, s, "conv");
+    return rc == MI355_OK ? guards_intact(ybuf.p, guard, ybytes, g_last_conv_kernel.c_str()) : rc;
 }
 
 extern "C" int mi355_conv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
@@ -1513,6 +1542,14 @@ extern "C" int mi355_conv3d_plan(int dtype, int n, int d, int h, int w, int c0, 
     out->splitk = 1;
     out->rc = conv3d_plan_impl(dtype, n, d, h, w, c0, c1, cout, stride, impl, has_stats != 0, has_in_norm != 0, head_ncls, out);
     return out->rc;
+}
+
+extern "C" int64_t mi355_conv_kernel_names(char *buf, int64_t buf_bytes) {
+    MI355_REQUIRE(buf != nullptr || buf_bytes == 0, "mi355_conv_kernel_names: buf is null");
+    std::string s;
+    list_f32_rows(&s); list_wino3_rows(&s); list_f16_rows(&s); list_s2h_rows(&s);
+    if (buf_bytes > 0) snprintf(buf, (size_t)buf_bytes, "%s", s.c_str());
+    return (int64_t)s.size() + 1;
 }
 
 extern "C" int mi355_stage0_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes, int r,

@@ -248,6 +248,17 @@ def conv3d_plan(dtype, shape, c0, cout, c1=0, stride=1, impl="mfma", stats=False
             "tile": tuple(p.tile), "fuses_in_norm": bool(p.fuses_in_norm), "error": (lib.mi355_last_error() or b"").decode() if rc < 0 else ""}
 
 
+def conv_kernel_names():
+    """Every kernel instantiation the 3x3x3 conv dispatch can launch (test aid, ``mi355_conv_kernel_names``; no GPU needed): a list
+    of (table, name), one per row of the four row tables, names as ``conv3d_plan`` reports them (without " split-K")."""
+    lib = _lib.load()
+    need = lib.mi355_conv_kernel_names(None, 0)
+    _lib.check(need, "mi355_conv_kernel_names")
+    buf = C.create_string_buffer(int(need))
+    _lib.check(lib.mi355_conv_kernel_names(buf, need), "mi355_conv_kernel_names")
+    return [tuple(line.split(" | ", 1)) for line in buf.value.decode().splitlines()]
+
+
 def stage0_plan(volume, patch, step_size=0.5, mirror_axes=(), r=2):
     """Dry run of the sliding window's shared stage 0 (``mi355_stage0_plan``; no GPU needed) for a volume (Z, Y, X), a patch and
     the mirror axes (a subset of (0, 1, 2)); ``r`` = blocks of encoder stage 0 (0: the network does not qualify).  Returns a dict:

@@ -442,7 +442,9 @@ int mi355_conv3d_ndhwc(const float *x_dev, int n, int d, int h, int w, int cin, 
 int mi355_tconv3d_ndhwc(const float *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
                         int cout, float *y_dev, void *stream);
 /* fp16-storage variants: x_dev / y_dev hold IEEE half plain NDHWC tensors (cin % 16 == 0, cout % 32 == 0); inside the library
- * fp16 activations are channel-blocked ([N][C/8][D][H][W][8]) and these entry points convert on the way in and out. */
+ * fp16 activations are channel-blocked ([N][C/8][D][H][W][8]) and these entry points convert on the way in and out.  The conv
+ * entry points (this one, mi355_conv3d_sums_ndhwc and mi355_conv3d_fused_ndhwc with fp16) keep the kernel's channel-blocked output
+ * between two guard bands and return MI355_ERR_HIP, with the byte counts in mi355_last_error, if the launch changed either. */
 int mi355_conv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
                            const float *bias_host, int cout, int stride, int act, float slope, void *y_dev,
                            void *stream);
@@ -487,6 +489,11 @@ typedef struct mi355_conv_plan {
 } mi355_conv_plan;
 int mi355_conv3d_plan(int dtype, int n, int d, int h, int w, int c0, int c1, int cout, int stride, int impl, int has_stats,
                       int has_in_norm, int head_ncls, mi355_conv_plan *out);
+/* The kernel instantiations the 3x3x3 conv dispatch can launch (test aid; needs no device and launches nothing): one
+ * "table | name\n" line per row of the four row tables (f32_rows, wino3_rows, f16_rows, s2h_rows), name as mi355_conv3d_plan and
+ * mi355_last_conv_kernel spell it (without the " split-K" suffix).  Writes at most buf_bytes bytes, NUL-terminated, and returns
+ * the bytes the whole list needs (buf may be NULL when buf_bytes is 0).  No reference counterpart. */
+int64_t mi355_conv_kernel_names(char *buf, int64_t buf_bytes);
 /* Dry run of the shared stage 0 of the sliding window (needs no device and launches nothing; the same code mi355_sw_predict /
  * mi355_sw_partial[_folds] run).  An fp32 network whose encoder stage 0 is r stride-1 blocks without run-time statistics
  * (BatchNorm folded or no norm) computes that stage once per mirror over the whole padded volume, and per (tile, mirror) over
