@@ -33,7 +33,7 @@ EXPORTS = [
     "mi355_label_components", "mi355_component_stats", "mi355_component_filter",
     "mi355_binary_morphology", "mi355_edt_squared", "mi355_surface_gradient_stats", "mi355_mask_second_moments",
     "mi355_masked_moments", "mi355_flag_from_labels", "mi355_flag_from_flags",
-    "mi355_masked_percentiles",
+    "mi355_masked_percentiles", "mi355_masked_percentiles_multi",
     "mi355_binary_fill_holes", "mi355_sobel_magnitude_stats", "mi355_radial_shell_moments", "mi355_face_slab_counts",
     "mi355_axis_counts", "mi355_box_counts", "mi355_select_ranked", "mi355_min_pair_dist2", "mi355_masked_min_i32",
     "mi355_label_components_nb", "mi355_cityblock_distance", "mi355_flag_from_i32", "mi355_flag_from_box", "mi355_masked_order_stats_i32",
@@ -227,6 +227,8 @@ def load():
     lib.mi355_flag_from_flags.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_int64, vp]
     lib.mi355_masked_percentiles.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_int,
                                              C.POINTER(C.c_int64), c_float_p, c_float_p, vp]
+    lib.mi355_masked_percentiles_multi.argtypes = [C.POINTER(vp), C.c_int, C.c_int64, vp, c_int32_p, c_int32_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                   C.POINTER(C.POINTER(C.c_double)), c_int32_p, C.POINTER(C.c_int64), c_float_p, c_float_p, c_int32_p, vp]
     lib.mi355_binary_fill_holes.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_int64), vp]
     lib.mi355_sobel_magnitude_stats.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), vp]
     lib.mi355_radial_shell_moments.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double,

@@ -239,12 +239,15 @@ def multiplicity_from_stats(tumour_stats, enhancing_stats, voxel_dims):
             'distribution_pattern': _distribution_pattern(comp, dist, sat, enh)}
 
 
-def lesion_multiplicity(seg, voxel_dims):
+def lesion_multiplicity(seg, voxel_dims, ctx=None):
     """seg: CUDA uint8 label map [d0, d1, d2] (1 = ncr, 2 = ed, 3 = et, as step 3 reads them) -> the dict of
-    ``multiplicity_from_stats``.  Two labellings and two statistics passes on the device."""
+    ``multiplicity_from_stats``.  Two labellings and two statistics passes on the device.  ``ctx``: the ``features.CaseContext`` of
+    ``seg``, which has the tumour's labelling, or None."""
     import torch
+    if ctx is not None:
+        seg = ctx.volumes(seg, (), "lesion_multiplicity")[0]
     seg = _check_volume(seg, torch.uint8, "lesion_multiplicity")
-    labels, n = label_components(seg, 3)                      # tumour = seg > 0
+    labels, n = label_components(seg, 3) if ctx is None else ctx.tumour_components  # tumour = seg > 0
     tumour = component_stats(labels, n, seg)
     labels, n = label_components(_indicator(seg, (3,)), 3)    # enhancing = seg == 3
     enhancing = component_stats(labels, n)

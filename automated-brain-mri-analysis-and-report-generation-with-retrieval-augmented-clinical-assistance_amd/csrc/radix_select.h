@@ -1,6 +1,7 @@
 // The radix select behind mi355_masked_percentiles (percentile.hip, float32 values) and mi355_masked_order_stats_i32
 // (normal_structures.hip, int32 values): one histogram kernel and one host driver, templated on how a 32-bit word of the volume
-// becomes an order-preserving 32-bit key.  The method is described at the top of percentile.hip.
+// becomes an order-preserving 32-bit key.  The method is described at the top of percentile.hip.  Beside them the histogram kernel
+// of the batched float32 select (mi355_masked_percentiles_multi), which shares PctGroups, wave_hist_add and the Key classifier.
 #pragma once
 #include <cmath>
 
@@ -89,6 +90,97 @@ __global__ __launch_bounds__(256) void pct_hist_kernel(const unsigned *x, const 
         if (h) atomicAdd(table + i, h);
     }
     if (threadIdx.x == 0 && aside_count) atomicAdd(table + PCT_MAX_GROUPS * 256, aside_count);
+}
+
+// ---- the batched form: up to PCT_MAX_VOLUMES volumes of one length that share the flag byte (mi355_masked_percentiles_multi,
+// percentile.hip).  One launch counts for all of them: a thread loads the flag byte of a voxel once and the word of a volume only
+// when the byte passes that volume's flag test.  The histogram of a launch is the groups of its volumes one after the other
+// (`base`), then one side counter per volume, in LDS and in the global table alike; LDS is dynamic and sized by those groups.
+constexpr int PCT_MAX_VOLUMES = 4;
+constexpr int PCT_MULTI_WORDS = PCT_MAX_VOLUMES * (PCT_MAX_GROUPS * 256 + 1);  // the most a pass can count
+
+struct PctMultiVolume {
+    const unsigned *x;
+    double lo, hi;
+    int require, forbid;
+    int base;            // first counter of the volume's groups within the launch's histogram
+    PctGroups groups;
+};
+struct PctMultiArgs {
+    int count;           // volumes of this launch
+    int bins;            // 256 x the groups of all of them; the side counter of volume v is counter bins + v
+    PctMultiVolume vol[PCT_MAX_VOLUMES];
+};
+
+// table[vol[v].base + g * 256 + d] and table[bins + v]: what pct_hist_kernel counts, per volume of the launch.  Dynamic LDS:
+// (bins + count) words.  Per wave, then per block, then one global integer atomic per nonzero counter, as pct_hist_kernel.
+template <class Key>
+__global__ __launch_bounds__(256) void pct_hist_multi_kernel(PctMultiArgs a, const uint8_t *flags, int64_t n, int shift, int count_aside, unsigned *table) {
+    extern __shared__ unsigned multi_hist[];
+    const int words = a.bins + a.count;
+    for (int i = threadIdx.x; i < words; i += 256) multi_hist[i] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t base = (int64_t)blockIdx.x * PCT_CHUNK + threadIdx.x;
+    int aside[PCT_MAX_VOLUMES] = {0, 0, 0, 0};
+    int f[PCT_UNROLL], f_next[PCT_UNROLL];
+#pragma unroll
+    for (int u = 0; u < PCT_UNROLL; ++u) {
+        const int64_t i = base + (int64_t)u * 256;
+        f[u] = i < n ? (flags ? (int)flags[i] : 0) : -1;
+    }
+    for (int it = 0; it < PCT_CHUNK / 256; it += PCT_UNROLL) {  // (no lane leaves the loop early: the ballots need the whole wave)
+        unsigned bits[PCT_MAX_VOLUMES][PCT_UNROLL];
+        unsigned pass[PCT_MAX_VOLUMES];   // bit u: the flag byte of voxel u passes the volume's test
+#pragma unroll
+        for (int v = 0; v < PCT_MAX_VOLUMES; ++v) {
+            pass[v] = 0;
+            if (v < a.count) {            // (the same in every lane)
+#pragma unroll
+                for (int u = 0; u < PCT_UNROLL; ++u) {
+                    const bool p = f[u] >= 0 && (f[u] & a.vol[v].require) == a.vol[v].require && !(f[u] & a.vol[v].forbid);
+                    bits[v][u] = p ? a.vol[v].x[base + (int64_t)(it + u) * 256] : 0u;
+                    pass[v] |= (unsigned)p << u;
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PCT_UNROLL; ++u) {  // the flag bytes of the next round, in flight behind the words of this one
+            const int64_t i = base + (int64_t)(it + PCT_UNROLL + u) * 256;
+            f_next[u] = (it + PCT_UNROLL < PCT_CHUNK / 256 && i < n) ? (flags ? (int)flags[i] : 0) : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < PCT_UNROLL; ++u) {
+#pragma unroll
+            for (int v = 0; v < PCT_MAX_VOLUMES; ++v) {
+                if (v < a.count) {
+                    int slot = -1;
+                    if (pass[v] >> u & 1u) {
+                        unsigned key = 0;
+                        const int kind = Key::classify(bits[v][u], a.vol[v].lo, a.vol[v].hi, key);
+                        if (kind == PCT_ASIDE) {
+                            aside[v] += count_aside;
+                        } else if (kind == PCT_KEYED) {
+                            const unsigned head = key & a.vol[v].groups.mask;
+                            for (int g = 0; g < a.vol[v].groups.count; ++g)
+                                if (head == a.vol[v].groups.prefix[g]) slot = a.vol[v].base + g * 256 + (int)((key >> shift) & 255u);
+                        }
+                    }
+                    wave_hist_add(multi_hist, slot, lane);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PCT_UNROLL; ++u) f[u] = f_next[u];
+    }
+#pragma unroll
+    for (int v = 0; v < PCT_MAX_VOLUMES; ++v)
+        if (v < a.count && aside[v]) atomicAdd(&multi_hist[a.bins + v], (unsigned)aside[v]);
+    __syncthreads();
+    for (int i = threadIdx.x; i < words; i += 256) {
+        const unsigned h = multi_hist[i];
+        if (h) atomicAdd(table + i, h);
+    }
 }
 
 // count_host[0] = m, the voxels that take part, count_host[1] = the words set aside; below_key[j] / above_key[j] = the keys of

@@ -406,18 +406,23 @@ def sample_ranks(n_tumour, n_csf, rng=None):
     return tumour, csf
 
 
-def mass_effect_stats(seg, t1, rng=None, distance='sampled'):
-    """What ``mass_effect_from_stats`` reads, from a CUDA uint8 label map with the labels 0..4 and the CUDA float32 T1 volume."""
+def mass_effect_stats(seg, t1, rng=None, distance='sampled', ctx=None):
+    """What ``mass_effect_from_stats`` reads, from a CUDA uint8 label map with the labels 0..4 and the CUDA float32 T1 volume.
+    ``ctx``: the ``features.CaseContext`` of these tensors, which has the label statistics, the percentiles and the dilation."""
     import torch
     from . import components, evaluate
     if distance not in DISTANCES:
         raise ValueError(f"mass_effect: distance {distance!r} (one of {', '.join(DISTANCES)})")
-    stats = {'shape': tuple(seg.shape), 'label_stats': evaluate.label_stats(seg, 8), 'n_brain': 0, 'dist2': None}
+    stats = {'shape': tuple(seg.shape), 'label_stats': evaluate.label_stats(seg, 8) if ctx is None else ctx.label_stats, 'n_brain': 0, 'dist2': None}
     n_tumour = int(stats['label_stats'][1:5, 0].sum())
     flags = torch.zeros_like(seg)
-    count, p5 = masked_percentiles(t1, 5, lo=0)                                          # utils.get_brain_mask, utils.py:63-68
+    if ctx is None:
+        count, p5 = masked_percentiles(t1, 5, lo=0)                                      # utils.get_brain_mask, utils.py:63-68
+        if count:
+            flag_from_flags(flags, BRAIN, x=t1, lo=float(p5[0]))
+    else:
+        count = ctx.brain_into(flags, BRAIN)
     if count:                                                                            # (no positive voxel: `data > 0`, an empty mask)
-        flag_from_flags(flags, BRAIN, x=t1, lo=float(p5[0]))
         stats['brain_counts0'] = axis_counts(flags, 1 << BRAIN)[0]                       # :54-99
         stats['n_brain'] = int(stats['brain_counts0'].sum())
         if stats['n_brain'] == 0:
@@ -427,12 +432,15 @@ def mass_effect_stats(seg, t1, rng=None, distance='sampled'):
     if n_tumour:
         flag_from_labels(seg, range(1, 256), TUMOUR, flags)
     if stats['n_brain']:
-        p15 = masked_percentiles(t1, 15, flags, require=1 << BRAIN)[1]                   # :179
+        p15 = (masked_percentiles(t1, 15, flags, require=1 << BRAIN) if ctx is None else ctx.brain_percentiles(0, 15))[1]  # :179
         flag_from_flags(flags, CSF, forbid=1 << TUMOUR, x=t1, lo=0.0, hi=float(p15[0]))  # :180-181
         stats['csf_counts0'] = axis_counts(flags, 1 << CSF)[0]                           # :186-193
         n_csf = int(stats['csf_counts0'].sum())
     if n_tumour:
-        flag_from_labels(binary_dilation(seg, DILATIONS), (1,), DILATED, flags)          # :373
+        if ctx is None:
+            flag_from_labels(binary_dilation(seg, DILATIONS), (1,), DILATED, flags)      # :373
+        else:
+            ctx.dilated_into(flags, DILATED, DILATIONS)
         flag_from_flags(flags, PERITUMORAL, require=(1 << DILATED) | (1 << BRAIN), forbid=1 << TUMOUR)  # :374
         flag_from_flags(flags, DISTANT, require=1 << BRAIN, forbid=1 << DILATED)         # :383
         m = masked_moments(t1.reshape((1,) + tuple(t1.shape)), flags)[:, 0, :]           # :392-393
@@ -451,7 +459,7 @@ def mass_effect_stats(seg, t1, rng=None, distance='sampled'):
     return stats
 
 
-def mass_effect(seg, t1, voxel_dims, rng=None, distance='sampled'):
+def mass_effect(seg, t1, voxel_dims, rng=None, distance='sampled', ctx=None):
     """seg: CUDA uint8 label map [d0, d1, d2] (1 = ncr, 2 = ed, 3 / 4 = et, nothing above 4); t1: CUDA float32 volume of that
     shape -> the dicts ``anatomical_location``, ``midline_shift``, ``ventricular_compression``, ``sulcal_effacement`` and
     ``herniation_risk`` of the reference's step 2.
@@ -459,8 +467,13 @@ def mass_effect(seg, t1, voxel_dims, rng=None, distance='sampled'):
     ``distance='sampled'`` measures the tumour-to-CSF distance between the voxels the reference would draw: from ``rng`` (a
     ``numpy.random.RandomState`` or ``Generator``), or from the ``numpy.random`` module's global state when ``rng`` is None - after
     ``np.random.seed(s)`` the result is the reference's under that seed.  ``distance='exact'`` takes the minimum over all pairs
-    and leaves every generator alone."""
+    and leaves every generator alone.  ``ctx``: the ``features.CaseContext`` of these tensors (it has checked them), or None."""
     import torch
+    if ctx is not None:
+        if distance not in DISTANCES:
+            raise ValueError(f"mass_effect: distance {distance!r} (one of {', '.join(DISTANCES)})")
+        seg, (t1,) = ctx.volumes(seg, (t1,), "mass_effect")
+        return mass_effect_from_stats(mass_effect_stats(seg, t1, rng, distance, ctx), voxel_dims)
     seg = _check_volume(seg, torch.uint8, "mass_effect")
     t1 = _check_volume(t1, torch.float32, "mass_effect")
     if t1.shape != seg.shape:

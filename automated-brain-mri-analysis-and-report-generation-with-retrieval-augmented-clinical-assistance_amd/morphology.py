@@ -347,53 +347,65 @@ def csf_thresholds(t1, t2, flair):
     return float(csf_t1_upper * 1.5), float(csf_t2_lower * 0.8), float(csf_flair_upper * 2)
 
 
-def region_flags(seg, t1, t2, flair):
+def region_flags(seg, t1, t2, flair, ctx=None):
     """The flag byte per voxel ``tumor_morphology`` reduces over: bits WT, BAND, INNER, OUTER, NCR and CYSTIC of a CUDA uint8 label
-    map and three CUDA float32 volumes (T1ce takes no part in any region).  Only the WT bit when there is no tumour."""
+    map and three CUDA float32 volumes (T1ce takes no part in any region).  Only the WT bit when there is no tumour.  ``ctx``: the
+    ``features.CaseContext`` of these tensors, which has the erosion, the dilations and the three percentiles."""
     import torch
     flags = torch.zeros_like(seg)
     flag_from_labels(seg, range(1, 256), WT, flags)                      # utils.py:177, wt = seg > 0
     if not bool(seg.any()):                                              # :38, :141, :219, :305 return early
         return flags
-    flag_from_labels(binary_erosion(seg), (1,), INNER, flags)            # :42, :149-150, :252-253: wt & ~eroded
-    flag_from_flags(flags, INNER, require=1 << WT, forbid=1 << INNER)
-    flag_from_labels(binary_dilation(seg), (1,), OUTER, flags)           # :254
-    flag_from_flags(flags, OUTER, require=1 << OUTER, forbid=1 << WT)
-    flag_from_labels(binary_dilation(seg, 5), (1,), BAND, flags)         # :227-228
-    flag_from_flags(flags, BAND, require=1 << BAND, forbid=1 << WT)
-    flag_from_labels(seg, (1,), NCR, flags)                              # utils.py:173
     from .percentile import masked_percentiles
-    t1_hi = float(masked_percentiles(t1, 10, lo=0)[1][0] * 1.5)          # :317-320 and the factors of :330-332, as csf_thresholds
-    t2_lo = float(masked_percentiles(t2, 85, lo=0)[1][0] * 0.8)
-    flair_hi = float(masked_percentiles(flair, 20, lo=0)[1][0] * 2)
+    if ctx is None:
+        flag_from_labels(binary_erosion(seg), (1,), INNER, flags)        # :42, :149-150, :252-253: wt & ~eroded
+        flag_from_flags(flags, INNER, require=1 << WT, forbid=1 << INNER)
+        flag_from_labels(binary_dilation(seg), (1,), OUTER, flags)       # :254
+        flag_from_flags(flags, OUTER, require=1 << OUTER, forbid=1 << WT)
+        flag_from_labels(binary_dilation(seg, 5), (1,), BAND, flags)     # :227-228
+        flag_from_flags(flags, BAND, require=1 << BAND, forbid=1 << WT)
+        p_t1, p_t2, p_flair = masked_percentiles(t1, 10, lo=0)[1], masked_percentiles(t2, 85, lo=0)[1], masked_percentiles(flair, 20, lo=0)[1]
+    else:
+        ctx.eroded_into(flags, INNER, 1)
+        flag_from_flags(flags, INNER, require=1 << WT, forbid=1 << INNER)
+        ctx.dilated_into(flags, OUTER, 1, forbid=1 << WT)
+        ctx.dilated_into(flags, BAND, 5, forbid=1 << WT)
+        p_t1, p_t2, p_flair = ctx.positive_percentiles(T1, 10)[1], ctx.positive_percentiles(T2, 85)[1], ctx.positive_percentiles(FLAIR, 20)[1]
+    flag_from_labels(seg, (1,), NCR, flags)                              # utils.py:173
+    t1_hi = float(p_t1[0] * 1.5)                                         # :317-320 and the factors of :330-332, as csf_thresholds
+    t2_lo = float(p_t2[0] * 0.8)
+    flair_hi = float(p_flair[0] * 2)
     flag_from_flags(flags, CYSTIC, require=1 << NCR, x=t1, hi=t1_hi)     # :329-333
     flag_from_flags(flags, CYSTIC, require=1 << CYSTIC, x=t2, lo=t2_lo)
     flag_from_flags(flags, CYSTIC, require=1 << CYSTIC, x=flair, hi=flair_hi)
     return flags
 
 
-def tumor_morphology(seg, t1, t1ce, t2, flair, voxel_dims):
+def tumor_morphology(seg, t1, t1ce, t2, flair, voxel_dims, ctx=None):
     """seg: CUDA uint8 label map [d0, d1, d2] (1 = ncr, 2 = ed, 3 / 4 = et); t1, t1ce, t2, flair: CUDA float32 volumes of that
     shape -> the dicts ``shape_descriptors``, ``border_regularity``, ``margin_definition``, ``necrosis_pattern`` and
     ``cystic_solid_classification`` of the reference's step 4.
 
     Everything comes from device results, the three ``np.percentile`` thresholds of :317-320 included: ``masked_percentiles``
     selects their order statistics on the device and interpolates as numpy does, bit for bit (``csf_thresholds`` is the same
-    on host arrays)."""
+    on host arrays).  ``ctx``: the ``features.CaseContext`` of these tensors (it has checked them), or None."""
     import torch
     from . import components, evaluate
-    seg = _check_volume(seg, torch.uint8, "tumor_morphology")
-    chans = [_check_volume(v, torch.float32, "tumor_morphology") for v in (t1, t1ce, t2, flair)]
-    if any(v.shape != seg.shape for v in chans):
-        raise ValueError("tumor_morphology: the volumes and the label map differ in shape")
-    flags = region_flags(seg, chans[T1], chans[T2], chans[FLAIR])
+    if ctx is not None:
+        seg, chans = ctx.volumes(seg, (t1, t1ce, t2, flair), "tumor_morphology")
+    else:
+        seg = _check_volume(seg, torch.uint8, "tumor_morphology")
+        chans = [_check_volume(v, torch.float32, "tumor_morphology") for v in (t1, t1ce, t2, flair)]
+        if any(v.shape != seg.shape for v in chans):
+            raise ValueError("tumor_morphology: the volumes and the label map differ in shape")
+    flags = region_flags(seg, chans[T1], chans[T2], chans[FLAIR], ctx)
     region_moments = masked_moments(torch.stack(chans), flags)
     gradient = None
     if region_moments[INNER][0][0] >= 10:                                # :152
         d2_in = distance_transform_edt_sq(seg)                           # :160-161
         d2_out = distance_transform_edt_sq(components._indicator(seg, (0,)))
         gradient = surface_gradient_stats(d2_in, d2_out, flags, 1 << INNER)
-    return morphology_from_stats(evaluate.label_stats(seg, 8), second_moments(seg), gradient, region_moments, voxel_dims)
+    return morphology_from_stats(evaluate.label_stats(seg, 8) if ctx is None else ctx.label_stats, second_moments(seg), gradient, region_moments, voxel_dims)
 
 
 # ---- the command ------------------------------------------------------------------------------------------------------

@@ -323,27 +323,34 @@ def keep_ventricles(component_stats, d0):
     return keep
 
 
-def normal_structures_stats(seg, chans):
+def normal_structures_stats(seg, chans, ctx=None):
     """What ``normal_structures_from_stats`` reads, from a CUDA uint8 label map with the labels 0..4 and the four CUDA float32
-    volumes T1, T1ce, T2, FLAIR."""
+    volumes T1, T1ce, T2, FLAIR.  ``ctx``: the ``features.CaseContext`` of these tensors, which has the brain's percentiles and the
+    tumour's distance transform."""
     import torch
     from . import components
     t1, t1ce, t2, flair = chans
     d0, d1, d2 = seg.shape
     stats = {'shape': (d0, d1, d2), 'n_brain': 0}
     flags = torch.zeros_like(seg)
-    count, p5 = masked_percentiles(t1, 5, lo=0)                                          # utils.get_brain_mask, utils.py:63-68
-    if count == 0:
+    if ctx is None:
+        count, p5 = masked_percentiles(t1, 5, lo=0)                                      # utils.get_brain_mask, utils.py:63-68
+        if count == 0:
+            return stats
+        flag_from_flags(flags, BRAIN, x=t1, lo=float(p5[0]))
+    elif not ctx.brain_into(flags, BRAIN):
         return stats
-    flag_from_flags(flags, BRAIN, x=t1, lo=float(p5[0]))
     flag_from_labels(seg, range(1, 256), TUMOUR, flags)                                  # utils.py:177
     flag_from_flags(flags, NORMAL, require=1 << BRAIN, forbid=1 << TUMOUR)               # :101, :193
     # identify_ventricles, :33-84, once
     brain = 1 << BRAIN
-    n_brain, p15 = masked_percentiles(t1, 15, flags, require=brain)                      # :48-50
+    n_brain, p15 = masked_percentiles(t1, 15, flags, require=brain) if ctx is None else ctx.brain_percentiles(0, 15)  # :48-50
     if n_brain == 0:
         return stats
-    p85, p25 = masked_percentiles(t2, 85, flags, require=brain)[1], masked_percentiles(flair, 25, flags, require=brain)[1]
+    if ctx is None:
+        p85, p25 = masked_percentiles(t2, 85, flags, require=brain)[1], masked_percentiles(flair, 25, flags, require=brain)[1]
+    else:
+        p85, p25 = ctx.brain_percentiles(2, 85)[1], ctx.brain_percentiles(3, 25)[1]
     flag_from_flags(flags, VENTRICLE, require=1 << NORMAL, x=t1, hi=float(p15[0]))       # :53-59
     flag_from_flags(flags, VENTRICLE, require=1 << VENTRICLE, x=t2, lo=float(p85[0]))
     flag_from_flags(flags, VENTRICLE, require=1 << VENTRICLE, x=flair, hi=float(p25[0]))
@@ -361,7 +368,7 @@ def normal_structures_stats(seg, chans):
         frontal_y = coordinate_percentile(counts1, 75)                                   # :127-131
         stats['frontal_width'] = column_count_max(flags, int(frontal_y), 1 << VENTRICLE)
     # one transform of the tumour for :152 and :345, one of the ventricles for :215
-    tumour_dist = cityblock_distance(seg, True)
+    tumour_dist = cityblock_distance(seg, True) if ctx is None else ctx.tumour_distance
     flag_from_i32(flags, OBSTRUCTED, tumour_dist, 0, OBSTRUCTION_STEPS, require=1 << VENTRICLE)                       # :152-153
     flag_from_i32(flags, PERIVENTRICULAR, cityblock_distance(components._indicator(flags, [v for v in range(256) if v & (1 << VENTRICLE)]), True), 0,
                   PERI_STEPS, require=1 << NORMAL, forbid=1 << VENTRICLE)                                             # :215-216
@@ -386,10 +393,14 @@ def normal_structures_stats(seg, chans):
     return stats
 
 
-def normal_structures(seg, t1, t1ce, t2, flair, voxel_dims):
+def normal_structures(seg, t1, t1ce, t2, flair, voxel_dims, ctx=None):
     """seg: CUDA uint8 label map [d0, d1, d2] (1 = ncr, 2 = ed, 3 / 4 = et, nothing above 4); t1, t1ce, t2, flair: CUDA float32
-    volumes of that shape -> the dicts ``ventricular_system``, ``parenchyma`` and ``major_vessels`` of the reference's step 6."""
+    volumes of that shape -> the dicts ``ventricular_system``, ``parenchyma`` and ``major_vessels`` of the reference's step 6.
+    ``ctx``: the ``features.CaseContext`` of these tensors (it has checked them), or None."""
     import torch
+    if ctx is not None:
+        seg, chans = ctx.volumes(seg, (t1, t1ce, t2, flair), "normal_structures")
+        return normal_structures_from_stats(normal_structures_stats(seg, chans, ctx), voxel_dims)
     seg = _check_volume(seg, torch.uint8, "normal_structures")
     chans = [_check_volume(v, torch.float32, "normal_structures") for v in (t1, t1ce, t2, flair)]
     if any(v.shape != seg.shape for v in chans):

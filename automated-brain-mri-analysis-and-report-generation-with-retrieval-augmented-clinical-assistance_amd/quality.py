@@ -320,36 +320,44 @@ def quality_from_stats(stats, voxel_dims):
             'limitations_and_caveats': _limitations(seg_quality, image_quality, n_et)}
 
 
-def quality_stats(seg, chans):
+def quality_stats(seg, chans, ctx=None):
     """What ``quality_from_stats`` reads, from a CUDA uint8 label map with the labels 0..4 and the four CUDA float32 volumes in
-    the order of SEQUENCES."""
+    the order of SEQUENCES.  ``ctx``: the ``features.CaseContext`` of these tensors, which has the label statistics, the tumour's
+    labelling, its erosion and the percentiles."""
     import torch
     from . import components, evaluate
     t1 = chans[0]
-    stats = {'shape': tuple(seg.shape), 'label_stats': evaluate.label_stats(seg, 8)}
+    stats = {'shape': tuple(seg.shape), 'label_stats': evaluate.label_stats(seg, 8) if ctx is None else ctx.label_stats}
     n_wt = int(stats['label_stats'][1:5, 0].sum())
     if n_wt:
-        stats['num_components'] = components.label_components(seg, 3)[1]                 # :88-89
+        stats['num_components'] = (components.label_components(seg, 3) if ctx is None else ctx.tumour_components)[1]  # :88-89
         stats['filled'] = binary_fill_holes(seg)[1]                                      # :103-105
     flags = torch.zeros_like(seg)
-    count, p = masked_percentiles(t1, 5, lo=0)                                           # utils.get_brain_mask, utils.py:63-68
-    if count:                                                                            # (no positive voxel: `data > 0`, an empty mask)
-        flag_from_flags(flags, BRAIN, x=t1, lo=float(p[0]))
+    if ctx is None:
+        count, p = masked_percentiles(t1, 5, lo=0)                                       # utils.get_brain_mask, utils.py:63-68
+        if count:                                                                        # (no positive voxel: `data > 0`, an empty mask)
+            flag_from_flags(flags, BRAIN, x=t1, lo=float(p[0]))
+    else:
+        ctx.brain_into(flags, BRAIN)
     brain_moments = second_moments(flags)                                                # only the BRAIN bit is set so far
     n_brain = stats['n_brain'] = int(brain_moments[0])
     if n_wt:                                                                             # :407-409
         flag_from_labels(seg, range(1, 256), EDGE, flags)
-        flag_from_labels(binary_erosion(seg, 2), (1,), ERODED, flags)
+        if ctx is None:
+            flag_from_labels(binary_erosion(seg, 2), (1,), ERODED, flags)
+        else:
+            ctx.eroded_into(flags, ERODED, 2)
         flag_from_flags(flags, EDGE, require=1 << EDGE, forbid=1 << ERODED)
     stats['sequences'] = {}
-    for name, x in zip(SEQUENCES, chans):
+    for c, (name, x) in enumerate(zip(SEQUENCES, chans)):
         if n_brain:
-            count, p10 = masked_percentiles(x, 10, lo=0)                                 # :194
+            count, p10 = masked_percentiles(x, 10, lo=0) if ctx is None else ctx.positive_percentiles(c, 10)  # :194
             if count == 0:
                 raise ValueError(f"quality_control: {name} has no positive voxel (the reference takes a percentile of an empty array there)")
             flag_from_flags(flags, BACKGROUND, forbid=1 << BRAIN, x=x, lo=0.0, hi=float(p10[0]))
             flag_from_flags(flags, ZERO, require=1 << BRAIN, x=x, lo=-_TINY, hi=_TINY)   # :203
-            q01, q25, q75, q99 = (np.float64(v) for v in masked_percentiles(x, (1, 25, 75, 99), flags, require=1 << BRAIN)[1])  # :210-212
+            q01, q25, q75, q99 = (np.float64(v) for v in (masked_percentiles(x, (1, 25, 75, 99), flags, require=1 << BRAIN) if ctx is None
+                                                          else ctx.brain_percentiles(c, (1, 25, 75, 99)))[1])  # :210-212
             iqr = q75 - q25
             flag_from_flags(flags, HIGH, require=1 << BRAIN, x=x, lo=float(q99 + 3 * iqr))  # :214-215
             flag_from_flags(flags, LOW, require=1 << BRAIN, x=x, hi=float(q01 - 3 * iqr))
@@ -368,11 +376,15 @@ def quality_stats(seg, chans):
     return stats
 
 
-def quality_control(seg, t1, t1ce, t2, flair, voxel_dims):
+def quality_control(seg, t1, t1ce, t2, flair, voxel_dims, ctx=None):
     """seg: CUDA uint8 label map [d0, d1, d2] (1 = ncr, 2 = ed, 3 / 4 = et, nothing above 4); t1, t1ce, t2, flair: CUDA float32
     volumes of that shape -> the dicts ``segmentation_quality``, ``image_quality``, ``artifact_detection``,
-    ``measurement_confidence`` and ``limitations_and_caveats`` of the reference's step 5."""
+    ``measurement_confidence`` and ``limitations_and_caveats`` of the reference's step 5.  ``ctx``: the ``features.CaseContext`` of these
+    tensors (it has checked them), or None."""
     import torch
+    if ctx is not None:
+        seg, chans = ctx.volumes(seg, (t1, t1ce, t2, flair), "quality_control")
+        return quality_from_stats(quality_stats(seg, chans, ctx), voxel_dims)
     seg = _check_volume(seg, torch.uint8, "quality_control")
     chans = [_check_volume(v, torch.float32, "quality_control") for v in (t1, t1ce, t2, flair)]
     if any(v.shape != seg.shape for v in chans):

@@ -165,9 +165,9 @@ def sequence_findings_from_stats(region_moments, voxel_dims):
                         'Necrotic Core (NCR)': volume(n_ncr), 'Peritumoral Edema (ED)': volume(n_ed)}}  # :508-514
 
 
-def region_flags(seg, chans):
+def region_flags(seg, chans, ctx=None):
     """The flag byte per voxel ``sequence_findings`` reduces over, from a CUDA uint8 label map with the labels 0..4 and the four
-    CUDA float32 volumes in channel order."""
+    CUDA float32 volumes in channel order.  ``ctx``: the ``features.CaseContext`` of these tensors, which has the four percentiles."""
     import torch
     from . import components
     flags = torch.zeros_like(seg)
@@ -175,7 +175,7 @@ def region_flags(seg, chans):
     flag_from_labels(seg, (2,), ED, flags)
     flag_from_labels(seg, (3, 4), ET, flags)
     for c, bit in enumerate(NORMAL):                                      # utils.py:57-58
-        count, p = masked_percentiles(chans[c], 5, lo=0)
+        count, p = masked_percentiles(chans[c], 5, lo=0) if ctx is None else ctx.positive_percentiles(c, 5)
         if count:                                                         # (no positive voxel: `data > 0`, an empty mask)
             flag_from_flags(flags, bit, forbid=TUMOUR, x=chans[c], lo=float(p[0]))
     flag_from_labels(binary_dilation(components._indicator(seg, (1,)), 2), (1,), RING, flags)  # :225-226
@@ -183,11 +183,14 @@ def region_flags(seg, chans):
     return flags
 
 
-def sequence_findings(seg, t1, t1ce, t2, flair, voxel_dims):
+def sequence_findings(seg, t1, t1ce, t2, flair, voxel_dims, ctx=None):
     """seg: CUDA uint8 label map [d0, d1, d2] (1 = ncr, 2 = ed, 3 / 4 = et, nothing above 4); t1, t1ce, t2, flair: CUDA float32
     volumes of that shape -> the dicts ``region_signal_analysis``, ``contrast_enhancement``, ``t2_flair_mismatch`` and ``volumes``
-    of the reference's step 1."""
+    of the reference's step 1.  ``ctx``: the ``features.CaseContext`` of these tensors (it has checked them), or None."""
     import torch
+    if ctx is not None:
+        seg, chans = ctx.volumes(seg, (t1, t1ce, t2, flair), "sequence_findings")
+        return sequence_findings_from_stats(masked_moments(torch.stack(chans), region_flags(seg, chans, ctx)), voxel_dims)
     seg = _check_volume(seg, torch.uint8, "sequence_findings")
     chans = [_check_volume(v, torch.float32, "sequence_findings") for v in (t1, t1ce, t2, flair)]
     if any(v.shape != seg.shape for v in chans):

@@ -302,6 +302,22 @@ int mi355_flag_from_flags(uint8_t *flags_dev, int bit, int require, int forbid, 
  * outside 0..255 or sharing a bit.  Synchronous. */
 int mi355_masked_percentiles(const float *x_dev, int64_t n, const uint8_t *flags_dev, int require, int forbid, double lo, double hi,
                              const double *q_host, int nq, int64_t *count_host, float *below_host, float *above_host, void *stream);
+/* mi355_masked_percentiles for nvol = 1..4 volumes x_dev[v] [n] fp32 that share flags_dev: the reference's six steps take the same
+ * percentiles again and again (the positive voxels of each modality: utils.py:57, :67, step4_morphology.py:317-320,
+ * step5_quality.py:194; the brain's: step2_mass_effect.py:179, step5_quality.py:210-212, step6_normal_structures.py:48-50), and
+ * feature_extraction/run_all.py:411-446 runs all six on one case.  Volume v has its own require[v], forbid[v], lo[v], hi[v] and
+ * its own nq[v] = 1..8 percentiles q_host[v][0..nq[v]).  count_host[2 v], count_host[2 v + 1], below_host[8 v + j] and
+ * above_host[8 v + j] are what mi355_masked_percentiles returns for that volume alone, bit for bit; a volume that selects nothing
+ * leaves its below / above untouched and does not keep the others from being selected.  Each of the four passes is one launch
+ * over the voxels and one read-back for all volumes: a thread loads the flag byte once and the word of a volume only when the byte
+ * passes that volume's flag test.  LDS is sized by the prefixes that are live in the pass; where they exceed what the device
+ * allows a workgroup, the pass is split by volume into several launches ahead of the one read-back.  launches_host (NULL allowed)
+ * receives the number of launches: 4 when no pass was split and every volume selects something.  Refused: nvol outside 1..4, an
+ * nq[v] outside 1..8, a q outside [0, 100] or NaN, n outside 1..2^31-1, a NaN bound, require[v] or forbid[v] outside 0..255 or
+ * sharing a bit - all before anything is launched.  Synchronous. */
+int mi355_masked_percentiles_multi(const float *const *x_dev, int nvol, int64_t n, const uint8_t *flags_dev, const int *require, const int *forbid,
+                                   const double *lo, const double *hi, const double *const *q_host, const int *nq, int64_t *count_host,
+                                   float *below_host, float *above_host, int *launches_host, void *stream);
 
 /* ---- hole filling, Sobel gradient statistics, radial shells and face slabs (csrc/quality.hip): the primitives under
  * feature_extraction/step5_quality.py that the entries above do not cover.  Conventions as for csrc/morphology.hip: volumes are
