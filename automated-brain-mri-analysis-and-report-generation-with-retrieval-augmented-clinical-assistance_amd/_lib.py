@@ -42,6 +42,7 @@ EXPORTS = [
     "mi355_norm_finalize", "mi355_norm_apply", "mi355_extract_tiles", "mi355_head_logits", "mi355_head_aggregate",
     "mi355_logits_aggregate", "mi355_cnt_add_tile", "mi355_stage0_gather", "mi355_stage0_mask",
     "mi355_stage0_view_plan", "mi355_conv3d_s2dma_view_ndhwc", "mi355_conv3d_wino3_view_ndhwc", "mi355_stage0_gather_shells",
+    "mi355_logits_aggregate_tiles", "mi355_stage0_merge_plan", "mi355_stage0_gather_merged",
 ]
 
 
@@ -112,6 +113,26 @@ class Stage0GatherArgs(C.Structure):
     _fields_ = [("wv_dev", C.c_void_p), ("slab_dev", C.c_void_p * 3), ("out_dev", C.c_void_p),
                 ("patch", C.c_int32 * 3), ("volume", C.c_int32 * 3), ("slab_thickness", C.c_int32 * 3),
                 ("r", C.c_int32), ("channels", C.c_int32), ("n_samples", C.c_int32), ("samples", Stage0GatherSample * 64)]
+
+
+class Stage0MergeGeom(C.Structure):
+    _fields_ = [("shared", C.c_int32), ("r", C.c_int32), ("rs", C.c_int32), ("n_tiles", C.c_int32), ("n_mirrors", C.c_int32),
+                ("padded", C.c_int32 * 3), ("volume", C.c_int32 * 3), ("slab_thickness", C.c_int32 * 3), ("n_slabs", C.c_int32 * 3),
+                ("slab_shape", (C.c_int32 * 3) * 3), ("voxels", C.c_int64 * 3), ("voxels_per_tile", C.c_int64)]
+
+
+class Stage0MergeSlab(C.Structure):
+    _fields_ = [("axis", C.c_int32), ("mirror", C.c_int32), ("side", C.c_int32), ("origin", C.c_int32 * 3)]
+
+
+class Stage0MergeSample(C.Structure):
+    _fields_ = [("tile", C.c_int32), ("mirror", C.c_int32), ("origin", C.c_int32 * 3), ("slab", C.c_int32 * 6),
+                ("offset", (C.c_int32 * 3) * 6)]
+
+
+class Stage0GatherMergedArgs(C.Structure):
+    _fields_ = [("base", Stage0GatherArgs), ("slab_shape", (C.c_int32 * 3) * 3), ("spans_volume", (C.c_int32 * 3) * 3),
+                ("wv2_dev", C.c_void_p), ("slab2_dev", C.c_void_p * 3), ("out2_dev", C.c_void_p), ("r2", C.c_int32), ("channels2", C.c_int32)]
 
 
 class Stage0ViewGeom(C.Structure):
@@ -255,9 +276,14 @@ def load():
                                          C.c_int, c_int32_p, C.c_int, vp, vp, vp, c_int32_p, c_int32_p, vp]
     lib.mi355_logits_aggregate.argtypes = [vp, C.c_int, C.c_int, c_int32_p, C.c_int, c_int32_p, C.c_int, vp, vp, vp, c_int32_p,
                                            c_int32_p, vp]
+    lib.mi355_logits_aggregate_tiles.argtypes = [vp, C.c_int, C.c_int, c_int32_p, C.c_int, c_int32_p, C.c_int, vp, vp, vp, c_int32_p,
+                                                 c_int32_p, C.c_int, vp]
     lib.mi355_cnt_add_tile.argtypes = [vp, c_int32_p, vp, c_int32_p, c_int32_p, vp]
     lib.mi355_stage0_gather.argtypes = [C.POINTER(Stage0GatherArgs), vp]
     lib.mi355_stage0_mask.argtypes = [vp, C.c_int, c_int32_p, c_int32_p, C.c_int, vp]
+    lib.mi355_stage0_merge_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(Stage0MergeGeom),
+                                            C.POINTER(Stage0MergeSlab), C.c_int, C.POINTER(Stage0MergeSample), C.c_int]
+    lib.mi355_stage0_gather_merged.argtypes = [C.POINTER(Stage0GatherMergedArgs), C.c_int, vp]
     lib.mi355_stage0_gather_shells.argtypes = [C.POINTER(Stage0GatherArgs), vp]
     lib.mi355_stage0_view_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.POINTER(SkipShareNet), C.c_int, C.c_int,
                                            C.POINTER(Stage0ViewGeom), C.POINTER(Stage0ViewSample), C.c_int]

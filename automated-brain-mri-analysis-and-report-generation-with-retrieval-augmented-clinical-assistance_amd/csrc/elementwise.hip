@@ -225,6 +225,16 @@ struct S0GatherSet {
     float *out;
     int r, C4;
 };
+// voxel (v0, v1, v2) of slab `idx` of axis ax, given the tile voxel (z, y, x) and the face's side: along ax the slab's own layer
+// (a hi slab covers the last t[ax] layers of the tile), across it the tile voxel plus the tile's origin inside the slab
+static __device__ __forceinline__ int64_t s0_slab_voxel(const S0GatherArgs &a, const S0Sample &sm, int ax, int side, int idx, int z, int y, int x) {
+    int v[3] = {z, y, x};
+    if (side) v[ax] -= a.P[ax] - a.t[ax];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] += a.so[ax][k] * sm.org[k];
+    return (((int64_t)idx * a.D[ax][0] + v[0]) * a.D[ax][1] + v[1]) * a.D[ax][2] + v[2];
+}
+
 static __device__ __forceinline__ void stage0_gather_row(const S0GatherArgs &a, const S0GatherSet &t, int m, int Z, int Y) {
     const int r = t.r, C4 = t.C4;
     const f32x4 *wrow = (const f32x4 *)t.wv + (((int64_t)m * a.Ve[0] + Z) * a.Ve[1] + Y) * a.Ve[2] * C4;
@@ -242,15 +252,16 @@ static __device__ __forceinline__ void stage0_gather_row(const S0GatherArgs &a, 
             // the row's source when a z or y shell holds it: slab base (in quads) of voxel x = 0
             const f32x4 *row = nullptr;
             if (sm.slab[0] >= 0 && z < r)
-                row = (const f32x4 *)t.slab[0] + (((int64_t)sm.slab[0] * a.t[0] + z) * a.P[1] + y) * a.P[2] * C4;
+                row = (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, 0, 0, sm.slab[0], z, y, 0) * C4;
             else if (sm.slab[1] >= 0 && z >= a.P[0] - r)
-                row = (const f32x4 *)t.slab[0] + (((int64_t)sm.slab[1] * a.t[0] + (z - (a.P[0] - a.t[0]))) * a.P[1] + y) * a.P[2] * C4;
+                row = (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, 0, 1, sm.slab[1], z, y, 0) * C4;
             else if (sm.slab[2] >= 0 && y < r)
-                row = (const f32x4 *)t.slab[1] + (((int64_t)sm.slab[2] * a.P[0] + z) * a.t[1] + y) * a.P[2] * C4;
+                row = (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, 1, 0, sm.slab[2], z, y, 0) * C4;
             else if (sm.slab[3] >= 0 && y >= a.P[1] - r)
-                row = (const f32x4 *)t.slab[1] + (((int64_t)sm.slab[3] * a.P[0] + z) * a.t[1] + (y - (a.P[1] - a.t[1]))) * a.P[2] * C4;
-            const f32x4 *xlo = sm.slab[4] < 0 ? nullptr : (const f32x4 *)t.slab[2] + (((int64_t)sm.slab[4] * a.P[0] + z) * a.P[1] + y) * a.t[2] * C4;
-            const f32x4 *xhi = sm.slab[5] < 0 ? nullptr : (const f32x4 *)t.slab[2] + (((int64_t)sm.slab[5] * a.P[0] + z) * a.P[1] + y) * a.t[2] * C4;
+                row = (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, 1, 1, sm.slab[3], z, y, 0) * C4;
+            // (the x slabs: base of the slab's voxel that holds tile voxel x = 0, lo, and x = P2 - t2, hi)
+            const f32x4 *xlo = sm.slab[4] < 0 ? nullptr : (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, 2, 0, sm.slab[4], z, y, 0) * C4;
+            const f32x4 *xhi = sm.slab[5] < 0 ? nullptr : (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, 2, 1, sm.slab[5], z, y, a.P[2] - a.t[2]) * C4;
             f32x4 *dst = (f32x4 *)t.out + (((int64_t)n * a.P[0] + z) * a.P[1] + y) * rowq;
             const int qorg = sm.org[2] * C4;
 #pragma unroll
@@ -351,17 +362,17 @@ __global__ __launch_bounds__(256) void stage0_gather_shell_kernel(S0GatherArgs a
     }
     const f32x4 *src;
     if (sm.slab[0] >= 0 && z < r)
-        src = (const f32x4 *)t.slab[0] + ((((int64_t)sm.slab[0] * a.t[0] + z) * a.P[1] + y) * a.P[2] + x) * C4;
+        src = (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, 0, 0, sm.slab[0], z, y, x) * C4;
     else if (sm.slab[1] >= 0 && z >= a.P[0] - r)
-        src = (const f32x4 *)t.slab[0] + ((((int64_t)sm.slab[1] * a.t[0] + (z - (a.P[0] - a.t[0]))) * a.P[1] + y) * a.P[2] + x) * C4;
+        src = (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, 0, 1, sm.slab[1], z, y, x) * C4;
     else if (sm.slab[2] >= 0 && y < r)
-        src = (const f32x4 *)t.slab[1] + ((((int64_t)sm.slab[2] * a.P[0] + z) * a.t[1] + y) * a.P[2] + x) * C4;
+        src = (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, 1, 0, sm.slab[2], z, y, x) * C4;
     else if (sm.slab[3] >= 0 && y >= a.P[1] - r)
-        src = (const f32x4 *)t.slab[1] + ((((int64_t)sm.slab[3] * a.P[0] + z) * a.t[1] + (y - (a.P[1] - a.t[1]))) * a.P[2] + x) * C4;
+        src = (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, 1, 1, sm.slab[3], z, y, x) * C4;
     else if (sm.slab[4] >= 0 && x < r)
-        src = (const f32x4 *)t.slab[2] + ((((int64_t)sm.slab[4] * a.P[0] + z) * a.P[1] + y) * a.t[2] + x) * C4;
+        src = (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, 2, 0, sm.slab[4], z, y, x) * C4;
     else if (sm.slab[5] >= 0 && x >= a.P[2] - r)
-        src = (const f32x4 *)t.slab[2] + ((((int64_t)sm.slab[5] * a.P[0] + z) * a.P[1] + y) * a.t[2] + (x - (a.P[2] - a.t[2]))) * C4;
+        src = (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, 2, 1, sm.slab[5], z, y, x) * C4;
     else   // (not reached: every enumerated voxel lies in a shell)
         src = (const f32x4 *)t.wv + ((((int64_t)sm.wv * a.Ve[0] + sm.org[0] + z) * a.Ve[1] + sm.org[1] + y) * a.Ve[2] + sm.org[2] + x) * C4;
     ((f32x4 *)t.out)[((((int64_t)n * a.P[0] + z) * a.P[1] + y) * a.P[2] + x) * C4 + c4] = src[c4];
@@ -377,6 +388,14 @@ static int stage0_gather_check(const S0GatherArgs &a, int n_samples, int *n_wv) 
     for (int i = 0; i < n_samples; ++i)
         for (int k = 0; k < 3; ++k)
             MI355_REQUIRE(a.smp[i].org[k] >= 0 && a.smp[i].org[k] + a.P[k] <= a.Ve[k], "stage0_gather: sample %d leaves the volume", i);
+    // a slab holds every tile voxel that is read from it: its own thickness along its axis; across it the tile's extent with the
+    // tile at 0, or the volume's with the tile at its origin (inside the volume, above)
+    for (int ax = 0; ax < 3; ++ax)
+        for (int k = 0; k < 3; ++k) {
+            const int want = k == ax ? a.t[k] : (a.so[ax][k] ? a.Ve[k] : a.P[k]);
+            MI355_REQUIRE((a.so[ax][k] == 0 || (a.so[ax][k] == 1 && k != ax)) && a.D[ax][k] == want,
+                          "stage0_gather: slab of axis %d: extent %d along %d (expected %d)", ax, a.D[ax][k], k, want);
+        }
     *n_wv = 0;
     for (int i = 0; i < n_samples; ++i) {
         MI355_REQUIRE(a.smp[i].wv >= 0 && a.smp[i].wv < 65535, "stage0_gather: sample %d: whole-volume index %d", i, a.smp[i].wv);
@@ -752,51 +771,67 @@ int head_aggregate(const HeadWeights &w, const void *feat, int dtype, int first_
     return MI355_OK;
 }
 
+// One tile's term of a voxel, from the logits [n_mirrors][ncls][PV] of that tile: acc[k] += (sum_m mult * nonlin(logits_m))[k] * g and
+// c += g at the tile's voxel (pz, py, px).  The one expression of both kernels below, so that they cannot drift by a rounding.
+static __device__ __forceinline__ void logits_tile_term(const float *logits, int ncls, const MirrorList &ml, int P0, int P1, int P2, int nonlin,
+                                                        const float *gauss, int pz, int py, int px, float acc[HEAD_MAX_CLS], float &c) {
+    const int64_t PV = (int64_t)P0 * P1 * P2;
+    const float mult = 1.0f / (float)ml.n;
+    float res[HEAD_MAX_CLS];
+#pragma unroll
+    for (int k = 0; k < HEAD_MAX_CLS; ++k) res[k] = 0.f;
+    for (int mi = 0; mi < ml.n; ++mi) {
+        const int m = ml.m[mi];
+        const int sz = (m & 1) ? P0 - 1 - pz : pz;
+        const int sy = (m & 2) ? P1 - 1 - py : py;
+        const int sx = (m & 4) ? P2 - 1 - px : px;
+        const int64_t sv = ((int64_t)sz * P1 + sy) * P2 + sx;
+        float lg[HEAD_MAX_CLS];
+#pragma unroll
+        for (int k = 0; k < HEAD_MAX_CLS; ++k) lg[k] = (k < ncls) ? logits[((int64_t)mi * ncls + k) * PV + sv] : 0.f;
+        if (nonlin == MI355_NONLIN_SIGMOID) {
+#pragma unroll
+            for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) lg[k] = 1.0f / (1.0f + expf(-lg[k]));
+        } else if (nonlin == MI355_NONLIN_SOFTMAX) {
+            float mx = lg[0];
+#pragma unroll
+            for (int k = 1; k < HEAD_MAX_CLS; ++k) if (k < ncls) mx = fmaxf(mx, lg[k]);
+            float den = 0.f;
+#pragma unroll
+            for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) { lg[k] = expf(lg[k] - mx); den += lg[k]; }
+#pragma unroll
+            for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) lg[k] = lg[k] / den;
+        }
+#pragma unroll
+        for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) res[k] += mult * lg[k];
+    }
+    const float g = gauss ? gauss[((int64_t)pz * P1 + py) * P2 + px] : 1.0f;
+#pragma unroll
+    for (int k = 0; k < HEAD_MAX_CLS; ++k)
+        if (k < ncls) acc[k] += res[k] * g;
+    c += g;
+}
+
 // Same as head_aggregate_kernel when the last conv already applied the head (logits [n_mirrors][ncls][PV] of this tile).
 __global__ void logits_aggregate_kernel(const float *logits, int ncls, MirrorList ml, int P0, int P1, int P2, int nonlin,
                                         const float *gauss, float *agg, float *cnt, int Zp, int Yp, int Xp, int z0, int y0,
                                         int x0) {
     const int64_t PV = (int64_t)P0 * P1 * P2;
     const int64_t ZYXp = (int64_t)Zp * Yp * Xp;
-    const float mult = 1.0f / (float)ml.n;
     for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < PV; v += (int64_t)gridDim.x * blockDim.x) {
         const int px = (int)(v % P2);
         const int py = (int)((v / P2) % P1);
         const int pz = (int)(v / ((int64_t)P2 * P1));
-        float res[HEAD_MAX_CLS];
-#pragma unroll
-        for (int k = 0; k < HEAD_MAX_CLS; ++k) res[k] = 0.f;
-        for (int mi = 0; mi < ml.n; ++mi) {
-            const int m = ml.m[mi];
-            const int sz = (m & 1) ? P0 - 1 - pz : pz;
-            const int sy = (m & 2) ? P1 - 1 - py : py;
-            const int sx = (m & 4) ? P2 - 1 - px : px;
-            const int64_t sv = ((int64_t)sz * P1 + sy) * P2 + sx;
-            float lg[HEAD_MAX_CLS];
-#pragma unroll
-            for (int k = 0; k < HEAD_MAX_CLS; ++k) lg[k] = (k < ncls) ? logits[((int64_t)mi * ncls + k) * PV + sv] : 0.f;
-            if (nonlin == MI355_NONLIN_SIGMOID) {
-#pragma unroll
-                for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) lg[k] = 1.0f / (1.0f + expf(-lg[k]));
-            } else if (nonlin == MI355_NONLIN_SOFTMAX) {
-                float mx = lg[0];
-#pragma unroll
-                for (int k = 1; k < HEAD_MAX_CLS; ++k) if (k < ncls) mx = fmaxf(mx, lg[k]);
-                float den = 0.f;
-#pragma unroll
-                for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) { lg[k] = expf(lg[k] - mx); den += lg[k]; }
-#pragma unroll
-                for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) lg[k] = lg[k] / den;
-            }
-#pragma unroll
-            for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) res[k] += mult * lg[k];
-        }
-        const float g = gauss ? gauss[v] : 1.0f;
         const int64_t gi = ((int64_t)(z0 + pz) * Yp + (y0 + py)) * Xp + (x0 + px);
+        float acc[HEAD_MAX_CLS];
+#pragma unroll
+        for (int k = 0; k < HEAD_MAX_CLS; ++k) acc[k] = (k < ncls) ? agg[k * ZYXp + gi] : 0.f;
+        float c = cnt ? cnt[gi] : 0.f;
+        logits_tile_term(logits, ncls, ml, P0, P1, P2, nonlin, gauss, pz, py, px, acc, c);
 #pragma unroll
         for (int k = 0; k < HEAD_MAX_CLS; ++k)
-            if (k < ncls) agg[k * ZYXp + gi] += res[k] * g;
-        if (cnt) cnt[gi] += g;
+            if (k < ncls) agg[k * ZYXp + gi] = acc[k];
+        if (cnt) cnt[gi] = c;
     }
 }
 
@@ -811,9 +846,84 @@ int logits_aggregate(const float *logits, int ncls, int first_sample, const int 
     int64_t blocks = (PV + 255) / 256;
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(logits_aggregate_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
-                       logits + (size_t)first_sample * ncls * PV, ncls, ml, P0, P1, P2, nonlin, gauss, agg, cnt, Zp, Yp, Xp, z0,
-                       y0, x0);
+                       logits + (size_t)first_sample * ncls * PV, ncls, ml, P0, P1, P2, nonlin, gauss, agg, cnt, Zp, Yp, Xp, z0, y0,
+                       x0);
     MI355_HIP(hipGetLastError());
+    return MI355_OK;
+}
+
+// The tiles of one forward in ONE launch: a launch per tile reads and rewrites agg / cnt once per tile, eight times for a voxel that
+// eight tiles cover.  One thread = one voxel of the padded grid inside the bounding box [lo, lo + B) of the tiles; it loads agg / cnt
+// once, walks the tiles in their order - tile i's logits are samples i * n_mirrors .. of `logits` - and adds, for each tile that
+// holds the voxel, that tile's term (logits_tile_term) to the value it carries: the same additions in the same order as the
+// launches per tile, so the result is bit-identical.  A voxel that no tile holds is not written.
+struct AggTileList {
+    int n;
+    int org[LOGITS_AGG_MAX_TILES][3];
+};
+__global__ __launch_bounds__(256) void logits_aggregate_tiles_kernel(const float *logits, int ncls, MirrorList ml, int P0, int P1, int P2, int nonlin,
+                                                                     const float *gauss, float *agg, float *cnt, int Zp, int Yp, int Xp, AggTileList tl,
+                                                                     int lo0, int lo1, int lo2, int B0, int B1, int B2) {
+    const int64_t PV = (int64_t)P0 * P1 * P2;
+    const int64_t ZYXp = (int64_t)Zp * Yp * Xp;
+    const int64_t BV = (int64_t)B0 * B1 * B2;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < BV; v += (int64_t)gridDim.x * blockDim.x) {
+        const int x = lo2 + (int)(v % B2);
+        const int y = lo1 + (int)((v / B2) % B1);
+        const int z = lo0 + (int)(v / ((int64_t)B2 * B1));
+        const int64_t gi = ((int64_t)z * Yp + y) * Xp + x;
+        float acc[HEAD_MAX_CLS];
+        float c = 0.f;
+        bool held = false;
+        for (int i = 0; i < tl.n; ++i) {
+            const int pz = z - tl.org[i][0], py = y - tl.org[i][1], px = x - tl.org[i][2];
+            if ((unsigned)pz >= (unsigned)P0 || (unsigned)py >= (unsigned)P1 || (unsigned)px >= (unsigned)P2) continue;
+            if (!held) {
+#pragma unroll
+                for (int k = 0; k < HEAD_MAX_CLS; ++k) acc[k] = (k < ncls) ? agg[k * ZYXp + gi] : 0.f;
+                c = cnt ? cnt[gi] : 0.f;
+                held = true;
+            }
+            logits_tile_term(logits + (int64_t)i * ml.n * ncls * PV, ncls, ml, P0, P1, P2, nonlin, gauss, pz, py, px, acc, c);
+        }
+        if (!held) continue;
+#pragma unroll
+        for (int k = 0; k < HEAD_MAX_CLS; ++k)
+            if (k < ncls) agg[k * ZYXp + gi] = acc[k];
+        if (cnt) cnt[gi] = c;
+    }
+}
+
+// origins_host: [n_tiles][3], inside the padded grid (the caller checks).  More than LOGITS_AGG_MAX_TILES tiles run as consecutive
+// launches in order, each over the bounding box of its own tiles.
+int logits_aggregate_tiles(const float *logits, int ncls, int first_sample, const int *mirrors_host, int n_mirrors, int P0, int P1, int P2,
+                           int nonlin, const float *gauss, float *agg, float *cnt, int Zp, int Yp, int Xp, const int *origins_host, int n_tiles,
+                           hipStream_t s) {
+    MI355_REQUIRE(n_mirrors >= 1 && n_mirrors <= 8 && ncls >= 1 && ncls <= HEAD_MAX_CLS && n_tiles >= 1, "logits_aggregate_tiles: bad arguments");
+    MirrorList ml;
+    ml.n = n_mirrors;
+    for (int i = 0; i < 8; ++i) ml.m[i] = i < n_mirrors ? mirrors_host[i] : 0;
+    const int64_t PV = (int64_t)P0 * P1 * P2;
+    const int P[3] = {P0, P1, P2};
+    for (int t0 = 0; t0 < n_tiles; t0 += LOGITS_AGG_MAX_TILES) {
+        AggTileList tl = {};
+        tl.n = std::min(LOGITS_AGG_MAX_TILES, n_tiles - t0);
+        int lo[3], hi[3];
+        for (int i = 0; i < tl.n; ++i)
+            for (int a = 0; a < 3; ++a) {
+                const int o = origins_host[(size_t)(t0 + i) * 3 + a];
+                tl.org[i][a] = o;
+                lo[a] = i ? std::min(lo[a], o) : o;
+                hi[a] = i ? std::max(hi[a], o + P[a]) : o + P[a];
+            }
+        const int64_t BV = (int64_t)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
+        int64_t blocks = (BV + 255) / 256;
+        if (blocks > 65536) blocks = 65536;
+        hipLaunchKernelGGL(logits_aggregate_tiles_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
+                           logits + ((size_t)first_sample + (size_t)t0 * n_mirrors) * ncls * PV, ncls, ml, P0, P1, P2, nonlin, gauss, agg, cnt, Zp, Yp,
+                           Xp, tl, lo[0], lo[1], lo[2], hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]);
+        MI355_HIP(hipGetLastError());
+    }
     return MI355_OK;
 }
 

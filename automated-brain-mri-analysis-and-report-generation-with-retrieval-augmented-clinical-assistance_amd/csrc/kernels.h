@@ -171,6 +171,10 @@ struct S0GatherArgs {
     const float *slab[3];  // per axis a: [n_slabs][S0][S1][S2][C], S[a] = t[a], S[k] = P[k] otherwise
     float *out;            // [n_samples][P0][P1][P2][C]
     int P[3], Ve[3], t[3];
+    // Merged slabs (unet.hip "merged slabs"): D[a] = extent of one slab of axis a - t[a] along a; along k != a either P[k] (the slab
+    // carries the tile's own padding: the tile starts at 0 in it) or Ve[k] (the slab spans the volume: the tile starts at its origin,
+    // so[a][k] = 1).  stage0_gather_dense() fills the per-tile form: D[a][k] = P[k], so = 0.
+    int D[3][3], so[3][3];
     int r;                 // voxel layers taken from a slab at each of its faces
     int C4;                // C / 4
     // optional second tensor gathered for the same samples (out2 == nullptr: none): the shared skip half of the last decoder
@@ -182,6 +186,11 @@ struct S0GatherArgs {
     int n;                 // samples (set by stage0_gather)
     S0Sample smp[S0_MAX_SAMPLES];
 };
+// the slabs of every axis have the tile's extent across their axis (the form before merged slabs)
+inline void stage0_gather_dense(S0GatherArgs *a) {
+    for (int ax = 0; ax < 3; ++ax)
+        for (int k = 0; k < 3; ++k) { a->D[ax][k] = k == ax ? a->t[k] : a->P[k]; a->so[ax][k] = 0; }
+}
 // fp32 NDHWC, 16 bytes per lane.  Where the shells of two or three faces meet the first face in the order above wins.
 int stage0_gather(const S0GatherArgs &a, int n_samples, hipStream_t s);
 // The same for a tensor whose reader takes a stage-0 view (S0View): only the voxels within r of a face that has a slab are written,
@@ -229,6 +238,12 @@ int head_aggregate(const HeadWeights &w, const void *feat, int dtype, int first_
 int logits_aggregate(const float *logits, int ncls, int first_sample, const int *mirrors_host, int n_mirrors, int P0, int P1,
                      int P2, int nonlin, const float *gauss, float *agg, float *cnt, int Zp, int Yp, int Xp, int z0, int y0,
                      int x0, hipStream_t s);
+// The same for n_tiles tiles of one forward in one launch (per LOGITS_AGG_MAX_TILES tiles): tile i's logits are samples
+// first_sample + i * n_mirrors .., its origin origins_host[3 i ..]; bit-identical to logits_aggregate called tile by tile in order.
+constexpr int LOGITS_AGG_MAX_TILES = 64;
+int logits_aggregate_tiles(const float *logits, int ncls, int first_sample, const int *mirrors_host, int n_mirrors, int P0, int P1, int P2,
+                           int nonlin, const float *gauss, float *agg, float *cnt, int Zp, int Yp, int Xp, const int *origins_host, int n_tiles,
+                           hipStream_t s);
 // probs[c][z][y][x] (+)= agg[c][z+pz][y+py][x+px] / cnt[...]; then optional scale (fold mean)
 int finish_probs(const float *agg, const float *cnt, int C, int Z, int Y, int X, int Zp, int Yp, int Xp,
                  int pz, int py, int px, float *probs, int accumulate, hipStream_t s);

@@ -7,9 +7,11 @@
 //   * nnU-Net v1 SegmentationNetwork._internal_predict_3D_3Dconv_tiled / _compute_steps_for_
 //     sliding_window / _get_gaussian / _internal_maybe_mirror_and_pred_3D (un-vendored upstream;
 //     SURVEY.md 8a rows T1-T5) as driven by run_brats2021_inference_singlethread.py:97-128.
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -663,6 +665,7 @@ static int make_geom(const mi355_sw_opts &o, int Z, int Y, int X, SwGeom *g) {
 // planner picks, and with it the summation order, must not change with the number of tiles a rank or batch happens to hold.
 // Coordinates: a mirrored pass works on the flipped padded volume, where a tile's origin along a flipped axis is Zp - P - origin.
 constexpr int S0_SLAB_GROUP = 8;  // (8 slabs of 4 x 128 x 128: 2048 tiles of the F(2x2x2,3x3x3) kernel, 8 per CU)
+struct S0Merged { int wv, side, org[3]; };  // a merged slab: its (mirrored) pass, the side of the faces it serves, its origin in that pass
 struct S0Geom {
     bool shared = false;
     int r = 0;
@@ -671,6 +674,11 @@ struct S0Geom {
     int t[3] = {0, 0, 0};          // slab thickness per axis: the smallest multiple of (4, 8, 8) that is >= 2 rs
     int max_faces[3] = {0, 0, 0};  // most interior faces any tile has on an axis
     std::vector<S0Sample> smp;     // [tile][mirror]; slab[f] = 0 where face f needs a slab, -1 where it is a volume face
+    // merged slabs (stage0_merge_geometry): the y- and x-slabs of ALL tiles, one per key, sorted by key
+    bool merge = false;
+    std::vector<S0Merged> merged[3];         // [1] y-slabs, [2] x-slabs ([0] stays empty: z-slabs are per tile)
+    int mdim[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // extent of one slab of each axis
+    std::vector<std::array<int, 6>> mslab;   // per sample: index of face f (2 .. 5) in merged[f >> 1], or -1
 };
 
 static void stage0_geometry(const SwGeom &g, int r, S0Geom *o, int extra = 0) {
@@ -698,6 +706,51 @@ static void stage0_geometry(const SwGeom &g, int r, S0Geom *o, int extra = 0) {
             }
             o->smp.push_back(sm);
         }
+}
+
+// ---- merged slabs (MI355_MERGE_SLABS).  Tiles that share a cut plane compute nearly the same y- and x-slabs.  The gather takes
+// a voxel from the first shell that holds it, z before y before x, and that order decides which padding a slab must reproduce:
+//   * a z-slab serves every voxel within the shell depth of an interior z face, the edges and corners it shares with y and x
+//     faces included: it needs the tile's own y and x padding and stays per tile (stage0_tiles);
+//   * a y-slab serves voxels within the depth of an interior y face and NOT within it of an interior z face: their receptive
+//     field crosses a z face of the tile only where that is a volume face, so the slab may span the whole extended volume in z
+//     (zeros outside [0, Zp0) restored between the layers as in the whole-volume pass).  It still carries the tile's x padding,
+//     for the y-x edge.  Key (mirror, side, y of the slab, x origin of the tile), box Ve0 x t1 x P2;
+//   * an x-slab serves voxels in neither other shell and needs no tile padding.  Key (mirror, side, x of the slab), box
+//     Ve0 x Ve1 x t2.
+// The keys are a function of the network and the geometry of all tiles; every rank computes all of them, once per volume, right
+// behind the whole-volume pass, in one launch group per axis with N = number of keys - so the kernel the planner picks, and the
+// summation order with it, cannot depend on who asks.  A rank of a tile-sharded run pays for slabs of tiles it does not hold.
+static void stage0_merge_geometry(const SwGeom &g, S0Geom *o) {
+    for (int a = 0; a < 3; ++a) o->merged[a].clear();
+    o->mslab.clear();
+    o->merge = false;
+    if (!o->shared) return;
+    const int dims[3][3] = {{o->t[0], g.P[1], g.P[2]}, {o->Ve[0], o->t[1], g.P[2]}, {o->Ve[0], o->Ve[1], o->t[2]}};
+    memcpy(o->mdim, dims, sizeof(dims));
+    typedef std::array<int, 5> Key;  // (wv, side, origin): sorted = the order of the slabs
+    auto key_of = [&](const S0Sample &sm, int a, int side) {
+        Key k = {sm.wv, side, 0, 0, 0};
+        k[2 + a] = sm.org[a] + (side ? g.P[a] - o->t[a] : 0);
+        if (a == 1) k[4] = sm.org[2];
+        return k;
+    };
+    std::map<Key, int> keys[3];
+    for (const S0Sample &sm : o->smp)
+        for (int f = 2; f < 6; ++f)
+            if (sm.slab[f] >= 0) keys[f >> 1][key_of(sm, f >> 1, f & 1)] = 0;
+    for (int a = 1; a < 3; ++a)
+        for (auto &kv : keys[a]) {
+            kv.second = (int)o->merged[a].size();
+            o->merged[a].push_back(S0Merged{kv.first[0], kv.first[1], {kv.first[2], kv.first[3], kv.first[4]}});
+        }
+    for (const S0Sample &sm : o->smp) {
+        std::array<int, 6> idx = {-1, -1, -1, -1, -1, -1};
+        for (int f = 2; f < 6; ++f)
+            if (sm.slab[f] >= 0) idx[f] = keys[f >> 1][key_of(sm, f >> 1, f & 1)];
+        o->mslab.push_back(idx);
+    }
+    o->merge = !o->merged[1].empty() || !o->merged[2].empty();
 }
 
 // blocks of enc[0] when the network allows the shared stage 0, else 0
@@ -773,6 +826,8 @@ static void stage0_plan(const mi355_unet &net, const SwGeom &g, const S0Geom &sg
         int S[3];
         slab_dims(g, sg, a, S);
         sl_a[a] = (size_t)ceil_div(n_samples * sg.max_faces[a], S0_SLAB_GROUP) * S0_SLAB_GROUP * S[0] * S[1] * S[2];
+        if (sg.merge && a > 0)  // merged slabs: every key's slab, for all mirrors, lives from the whole-volume pass to the last forward
+            sl_a[a] = sg.merged[a].size() * (size_t)sg.mdim[a][0] * sg.mdim[a][1] * sg.mdim[a][2];
         sl = std::max(sl, sl_a[a]);
     }
     pl->s0.wv_in = take(wv * net.cin_pad * 4);
@@ -799,15 +854,17 @@ static TileDesc pass_box(const SwGeom &g, int mirror, const int b[3], const int 
 
 // enc[0] over n boxes of S voxels each, gathered from the volume: `in` receives the input, the last block writes `out`.
 // group > 0: the convs run as launches of exactly `group` boxes each (n is a multiple of it).
+// label: suffix of the gather's profile entry (the merged slabs name theirs).
 // skip_off != 0 (shared skip half): one more launch behind the last block - the skip half of the last decoder stage's first conv,
 // zero bias, no activation - writes S there.
 static int stage0_run(mi355_unet *net, const Plan &pl, const float *vol, int Z, int Y, int X, const SwGeom &g, const std::vector<TileDesc> &boxes,
-                      const int S[3], const int *mask_zp, int group, size_t in_off, const size_t tmp_off[2], size_t out_off, size_t skip_off, hipStream_t s) {
+                      const int S[3], const int *mask_zp, int group, size_t in_off, const size_t tmp_off[2], size_t out_off, size_t skip_off, hipStream_t s,
+                      const char *label = "") {
     const int n = (int)boxes.size();
     const size_t vox = (size_t)S[0] * S[1] * S[2];
     for (int b0 = 0; b0 < n; b0 += S0_MAX_SAMPLES) {
         const int nb = std::min(S0_MAX_SAMPLES, n - b0);
-        ProfScope ps(net, s, "extract_tiles_kernel", 0.0, (double)nb * vox * 4.0 * (net->in_channels + net->cin_pad));
+        ProfScope ps(net, s, std::string("extract_tiles_kernel") + label, 0.0, (double)nb * vox * 4.0 * (net->in_channels + net->cin_pad));
         MI355_TRY(extract_tiles(vol, net->in_channels, Z, Y, X, g.pad_lo[0], g.pad_lo[1], g.pad_lo[2], boxes.data() + b0, nb, S[0], S[1], S[2],
                                 net->cin_pad, (void *)(pl.arena + in_off + (size_t)b0 * vox * net->cin_pad * 4), net->dtype, s));
     }
@@ -846,6 +903,21 @@ static int stage0_whole(mi355_unet *net, const Plan &pl, const float *vol, int Z
     for (int m : g.mirrors) boxes.push_back(pass_box(g, m, zero, sg.Ve));
     const bool extended = sg.Ve[0] != g.Zp[0] || sg.Ve[1] != g.Zp[1] || sg.Ve[2] != g.Zp[2];
     return stage0_run(net, pl, vol, Z, Y, X, g, boxes, sg.Ve, extended ? g.Zp : nullptr, 0, pl.s0.wv_in, pl.s0.wv_tmp, pl.s0.wv_out, pl.s0.wv_skip, s);
+}
+
+// merged y- and x-slabs: every key, one launch group per axis (stage0_merge_geometry)
+static int stage0_merged(mi355_unet *net, const Plan &pl, const float *vol, int Z, int Y, int X, const SwGeom &g, const S0Geom &sg, hipStream_t s) {
+    for (int a = 1; a < 3; ++a) {
+        if (sg.merged[a].empty()) continue;
+        std::vector<TileDesc> boxes;
+        for (const S0Merged &k : sg.merged[a]) boxes.push_back(pass_box(g, g.mirrors[k.wv], k.org, sg.mdim[a]));
+        // along the axes a slab spans the extended volume it holds [Zp, Ve), which is zero in front of every conv
+        const int keep[3] = {g.Zp[0], a == 1 ? sg.mdim[a][1] : g.Zp[1], sg.mdim[a][2]};
+        const bool extended = keep[0] != sg.mdim[a][0] || keep[1] != sg.mdim[a][1];
+        MI355_TRY(stage0_run(net, pl, vol, Z, Y, X, g, boxes, sg.mdim[a], extended ? keep : nullptr, 0, pl.s0.slab_in, pl.s0.slab_tmp, pl.s0.slab_out[a],
+                             pl.s0.slab_skip[a], s, " merged-slabs"));
+    }
+    return MI355_OK;
 }
 
 // ---- stage-0 views (MI355_STAGE0_VIEWS).  The gather above copies, per tile, mostly values that already lie in the whole-volume
@@ -894,6 +966,13 @@ static int stage0_tiles(mi355_unet *net, const Plan &pl, const float *vol, int Z
     for (int a = 0; a < 3; ++a) {
         int S[3];
         slab_dims(g, sg, a, S);
+        if (sg.merge && a > 0) {  // merged slabs: computed behind the whole-volume pass, the sample's faces index them
+            for (int i = 0; i < n; ++i)
+                for (int side = 0; side < 2; ++side) ga.smp[i].slab[2 * a + side] = sg.mslab[samples[i]][2 * a + side];
+            ga.slab[a] = (const float *)(pl.arena + pl.s0.slab_out[a]);
+            ga.slab2[a] = (const float *)(pl.arena + pl.s0.slab_skip[a]);
+            continue;
+        }
         std::vector<TileDesc> boxes;
         for (int i = 0; i < n; ++i)
             for (int side = 0; side < 2; ++side) {
@@ -913,6 +992,10 @@ static int stage0_tiles(mi355_unet *net, const Plan &pl, const float *vol, int Z
     ga.wv = (const float *)(pl.arena + pl.s0.wv_out);
     ga.out = (float *)(pl.arena + pl.off[(net->enc[0].size() - 1) & 1][0]);
     for (int a = 0; a < 3; ++a) { ga.P[a] = g.P[a]; ga.Ve[a] = sg.Ve[a]; ga.t[a] = sg.t[a]; }
+    stage0_gather_dense(&ga);
+    if (sg.merge)
+        for (int a = 1; a < 3; ++a)
+            for (int k = 0; k < 3; ++k) { ga.D[a][k] = sg.mdim[a][k]; ga.so[a][k] = k < a && (k == 0 || a == 2); }
     ga.r = sg.r; ga.C4 = C / 4;
     int C2 = 0;
     if (sg.rs > sg.r) {  // shared skip half: S rides along, into the level-0 buffer that is not the skip's
@@ -977,10 +1060,12 @@ static int sw_accumulate(mi355_unet *net, const float *vol, int Z, int Y, int X,
     S0Geom sg;
     const bool share_skip = skip_share_decide(skip_share_net(*net), g);
     stage0_geometry(g, stage0_blocks(*net), &sg, share_skip ? 1 : 0);
+    if (env_switch("MI355_MERGE_SLABS")) stage0_merge_geometry(g, &sg);
     if (sg.shared) stage0_plan(*net, g, sg, bt * nm, &pl);
     MI355_TRY(ensure_arena(&pl, s));
     if (mine.empty()) return MI355_OK;
     if (sg.shared) MI355_TRY(stage0_whole(net, pl, vol, Z, Y, X, g, sg, s));
+    if (sg.merge) MI355_TRY(stage0_merged(net, pl, vol, Z, Y, X, g, sg, s));
     for (size_t b0 = 0; b0 < mine.size(); b0 += bt) {
         const int nb = (int)std::min<size_t>(bt, mine.size() - b0);
         std::vector<TileDesc> samples;
@@ -1009,16 +1094,28 @@ static int sw_accumulate(mi355_unet *net, const float *vol, int Z, int Y, int X,
                                    share_skip ? (const float *)(pl.arena + pl.off[((net->enc[0].size() - 1) & 1) ^ 1][0]) : nullptr,
                                    enc0_view.src ? &enc0_view : nullptr, half_view.src ? &half_view : nullptr));
         MI355_REQUIRE(is_logits || fc == net->head.cin, "head expects %d channels, decoder gives %d", net->head.cin, fc);
+        if (is_logits) {  // the forward's tiles in one launch: agg / cnt are read and written once per voxel, not once per tile
+            std::vector<int> origins;
+            int lo[3], hi[3];
+            for (int i = 0; i < nb; ++i) {
+                const TileDesc &td = g.tiles[mine[b0 + i]];
+                const int org[3] = {td.z0, td.y0, td.x0};
+                for (int a = 0; a < 3; ++a) {
+                    origins.push_back(org[a]);
+                    lo[a] = i ? std::min(lo[a], org[a]) : org[a];
+                    hi[a] = i ? std::max(hi[a], org[a] + g.P[a]) : org[a] + g.P[a];
+                }
+            }
+            const double pv = (double)g.P[0] * g.P[1] * g.P[2], box = (double)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
+            ProfScope ps(net, s, "logits_aggregate_tiles_kernel", 0.0, 4.0 * (nb * pv * (nm * net->num_classes + 1.0) + box * (2.0 * net->num_classes + 2.0)));
+            MI355_TRY(logits_aggregate_tiles((const float *)feat, net->num_classes, 0, g.mirrors.data(), nm, g.P[0], g.P[1], g.P[2], o.nonlin,
+                                             use_gauss ? net->gauss_dev : nullptr, agg, (cnt && world == 1) ? cnt : nullptr, g.Zp[0], g.Zp[1],
+                                             g.Zp[2], origins.data(), nb, s));
+            continue;
+        }
         for (int i = 0; i < nb; ++i) {
             const TileDesc &td = g.tiles[mine[b0 + i]];
             const double pv = (double)g.P[0] * g.P[1] * g.P[2];
-            if (is_logits) {
-                ProfScope ps(net, s, "logits_aggregate_kernel", 0.0, 4.0 * pv * (nm * net->num_classes + 2.0 * net->num_classes + 3.0));
-                MI355_TRY(logits_aggregate((const float *)feat, net->num_classes, i * nm, g.mirrors.data(), nm, g.P[0], g.P[1], g.P[2],
-                                           o.nonlin, use_gauss ? net->gauss_dev : nullptr, agg, (cnt && world == 1) ? cnt : nullptr,
-                                           g.Zp[0], g.Zp[1], g.Zp[2], td.z0, td.y0, td.x0, s));
-                continue;
-            }
             ProfScope ps(net, s, "head_aggregate_kernel", 2.0 * pv * nm * fc * net->num_classes,
                          pv * ((net->dtype == MI355_F16 ? 2.0 : 4.0) * nm * fc + 4.0 * (2.0 * net->num_classes + 3.0)));
             MI355_TRY(head_aggregate(net->head, feat, net->dtype, i * nm, g.mirrors.data(), nm, g.P[0], g.P[1], g.P[2], o.nonlin,
@@ -1586,6 +1683,61 @@ extern "C" int mi355_stage0_plan(int z, int y, int x, const int32_t patch[3], fl
     return n;
 }
 
+extern "C" int mi355_stage0_merge_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes, int r, int skip_half,
+                                       mi355_stage0_merge_geom *out, mi355_stage0_merge_slab *slabs, int max_slabs,
+                                       mi355_stage0_merge_sample *samples, int max_samples) {
+    MI355_REQUIRE(out && patch && r >= 0 && (slabs || max_slabs == 0) && (samples || max_samples == 0), "mi355_stage0_merge_plan: bad argument");
+    mi355_sw_opts o;
+    memset(&o, 0, sizeof(o));
+    for (int a = 0; a < 3; ++a) o.patch[a] = patch[a];
+    o.step_size = step_size; o.mirror_axes = mirror_axes;
+    SwGeom g;
+    MI355_TRY(make_geom(o, z, y, x, &g));
+    S0Geom sg;
+    stage0_geometry(g, r, &sg, skip_half ? 1 : 0);
+    stage0_merge_geometry(g, &sg);
+    memset(out, 0, sizeof(*out));
+    out->shared = sg.shared; out->r = sg.r; out->rs = sg.rs;
+    out->n_tiles = (int32_t)g.tiles.size(); out->n_mirrors = (int32_t)g.mirrors.size();
+    for (int a = 0; a < 3; ++a) { out->padded[a] = g.Zp[a]; out->volume[a] = sg.Ve[a]; out->slab_thickness[a] = sg.t[a]; }
+    if (!sg.shared) return 0;
+    for (int a = 0; a < 3; ++a) {
+        int S[3];
+        slab_dims(g, sg, a, S);
+        int64_t faces = 0;
+        for (const S0Sample &sm : sg.smp) faces += (sm.slab[2 * a] >= 0) + (sm.slab[2 * a + 1] >= 0);
+        out->voxels_per_tile += faces * S[0] * S[1] * S[2];
+        out->n_slabs[a] = a ? (int32_t)sg.merged[a].size() : (int32_t)faces;
+        for (int k = 0; k < 3; ++k) out->slab_shape[a][k] = sg.mdim[a][k];
+        out->voxels[a] = (int64_t)out->n_slabs[a] * sg.mdim[a][0] * sg.mdim[a][1] * sg.mdim[a][2];
+    }
+    int ns = 0;
+    for (int a = 1; a < 3; ++a)
+        for (const S0Merged &k : sg.merged[a]) {
+            if (ns < max_slabs) {
+                mi355_stage0_merge_slab &q = slabs[ns];
+                q.axis = a; q.mirror = g.mirrors[k.wv]; q.side = k.side;
+                for (int c = 0; c < 3; ++c) q.origin[c] = k.org[c];
+            }
+            ++ns;
+        }
+    const int n = (int)sg.smp.size();
+    for (int i = 0; i < n && i < max_samples; ++i) {
+        const S0Sample &sm = sg.smp[i];
+        mi355_stage0_merge_sample &q = samples[i];
+        memset(&q, 0, sizeof(q));
+        q.tile = i / (int)g.mirrors.size(); q.mirror = g.mirrors[sm.wv];
+        for (int a = 0; a < 3; ++a) q.origin[a] = sm.org[a];
+        for (int f = 0; f < 6; ++f) {
+            const int a = f >> 1;
+            q.slab[f] = a == 0 ? sm.slab[f] : sg.mslab[i][f];
+            if (q.slab[f] < 0 || a == 0) continue;
+            for (int k = 0; k < 3; ++k) q.offset[f][k] = sm.org[k] + (k == a && (f & 1) ? g.P[a] - sg.t[a] : 0) - sg.merged[a][q.slab[f]].org[k];
+        }
+    }
+    return n;
+}
+
 extern "C" int mi355_skip_share_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes,
                                      const mi355_skip_share_net *nd, int batch_tiles, int rank, int world, mi355_skip_share_geom *out) {
     MI355_REQUIRE(out && patch && nd && batch_tiles >= 0 && world >= 1 && rank >= 0 && rank < world, "mi355_skip_share_plan: bad argument");
@@ -1850,6 +2002,22 @@ extern "C" int mi355_logits_aggregate(const float *logits_dev, int ncls, int fir
                   s, "logits_aggregate");
 }
 
+extern "C" int mi355_logits_aggregate_tiles(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
+                                            const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *cnt_dev,
+                                            const int32_t padded[3], const int32_t *origins, int n_tiles, void *stream) {
+    MI355_REQUIRE(logits_dev && mirrors_host && patch && agg_dev && padded && origins && first_sample >= 0 && n_tiles >= 1,
+                  "mi355_logits_aggregate_tiles: bad argument");
+    for (int i = 0; i < n_tiles; ++i)
+        MI355_REQUIRE(tile_in_grid(patch, padded, origins + 3 * (size_t)i), "mi355_logits_aggregate_tiles: tile %d leaves the padded grid", i);
+    MI355_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> mirrors(mirrors_host, mirrors_host + std::max(n_mirrors, 0));
+    std::vector<int> org(origins, origins + 3 * (size_t)n_tiles);
+    return synced(logits_aggregate_tiles(logits_dev, ncls, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev,
+                                         agg_dev, cnt_dev, padded[0], padded[1], padded[2], org.data(), n_tiles, s),
+                  s, "logits_aggregate_tiles");
+}
+
 extern "C" int mi355_cnt_add_tile(const float *gauss_dev, const int32_t patch[3], float *cnt_dev, const int32_t padded[3],
                                   const int32_t origin[3], void *stream) {
     MI355_REQUIRE(patch && cnt_dev && padded && origin, "mi355_cnt_add_tile: bad argument");
@@ -1869,6 +2037,7 @@ static int stage0_gather_abi(const mi355_stage0_gather_args *a, void *stream, bo
     ga.wv = a->wv_dev; ga.out = a->out_dev;
     for (int k = 0; k < 3; ++k) { ga.slab[k] = a->slab_dev[k]; ga.P[k] = a->patch[k]; ga.Ve[k] = a->volume[k]; ga.t[k] = a->slab_thickness[k]; }
     ga.r = a->r; ga.C4 = a->channels / 4;
+    stage0_gather_dense(&ga);
     for (int i = 0; i < a->n_samples; ++i) {
         S0Sample &sm = ga.smp[i];
         sm.wv = a->samples[i].wv;
@@ -1885,6 +2054,46 @@ static int stage0_gather_abi(const mi355_stage0_gather_args *a, void *stream, bo
 }
 extern "C" int mi355_stage0_gather(const mi355_stage0_gather_args *a, void *stream) { return stage0_gather_abi(a, stream, false); }
 extern "C" int mi355_stage0_gather_shells(const mi355_stage0_gather_args *a, void *stream) { return stage0_gather_abi(a, stream, true); }
+
+extern "C" int mi355_stage0_gather_merged(const mi355_stage0_gather_merged_args *m, int shells_only, void *stream) {
+    MI355_REQUIRE(m, "mi355_stage0_gather_merged: bad argument");
+    const mi355_stage0_gather_args *a = &m->base;
+    MI355_REQUIRE(a->wv_dev && a->out_dev && a->channels > 0 && a->channels % 4 == 0, "mi355_stage0_gather_merged: bad argument");
+    MI355_REQUIRE(a->n_samples > 0 && a->n_samples <= S0_MAX_SAMPLES, "mi355_stage0_gather_merged: %d samples (max %d)", a->n_samples, S0_MAX_SAMPLES);
+    MI355_REQUIRE(!m->out2_dev || (m->wv2_dev && m->channels2 > 0 && m->channels2 % 4 == 0), "mi355_stage0_gather_merged: bad second tensor");
+    MI355_TRY(require_device());
+    S0GatherArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.wv = a->wv_dev; ga.out = a->out_dev;
+    for (int k = 0; k < 3; ++k) { ga.slab[k] = a->slab_dev[k]; ga.P[k] = a->patch[k]; ga.Ve[k] = a->volume[k]; ga.t[k] = a->slab_thickness[k]; }
+    ga.r = a->r; ga.C4 = a->channels / 4;
+    if (m->out2_dev) {
+        ga.wv2 = m->wv2_dev; ga.out2 = m->out2_dev; ga.r2 = m->r2; ga.C42 = m->channels2 / 4;
+        for (int k = 0; k < 3; ++k) ga.slab2[k] = m->slab2_dev[k];
+    }
+    for (int ax = 0; ax < 3; ++ax)
+        for (int k = 0; k < 3; ++k) {
+            ga.D[ax][k] = m->slab_shape[ax][k];
+            MI355_REQUIRE(m->spans_volume[ax][k] == 0 || m->spans_volume[ax][k] == 1, "mi355_stage0_gather_merged: spans_volume[%d][%d]", ax, k);
+            ga.so[ax][k] = m->spans_volume[ax][k];
+        }
+    for (int i = 0; i < a->n_samples; ++i) {
+        S0Sample &sm = ga.smp[i];
+        sm.wv = a->samples[i].wv;
+        MI355_REQUIRE(sm.wv >= 0, "mi355_stage0_gather_merged: sample %d: whole-volume index %d", i, sm.wv);
+        for (int k = 0; k < 3; ++k) sm.org[k] = a->samples[i].origin[k];
+        for (int f = 0; f < 6; ++f) {
+            sm.slab[f] = a->samples[i].slab[f];
+            MI355_REQUIRE(sm.slab[f] < 0 || (a->slab_dev[f >> 1] && (!m->out2_dev || m->slab2_dev[f >> 1])),
+                          "mi355_stage0_gather_merged: sample %d: face %d without a slab tensor", i, f);
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (!shells_only) return synced(stage0_gather(ga, a->n_samples, s), s, "stage0_gather");
+    MI355_TRY(stage0_gather_shells(ga, a->n_samples, 0, s));
+    if (ga.out2) MI355_TRY(stage0_gather_shells(ga, a->n_samples, 1, s));
+    return synced(MI355_OK, s, "stage0_gather_shells");
+}
 
 extern "C" int mi355_stage0_mask(float *x_dev, int n, const int32_t volume[3], const int32_t keep[3], int c, void *stream) {
     MI355_REQUIRE(x_dev && volume && keep, "mi355_stage0_mask: bad argument");

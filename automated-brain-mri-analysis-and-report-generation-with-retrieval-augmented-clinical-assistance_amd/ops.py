@@ -284,6 +284,40 @@ def stage0_plan(volume, patch, step_size=0.5, mirror_axes=(), r=2):
             "volume": tuple(g.volume), "slab_thickness": tuple(g.slab_thickness), "samples": samples}
 
 
+def stage0_merge_plan(volume, patch, step_size=0.5, mirror_axes=(), r=2, skip_half=True):
+    """Dry run of the merged stage-0 slabs (``mi355_stage0_merge_plan``; no GPU needed).  Returns a dict: shared, r, rs (the shell
+    depths of the level-0 features and of the slab chain), n_tiles, n_mirrors, padded, volume, slab_thickness, n_slabs / slab_shape /
+    voxels per axis (z per tile; y, x per key), voxels_per_tile (what per-tile slabs on all axes hold), slabs {1: [...], 2: [...]} of
+    dicts mirror (tuple of flipped axes), side, origin - in key order -, and samples: one dict per (tile, mirror), tile-major, with
+    tile, mirror, origin, slab (six entries: z faces 0 = per-tile slab, y / x faces the index in slabs[axis], -1 = a volume face)
+    and offset {face: (z, y, x)} of the tile's part inside the slab."""
+    lib = _lib.load()
+    g = _lib.Stage0MergeGeom()
+    p3 = (C.c_int32 * 3)(*(int(v) for v in patch))
+    z, y, x = (int(v) for v in volume)
+    mask = sum(1 << int(a) for a in mirror_axes)
+    args = (z, y, x, p3, float(step_size), mask, int(r), int(bool(skip_half)), C.byref(g))
+    n = lib.mi355_stage0_merge_plan(*args, None, 0, None, 0)
+    _lib.check(n, "mi355_stage0_merge_plan")
+    nk = int(g.n_slabs[1]) + int(g.n_slabs[2])
+    kbuf, sbuf = (_lib.Stage0MergeSlab * max(nk, 1))(), (_lib.Stage0MergeSample * max(n, 1))()
+    _lib.check(lib.mi355_stage0_merge_plan(*args, kbuf, nk, sbuf, n), "mi355_stage0_merge_plan")
+    axes = lambda m: tuple(a for a in range(3) if m >> a & 1)
+    slabs = {1: [], 2: []}
+    for i in range(nk):
+        k = kbuf[i]
+        slabs[int(k.axis)].append({"mirror": axes(k.mirror), "side": int(k.side), "origin": tuple(k.origin)})
+    samples = []
+    for i in range(n):
+        q = sbuf[i]
+        samples.append({"tile": int(q.tile), "mirror": axes(q.mirror), "origin": tuple(q.origin), "slab": tuple(int(v) for v in q.slab),
+                        "offset": {f: tuple(q.offset[f]) for f in range(2, 6) if q.slab[f] >= 0}})
+    return {"shared": bool(g.shared), "r": int(g.r), "rs": int(g.rs), "n_tiles": int(g.n_tiles), "n_mirrors": int(g.n_mirrors),
+            "padded": tuple(g.padded), "volume": tuple(g.volume), "slab_thickness": tuple(g.slab_thickness), "n_slabs": tuple(g.n_slabs),
+            "slab_shape": tuple(tuple(v) for v in g.slab_shape), "voxels": tuple(int(v) for v in g.voxels),
+            "voxels_per_tile": int(g.voxels_per_tile), "slabs": slabs, "samples": samples}
+
+
 def skip_share_plan(volume, patch, step_size=0.5, mirror_axes=(), dtype="f32", norm="batch", nonlin_first=False, enc0_blocks=2,
                     stride=1, skip_is_enc0=True, c_up=32, c_skip=32, cout=32, head_ncls=0, batch_tiles=0, rank=0, world=1):
     """Dry run of the shared skip half (``mi355_skip_share_plan``; no GPU needed): whether the last decoder stage's first conv takes
@@ -617,6 +651,28 @@ def logits_aggregate_(logits, mirrors, patch, nonlin, agg, cnt, origin, gauss=No
                                                   _i3(origin), _stream(logits)), "mi355_logits_aggregate")
 
 
+def logits_aggregate_tiles_(logits, mirrors, patch, nonlin, agg, cnt, origins, gauss=None, first_sample=0):
+    """``mi355_logits_aggregate_tiles``: the tiles at ``origins`` (tile i: samples first_sample + i * len(mirrors) ..) in one launch,
+    bit-identical to ``logits_aggregate_`` tile by tile in that order."""
+    import torch
+    logits = _require_cuda(logits, torch.float32, "logits")
+    n, ncls, v = logits.shape
+    mirrors = [int(m) for m in mirrors]
+    origins = [[int(k) for k in o] for o in origins]
+    if not origins:
+        raise ValueError("logits_aggregate_tiles_: no tile")
+    for o in origins:
+        gauss_dev, padded, pv = _tile_operands(agg, cnt, gauss, ncls, patch, o, "logits_aggregate_tiles_")
+    if v != pv or first_sample < 0 or first_sample + len(origins) * len(mirrors) > n:
+        raise ValueError("logits_aggregate_tiles_: logits do not hold the tiles' samples")
+    flat = [k for o in origins for k in o]
+    from .predictor import NONLIN
+    _lib.check(_lib.load().mi355_logits_aggregate_tiles(logits.data_ptr(), ncls, int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
+                                                        len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss_dev), agg.data_ptr(), _ptr(cnt),
+                                                        _i3(padded), (C.c_int32 * len(flat))(*flat), len(origins), _stream(logits)),
+               "mi355_logits_aggregate_tiles")
+
+
 def cnt_add_tile_(cnt, patch, origin, gauss=None):
     """``mi355_cnt_add_tile``: cnt [Zp, Yp, Xp] (CUDA fp32, in place) += gauss [patch] (None: 1) at origin."""
     gauss, padded, _ = _tile_operands(cnt[None], cnt, gauss, 1, patch, origin, "cnt_add_tile_")
@@ -675,6 +731,95 @@ def stage0_gather(wv, slabs, samples, patch, r, shells_only=False, out=None):
     else:
         _lib.check(_lib.load().mi355_stage0_gather(C.byref(a), _stream(wv)), "mi355_stage0_gather")
     return out
+
+
+def stage0_gather_merged(wv, slabs, samples, patch, r, spans, shells_only=False, out=None, second=None):
+    """``mi355_stage0_gather_merged``: ``stage0_gather`` with slabs that may span the volume.  slabs[a]: CUDA fp32 [n, S0, S1, S2, C] or
+    None; spans[a][k] truthy: the slabs of axis a span the volume along k (S[k] = volume[k], the tile at its origin) instead of
+    holding the tile's extent (S[k] = patch[k]).  second: None or a dict wv, slabs, r and optionally out - a second tensor gathered
+    for the same samples.  Returns (out, out2); out / out2 given are written in place (shells_only: the shell voxels alone)."""
+    import torch
+    wv = _require_cuda(wv, torch.float32, "wv")
+    nwv = int(wv.shape[0])
+    patch = [int(p) for p in patch]
+    m = _lib.Stage0GatherMergedArgs()
+    a = m.base
+    keep = [wv]
+    vol = [int(wv.shape[1 + k]) for k in range(3)]
+    counts = [0, 0, 0]
+
+    def bind(t, sl_list, name):
+        c = int(t.shape[4])
+        if list(t.shape[1:4]) != vol or t.shape[0] != nwv:
+            raise ValueError(f"{name}: shape {tuple(t.shape)}")
+        ptrs = [None, None, None]
+        for k, sl in enumerate(sl_list):
+            if sl is None:
+                continue
+            sl = _require_cuda(sl, torch.float32, f"{name} slabs[{k}]")
+            keep.append(sl)
+            thick = int(sl.shape[1 + k])
+            want = [thick if j == k else (vol[j] if spans[k][j] else patch[j]) for j in range(3)]
+            if sl.dim() != 5 or list(sl.shape[1:4]) != want or sl.shape[4] != c or (counts[k] and counts[k] != sl.shape[0]):
+                raise ValueError(f"{name} slabs[{k}]: shape {tuple(sl.shape)}, expected [n, {want}, {c}]")
+            if a.slab_thickness[k] not in (0, thick):
+                raise ValueError(f"{name} slabs[{k}]: thickness {thick}")
+            a.slab_thickness[k], counts[k] = thick, int(sl.shape[0])
+            for j in range(3):
+                m.slab_shape[k][j], m.spans_volume[k][j] = want[j], int(bool(spans[k][j]))
+            ptrs[k] = sl.data_ptr()
+        return c, ptrs
+
+    c, ptrs = bind(wv, slabs, "first")
+    a.wv_dev, a.r, a.channels, a.n_samples = wv.data_ptr(), int(r), c, len(samples)
+    for k in range(3):
+        a.patch[k], a.volume[k] = patch[k], vol[k]
+        a.slab_dev[k] = ptrs[k]
+    c2 = 0
+    if second is not None:
+        wv2 = _require_cuda(second["wv"], torch.float32, "second wv")
+        keep.append(wv2)
+        c2, ptrs2 = bind(wv2, second["slabs"], "second")
+        if any((p is None) != (q is None) for p, q in zip(ptrs, ptrs2)):
+            raise ValueError("stage0_gather_merged: the two tensors need slabs on the same axes")
+        m.wv2_dev, m.r2, m.channels2 = wv2.data_ptr(), int(second["r"]), c2
+        for k in range(3):
+            m.slab2_dev[k] = ptrs2[k]
+    for k in range(3):
+        if ptrs[k] is None:   # an axis without slabs: the per-tile form, never indexed
+            a.slab_thickness[k] = 2 * int(second["r"] if second is not None else r)
+            for j in range(3):
+                m.slab_shape[k][j], m.spans_volume[k][j] = (a.slab_thickness[k] if j == k else patch[j]), 0
+    if len(samples) > 64:
+        raise ValueError("stage0_gather_merged: more than 64 samples")
+    for i, sm in enumerate(samples):
+        if not 0 <= int(sm["wv"]) < nwv:
+            raise ValueError(f"stage0_gather_merged: sample {i}: whole-volume index")
+        a.samples[i].wv = int(sm["wv"])
+        for k in range(3):
+            a.samples[i].origin[k] = int(sm["origin"][k])
+        for f in range(6):
+            idx = int(sm["slab"][f])
+            if idx >= counts[f >> 1]:
+                raise ValueError(f"stage0_gather_merged: sample {i}: face {f} has no slab {idx}")
+            a.samples[i].slab[f] = idx
+
+    def result(given, ch):
+        shape = (max(len(samples), 1), patch[0], patch[1], patch[2], ch)
+        if given is None:
+            return torch.full(shape, float("nan"), dtype=torch.float32, device=wv.device)
+        if not (given.is_cuda and given.is_contiguous() and given.dtype == torch.float32 and tuple(given.shape) == shape):
+            raise ValueError(f"stage0_gather_merged: out must be a contiguous CUDA fp32 {shape}")
+        return given
+
+    out = result(out, c)
+    a.out_dev = out.data_ptr()
+    out2 = None
+    if second is not None:
+        out2 = result(second.get("out"), c2)
+        m.out2_dev = out2.data_ptr()
+    _lib.check(_lib.load().mi355_stage0_gather_merged(C.byref(m), int(bool(shells_only)), _stream(wv)), "mi355_stage0_gather_merged")
+    return out, out2
 
 
 def stage0_mask_(x, keep):

@@ -663,6 +663,13 @@ int mi355_head_aggregate(const void *feat_dev, int dtype, int cin, const float *
 int mi355_logits_aggregate(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
                            const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *cnt_dev,
                            const int32_t padded[3], const int32_t origin[3], void *stream);
+/* The same for the n_tiles tiles of one forward in one launch (per 64 tiles): tile i's samples are first_sample + i * n_mirrors ..
+ * of logits_dev, its origin origins[3 i .. 3 i + 2].  Every voxel of agg_dev / cnt_dev that a tile covers is read once, receives the
+ * covering tiles' terms in list order and is written once: bit-identical to mi355_logits_aggregate called tile by tile in that
+ * order.  A voxel no tile covers is not written. */
+int mi355_logits_aggregate_tiles(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
+                                 const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *cnt_dev,
+                                 const int32_t padded[3], const int32_t *origins, int n_tiles, void *stream);
 /* cnt_dev [padded] += gauss_dev [patch] (NULL: 1) at origin[]: the normaliser of a tile another rank evaluates. */
 int mi355_cnt_add_tile(const float *gauss_dev, const int32_t patch[3], float *cnt_dev, const int32_t padded[3],
                        const int32_t origin[3], void *stream);
@@ -689,6 +696,51 @@ int mi355_stage0_gather(const mi355_stage0_gather_args *args, void *stream);
 /* The same for a tensor whose reader takes a stage-0 view: only the voxels within r of a face with a slab are written (from that
  * slab, same precedence); every other element of out_dev is left as it is. */
 int mi355_stage0_gather_shells(const mi355_stage0_gather_args *args, void *stream);
+/* ---- merged slabs (MI355_MERGE_SLABS, default on; csrc/unet.hip "merged slabs").  Tiles that share a cut plane compute nearly the
+ * same y- and x-slabs of the shared stage 0.  The gather's precedence (z shell, then y, then x) decides which padding a slab must
+ * reproduce: z-slabs stay per tile; a y-slab serves only voxels outside the z shells, so it spans the extended volume in z and keeps
+ * the tile's x padding - one per (mirror, side, y, x origin), box volume[0] x thickness[1] x patch[2]; an x-slab serves voxels in
+ * neither other shell - one per (mirror, side, x), box volume[0] x volume[1] x thickness[2].  All keys are computed once per volume
+ * behind the whole-volume pass, on every rank. ---- */
+/* Dry run (no device).  r = blocks of encoder stage 0, skip_half != 0: the slab chain is one conv deeper (shared skip half).
+ * Returns the number of (tile, mirror) samples, tile-major, written to samples[] (at most max_samples); slabs[] receives the
+ * merged slabs, the y-slabs then the x-slabs, each list sorted by (mirror index, side, origin): n_slabs[1] + n_slabs[2] entries. */
+typedef struct mi355_stage0_merge_geom {
+    int32_t shared;
+    int32_t r, rs;               /* shell depth of the level-0 features, and of the slab chain (r + 1 with the skip half) */
+    int32_t n_tiles, n_mirrors;
+    int32_t padded[3], volume[3], slab_thickness[3];
+    int32_t n_slabs[3];          /* z: one per interior z face of every sample; y, x: keys */
+    int32_t slab_shape[3][3];
+    int64_t voxels[3];           /* n_slabs x box, per axis */
+    int64_t voxels_per_tile;     /* what per-tile slabs on all three axes hold (MI355_MERGE_SLABS=0) */
+} mi355_stage0_merge_geom;
+typedef struct mi355_stage0_merge_slab {
+    int32_t axis, mirror, side;  /* 1 = y, 2 = x; mirror mask of its pass; 0 = serves lo faces, 1 = hi faces */
+    int32_t origin[3];           /* of the box, in its pass */
+} mi355_stage0_merge_slab;
+typedef struct mi355_stage0_merge_sample {
+    int32_t tile, mirror;
+    int32_t origin[3];
+    int32_t slab[6];             /* z faces: 0 = the face gets a per-tile slab; y, x faces: index in that axis's list; -1: a volume face */
+    int32_t offset[6][3];        /* y, x faces: where the tile's part of the slab (for a hi face its last thickness layers) starts in the slab */
+} mi355_stage0_merge_sample;
+int mi355_stage0_merge_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes, int r, int skip_half,
+                            mi355_stage0_merge_geom *out, mi355_stage0_merge_slab *slabs, int max_slabs,
+                            mi355_stage0_merge_sample *samples, int max_samples);
+/* mi355_stage0_gather / mi355_stage0_gather_shells (shells_only != 0) in their general form: the slabs of axis a are
+ * slab_shape[a] voxels each - base.slab_thickness[a] along a; along k != a either patch[k], the tile starting at 0 (spans_volume[a][k]
+ * = 0), or volume[k], the tile starting at its origin[k] (spans_volume[a][k] = 1).  An optional second tensor (out2_dev != NULL)
+ * is gathered for the same samples and slab indices from its own sources, r2 >= r layers deep.  Anything else is refused. */
+typedef struct mi355_stage0_gather_merged_args {
+    mi355_stage0_gather_args base;
+    int32_t slab_shape[3][3], spans_volume[3][3];
+    const float *wv2_dev;
+    const float *slab2_dev[3];
+    float *out2_dev;
+    int32_t r2, channels2;
+} mi355_stage0_gather_merged_args;
+int mi355_stage0_gather_merged(const mi355_stage0_gather_merged_args *args, int shells_only, void *stream);
 /* x_dev [n][volume][c] fp32: zero every voxel outside [0, keep) (c % 4 == 0, 0 < keep <= volume); the rest is not written. */
 int mi355_stage0_mask(float *x_dev, int n, const int32_t volume[3], const int32_t keep[3], int c, void *stream);
 /* Name of the kernel instantiation the calling thread's last mi355_conv3d_ndhwc / mi355_conv3d_ndhwc_f16 call dispatched
