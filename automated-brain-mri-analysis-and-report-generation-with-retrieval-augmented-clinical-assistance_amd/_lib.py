@@ -43,6 +43,7 @@ EXPORTS = [
     "mi355_logits_aggregate", "mi355_cnt_add_tile", "mi355_stage0_gather", "mi355_stage0_mask",
     "mi355_stage0_view_plan", "mi355_conv3d_s2dma_view_ndhwc", "mi355_conv3d_wino3_view_ndhwc", "mi355_stage0_gather_shells",
     "mi355_logits_aggregate_tiles", "mi355_stage0_merge_plan", "mi355_stage0_gather_merged",
+    "mi355_scratch_sizes", "mi355_scratch_fill", "mi355_scratch_release", "mi355_scratch_zero_pages",
 ]
 
 
@@ -291,6 +292,11 @@ def load():
                                                   C.c_int, C.c_int, C.c_float, C.c_int, vp, vp]
     lib.mi355_conv3d_wino3_view_ndhwc.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, C.c_int, C.c_int,
                                                   C.c_float, vp, C.POINTER(Stage0View), vp, vp]
+    lib.mi355_scratch_sizes.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
+    lib.mi355_scratch_fill.argtypes = [vp, C.c_int, C.c_uint32]
+    lib.mi355_scratch_fill.restype = C.c_int64
+    lib.mi355_scratch_release.argtypes = [vp]
+    lib.mi355_scratch_zero_pages.argtypes = [C.POINTER(C.c_int64)]
     lib.mi355_profile_enable.argtypes = [vp, C.c_int]
     lib.mi355_profile_read.argtypes = [vp, C.POINTER(ProfEntry), C.c_int]
     _lib = lib

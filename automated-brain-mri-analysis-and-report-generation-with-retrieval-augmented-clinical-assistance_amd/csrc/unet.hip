@@ -112,7 +112,7 @@ int bind_device() {
 // config-3 step) then run beside the matrix-bound kernels of the other instead of in front of them.  Work on ONE stream is ordered
 // by that stream, as before.  A stream beyond the table takes over the least recently used lane after a device synchronise.
 // SCR_ZEROS / SCR_ZERO_BIAS are read-only once cleared and shared by all lanes.
-constexpr int MAX_LANES = 4;
+constexpr int MAX_LANES = MI355_SCRATCH_LANES;
 static struct { void *p; size_t bytes; } g_scratch[MAX_LANES][SCR_COUNT];
 static struct { hipStream_t s; bool used; unsigned long tick; } g_lane[MAX_LANES];
 static unsigned long g_lane_tick = 0;
@@ -151,6 +151,75 @@ int device_scratch(int slot, hipStream_t stream, size_t bytes, void **out, bool 
         if (zeroed) MI355_HIP(hipMemset(b.p, 0, bytes));
     }
     *out = b.p;
+    return MI355_OK;
+}
+
+// Test aids (mi355_nnunet.h, "Device scratch, for tests"): look at, overwrite and drop what device_scratch hands out.  Host code.
+static bool scratch_slot_shared(int slot) { return slot == SCR_ZEROS || slot == SCR_ZERO_BIAS; }
+static int lane_peek_locked(hipStream_t s) {  // the lane of a stream, or -1: claims nothing, touches no tick
+    for (int i = 0; i < MAX_LANES; ++i)
+        if (g_lane[i].used && g_lane[i].s == s) return i;
+    return -1;
+}
+
+extern "C" int mi355_scratch_sizes(void *stream, int64_t *bytes, int n) {
+    MI355_REQUIRE(n >= 0 && (bytes || n == 0), "mi355_scratch_sizes: bad arguments");
+    std::lock_guard<std::mutex> lk(g_mu);
+    const int lane = lane_peek_locked((hipStream_t)stream);
+    for (int slot = 0; slot < SCR_COUNT && slot < n; ++slot) {
+        if (scratch_slot_shared(slot)) bytes[slot] = (int64_t)g_scratch[0][slot].bytes;
+        else bytes[slot] = lane < 0 ? 0 : (int64_t)g_scratch[lane][slot].bytes;
+    }
+    return SCR_COUNT;
+}
+
+extern "C" int64_t mi355_scratch_fill(void *stream, int slot, uint32_t word) {
+    MI355_REQUIRE(slot >= -1 && slot < SCR_COUNT, "mi355_scratch_fill: bad scratch slot %d", slot);
+    MI355_REQUIRE(slot < 0 || !scratch_slot_shared(slot), "mi355_scratch_fill: slot %d is a shared zero page", slot);
+    MI355_TRY(bind_device());
+    std::lock_guard<std::mutex> lk(g_mu);
+    const int lane = lane_peek_locked((hipStream_t)stream);
+    if (lane < 0) return 0;
+    int64_t filled = 0;
+    for (int i = 0; i < SCR_COUNT; ++i) {
+        if (scratch_slot_shared(i) || (slot >= 0 && i != slot)) continue;
+        auto &b = g_scratch[lane][i];
+        if (!b.p || b.bytes < 4) continue;
+        MI355_HIP(hipMemsetD32Async((hipDeviceptr_t)b.p, (int)word, b.bytes / 4, (hipStream_t)stream));
+        filled += (int64_t)(b.bytes / 4 * 4);
+    }
+    return filled;
+}
+
+extern "C" int mi355_scratch_release(void *stream) {
+    MI355_TRY(bind_device());
+    std::lock_guard<std::mutex> lk(g_mu);
+    const int lane = lane_peek_locked((hipStream_t)stream);
+    if (lane < 0) return MI355_OK;
+    MI355_HIP(hipDeviceSynchronize());  // work in flight may still use the buffers
+    for (int i = 0; i < SCR_COUNT; ++i) {
+        if (scratch_slot_shared(i)) continue;  // (lane 0 also holds the zero pages of every lane)
+        auto &b = g_scratch[lane][i];
+        if (b.p) MI355_HIP(hipFree(b.p));
+        b.p = nullptr; b.bytes = 0;
+    }
+    g_lane[lane].used = false; g_lane[lane].s = nullptr; g_lane[lane].tick = 0;
+    return MI355_OK;
+}
+
+extern "C" int mi355_scratch_zero_pages(int64_t *nonzero_bytes) {
+    MI355_REQUIRE(nonzero_bytes, "mi355_scratch_zero_pages: null output");
+    const int slots[2] = {SCR_ZEROS, SCR_ZERO_BIAS};
+    nonzero_bytes[0] = nonzero_bytes[1] = 0;
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (int k = 0; k < 2; ++k) {
+        auto &b = g_scratch[0][slots[k]];
+        if (!b.p) continue;
+        MI355_HIP(hipDeviceSynchronize());
+        std::vector<unsigned char> host(b.bytes);
+        MI355_HIP(hipMemcpy(host.data(), b.p, b.bytes, hipMemcpyDeviceToHost));
+        for (unsigned char v : host) nonzero_bytes[k] += v != 0;
+    }
     return MI355_OK;
 }
 

@@ -830,3 +830,59 @@ def stage0_mask_(x, keep):
     _lib.check(_lib.load().mi355_stage0_mask(x.data_ptr(), int(x.shape[0]), _i3(x.shape[1:4]), _i3(keep), int(x.shape[4]), _stream(x)),
                "mi355_stage0_mask")
     return x
+
+
+# Device scratch, for tests (include/mi355_nnunet.h; DESIGN.md "Scratch holds no state").
+#: the slots of csrc/common.h's enum ScratchSlot, in its order
+SCRATCH_SLOTS = ("SCR_ARENA", "SCR_SW_AGG", "SCR_SPLITK_F32", "SCR_SPLITK_F16", "SCR_ZEROS", "SCR_ZERO_BIAS", "SCR_SMALL", "SCR_TOPK",
+                 "SCR_CROP", "SCR_ZSCORE", "SCR_RESAMPLE", "SCR_RESAMPLE_MM", "SCR_COMPONENTS", "SCR_MORPHOLOGY", "SCR_QUALITY",
+                 "SCR_MASS_EFFECT")
+#: the slots every lane shares (the zero pages): never filled, never released
+SCRATCH_SHARED = ("SCR_ZEROS", "SCR_ZERO_BIAS")
+#: MI355_SCRATCH_LANES: streams that hold scratch of their own at one time
+SCRATCH_LANES = 4
+
+
+def _scratch_stream(stream):
+    """A raw stream handle, a torch stream, or None for torch's current stream."""
+    if stream is None:
+        import torch
+        return torch.cuda.current_stream().cuda_stream
+    return int(getattr(stream, "cuda_stream", stream))
+
+
+def scratch_slot_count() -> int:
+    """The library's number of scratch slots (host code: needs no GPU)."""
+    return int(_lib.load().mi355_scratch_sizes(None, None, 0))
+
+
+def scratch_sizes(stream=None) -> dict:
+    """{slot name: bytes allocated} for the lane of ``stream``; claims no lane and allocates nothing."""
+    n = len(SCRATCH_SLOTS)
+    buf = (C.c_int64 * n)()
+    rc = _lib.load().mi355_scratch_sizes(_scratch_stream(stream), buf, n)
+    _lib.check(rc, "mi355_scratch_sizes")
+    if rc != n:
+        raise _lib.Mi355Error(f"the library has {rc} scratch slots, ops.SCRATCH_SLOTS names {n}")
+    return {name: int(buf[i]) for i, name in enumerate(SCRATCH_SLOTS)}
+
+
+def scratch_fill(slot, word: int, stream=None) -> int:
+    """Fill the whole buffer of ``slot`` (a name of SCRATCH_SLOTS; None: every lane-owned slot) of the lane of ``stream`` with
+    the 32-bit ``word``, on that stream.  Returns the bytes filled."""
+    idx = -1 if slot is None else SCRATCH_SLOTS.index(slot)
+    rc = int(_lib.load().mi355_scratch_fill(_scratch_stream(stream), idx, int(word) & 0xFFFFFFFF))
+    _lib.check(rc, "mi355_scratch_fill")
+    return rc
+
+
+def scratch_release(stream=None) -> None:
+    """Free the lane-owned scratch of the lane of ``stream`` and forget the lane."""
+    _lib.check(_lib.load().mi355_scratch_release(_scratch_stream(stream)), "mi355_scratch_release")
+
+
+def scratch_zero_pages() -> tuple:
+    """Non-zero bytes in (SCR_ZEROS, SCR_ZERO_BIAS); 0 for a page that does not exist yet."""
+    out = (C.c_int64 * 2)()
+    _lib.check(_lib.load().mi355_scratch_zero_pages(out), "mi355_scratch_zero_pages")
+    return int(out[0]), int(out[1])

@@ -440,6 +440,24 @@ int mi355_masked_order_stats_i32(const int32_t *values_dev, int64_t n, const uin
  * there.  Refused: i1_from < 0.  Synchronous. */
 int mi355_column_count_max(const uint8_t *flags_dev, int require, int forbid, int d0, int d1, int d2, int i1_from, int64_t *out_host, void *stream);
 
+/* Device scratch, for tests (DESIGN.md "Scratch holds no state").  Working memory lives in slots (csrc/common.h, enum ScratchSlot;
+ * ops.SCRATCH_SLOTS names them in that order), one set per stream lane; the first MI355_SCRATCH_LANES distinct streams get a lane
+ * each, a further stream takes over the least recently used one.  The two zero pages (slots 4 and 5) are shared by all lanes.
+ * A result never depends on what a slot held on entry: these four let a test put something there.  Host code, no kernels. */
+#define MI355_SCRATCH_LANES 4
+/* bytes[i] = bytes now allocated for slot i, i < min(n, slot count), for the lane of `stream` (zero pages: the shared ones).
+ * Allocates nothing and claims no lane: a stream without a lane reports 0 for the lane-owned slots.  Returns the slot count. */
+int mi355_scratch_sizes(void *stream, int64_t *bytes, int n);
+/* hipMemsetD32Async(word) on `stream` over the whole buffer of `slot` of the stream's lane; slot = -1: every lane-owned slot of
+ * the lane.  Returns the bytes filled (0: no lane, or nothing allocated).  Refused: a zero page, a slot out of range. */
+int64_t mi355_scratch_fill(void *stream, int slot, uint32_t word);
+/* Synchronises the device, frees the lane-owned buffers of the stream's lane and forgets the lane: the next request on that
+ * stream claims a lane and allocates afresh.  A stream without a lane: nothing happens. */
+int mi355_scratch_release(void *stream);
+/* nonzero_bytes[0], [1] = the number of non-zero bytes in the two shared zero pages (0 for a page that does not exist yet),
+ * after a device synchronise. */
+int mi355_scratch_zero_pages(int64_t *nonzero_bytes);
+
 /* Per-kernel timing with HIP events on the stream the kernels are launched on (bench.py's
  * roofline). flops / bytes are the ALGORITHMIC work of the recorded launches. */
 typedef struct {
