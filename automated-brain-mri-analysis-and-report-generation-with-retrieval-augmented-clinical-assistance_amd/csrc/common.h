@@ -20,7 +20,7 @@ void set_error(const char *fmt, ...);
 int bind_device();
 
 // Process-wide scratch on the bound device, one buffer per (lane, slot) - a lane = one of the first few streams the caller
-// launches on (unet.hip, "Lanes") -, grown on demand (synchronise, free, allocate) under a mutex and never freed per call;
+// launches on (runtime.hip, "Lanes") -, grown on demand (synchronise, free, allocate) under a mutex and never freed per call;
 // `zeroed` buffers are cleared when (re)allocated.  Work that uses a slot is ordered by the stream it was asked for
 // ("Stream semantics").
 enum ScratchSlot { SCR_ARENA = 0, SCR_SW_AGG, SCR_SPLITK_F32, SCR_SPLITK_F16, SCR_ZEROS, SCR_ZERO_BIAS, SCR_SMALL, SCR_TOPK,

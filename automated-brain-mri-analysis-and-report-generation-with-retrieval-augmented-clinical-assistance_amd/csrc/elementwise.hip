@@ -279,7 +279,7 @@ static __device__ __forceinline__ void stage0_gather_row(const S0GatherArgs &a, 
     }
 }
 
-// A second tensor may ride along (the shared skip half of the last decoder stage's concat conv, unet.hip): same samples, same
+// A second tensor may ride along (the shared skip half of the last decoder stage's concat conv, sliding_window.hip): same samples, same
 // slab indices, its own sources, channel count and shell depth.
 __global__ __launch_bounds__(256) void stage0_gather_kernel(S0GatherArgs a) {
     const int m = blockIdx.y;

@@ -592,7 +592,7 @@ int mi355_skip_share_plan(int z, int y, int x, const int32_t patch[3], float ste
 int mi355_conv3d_wino3_ndhwc(const float *x0_dev, const float *x1_dev, int n, int d, int h, int w, int c0, int c1,
                              const float *weight_host, const float *bias_host, int cout, int act, float slope,
                              const float *addend_dev, float *y_dev, void *stream);
-/* ---- stage-0 views (MI355_STAGE0_VIEWS; csrc/unet.hip "stage-0 views").  With the shared stage 0 and the shared skip half on, the
+/* ---- stage-0 views (MI355_STAGE0_VIEWS; csrc/sliding_window.hip "stage-0 views").  With the shared stage 0 and the shared skip half on, the
  * two tile tensors a forward gathers - the level-0 features and the skip half S - differ from the whole-volume tensors only inside
  * the shells (within r, for S r + 1, voxels of a tile face that lies inside the volume), and each has one reader: the first
  * stride-2 conv, the addend epilogue of the up-half launch.  Where the reader can, it reads the whole-volume tensor in place
@@ -714,7 +714,7 @@ int mi355_stage0_gather(const mi355_stage0_gather_args *args, void *stream);
 /* The same for a tensor whose reader takes a stage-0 view: only the voxels within r of a face with a slab are written (from that
  * slab, same precedence); every other element of out_dev is left as it is. */
 int mi355_stage0_gather_shells(const mi355_stage0_gather_args *args, void *stream);
-/* ---- merged slabs (MI355_MERGE_SLABS, default on; csrc/unet.hip "merged slabs").  Tiles that share a cut plane compute nearly the
+/* ---- merged slabs (MI355_MERGE_SLABS, default on; csrc/sliding_window.hip "merged slabs").  Tiles that share a cut plane compute nearly the
  * same y- and x-slabs of the shared stage 0.  The gather's precedence (z shell, then y, then x) decides which padding a slab must
  * reproduce: z-slabs stay per tile; a y-slab serves only voxels outside the z shells, so it spans the extended volume in z and keeps
  * the tile's x padding - one per (mirror, side, y, x origin), box volume[0] x thickness[1] x patch[2]; an x-slab serves voxels in

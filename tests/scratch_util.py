@@ -1,4 +1,4 @@
-"""One case per entry point that takes working memory from device_scratch (csrc/unet.hip): what test_gpu_scratch_hygiene.py runs on
+"""One case per entry point that takes working memory from device_scratch (csrc/runtime.hip): what test_gpu_scratch_hygiene.py runs on
 poisoned, stale and taken-over scratch, and what test_scratch_cases_cpu.py keeps closed against the call sites under csrc/.
 
 A case names the call sites it reaches (file, ordinal of the ``device_scratch(`` call within that file), the slots it uses, builds small
@@ -579,7 +579,7 @@ CONV_CASES = tuple(c.name for c in CASES if c.name.startswith("conv_"))
 #: the network's scratch users: run by the network tests of test_gpu_scratch_hygiene.py, not through Case.call
 NETWORK_SITES = {
     "unet_forward": {"sites": (("unet.hip", 0),), "slots": ("SCR_ARENA", "SCR_SPLITK_F32", "SCR_SPLITK_F16"), "reference_of": "oracle.unet_ref.unet_forward"},
-    "sw_predict": {"sites": (("unet.hip", 0), ("unet.hip", 1)), "slots": ("SCR_ARENA", "SCR_SW_AGG", "SCR_SPLITK_F32", "SCR_SPLITK_F16"),
+    "sw_predict": {"sites": (("unet.hip", 0), ("sliding_window.hip", 0)), "slots": ("SCR_ARENA", "SCR_SW_AGG", "SCR_SPLITK_F32", "SCR_SPLITK_F16"),
                    "reference_of": "oracle.tiler_ref.predict_3d_tiled"},
 }
 

@@ -19,7 +19,7 @@ c. nothing outside the N x Do x Ho x Wo x Cout outputs may be written: a store p
      sample's worth on either side - are read back here and must be untouched.
    - fp16: the kernels store into a channel-blocked buffer that the single-op entry point owns; only its layout converter
      writes the caller's tensor.  The entry point therefore puts its own guard bands (a sample's worth, at most 4 MiB) around
-     that buffer, reads them back after the launch and fails the call if a byte changed (unet.hip guards_intact): for an fp16
+     that buffer, reads them back after the launch and fails the call if a byte changed (single_op.hip guards_intact): for an fp16
      entry the check is that the call returns without that error.  The sentinels here then only watch the converter.
    - split-K, both dtypes: the conv kernel stores partial sums into library scratch, which nothing guards; what is checked
      as above is the finishing pass.

@@ -43,8 +43,8 @@ def test_the_slot_names_are_the_librarys(amd):
     api = open(os.path.join(ROOT, "include", "mi355_nnunet.h"), encoding="utf-8").read()
     lanes = int(re.search(r"#define MI355_SCRATCH_LANES (\d+)", api).group(1))
     assert lanes == amd.ops.SCRATCH_LANES
-    unet = open(os.path.join(CSRC, "unet.hip"), encoding="utf-8").read()
-    assert "constexpr int MAX_LANES = MI355_SCRATCH_LANES;" in unet
+    runtime = open(os.path.join(CSRC, "runtime.hip"), encoding="utf-8").read()
+    assert "constexpr int MAX_LANES = MI355_SCRATCH_LANES;" in runtime
     binding = open(os.path.join(PKG, "_lib.py"), encoding="utf-8").read()
     for sym in ("mi355_scratch_sizes", "mi355_scratch_fill", "mi355_scratch_release", "mi355_scratch_zero_pages"):
         assert sym in amd._lib.EXPORTS and f"lib.{sym}.argtypes" in binding, sym
