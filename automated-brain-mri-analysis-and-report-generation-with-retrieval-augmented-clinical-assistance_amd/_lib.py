@@ -44,6 +44,7 @@ EXPORTS = [
     "mi355_stage0_view_plan", "mi355_conv3d_s2dma_view_ndhwc", "mi355_conv3d_wino3_view_ndhwc", "mi355_stage0_gather_shells",
     "mi355_logits_aggregate_tiles", "mi355_stage0_merge_plan", "mi355_stage0_gather_merged",
     "mi355_scratch_sizes", "mi355_scratch_fill", "mi355_scratch_release", "mi355_scratch_zero_pages",
+    "mi355_level1_share_plan",
 ]
 
 
@@ -152,6 +153,28 @@ class Stage0ViewItem(C.Structure):
 class Stage0View(C.Structure):
     _fields_ = [("src_dev", C.c_void_p), ("n_wv", C.c_int32), ("volume", C.c_int32 * 3), ("depth", C.c_int32), ("n_samples", C.c_int32),
                 ("samples", Stage0ViewItem * 64)]
+
+
+class Level1ShareNet(C.Structure):
+    _fields_ = [("last", SkipShareNet), ("num_pool", C.c_int32), ("enc1_blocks", C.c_int32), ("c_level1", C.c_int32),
+                ("skip_is_enc1", C.c_int32), ("dec1_blocks", C.c_int32), ("c_up1", C.c_int32), ("cout1", C.c_int32)]
+
+
+class Level1ShareGeom(C.Structure):
+    _fields_ = [("possible", C.c_int32), ("on", C.c_int32), ("r0", C.c_int32), ("k1", C.c_int32), ("d1", C.c_int32), ("dS", C.c_int32),
+                ("n_tiles", C.c_int32), ("n_mirrors", C.c_int32), ("n_regions", C.c_int32), ("padded", C.c_int32 * 3),
+                ("volume", C.c_int32 * 3), ("stage0_slab_thickness", C.c_int32 * 3), ("merged", C.c_int32 * 3), ("region", C.c_int32 * 3),
+                ("slab_thickness", C.c_int32 * 3), ("n_slabs", C.c_int32 * 3),
+                ("region_voxels", C.c_int64), ("slab_voxels", C.c_int64), ("tile_voxels", C.c_int64)]
+
+
+class Level1ShareRegion(C.Structure):
+    _fields_ = [("mirror", C.c_int32), ("origin", C.c_int32 * 3), ("faces", C.c_int32)]
+
+
+class Level1ShareSample(C.Structure):
+    _fields_ = [("tile", C.c_int32), ("mirror", C.c_int32), ("region", C.c_int32), ("origin", C.c_int32 * 3), ("origin1", C.c_int32 * 3),
+                ("faces", C.c_int32), ("slab", C.c_int32 * 6), ("slab_offset", (C.c_int32 * 3) * 6), ("slab_shape", (C.c_int32 * 3) * 6)]
 
 
 class Mi355Error(RuntimeError):
@@ -292,6 +315,8 @@ def load():
                                                   C.c_int, C.c_int, C.c_float, C.c_int, vp, vp]
     lib.mi355_conv3d_wino3_view_ndhwc.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, C.c_int, C.c_int,
                                                   C.c_float, vp, C.POINTER(Stage0View), vp, vp]
+    lib.mi355_level1_share_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.POINTER(Level1ShareNet), C.c_int,
+                                            C.POINTER(Level1ShareGeom), C.POINTER(Level1ShareRegion), C.c_int, C.POINTER(Level1ShareSample), C.c_int]
     lib.mi355_scratch_sizes.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     lib.mi355_scratch_fill.argtypes = [vp, C.c_int, C.c_uint32]
     lib.mi355_scratch_fill.restype = C.c_int64

@@ -227,11 +227,11 @@ struct S0GatherSet {
 };
 // voxel (v0, v1, v2) of slab `idx` of axis ax, given the tile voxel (z, y, x) and the face's side: along ax the slab's own layer
 // (a hi slab covers the last t[ax] layers of the tile), across it the tile voxel plus the tile's origin inside the slab
-static __device__ __forceinline__ int64_t s0_slab_voxel(const S0GatherArgs &a, const S0Sample &sm, int ax, int side, int idx, int z, int y, int x) {
+static __device__ __forceinline__ int64_t s0_slab_voxel(const S0GatherArgs &a, const S0Sample &sm, const int *sub, int ax, int side, int idx, int z, int y, int x) {
     int v[3] = {z, y, x};
     if (side) v[ax] -= a.P[ax] - a.t[ax];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) v[k] += a.so[ax][k] * sm.org[k];
+    for (int k = 0; k < 3; ++k) v[k] += a.so[ax][k] ? sm.org[k] : (k != ax ? sub[k] : 0);
     return (((int64_t)idx * a.D[ax][0] + v[0]) * a.D[ax][1] + v[1]) * a.D[ax][2] + v[2];
 }
 
@@ -252,16 +252,16 @@ static __device__ __forceinline__ void stage0_gather_row(const S0GatherArgs &a, 
             // the row's source when a z or y shell holds it: slab base (in quads) of voxel x = 0
             const f32x4 *row = nullptr;
             if (sm.slab[0] >= 0 && z < r)
-                row = (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, 0, 0, sm.slab[0], z, y, 0) * C4;
+                row = (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, a.sub[n], 0, 0, sm.slab[0], z, y, 0) * C4;
             else if (sm.slab[1] >= 0 && z >= a.P[0] - r)
-                row = (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, 0, 1, sm.slab[1], z, y, 0) * C4;
+                row = (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, a.sub[n], 0, 1, sm.slab[1], z, y, 0) * C4;
             else if (sm.slab[2] >= 0 && y < r)
-                row = (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, 1, 0, sm.slab[2], z, y, 0) * C4;
+                row = (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, a.sub[n], 1, 0, sm.slab[2], z, y, 0) * C4;
             else if (sm.slab[3] >= 0 && y >= a.P[1] - r)
-                row = (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, 1, 1, sm.slab[3], z, y, 0) * C4;
+                row = (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, a.sub[n], 1, 1, sm.slab[3], z, y, 0) * C4;
             // (the x slabs: base of the slab's voxel that holds tile voxel x = 0, lo, and x = P2 - t2, hi)
-            const f32x4 *xlo = sm.slab[4] < 0 ? nullptr : (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, 2, 0, sm.slab[4], z, y, 0) * C4;
-            const f32x4 *xhi = sm.slab[5] < 0 ? nullptr : (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, 2, 1, sm.slab[5], z, y, a.P[2] - a.t[2]) * C4;
+            const f32x4 *xlo = sm.slab[4] < 0 ? nullptr : (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, a.sub[n], 2, 0, sm.slab[4], z, y, 0) * C4;
+            const f32x4 *xhi = sm.slab[5] < 0 ? nullptr : (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, a.sub[n], 2, 1, sm.slab[5], z, y, a.P[2] - a.t[2]) * C4;
             f32x4 *dst = (f32x4 *)t.out + (((int64_t)n * a.P[0] + z) * a.P[1] + y) * rowq;
             const int qorg = sm.org[2] * C4;
 #pragma unroll
@@ -293,6 +293,7 @@ __global__ __launch_bounds__(256) void stage0_gather_kernel(S0GatherArgs a) {
 }
 
 static int stage0_gather_check(const S0GatherArgs &a, int n_samples, int *n_wv);
+static_assert(sizeof(S0GatherArgs) + sizeof(int) <= 4096, "the gather's arguments must fit the kernel-argument block");
 int stage0_gather(const S0GatherArgs &a, int n_samples, hipStream_t s) {
     int n_wv = 0;
     MI355_TRY(stage0_gather_check(a, n_samples, &n_wv));
@@ -362,17 +363,17 @@ __global__ __launch_bounds__(256) void stage0_gather_shell_kernel(S0GatherArgs a
     }
     const f32x4 *src;
     if (sm.slab[0] >= 0 && z < r)
-        src = (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, 0, 0, sm.slab[0], z, y, x) * C4;
+        src = (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, a.sub[n], 0, 0, sm.slab[0], z, y, x) * C4;
     else if (sm.slab[1] >= 0 && z >= a.P[0] - r)
-        src = (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, 0, 1, sm.slab[1], z, y, x) * C4;
+        src = (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, a.sub[n], 0, 1, sm.slab[1], z, y, x) * C4;
     else if (sm.slab[2] >= 0 && y < r)
-        src = (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, 1, 0, sm.slab[2], z, y, x) * C4;
+        src = (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, a.sub[n], 1, 0, sm.slab[2], z, y, x) * C4;
     else if (sm.slab[3] >= 0 && y >= a.P[1] - r)
-        src = (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, 1, 1, sm.slab[3], z, y, x) * C4;
+        src = (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, a.sub[n], 1, 1, sm.slab[3], z, y, x) * C4;
     else if (sm.slab[4] >= 0 && x < r)
-        src = (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, 2, 0, sm.slab[4], z, y, x) * C4;
+        src = (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, a.sub[n], 2, 0, sm.slab[4], z, y, x) * C4;
     else if (sm.slab[5] >= 0 && x >= a.P[2] - r)
-        src = (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, 2, 1, sm.slab[5], z, y, x) * C4;
+        src = (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, a.sub[n], 2, 1, sm.slab[5], z, y, x) * C4;
     else   // (not reached: every enumerated voxel lies in a shell)
         src = (const f32x4 *)t.wv + ((((int64_t)sm.wv * a.Ve[0] + sm.org[0] + z) * a.Ve[1] + sm.org[1] + y) * a.Ve[2] + sm.org[2] + x) * C4;
     ((f32x4 *)t.out)[((((int64_t)n * a.P[0] + z) * a.P[1] + y) * a.P[2] + x) * C4 + c4] = src[c4];
@@ -390,9 +391,19 @@ static int stage0_gather_check(const S0GatherArgs &a, int n_samples, int *n_wv) 
             MI355_REQUIRE(a.smp[i].org[k] >= 0 && a.smp[i].org[k] + a.P[k] <= a.Ve[k], "stage0_gather: sample %d leaves the volume", i);
     // a slab holds every tile voxel that is read from it: its own thickness along its axis; across it the tile's extent with the
     // tile at 0, or the volume's with the tile at its origin (inside the volume, above)
+    // sub-boxes: a sample lies inside its tile, and a face of it that takes a shell is a face of the tile - a slab holds the t
+    // outermost layers of the TILE, which s0_slab_voxel addresses from the sample's own face; without sub-boxes every offset is zero
+    const bool boxes = a.T[0] > 0;
+    for (int i = 0; i < n_samples; ++i)
+        for (int k = 0; k < 3; ++k) {
+            MI355_REQUIRE(boxes ? a.sub[i][k] >= 0 && a.sub[i][k] + a.P[k] <= a.T[k] && a.sub[i][k] <= a.smp[i].org[k] : (a.T[k] == 0 && a.sub[i][k] == 0),
+                          "stage0_gather: sample %d: sub-box offset %d on axis %d (tile %d)", i, a.sub[i][k], k, a.T[k]);
+            MI355_REQUIRE(!boxes || ((a.smp[i].slab[2 * k] < 0 || a.sub[i][k] == 0) && (a.smp[i].slab[2 * k + 1] < 0 || a.sub[i][k] + a.P[k] == a.T[k])),
+                          "stage0_gather: sample %d: a shell at a face on axis %d that is not the tile's (offset %d, extent %d of %d)", i, k, a.sub[i][k], a.P[k], a.T[k]);
+        }
     for (int ax = 0; ax < 3; ++ax)
         for (int k = 0; k < 3; ++k) {
-            const int want = k == ax ? a.t[k] : (a.so[ax][k] ? a.Ve[k] : a.P[k]);
+            const int want = k == ax ? a.t[k] : (a.so[ax][k] ? a.Ve[k] : (boxes ? a.T[k] : a.P[k]));
             MI355_REQUIRE((a.so[ax][k] == 0 || (a.so[ax][k] == 1 && k != ax)) && a.D[ax][k] == want,
                           "stage0_gather: slab of axis %d: extent %d along %d (expected %d)", ax, a.D[ax][k], k, want);
         }

@@ -185,6 +185,11 @@ struct S0GatherArgs {
     int r2, C42;
     int n;                 // samples (set by stage0_gather)
     S0Sample smp[S0_MAX_SAMPLES];
+    // Sub-boxes (sliding_window.hip "shared level 1"; T[0] > 0): sample i is the P-sized box at sub[i] of a tile of T voxels, org
+    // its own origin in the volume; in a slab that carries the tile's own padding along k (so[a][k] = 0: D[a][k] = T[k]) it
+    // starts at sub[i][k], not at 0.  T = 0 and sub = 0: the samples are the tiles.
+    int T[3];
+    int sub[S0_MAX_SAMPLES][3];
 };
 // the slabs of every axis have the tile's extent across their axis (the form before merged slabs)
 inline void stage0_gather_dense(S0GatherArgs *a) {

@@ -1,5 +1,5 @@
 // The sliding-window predictor (host side): tile geometry and the Gaussian map, the shared stage 0 and what is built on it (slabs,
-// merged slabs, the shared skip half, stage-0 views), sw_accumulate and the mi355_sw_* entry points declared in
+// merged slabs, the shared skip half, stage-0 views, the shared level 1), sw_accumulate and the mi355_sw_* entry points declared in
 // include/mi355_nnunet.h, and the geometry dry runs through which the CPU tests see the decisions taken here.
 //
 // Reference behaviour restated here:
@@ -443,7 +443,8 @@ static S0ViewChoice stage0_views_decide(const mi355_unet &net, const S0Geom &sg,
 // the slabs of one batch of samples (indices into sg.smp), then the gather of the batch's tile tensor.  want: which tensors'
 // readers will take a view; *enc0_view / *half_view receive the views that were built (src = null: none, the tensor is dense).
 static int stage0_tiles(mi355_unet *net, const Plan &pl, const SwVolume &v, const SwGeom &g, const S0Geom &sg, const std::vector<int> &samples,
-                        hipStream_t s, S0ViewChoice want = S0ViewChoice(), S0View *enc0_view = nullptr, S0View *half_view = nullptr) {
+                        hipStream_t s, S0ViewChoice want = S0ViewChoice(), S0View *enc0_view = nullptr, S0View *half_view = nullptr,
+                        S0GatherArgs *ga_out = nullptr) {
     const int n = (int)samples.size();
     MI355_REQUIRE(n <= S0_MAX_SAMPLES, "shared stage 0: %d samples per forward (max %d)", n, S0_MAX_SAMPLES);
     const int C = net->enc[0].back().cout;
@@ -495,6 +496,7 @@ static int stage0_tiles(mi355_unet *net, const Plan &pl, const SwVolume &v, cons
         ga.r2 = sg.rs; ga.C42 = C2 / 4;
     } else
         for (int a = 0; a < 3; ++a) ga.slab2[a] = nullptr;
+    if (ga_out) *ga_out = ga;  // (shared level 1: the sources of the batch's sub-boxes)
     const double pv = (double)n * g.P[0] * g.P[1] * g.P[2];
     // stage-0 views: a view that cannot be built leaves its tensor to the full gather
     const int n_wv = (int)g.mirrors.size();
@@ -523,6 +525,408 @@ static int stage0_tiles(mi355_unet *net, const Plan &pl, const SwVolume &v, cons
     return stage0_gather(g1, n, s);
 }
 
+// ---- shared level 1: the geometry (level1_geometry), the decision (level1_share_decide) and their dry run
+// (mi355_level1_share_plan), then the region pass and the per-forward slabs that run on them (MI355_SHARE_LEVEL1).
+// A stride-2 conv commutes with shifts by an even number of voxels.  Along an axis on which every sample's origin is even, encoder
+// level 1 (one stride-2 block, then stride-1 blocks) and the skip half of the conv that reads its output (dec[np - 2][0]) are
+// therefore once more the same numbers computed once per tile: the shared stage 0, one level down.
+//   * An axis is MERGED when it has more than one tile origin, every sample's origin on it (a mirrored origin is Zp - P - org) is
+//     even and Zp is even; else it is PER-ORIGIN.
+//   * A REGION is one box per (mirror, origin tuple on the per-origin axes): P[a] on a per-origin axis, at the tile's origin; the
+//     whole extended volume Ve[a] on a merged one (the whole-volume stage-0 tensor is Ve wide, so a region reads it in place).  Its
+//     level-0 input is enc[0]'s whole-volume result, with stage-0 shells (depth r0) at its faces on per-origin axes that lie inside
+//     the volume - the region is a "tile" of the shared stage 0 there.  enc[1] and the skip half run over the regions once per
+//     volume, zeros restored outside Zp / 2 between the layers.
+//   * A tile's own level-1 values differ from its region's only near a tile face that lies inside the region on a merged axis:
+//     within floor(r0 / 2) + 1 behind the stride-2 conv, one more per stride-1 block: d1 = floor(r0 / 2) + k1 for enc[1]'s output
+//     (k1 blocks, the stride-2 one included), dS = d1 + 1 for the skip half.
+//   * Those shells come from one level-1 SLAB per such face: the chain over the 2 t1 outermost level-0 layers of the tile (its own
+//     padding and stage-0 shells on every other face, zero padding at the cut).  At the cut a hi slab loses one layer per conv
+//     (k1 + 1 convs), so t1 - (k1 + 1) >= dS: t1 = the smallest multiple of (4, 8, 8) >= floor(r0 / 2) + 2 k1 + 2, and >= 2 dS as
+//     the gather asks of every slab.
+// Proved exactly, on an integer chain, in tests/test_level1_share_plan_cpu.py.
+struct L1Region { int wv; int org[3]; int face[6]; };  // org in the (mirrored) pass; face[f] = 0: face f needs stage-0 shells, -1: not
+struct L1Sample { int region; int org1[3]; int slab[6]; };  // origin inside the region at level 1; slab[f] = 0: face f has a level-1 slab, else -1
+struct L1Geom {
+    bool possible = false;
+    int r0 = 0, k1 = 0, d1 = 0, dS = 0;
+    bool merged[3] = {false, false, false};
+    int R[3] = {0, 0, 0};    // level-0 extent of a region
+    int t1[3] = {0, 0, 0};   // level-1 slab thickness (0 on a per-origin axis)
+    std::vector<L1Region> regions;  // sorted by (mirror, origin)
+    std::vector<L1Sample> smp;      // [tile][mirror], as S0Geom::smp
+};
+
+static void level1_geometry(const SwGeom &g, const S0Geom &sg, int k1, L1Geom *o) {
+    static const int unit[3] = {4, 8, 8};
+    *o = L1Geom();
+    o->r0 = sg.r; o->k1 = k1;
+    if (!sg.shared || k1 < 1) return;
+    o->d1 = sg.r / 2 + k1; o->dS = o->d1 + 1;
+    bool any = false, fits = true;
+    for (int a = 0; a < 3; ++a) {
+        bool even = g.Zp[a] % 2 == 0 && g.P[a] % 2 == 0, several = false;
+        for (const S0Sample &sm : sg.smp) { even = even && sm.org[a] % 2 == 0; several = several || sm.org[a] != sg.smp[0].org[a]; }
+        o->merged[a] = even && several;
+        o->R[a] = o->merged[a] ? sg.Ve[a] : g.P[a];
+        if (!o->merged[a]) continue;
+        any = true;
+        o->t1[a] = ceil_div(std::max(sg.r / 2 + 2 * k1 + 2, 2 * o->dS), unit[a]) * unit[a];
+        // a tile with two faces inside the region has room for both slabs; the sub-box a slab is cut from holds its stage-0 shells
+        fits = fits && g.P[a] / 2 >= 2 * o->t1[a] && 2 * o->t1[a] >= 2 * sg.r;
+    }
+    if (!any || !fits) return;
+    o->possible = true;
+    typedef std::array<int, 4> Key;  // (wv, origin): sorted = the order of the regions
+    std::map<Key, int> keys;
+    auto key_of = [&](const S0Sample &sm) {
+        Key k = {sm.wv, 0, 0, 0};
+        for (int a = 0; a < 3; ++a) k[1 + a] = o->merged[a] ? 0 : sm.org[a];
+        return k;
+    };
+    for (const S0Sample &sm : sg.smp) keys[key_of(sm)] = 0;
+    for (auto &kv : keys) {
+        kv.second = (int)o->regions.size();
+        L1Region rg;
+        rg.wv = kv.first[0];
+        for (int a = 0; a < 3; ++a) {
+            rg.org[a] = kv.first[1 + a];
+            rg.face[2 * a] = !o->merged[a] && rg.org[a] > 0 ? 0 : -1;
+            rg.face[2 * a + 1] = !o->merged[a] && rg.org[a] + g.P[a] < g.Zp[a] ? 0 : -1;
+        }
+        o->regions.push_back(rg);
+    }
+    for (const S0Sample &sm : sg.smp) {
+        L1Sample ls;
+        ls.region = keys[key_of(sm)];
+        for (int a = 0; a < 3; ++a) {
+            ls.org1[a] = o->merged[a] ? sm.org[a] / 2 : 0;
+            ls.slab[2 * a] = o->merged[a] ? sm.slab[2 * a] : -1;  // (S0Sample::slab: 0 where the face lies inside the volume)
+            ls.slab[2 * a + 1] = o->merged[a] ? sm.slab[2 * a + 1] : -1;
+        }
+        o->smp.push_back(ls);
+    }
+}
+
+// The network side: the last decoder stage as the shared skip half sees it, and level 1.
+struct L1ShareNet {
+    SkipShareNet last;
+    int num_pool = 0;
+    int k1 = 0;              // blocks of enc[1]; its first has stride 2, the others stride 1
+    int c1 = 0;              // their output channels
+    bool skip_is_enc1 = true;  // the second input of dec[np - 2][0] is enc[1]'s output
+    int dec_blocks = 0;      // blocks of dec[np - 2]
+    int c_up = 0, cout = 0;  // of dec[np - 2][0]: channels of the upsampled half, output channels
+};
+// mode: 0 off, 1 the default rule, 2 wherever it is structurally possible.  Depends on the network and the geometry of all tiles
+// only.  The default rule asks P / 2 >= 8 t1 on every merged axis: a slab costs t1 / (P / 2) of a tile per face, so smaller patches
+// lose, and it leaves the patch 64 and 32 paths that existing tests pin bit for bit alone.
+static bool level1_share_decide(const L1ShareNet &d, const SwGeom &g, int mode, L1Geom *lg) {
+    L1Geom local;
+    if (!lg) lg = &local;
+    *lg = L1Geom();
+    const bool skip_on = skip_share_decide(d.last, g);
+    S0Geom sg;
+    stage0_geometry(g, d.last.r, &sg, skip_on ? 1 : 0);
+    level1_geometry(g, sg, d.k1, lg);
+    if (mode == 0 || !lg->possible) return false;
+    // fp32 (skip_share_decide), the shared stage 0, the shared skip half and the stage-0 views all on
+    if (!skip_on || !sg.shared || !env_switch("MI355_STAGE0_VIEWS")) return false;
+    // run-time statistics and an unfolded BatchNorm are the network's, not a block's: skip_share_decide has refused them
+    if (d.num_pool < 2 || d.k1 < 1 || !d.skip_is_enc1 || d.dec_blocks < 2) return false;
+    if (d.c1 <= 0 || d.c1 % 4 || d.c_up <= 0 || d.c_up % 4 || d.cout % 4) return false;
+    // dec[np - 2][0] over the upsampled half alone must be the kernel with the addend epilogue, its skip half a packed conv
+    ConvPackLayout lu, ls;
+    if (conv_pack_layout(d.c_up, d.c_up, d.cout, 1, &lu) != MI355_OK || conv_pack_layout(d.c1, d.c1, d.cout, 1, &ls) != MI355_OK) return false;
+    if (!lu.wino3 || !ls.mfma) return false;
+    static float stand_in[2];
+    const ConvWeights cw = stand_in_conv_weights(lu, d.c_up, d.cout, 1);
+    ConvCall c = make_call<float>(stand_in, d.c_up, 1, g.P[0] / 2, g.P[1] / 2, g.P[2] / 2, stand_in, nullptr, ACT_LRELU, 0.01f);
+    c.addend = stand_in;
+    ConvPlan p;
+    if (!plan_wino3(cw, c, &p) || strcmp(p.name, "conv3_f32_wino3_kernel<3, false>") != 0) return false;
+    // the regions read enc[0]'s whole-volume result in place: their first conv must be the stride-2 kernel that takes a view
+    if ((int)lg->regions.size() > S0_VIEW_MAX_SAMPLES) return false;
+    ConvPackLayout l1;
+    if (conv_pack_layout(d.last.c_skip, d.last.c_skip, d.c1, 2, &l1) != MI355_OK || !l1.mfma) return false;
+    const ConvWeights cw1 = stand_in_conv_weights(l1, d.last.c_skip, d.c1, 2);
+    const ConvCall cr = make_call<float>(stand_in, d.last.c_skip, (int)lg->regions.size(), lg->R[0], lg->R[1], lg->R[2], stand_in, nullptr, ACT_LRELU, 0.01f);
+    if (plan_conv_f32(cw1, cr, &p) != MI355_OK || p.family != FAM_S2DMA) return false;
+    static const int unit[3] = {4, 8, 8};
+    if (mode == 1)
+        for (int a = 0; a < 3; ++a) {
+            if (!lg->merged[a]) continue;
+            if (g.P[a] / 2 < 8 * lg->t1[a]) return false;
+            if (lg->R[a] / 2 % unit[a]) return false;  // a region that is no whole number of conv tiles at level 1 leaves the F(2x2x2,3x3x3) kernel
+        }
+    return true;
+}
+
+static L1ShareNet level1_share_net(const mi355_unet &net) {
+    L1ShareNet d;
+    d.last = skip_share_net(net);
+    d.num_pool = net.num_pool;
+    if (net.num_pool < 2 || net.dtype != MI355_F32) return d;
+    const std::vector<ConvLayer> &e1 = net.enc[1], &st = net.dec[net.num_pool - 2];
+    bool ok = !e1.empty() && e1[0].stride == 2 && !e1[0].is_stem;
+    for (size_t i = 0; i < e1.size(); ++i) ok = ok && (i == 0 || e1[i].stride == 1) && !e1[i].runtime_norm && !e1[i].post_affine;
+    d.k1 = ok ? (int)e1.size() : 0;
+    d.c1 = e1.back().cout;
+    d.dec_blocks = (int)st.size();
+    d.c_up = st[0].cin - d.c1; d.cout = st[0].cout;
+    d.skip_is_enc1 = d.c_up > 0 && st[0].split_c0 == d.c_up;  // (Generic_UNet: that stage's skip is enc[1]'s; the packs of the two halves were made)
+    return d;
+}
+int level1_share_mode() {
+    const char *e = getenv("MI355_SHARE_LEVEL1");
+    return !e || !*e ? 1 : (e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1));
+}
+
+constexpr int L1_SLAB_GROUP = 8;  // level-1 slabs run as launches of exactly this many (the last one filled up), as the stage-0 slabs do
+static int level1_slab_rows(int n_samples) { return ceil_div(2 * n_samples, L1_SLAB_GROUP) * L1_SLAB_GROUP; }
+
+// appends the level-1 regions to the plan of `n_samples` samples per forward
+static void level1_plan(const mi355_unet &net, const SwGeom &g, const S0Geom &sg, const L1Geom &lg, int n_samples, Plan *pl) {
+    size_t o = pl->total;
+    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~size_t(255); return r; };
+    int maxc0 = 0;
+    for (auto &L : net.enc[0]) maxc0 = std::max(maxc0, L.cout);
+    const size_t c0 = net.enc[0].back().cout, c1 = net.enc[1].back().cout, cS = net.dec[net.num_pool - 2][0].cout;
+    size_t rs_a[3] = {0, 0, 0}, rs_max = 0;
+    for (int a = 0; a < 3; ++a) {
+        size_t box = sg.t[a];
+        for (int k = 0; k < 3; ++k) if (k != a) box *= lg.R[k];
+        for (const L1Region &rg : lg.regions) rs_a[a] += ((rg.face[2 * a] >= 0) + (rg.face[2 * a + 1] >= 0)) * box;
+        rs_max = std::max(rs_max, rs_a[a]);
+    }
+    if (rs_max) {
+        pl->l1.rs_in = take(rs_max * net.cin_pad * 4);
+        for (int k = 0; k < 2 && k < sg.r - 1; ++k) pl->l1.rs_tmp[k] = take(rs_max * maxc0 * 4);
+        for (int a = 0; a < 3; ++a) pl->l1.rs_out[a] = take(rs_a[a] * c0 * 4);
+    }
+    const size_t rv0 = lg.regions.size() * (size_t)lg.R[0] * lg.R[1] * lg.R[2], rv1 = rv0 / 8;
+    pl->l1.r_shell = take(rv0 * c0 * 4);
+    for (int k = 0; k < 2; ++k) pl->l1.r_e[k] = take(rv1 * c1 * 4);
+    pl->l1.r_s = take(rv1 * cS * 4);
+    size_t tmp = 0;
+    for (int a = 0; a < 3; ++a) {
+        if (!lg.merged[a]) continue;
+        size_t sv0 = (size_t)level1_slab_rows(n_samples) * 2 * lg.t1[a];
+        for (int k = 0; k < 3; ++k) if (k != a) sv0 *= g.P[k];
+        pl->l1.sub_in[a] = take(sv0 * c0 * 4);
+        pl->l1.s_e[a] = take(sv0 / 8 * c1 * 4);
+        pl->l1.s_s[a] = take(sv0 / 8 * cS * 4);
+        tmp = std::max(tmp, sv0 / 8 * c1 * 4);
+    }
+    pl->l1.s_tmp = take(tmp);
+    pl->total = o;
+}
+
+// zero what lies outside `keep` of n boxes of S voxels each (nothing to do where keep == S)
+static int level1_mask(mi355_unet *net, void *x, int n, const int S[3], const int keep[3], int C, hipStream_t s) {
+    if (keep[0] == S[0] && keep[1] == S[1] && keep[2] == S[2]) return MI355_OK;
+    ProfScope ps(net, s, "stage0_mask_kernel", 0.0, (double)n * ((double)S[0] * S[1] * S[2] - (double)keep[0] * keep[1] * keep[2]) * C * 4.0);
+    return stage0_mask((float *)x, n, S, keep, C, s);
+}
+
+// enc[1] (its first block through in0_view when given) and the skip half of dec[np - 2][0] over n boxes of S level-0 voxels:
+// x0 -> e_out (through tmp, and e_out itself, in turns) and s_out; keep1: zeros restored outside it behind every block
+static int level1_chain(mi355_unet *net, const Plan &pl, const void *x0, const S0View *view, int n, const int S[3], const int *keep1, void *tmp,
+                        void *e_out, void *s_out, hipStream_t s) {
+    const std::vector<ConvLayer> &e1 = net->enc[1];
+    const int S1[3] = {S[0] / 2, S[1] / 2, S[2] / 2};
+    const void *cur = x0;
+    int curC = net->enc[0].back().cout;
+    for (size_t i = 0; i < e1.size(); ++i) {
+        void *out = ((e1.size() - 1 - i) & 1) ? tmp : e_out;  // (the last block writes e_out)
+        BlockOpts bo;
+        if (i == 0) bo.in0_view = view;
+        MI355_TRY(run_block(net, pl, e1[i], cur, curC, nullptr, 0, n, i ? S1[0] : S[0], i ? S1[1] : S[1], i ? S1[2] : S[2], out, s, bo));
+        if (keep1) MI355_TRY(level1_mask(net, out, n, S1, keep1, e1[i].cout, s));
+        cur = out; curC = e1[i].cout;
+    }
+    const ConvLayer &Ld = net->dec[net->num_pool - 2][0];
+    BlockOpts bo;
+    bo.half = &Ld.w_skip; bo.half_name = " skip-half";
+    return run_block(net, pl, Ld, cur, curC, nullptr, 0, n, S1[0], S1[1], S1[2], s_out, s, bo);
+}
+
+// region pass, once per volume behind the whole-volume pass: the stage-0 slabs at the regions' faces on per-origin axes, the
+// regions' level-0 shells, then enc[1] and the skip half over the regions, their level-0 input read in place through a view
+static int level1_regions(mi355_unet *net, const Plan &pl, const SwVolume &v, const SwGeom &g, const S0Geom &sg, const L1Geom &lg, hipStream_t s) {
+    const int nreg = (int)lg.regions.size();
+    const int c0 = net->enc[0].back().cout;
+    MI355_REQUIRE(nreg > 0 && nreg <= S0_VIEW_MAX_SAMPLES, "shared level 1: %d regions (max %d)", nreg, S0_VIEW_MAX_SAMPLES);
+    S0GatherArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    for (int i = 0; i < nreg; ++i) {
+        ga.smp[i].wv = lg.regions[i].wv;
+        for (int k = 0; k < 3; ++k) ga.smp[i].org[k] = lg.regions[i].org[k];
+        for (int f = 0; f < 6; ++f) ga.smp[i].slab[f] = -1;
+    }
+    bool any = false;
+    for (int a = 0; a < 3; ++a) {
+        int S[3], keep[3];
+        for (int k = 0; k < 3; ++k) { S[k] = k == a ? sg.t[k] : lg.R[k]; keep[k] = lg.merged[k] ? g.Zp[k] : S[k]; }
+        std::vector<TileDesc> boxes;
+        for (int i = 0; i < nreg; ++i)
+            for (int side = 0; side < 2; ++side) {
+                if (lg.regions[i].face[2 * a + side] < 0) continue;
+                int b[3] = {lg.regions[i].org[0], lg.regions[i].org[1], lg.regions[i].org[2]};
+                if (side) b[a] += lg.R[a] - sg.t[a];
+                ga.smp[i].slab[2 * a + side] = (int)boxes.size();
+                boxes.push_back(pass_box(g, g.mirrors[lg.regions[i].wv], b, S));
+            }
+        ga.slab[a] = (const float *)(pl.arena + pl.l1.rs_out[a]);
+        if (boxes.empty()) continue;
+        any = true;
+        const bool extended = keep[0] != S[0] || keep[1] != S[1] || keep[2] != S[2];
+        S0Placement at;
+        at.S = S; at.mask_zp = extended ? keep : nullptr; at.label = " region-slabs";
+        at.in_off = pl.l1.rs_in; at.tmp_off = pl.l1.rs_tmp; at.out_off = pl.l1.rs_out[a];
+        MI355_TRY(stage0_run(net, pl, v, g, boxes, at, s));
+        // (stage0_run leaves its last layer unmasked when no skip half follows; the regions read it)
+        MI355_TRY(level1_mask(net, pl.arena + pl.l1.rs_out[a], (int)boxes.size(), S, keep, c0, s));
+    }
+    ga.wv = (const float *)(pl.arena + pl.s0.wv_out);
+    ga.out = (float *)(pl.arena + pl.l1.r_shell);
+    for (int k = 0; k < 3; ++k) { ga.P[k] = lg.R[k]; ga.Ve[k] = sg.Ve[k]; ga.t[k] = sg.t[k]; }
+    stage0_gather_dense(&ga);
+    ga.r = sg.r; ga.C4 = c0 / 4;
+    if (any) {
+        double shell = 0.0;
+        for (int i = 0; i < nreg; ++i) shell += (double)stage0_shell_voxels(ga.P, ga.r, ga.smp[i].slab);
+        ProfScope ps(net, s, "stage0_gather_kernel regions", 0.0, 2.0 * 4.0 * shell * c0);
+        MI355_TRY(stage0_gather_shells(ga, nreg, 0, s));
+    }
+    S0View view;
+    MI355_TRY(stage0_view_make(ga.wv, (int)g.mirrors.size(), ga.Ve, ga.P, c0, ga.r, ga.smp, nreg, &view));
+    int keep1[3], R1[3];
+    bool extended = false;
+    for (int k = 0; k < 3; ++k) { R1[k] = lg.R[k] / 2; keep1[k] = lg.merged[k] ? g.Zp[k] / 2 : R1[k]; extended = extended || keep1[k] != R1[k]; }
+    const int last = (int)((net->enc[1].size() - 1) & 1);
+    return level1_chain(net, pl, ga.out, &view, nreg, lg.R, extended ? keep1 : nullptr, pl.arena + pl.l1.r_e[last ^ 1], pl.arena + pl.l1.r_e[last],
+                        pl.arena + pl.l1.r_s, s);
+}
+
+// per forward: the level-1 slabs of the batch's samples (indices into sg.smp; ga0 = the stage-0 gather of the same batch, whose
+// sources give a sub-box its level-0 features), then the gather of the two level-1 tile tensors from the regions and the slabs
+static int level1_tiles(mi355_unet *net, const Plan &pl, const SwGeom &g, const S0Geom &sg, const L1Geom &lg, const S0GatherArgs &ga0,
+                        const std::vector<int> &samples, hipStream_t s, S0View *e1_view = nullptr, S0View *s1_view = nullptr) {
+    static const int unit[3] = {4, 8, 8};
+    const bool views = env_switch("MI355_STAGE0_VIEWS");
+    const int n = (int)samples.size();
+    const int c0 = net->enc[0].back().cout, c1 = net->enc[1].back().cout, cS = net->dec[net->num_pool - 2][0].cout;
+    MI355_REQUIRE(level1_slab_rows(n) <= S0_MAX_SAMPLES, "shared level 1: %d samples per forward", n);
+    S0GatherArgs fin;
+    memset(&fin, 0, sizeof(fin));
+    for (int i = 0; i < n; ++i) {
+        const L1Sample &ls = lg.smp[samples[i]];
+        fin.smp[i].wv = ls.region;
+        for (int k = 0; k < 3; ++k) fin.smp[i].org[k] = ls.org1[k];
+        for (int f = 0; f < 6; ++f) fin.smp[i].slab[f] = -1;
+    }
+    for (int a = 0; a < 3; ++a) {
+        fin.slab[a] = (const float *)(pl.arena + pl.l1.s_e[a]);
+        fin.slab2[a] = (const float *)(pl.arena + pl.l1.s_s[a]);
+        fin.t[a] = lg.merged[a] ? lg.t1[a] : ceil_div(2 * lg.dS, unit[a]) * unit[a];  // (a per-origin axis has no slab; the gather asks for a thickness all the same)
+        if (!lg.merged[a]) continue;
+        int Sb[3];
+        for (int k = 0; k < 3; ++k) Sb[k] = k == a ? 2 * lg.t1[a] : g.P[k];
+        // the sub-boxes' level-0 features, dense: the sources, slabs and precedence of the batch's stage-0 gather
+        S0GatherArgs gs = ga0;
+        gs.wv2 = nullptr; gs.out2 = nullptr; gs.r2 = 0; gs.C42 = 0;
+        for (int k = 0; k < 3; ++k) { gs.slab2[k] = nullptr; gs.P[k] = Sb[k]; gs.T[k] = g.P[k]; }
+        memset(gs.sub, 0, sizeof(gs.sub));
+        int ns = 0;
+        for (int i = 0; i < n; ++i)
+            for (int side = 0; side < 2; ++side) {
+                if (lg.smp[samples[i]].slab[2 * a + side] < 0) continue;
+                const int off = side ? g.P[a] - Sb[a] : 0;
+                S0Sample sb = ga0.smp[i];
+                sb.org[a] += off;
+                sb.slab[2 * a + (side ^ 1)] = -1;  // the cut: zero padding, no shell
+                gs.smp[ns] = sb;
+                gs.sub[ns][a] = off;
+                fin.smp[i].slab[2 * a + side] = ns++;
+            }
+        if (!ns) continue;
+        for (; ns % L1_SLAB_GROUP; ++ns) { gs.smp[ns] = gs.smp[ns - 1]; memcpy(gs.sub[ns], gs.sub[ns - 1], sizeof(gs.sub[0])); }  // (a whole last launch: its spare results are not read)
+        gs.out = (float *)(pl.arena + pl.l1.sub_in[a]);
+        const size_t sv0 = (size_t)Sb[0] * Sb[1] * Sb[2], sv1 = sv0 / 8;
+        // where a launch of L1_SLAB_GROUP sub-boxes goes to the stride-2 kernel that takes a view, it reads enc[0]'s whole-volume
+        // result in place and the gather writes the sub-boxes' shells alone (bit-identical: a view changes where bytes are read)
+        bool viewed = false;
+        if (views) {
+            static float stand_in[2];
+            const ConvCall c = make_call<float>(stand_in, c0, L1_SLAB_GROUP, Sb[0], Sb[1], Sb[2], stand_in, nullptr, ACT_LRELU, 0.01f);
+            ConvPlan p;
+            viewed = plan_conv_f32(net->enc[1][0].w, c, &p) == MI355_OK && p.family == FAM_S2DMA;
+            S0View probe;
+            viewed = viewed && stage0_view_make(gs.wv, (int)g.mirrors.size(), gs.Ve, gs.P, c0, gs.r, gs.smp, L1_SLAB_GROUP, &probe) == MI355_OK;
+        }
+        {
+            double shell = 0.0;
+            for (int i = 0; i < ns; ++i) shell += (double)stage0_shell_voxels(gs.P, gs.r, gs.smp[i].slab);
+            ProfScope ps(net, s, "stage0_gather_kernel sub-boxes", 0.0, 2.0 * 4.0 * (viewed ? shell : (double)ns * sv0) * c0);
+            if (viewed) MI355_TRY(stage0_gather_shells(gs, ns, 0, s));
+            else MI355_TRY(stage0_gather(gs, ns, s));
+        }
+        for (int g0 = 0; g0 < ns; g0 += L1_SLAB_GROUP) {
+            S0View view;
+            if (viewed) MI355_TRY(stage0_view_make(gs.wv, (int)g.mirrors.size(), gs.Ve, gs.P, c0, gs.r, gs.smp + g0, L1_SLAB_GROUP, &view));
+            MI355_TRY(level1_chain(net, pl, pl.arena + pl.l1.sub_in[a] + g0 * sv0 * c0 * 4, viewed ? &view : nullptr, L1_SLAB_GROUP, Sb, nullptr,
+                                   pl.arena + pl.l1.s_tmp, pl.arena + pl.l1.s_e[a] + g0 * sv1 * c1 * 4, pl.arena + pl.l1.s_s[a] + g0 * sv1 * cS * 4, s));
+        }
+    }
+    const int last = (int)((net->enc[1].size() - 1) & 1);
+    fin.wv = (const float *)(pl.arena + pl.l1.r_e[last]);
+    fin.wv2 = (const float *)(pl.arena + pl.l1.r_s);
+    fin.out = (float *)(pl.arena + pl.off[last][1]);
+    fin.out2 = (float *)(pl.arena + pl.off[last ^ 1][1]);
+    for (int k = 0; k < 3; ++k) { fin.P[k] = g.P[k] / 2; fin.Ve[k] = lg.R[k] / 2; }
+    stage0_gather_dense(&fin);
+    fin.r = lg.d1; fin.C4 = c1 / 4; fin.r2 = lg.dS; fin.C42 = cS / 4;
+    // the two readers take views where they can - enc[2][0] when the planner sends this forward's call to the stride-2 kernel that
+    // has one, the addend epilogue always - and the gather then writes the shells alone
+    const int nreg = (int)lg.regions.size();
+    bool v0 = false, v1 = false;
+    if (views && e1_view && s1_view && net->num_pool >= 2 && !net->enc[2].empty()) {
+        const ConvLayer &L2 = net->enc[2][0];
+        static float stand_in[2];
+        const ConvCall c = make_call<float>(stand_in, c1, n, fin.P[0], fin.P[1], fin.P[2], stand_in, L2.runtime_norm ? (double *)stand_in : nullptr, ACT_LRELU, 0.01f);
+        ConvPlan p;
+        v0 = !L2.is_stem && L2.w.wp_dev && L2.stride == 2 && plan_conv_f32(L2.w, c, &p) == MI355_OK && p.family == FAM_S2DMA &&
+             stage0_view_make(fin.wv, nreg, fin.Ve, fin.P, c1, fin.r, fin.smp, n, e1_view) == MI355_OK;
+        v1 = stage0_view_make(fin.wv2, nreg, fin.Ve, fin.P, cS, fin.r2, fin.smp, n, s1_view) == MI355_OK;
+    }
+    const double pv = (double)n * fin.P[0] * fin.P[1] * fin.P[2];
+    double shell0 = 0.0, shell1 = 0.0;
+    for (int i = 0; i < n; ++i) { shell0 += (double)stage0_shell_voxels(fin.P, fin.r, fin.smp[i].slab); shell1 += (double)stage0_shell_voxels(fin.P, fin.r2, fin.smp[i].slab); }
+    ProfScope ps(net, s, "stage0_gather_kernel level 1", 0.0, 2.0 * 4.0 * ((v0 ? shell0 : pv) * c1 + (v1 ? shell1 : pv) * cS));
+    if (!v0 && !v1) return stage0_gather(fin, n, s);
+    if (v0) MI355_TRY(stage0_gather_shells(fin, n, 0, s));
+    else {
+        S0GatherArgs f0 = fin;
+        f0.out2 = nullptr; f0.wv2 = nullptr;
+        MI355_TRY(stage0_gather(f0, n, s));
+    }
+    if (v1) return stage0_gather_shells(fin, n, 1, s);
+    S0GatherArgs f1 = fin;  // the skip half whole, alone: as the first tensor of a gather
+    f1.wv = fin.wv2; f1.out = fin.out2; f1.r = fin.r2; f1.C4 = fin.C42;
+    for (int a = 0; a < 3; ++a) f1.slab[a] = fin.slab2[a];
+    f1.out2 = nullptr; f1.wv2 = nullptr;
+    return stage0_gather(f1, n, s);
+}
+
+static L1ShareNet level1_share_net_from_abi(const mi355_level1_share_net *nd) {
+    L1ShareNet d;
+    d.last = skip_share_net_from_abi(&nd->last);
+    d.num_pool = nd->num_pool; d.k1 = nd->enc1_blocks; d.c1 = nd->c_level1;
+    d.skip_is_enc1 = nd->skip_is_enc1 != 0; d.dec_blocks = nd->dec1_blocks; d.c_up = nd->c_up1; d.cout = nd->cout1;
+    return d;
+}
+
 // Evaluates the tiles with (index % world) == rank of one net; adds into agg (and cnt if non-null,
 // for ALL tiles so that every rank holds the full normaliser).
 // `first_item`: index of this net's tile 0 in the caller's work list (fold f of a fold list: f * tiles): the work items
@@ -543,8 +947,14 @@ static int sw_accumulate(mi355_unet *net, const SwVolume &v, const mi355_sw_opts
     if (use_gauss) MI355_TRY(ensure_gaussian(net, g.P));
     std::vector<int> mine;
     for (size_t t = 0; t < g.tiles.size(); ++t) if ((int)((first_item + (long)t) % world) == rank) mine.push_back((int)t);
-    const int bt = sw_batch_tiles(net->dtype, o.batch_tiles, nm);
+    int bt = sw_batch_tiles(net->dtype, o.batch_tiles, nm);
     MI355_REQUIRE(nm <= 64, "too many mirrors");
+    // shared level 1: decided by the network and the geometry of all tiles alone; a forward then holds at most two slabs per sample
+    // and axis in one gather, so a batch the caller asked to be larger than S0_MAX_SAMPLES / 2 samples is split (the default batch
+    // of an fp32 net is 16; mi355_stage0_view_plan, asked for more samples than that, does not know of the cap)
+    L1Geom lg;
+    const bool share_l1 = level1_share_decide(level1_share_net(*net), g, level1_share_mode(), &lg);
+    if (share_l1 && level1_slab_rows(bt * nm) > S0_MAX_SAMPLES) bt = std::max(1, S0_MAX_SAMPLES / 2 / nm);
     Plan pl;
     MI355_TRY(make_plan(*net, bt * nm, g.P[0], g.P[1], g.P[2], &pl));
     S0Geom sg;
@@ -552,10 +962,13 @@ static int sw_accumulate(mi355_unet *net, const SwVolume &v, const mi355_sw_opts
     stage0_geometry(g, stage0_blocks(*net), &sg, share_skip ? 1 : 0);
     if (env_switch("MI355_MERGE_SLABS")) stage0_merge_geometry(g, &sg);
     if (sg.shared) stage0_plan(*net, g, sg, bt * nm, &pl);
+    MI355_REQUIRE(!share_l1 || (sg.shared && share_skip), "shared level 1 without the shared stage 0 and the shared skip half");
+    if (share_l1) level1_plan(*net, g, sg, lg, bt * nm, &pl);
     MI355_TRY(ensure_arena(&pl, s));
     if (mine.empty()) return MI355_OK;
     if (sg.shared) MI355_TRY(stage0_whole(net, pl, v, g, sg, s));
     if (sg.merge) MI355_TRY(stage0_merged(net, pl, v, g, sg, s));
+    if (share_l1) MI355_TRY(level1_regions(net, pl, v, g, sg, lg, s));
     for (size_t b0 = 0; b0 < mine.size(); b0 += bt) {
         const int nb = (int)std::min<size_t>(bt, mine.size() - b0);
         std::vector<TileDesc> samples;
@@ -567,10 +980,12 @@ static int sw_accumulate(mi355_unet *net, const SwVolume &v, const mi355_sw_opts
                 samples.push_back(td);
                 sample_ids.push_back(mine[b0 + i] * nm + m);
             }
-        S0View enc0_view, half_view;
+        S0View enc0_view, half_view, enc1_view, half1_view;
         if (sg.shared) {
             const S0ViewChoice want = stage0_views_decide(*net, sg, share_skip, (int)samples.size(), g.P);
-            MI355_TRY(stage0_tiles(net, pl, v, g, sg, sample_ids, s, want, &enc0_view, &half_view));
+            S0GatherArgs ga0;
+            MI355_TRY(stage0_tiles(net, pl, v, g, sg, sample_ids, s, want, &enc0_view, &half_view, share_l1 ? &ga0 : nullptr));
+            if (share_l1) MI355_TRY(level1_tiles(net, pl, g, sg, lg, ga0, sample_ids, s, &enc1_view, &half1_view));
         } else {
         const double pv = (double)samples.size() * g.P[0] * g.P[1] * g.P[2];
         ProfScope ps(net, s, "extract_tiles_kernel", 0.0, pv * (4.0 * net->in_channels + (net->dtype == MI355_F16 ? 2.0 : 4.0) * net->cin_pad));
@@ -585,6 +1000,12 @@ static int sw_accumulate(mi355_unet *net, const SwVolume &v, const mi355_sw_opts
         if (share_skip) fo.skip_half = (const float *)(pl.arena + pl.off[((net->enc[0].size() - 1) & 1) ^ 1][0]);
         if (enc0_view.src) fo.enc0_view = &enc0_view;
         if (half_view.src) fo.skip_half_view = &half_view;
+        if (share_l1) {
+            fo.after_enc1 = true;
+            fo.skip_half1 = (const float *)(pl.arena + pl.off[((net->enc[1].size() - 1) & 1) ^ 1][1]);
+            if (enc1_view.src) fo.enc1_view = &enc1_view;
+            if (half1_view.src) fo.skip_half1_view = &half1_view;
+        }
         MI355_TRY(forward_features(net, pl, (int)samples.size(), g.P[0], g.P[1], g.P[2], &feat, &fc, s, fo));
         MI355_REQUIRE(is_logits || fc == net->head.cin, "head expects %d channels, decoder gives %d", net->head.cin, fc);
         if (is_logits) {  // the forward's tiles in one launch: agg / cnt are read and written once per voxel, not once per tile
@@ -849,6 +1270,63 @@ extern "C" int mi355_stage0_view_plan(int z, int y, int x, const int32_t patch[3
         for (int f = 0; f < 6; ++f) q.faces |= sm.slab[f] >= 0 ? 1 << f : 0;
         q.shell_voxels[0] = stage0_shell_voxels(g.P, sg.r, sm.slab);
         q.shell_voxels[1] = on ? stage0_shell_voxels(g.P, sg.rs, sm.slab) : 0;
+    }
+    return n;
+}
+
+// ---- shared level 1: dry run
+extern "C" int mi355_level1_share_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes,
+                                       const mi355_level1_share_net *nd, int mode, mi355_level1_share_geom *out,
+                                       mi355_level1_share_region *regions, int max_regions, mi355_level1_share_sample *samples, int max_samples) {
+    MI355_REQUIRE(out && patch && nd && mode >= 0 && mode <= 2 && (regions || max_regions == 0) && (samples || max_samples == 0),
+                  "mi355_level1_share_plan: bad argument");
+    SwGeom g;
+    MI355_TRY(sw_geom_from_abi(z, y, x, patch, step_size, mirror_axes, &g));
+    const L1ShareNet d = level1_share_net_from_abi(nd);
+    L1Geom lg;
+    const bool on = level1_share_decide(d, g, mode, &lg);
+    S0Geom sg;
+    stage0_geometry(g, d.last.r, &sg, skip_share_decide(d.last, g) ? 1 : 0);
+    memset(out, 0, sizeof(*out));
+    out->possible = lg.possible; out->on = on;
+    out->r0 = lg.r0; out->k1 = lg.k1; out->d1 = lg.d1; out->dS = lg.dS;
+    out->n_tiles = (int32_t)g.tiles.size(); out->n_mirrors = (int32_t)g.mirrors.size();
+    for (int a = 0; a < 3; ++a) { out->padded[a] = g.Zp[a]; out->volume[a] = sg.Ve[a]; out->stage0_slab_thickness[a] = sg.t[a]; }
+    out->tile_voxels = (int64_t)sg.smp.size() * (g.P[0] / 2) * (g.P[1] / 2) * (g.P[2] / 2);
+    if (!lg.possible) return 0;
+    out->n_regions = (int32_t)lg.regions.size();
+    for (int a = 0; a < 3; ++a) { out->merged[a] = lg.merged[a]; out->region[a] = lg.R[a]; out->slab_thickness[a] = lg.t1[a]; }
+    out->region_voxels = (int64_t)lg.regions.size() * (lg.R[0] / 2) * (lg.R[1] / 2) * (lg.R[2] / 2);
+    for (size_t i = 0; i < lg.regions.size() && (int)i < max_regions; ++i) {
+        mi355_level1_share_region &q = regions[i];
+        memset(&q, 0, sizeof(q));
+        q.mirror = g.mirrors[lg.regions[i].wv];
+        for (int a = 0; a < 3; ++a) q.origin[a] = lg.regions[i].org[a];
+        for (int f = 0; f < 6; ++f) q.faces |= lg.regions[i].face[f] >= 0 ? 1 << f : 0;
+    }
+    const int n = (int)lg.smp.size();
+    for (int i = 0; i < n; ++i) {
+        const L1Sample &ls = lg.smp[i];
+        const S0Sample &sm = sg.smp[i];
+        mi355_level1_share_sample q;
+        memset(&q, 0, sizeof(q));
+        q.tile = i / (int)g.mirrors.size(); q.mirror = g.mirrors[sm.wv]; q.region = ls.region;
+        for (int a = 0; a < 3; ++a) { q.origin[a] = sm.org[a]; q.origin1[a] = ls.org1[a]; }
+        for (int f = 0; f < 6; ++f) {
+            q.faces |= sm.slab[f] >= 0 ? 1 << f : 0;
+            if (ls.slab[f] < 0) continue;
+            const int a = f >> 1;
+            q.slab[f] = 1;
+            out->n_slabs[a] += 1;
+            int64_t v = lg.t1[a];
+            for (int k = 0; k < 3; ++k) {
+                q.slab_shape[f][k] = k == a ? 2 * lg.t1[a] : g.P[k];
+                q.slab_offset[f][k] = k == a && (f & 1) ? g.P[a] - 2 * lg.t1[a] : 0;
+                if (k != a) v *= g.P[k] / 2;
+            }
+            out->slab_voxels += v;
+        }
+        if (i < max_samples) samples[i] = q;
     }
     return n;
 }

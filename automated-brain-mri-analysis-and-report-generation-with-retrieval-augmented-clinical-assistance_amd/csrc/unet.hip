@@ -247,8 +247,9 @@ int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W
     for (int l = 0; l <= np; ++l) {
         int Di = D >> l, Hi = H >> l, Wi = W >> l;
         bool pending = false;  // cur holds a raw conv output whose normalisation the next block applies
-        if (l == 0 && o.after_enc0) { cur = buf((int)((net->enc[0].size() - 1) & 1), 0); curC = net->enc[0].back().cout; }
-        for (size_t i = 0; i < net->enc[l].size() && !(l == 0 && o.after_enc0); ++i) {
+        const bool given = (l == 0 && o.after_enc0) || (l == 1 && o.after_enc1);
+        if (given) { cur = buf((int)((net->enc[l].size() - 1) & 1), l); curC = net->enc[l].back().cout; }
+        for (size_t i = 0; i < net->enc[l].size() && !given; ++i) {
             const ConvLayer &L = net->enc[l][i];
             int inD = Di, inH = Hi, inW = Wi;
             if (L.stride == 2) { inD = Di * 2; inH = Hi * 2; inW = Wi * 2; }
@@ -257,6 +258,7 @@ int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W
             BlockOpts bo;
             bo.defer_norm = defer; bo.in_norm = pending;
             if (l == 1 && i == 0 && o.after_enc0) bo.in0_view = o.enc0_view;
+            if (l == 2 && i == 0 && o.after_enc1) bo.in0_view = o.enc1_view;
             MI355_TRY(run_block(net, pl, L, cur, curC, nullptr, 0, N, inD, inH, inW, out, s, bo));
             pending = defer;
             cur = out; curC = L.cout;
@@ -264,6 +266,7 @@ int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W
         if (l < np) { skip[l] = cur; skipC[l] = curC; }
     }
     MI355_REQUIRE(!o.enc0_view || (o.skip_half && np >= 1), "stage-0 view of the level-0 features while the decoder reads them whole");
+    MI355_REQUIRE(!o.after_enc1 || (o.after_enc0 && o.skip_half && o.skip_half1 && np >= 2), "shared level 1 without the shared stage 0 and both skip halves");
     // decoder
     for (int u = 0; u < np; ++u) {
         const int l = np - 1 - u;
@@ -302,6 +305,14 @@ int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W
                 *o.is_logits = true;
                 *feat = lg; *feat_c = net->head.ncls;
                 return MI355_OK;
+            }
+            if (o.skip_half1 && l == 1 && i == 0) {
+                MI355_REQUIRE(L.split_c0 == C0 && (const void *)o.skip_half1 == freeAB && net->dec[u].size() > 1, "shared level 1: the block was not split at %d channels", C0);
+                BlockOpts bo;
+                bo.half = &L.w_up; bo.addend = o.skip_half1; bo.half_name = " up-half"; bo.addend_view = o.skip_half1_view;
+                MI355_TRY(run_block(net, pl, L, in0, C0, nullptr, 0, N, Dl, Hl, Wl, out, s, bo));
+                in0 = out; C0 = L.cout; in1 = nullptr; C1 = 0;
+                continue;
             }
             if (o.skip_half && u == np - 1 && i == 0) {
                 MI355_REQUIRE(L.split_c0 == C0 && (const void *)o.skip_half == freeAB, "shared skip half: the block was not split at %d channels", C0);
@@ -394,9 +405,13 @@ extern "C" int mi355_unet_create(const mi355_unet_desc *d, mi355_unet_t *out) {
             const mi355_conv_desc &cd = d->convs[ci++];
             if (cd.stride != 1 || cd.cin != inC) { set_error("decoder conv %d.%d: cin %d stride %d, expected %d / 1", u, i, cd.cin, cd.stride, inC); return fail(MI355_ERR_INVALID); }
             ConvLayer L;
+            // (the stage that reads enc[0]'s output - shared skip half - and, unless MI355_SHARE_LEVEL1 is 0 now, the one that reads
+            //  enc[1]'s - shared level 1; the latter is never the net's last conv.  A net made with the switch at 0 has no such packs
+            //  and never takes that path)
             const SkipShareNet half = skip_share_net_of(d->dtype, stage0_blocks(*net), cd.stride, d->norm, d->nonlin_first, td.cout, skipC[l], cd.cout,
                                                          d->dec_convs[u] == 1 ? d->num_classes : 0);
-            rc = build_conv(*net, cd, inC, &L, false, (u == d->num_pool - 1 && i == 0) ? &half : nullptr);
+            const bool split = i == 0 && (l == 0 || (l == 1 && d->dec_convs[u] > 1 && level1_share_mode() != 0));
+            rc = build_conv(*net, cd, inC, &L, false, split ? &half : nullptr);
             if (rc != MI355_OK) return fail(rc);
             net->dec[u].push_back(L);
             inC = cd.cout;

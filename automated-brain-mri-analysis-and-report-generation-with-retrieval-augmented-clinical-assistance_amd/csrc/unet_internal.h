@@ -73,6 +73,10 @@ struct Plan {
     // shared stage 0 (stage0_plan): whole-volume input / intermediate / result and the slab buffers, behind the tile plan
     struct { size_t wv_in = 0, wv_tmp[2] = {0, 0}, wv_out = 0, slab_in = 0, slab_tmp[2] = {0, 0}, slab_out[3] = {0, 0, 0};
              size_t wv_skip = 0, slab_skip[3] = {0, 0, 0}; } s0;  // (shared skip half: S over the whole volume and over the slabs)
+    // shared level 1 (level1_plan): the regions' stage-0 slabs and level-0 shells, their level-1 tensors, and per forward the
+    // level-0 sub-boxes of the tile slabs and their level-1 tensors
+    struct { size_t rs_in = 0, rs_tmp[2] = {0, 0}, rs_out[3] = {0, 0, 0}, r_shell = 0, r_e[2] = {0, 0}, r_s = 0;
+             size_t sub_in[3] = {0, 0, 0}, s_tmp = 0, s_e[3] = {0, 0, 0}, s_s[3] = {0, 0, 0}; } l1;
 };
 int make_plan(const mi355_unet &net, int N, int D, int H, int W, Plan *pl);
 int ensure_arena(Plan *pl, hipStream_t s);
@@ -160,6 +164,11 @@ struct ForwardOpts {
     bool after_enc0 = false;
     const float *skip_half = nullptr;
     const S0View *enc0_view = nullptr, *skip_half_view = nullptr;
+    // shared level 1: enc[1]'s output is already where its last block writes it and the pass starts at level 2; skip_half1 =
+    // the skip half of dec[np - 2][0], gathered into the level-1 buffer that stage leaves free
+    bool after_enc1 = false;
+    const float *skip_half1 = nullptr;
+    const S0View *enc1_view = nullptr, *skip_half1_view = nullptr;  // views into the regions' tensors: the tile tensors hold their shells only
 };
 int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W, const void **feat, int *feat_c, hipStream_t s,
                      const ForwardOpts &o = ForwardOpts());
@@ -200,5 +209,6 @@ inline SkipShareNet skip_share_net_of(int dtype, int r, int stride, int norm, in
 }
 bool skip_share_network_ok(const SkipShareNet &d);
 int stage0_blocks(const mi355_unet &net);
+int level1_share_mode();  // MI355_SHARE_LEVEL1: 0 off, 1 the default rule (unset), 2 wherever possible (sliding_window.hip "shared level 1")
 
 }  // namespace mi355

@@ -390,6 +390,41 @@ def stage0_view_plan(volume, patch, step_size=0.5, mirror_axes=(), dtype="f32", 
             "n_mirrors": int(g.n_mirrors), "volume": tuple(g.volume), "samples": samples}
 
 
+def level1_share_plan(volume, patch, step_size=0.5, mirror_axes=(), mode=1, dtype="f32", norm="batch", nonlin_first=False, enc0_blocks=2,
+                      c_level0=32, num_pool=5, enc1_blocks=2, c_level1=64, skip_is_enc1=True, dec1_blocks=2):
+    """Dry run of the shared level 1 (``mi355_level1_share_plan``; no GPU needed: the decision a sliding window runs under ``MI355_SHARE_LEVEL1``) for a volume
+    (Z, Y, X), a patch, the mirror axes and a description of the network (defaults: model A).  mode: 0 off, 1 the default rule,
+    2 wherever it is structurally possible.  Returns a dict: possible, on, r0, k1, d1, dS, n_tiles, n_mirrors, padded, volume,
+    stage0_slab_thickness, merged (per axis), region (level-0 extent), slab_thickness (level 1), n_slabs, region_voxels /
+    slab_voxels / tile_voxels (level-1 voxels), regions - dicts (mirror, origin, faces) - and samples, tile-major - dicts (tile,
+    mirror, region, origin, origin1, faces and slabs: face -> (offset, shape) of the level-0 sub-box of the tile)."""
+    last = _lib.SkipShareNet({"f32": 0, "f16": 1}[dtype], {"none": 0, "batch": 1, "instance": 2, "group": 3}[norm], int(bool(nonlin_first)),
+                             int(enc0_blocks), 1, 1, int(c_level0), int(c_level0), int(c_level0), 0)
+    nd = _lib.Level1ShareNet(last, int(num_pool), int(enc1_blocks), int(c_level1), int(bool(skip_is_enc1)), int(dec1_blocks),
+                             int(c_level1), int(c_level1))
+    lib = _lib.load()
+    g = _lib.Level1ShareGeom()
+    z, y, x = (int(v) for v in volume)
+    mask = sum(1 << int(a) for a in mirror_axes)
+    head = (z, y, x, _i3(patch), float(step_size), mask, C.byref(nd), int(mode), C.byref(g))
+    n = lib.mi355_level1_share_plan(*head, None, 0, None, 0)
+    _lib.check(n, "mi355_level1_share_plan")
+    regs = (_lib.Level1ShareRegion * max(int(g.n_regions), 1))()
+    smp = (_lib.Level1ShareSample * max(n, 1))()
+    _lib.check(lib.mi355_level1_share_plan(*head, regs, int(g.n_regions), smp, n), "mi355_level1_share_plan")
+    axes = lambda m: tuple(a for a in range(3) if m >> a & 1)  # noqa: E731
+    bits = lambda v: tuple(v >> f & 1 for f in range(6))  # noqa: E731
+    out = {k: int(getattr(g, k)) for k in ("r0", "k1", "d1", "dS", "n_tiles", "n_mirrors", "region_voxels", "slab_voxels", "tile_voxels")}
+    out.update({k: bool(getattr(g, k)) for k in ("possible", "on")})
+    out.update({k: tuple(int(v) for v in getattr(g, k)) for k in ("padded", "volume", "stage0_slab_thickness", "region", "slab_thickness", "n_slabs")})
+    out["merged"] = tuple(bool(v) for v in g.merged)
+    out["regions"] = [{"mirror": axes(regs[i].mirror), "origin": tuple(regs[i].origin), "faces": bits(regs[i].faces)} for i in range(int(g.n_regions))]
+    out["samples"] = [{"tile": int(s.tile), "mirror": axes(s.mirror), "region": int(s.region), "origin": tuple(s.origin), "origin1": tuple(s.origin1),
+                       "faces": bits(s.faces),
+                       "slabs": {f: (tuple(s.slab_offset[f]), tuple(s.slab_shape[f])) for f in range(6) if s.slab[f]}} for s in smp[:n]]
+    return out
+
+
 def _stage0_view(src, samples, depth):
     """src: CUDA fp32 [n_wv, Ve0, Ve1, Ve2, C]; samples: dicts {wv, origin, faces: six flags} -> (Stage0View, keep-alive)"""
     import torch

@@ -759,6 +759,62 @@ typedef struct mi355_stage0_gather_merged_args {
     int32_t r2, channels2;
 } mi355_stage0_gather_merged_args;
 int mi355_stage0_gather_merged(const mi355_stage0_gather_merged_args *args, int shells_only, void *stream);
+/* ---- shared level 1 (MI355_SHARE_LEVEL1: 0 off, unset the default rule, 2 wherever possible; csrc/sliding_window.hip "shared
+ * level 1"): the geometry and the decision mi355_sw_predict / mi355_sw_partial[_folds] run, as a dry run (no device; nothing is
+ * launched).  A stride-2 conv commutes with shifts by an even number of voxels, so along
+ * an axis on which every (tile, mirror) sample starts at an even voxel, encoder level 1 and the skip half of the conv that reads
+ * its output can be computed once per REGION - patch[a] on a per-origin axis, the whole extended volume on a merged one - and, per
+ * tile face that lies inside the region on a merged axis, over one thin level-1 SLAB cut from the 2 slab_thickness outermost
+ * level-0 layers of the tile; a tile's level-1 tensors are then the region's, with shells of depth d1 (enc[1]'s output) and dS
+ * (the skip half) from the slabs, z before y before x.
+ * On when: the shared stage 0, the shared skip half and the stage-0 views are on; encoder stage 1 and the first block of decoder
+ * stage num_pool - 2 carry no run-time statistics; that stage has a second block and reads encoder stage 1's output; one sample of
+ * the half patch with c_up1 channels goes to conv3_f32_wino3_kernel<3, false>; the regions' first conv goes to
+ * conv3_f32_s2dma_kernel; at least one axis is merged and patch / 2 >= 2 slab_thickness on each.
+ * net: the last decoder stage as mi355_skip_share_plan takes it, then level 1.  mode: 0 off, 1 the default rule (also patch / 2 >=
+ * 8 slab_thickness on every merged axis, and a region that is a whole number of 4 x 8 x 8 conv tiles at level 1), 2 wherever it
+ * is possible.  (The switch is also read at mi355_unet_create: at 0 the weight packs of the two halves are not made and the net never
+ * takes the path.  While the path is on a forward holds at most 32 samples; a larger batch_tiles is split, which
+ * mi355_stage0_view_plan, asked for more samples than that, does not know.)  Returns the number of samples, tile-major as
+ * mi355_stage0_plan lists them (0 when not possible), or a negative error code.  Takes no batch, rank or world: the plan depends
+ * on the network and the geometry of all tiles only. */
+typedef struct mi355_level1_share_net {
+    mi355_skip_share_net last;
+    int32_t num_pool;
+    int32_t enc1_blocks;         /* blocks of encoder stage 1: one stride-2 block, then stride-1 blocks */
+    int32_t c_level1;            /* their output channels */
+    int32_t skip_is_enc1;        /* the second input of the first block of decoder stage num_pool - 2 is encoder stage 1's output */
+    int32_t dec1_blocks;         /* blocks of that decoder stage */
+    int32_t c_up1, cout1;        /* of its first block: channels of the upsampled half, output channels */
+} mi355_level1_share_net;
+typedef struct mi355_level1_share_geom {
+    int32_t possible, on;        /* the geometry allows it; the decision under `mode` */
+    int32_t r0, k1, d1, dS;      /* blocks of stage 0 and of stage 1; shell depths at level 1 */
+    int32_t n_tiles, n_mirrors, n_regions;
+    int32_t padded[3], volume[3];
+    int32_t stage0_slab_thickness[3];  /* of the stage-0 slabs that give a region its level-0 shells */
+    int32_t merged[3];
+    int32_t region[3];           /* level-0 extent of a region */
+    int32_t slab_thickness[3];   /* level 1; 0 on a per-origin axis */
+    int32_t n_slabs[3];
+    int64_t region_voxels, slab_voxels, tile_voxels;  /* level-1 voxels: all regions, all slabs, all samples (the per-tile count) */
+} mi355_level1_share_geom;
+typedef struct mi355_level1_share_region {
+    int32_t mirror;              /* mask of its pass */
+    int32_t origin[3];           /* in that pass; 0 on a merged axis */
+    int32_t faces;               /* bit f: face f lies inside the volume on a per-origin axis and takes stage-0 shells */
+} mi355_level1_share_region;
+typedef struct mi355_level1_share_sample {
+    int32_t tile, mirror, region;
+    int32_t origin[3];           /* of the tile in its pass */
+    int32_t origin1[3];          /* of the tile inside its region, at level 1 */
+    int32_t faces;               /* bit f: tile face f lies inside the volume */
+    int32_t slab[6];             /* 1: face f has a level-1 slab */
+    int32_t slab_offset[6][3], slab_shape[6][3];  /* the level-0 sub-box of the tile the slab is cut from */
+} mi355_level1_share_sample;
+int mi355_level1_share_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes,
+                            const mi355_level1_share_net *net, int mode, mi355_level1_share_geom *out,
+                            mi355_level1_share_region *regions, int max_regions, mi355_level1_share_sample *samples, int max_samples);
 /* x_dev [n][volume][c] fp32: zero every voxel outside [0, keep) (c % 4 == 0, 0 < keep <= volume); the rest is not written. */
 int mi355_stage0_mask(float *x_dev, int n, const int32_t volume[3], const int32_t keep[3], int c, void *stream);
 /* Name of the kernel instantiation the calling thread's last mi355_conv3d_ndhwc / mi355_conv3d_ndhwc_f16 call dispatched

@@ -1,0 +1,230 @@
+"""The shared level 1 (csrc/sliding_window.hip "shared level 1"), checked without a device through the dry run
+mi355_level1_share_plan - the geometry and the decision a forward would run on.
+
+* The plan of the bench geometry and of small geometries: merged axes, regions, shell depths, slab thickness, voxel counts.
+* The plan is SUFFICIENT, EXACTLY: an int64 chain with small integer weights - stem, a second stage-0 block, a stride-2 block, a
+  stride-1 block (ReLU behind each), then the skip half (no bias, no activation).  Encoder level 1 and the skip half are evaluated
+  over the regions - whose level-0 input is the whole-volume stage-0 result with stage-0 shells at their faces on per-origin axes,
+  zeros restored outside the padded volume between the layers - and over the level-1 slabs, each cut from the tile's own level-0
+  features; each tile's two level-1 tensors are assembled as the plan says - the region's values, then the shells d1 / dS deep
+  from the slabs, z before y before x - and must EQUAL the tile computed on its own, on every voxel of every sample."""
+import inspect
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+BENCH = ((139, 172, 138), (128, 128, 128))
+P32 = (32, 32, 32)
+
+
+@pytest.fixture(scope="module")
+def ops(amd):
+    return amd.ops
+
+
+def test_bench_geometry(ops):
+    p = ops.level1_share_plan(*BENCH)
+    assert p["possible"] and p["on"]
+    assert (p["r0"], p["k1"], p["d1"], p["dS"]) == (2, 2, 3, 4)
+    assert p["merged"] == (False, True, True) and p["region"] == (128, 176, 144) and p["slab_thickness"] == (0, 8, 8)
+    assert [(r["origin"], r["faces"]) for r in p["regions"]] == [((0, 0, 0), (0, 1, 0, 0, 0, 0)), ((11, 0, 0), (1, 0, 0, 0, 0, 0))]
+    assert [d // 2 for d in p["region"]] == [64, 88, 72]
+    assert sorted({s["origin1"] for s in p["samples"]}) == [(0, y, x) for y in (0, 22) for x in (0, 5)]
+    assert all(s["region"] == (s["origin"][0] == 11) for s in p["samples"])
+    assert p["n_slabs"] == (0, 8, 8)
+    assert (p["region_voxels"], p["slab_voxels"], p["tile_voxels"]) == (811008, 524288, 2097152)
+    for s in p["samples"]:   # one slab per face inside the region: the 16 outermost level-0 layers of the tile
+        z, y, x = s["origin"]
+        assert set(s["slabs"]) == {3 if y == 0 else 2, 5 if x == 0 else 4}
+        for f, (off, shape) in s["slabs"].items():
+            a = f >> 1
+            assert shape == tuple(16 if c == a else 128 for c in range(3))
+            assert off == tuple(112 if c == a and f & 1 else 0 for c in range(3))
+    assert not ops.level1_share_plan(*BENCH, mode=0)["on"]
+    # the default rule: patch / 2 >= 8 slab thicknesses; half the bench patch does not pass it
+    small = ops.level1_share_plan((100, 100, 100), (64, 64, 64))
+    assert small["possible"] and not small["on"]
+
+
+def test_what_the_decision_refuses(ops):
+    for kw in ({"dtype": "f16"}, {"norm": "instance"}, {"nonlin_first": True}, {"skip_is_enc1": False}, {"dec1_blocks": 1}, {"num_pool": 1},
+               {"enc0_blocks": 0}):
+        assert not ops.level1_share_plan(*BENCH, mode=2, **kw)["on"], kw
+
+
+def test_no_merged_axis(ops):
+    """(41, 57, 43), patch 32^3: steps (0, 9) x (0, 12, 25) x (0, 11): an odd origin or an odd extent on every axis."""
+    for mode in (1, 2):
+        p = ops.level1_share_plan((41, 57, 43), P32, mode=mode, num_pool=2)
+        assert not p["possible"] and not p["on"] and p["regions"] == [] and p["samples"] == []
+
+
+def test_one_tile(ops):
+    for mode in (1, 2):
+        p = ops.level1_share_plan((32, 32, 32), P32, mode=mode, num_pool=2)
+        assert not p["possible"] and not p["on"]
+
+
+def test_three_tiles_along_y(ops):
+    """(41, 56, 44): z per-origin (0, 9); y merged, three tiles (0, 12, 24), the middle one with two faces inside the region; x
+    merged (0, 12)."""
+    p = ops.level1_share_plan((41, 56, 44), P32, mode=2, num_pool=2)
+    assert p["possible"] and p["merged"] == (False, True, True) and p["region"] == (32, 56, 48) and p["slab_thickness"] == (0, 8, 8)
+    assert [(r["origin"], r["faces"]) for r in p["regions"]] == [((0, 0, 0), (0, 1, 0, 0, 0, 0)), ((9, 0, 0), (1, 0, 0, 0, 0, 0))]
+    middle = [s for s in p["samples"] if s["origin"][1] == 12]
+    assert len(middle) == 4 and all({2, 3} <= set(s["slabs"]) and s["origin1"][1] == 6 for s in middle)
+    assert p["n_slabs"] == (0, 16, 12)
+
+
+def test_eight_mirrors(ops):
+    """(40, 56, 44) with 8 mirrors: every axis merged, one region per mirror."""
+    p = ops.level1_share_plan((40, 56, 44), P32, mirror_axes=(0, 1, 2), mode=2, num_pool=2)
+    assert p["possible"] and p["merged"] == (True, True, True) and p["n_mirrors"] == 8
+    assert [r["mirror"] for r in p["regions"]] == [(), (2,), (1,), (1, 2), (0,), (0, 2), (0, 1), (0, 1, 2)]
+    assert all(r["origin"] == (0, 0, 0) and r["faces"] == (0,) * 6 for r in p["regions"])
+    assert all(p["regions"][s["region"]]["mirror"] == s["mirror"] for s in p["samples"])
+
+
+def test_plan_takes_no_batch_or_rank(ops, amd):
+    assert not {"batch_tiles", "batch_samples", "rank", "world"} & set(inspect.signature(ops.level1_share_plan).parameters)
+    assert len(amd._lib.load().mi355_level1_share_plan.argtypes) == 13
+    assert ops.level1_share_plan(*BENCH, mirror_axes=(0, 1, 2)) == ops.level1_share_plan(*BENCH, mirror_axes=(0, 1, 2))
+
+
+# ------------------------------------------------------------------ the exact model
+def _box(t, org, shape):
+    return t[:, :, org[0]:org[0] + shape[0], org[1]:org[1] + shape[1], org[2]:org[2] + shape[2]]
+
+
+def _weights():
+    g = torch.Generator().manual_seed(21)
+    iw = lambda *s: torch.randint(-2, 3, s, generator=g)  # noqa: E731
+    enc0 = [(iw(4, 2, 3, 3, 3), iw(4) + 3), (iw(4, 4, 3, 3, 3), iw(4) - 1)]
+    enc1 = [(iw(4, 4, 3, 3, 3), iw(4) + 2), (iw(4, 4, 3, 3, 3), iw(4) + 1)]
+    return enc0, enc1, iw(4, 4, 3, 3, 3)
+
+
+def _masked(x, keep):
+    if keep is None:
+        return x
+    m = torch.zeros(1, 1, *x.shape[2:], dtype=torch.int64)
+    _box(m, (0, 0, 0), keep).fill_(1)
+    return x * m
+
+
+def _enc0(x, W, keep=None):
+    """stage 0 over a box; keep: its part inside the padded volume, zeros restored outside it behind every layer"""
+    for w, b in W[0]:
+        x = _masked(F.relu(F.conv3d(x, w, b, padding=1)), keep)
+    return x
+
+
+def _level1(x, W, keep=None):
+    """(enc[1]'s output, the skip half) of a box of level-0 features; keep as above, at level 1"""
+    for i, (w, b) in enumerate(W[1]):
+        x = _masked(F.relu(F.conv3d(x, w, b, stride=2 if i == 0 else 1, padding=1)), keep)
+    return x, F.conv3d(x, W[2], None, padding=1)
+
+
+def _put_shell(dst, src, a, side, depth):
+    """the shell of face (a, side) of dst <- the same layers of src, whose extent along a may be smaller (a slab)"""
+    d, s = [slice(None)] * 5, [slice(None)] * 5
+    n, t = dst.shape[2 + a], src.shape[2 + a]
+    d[2 + a] = slice(n - depth, n) if side else slice(0, depth)
+    s[2 + a] = slice(t - depth, t) if side else slice(0, depth)
+    dst[tuple(d)] = src[tuple(s)]
+
+
+@pytest.mark.parametrize("volume, axes", [((41, 56, 44), ()), ((40, 56, 44), (0, 1, 2)), ((37, 33, 68), (2,))])
+def test_assembly_equals_per_tile_exactly(ops, volume, axes):
+    """The third case: z and y per-origin with odd origins (regions with stage-0 shells on two axes and the edge between them), x
+    merged with four tiles (0, 12, 24, 36)."""
+    p = ops.level1_share_plan(volume, P32, mirror_axes=axes, mode=2, num_pool=2)
+    assert p["possible"]
+    W = _weights()
+    vol = torch.randint(-3, 4, (1, 2) + tuple(volume), generator=torch.Generator().manual_seed(22))
+    Zp, Ve, R, t0, t1 = p["padded"], p["volume"], p["region"], p["stage0_slab_thickness"], p["slab_thickness"]
+    half = tuple(d // 2 for d in P32)
+    lo = [(Zp[a] - volume[a]) // 2 for a in range(3)]
+    padded = torch.zeros(1, 2, *Zp, dtype=torch.int64)
+    _box(padded, lo, volume).copy_(vol)
+    ext, whole, region = {}, {}, {}
+
+    def pass_of(m):   # the extended volume of the mirrored pass, and stage 0 over it (zero outside the padded volume)
+        if m not in ext:
+            e = torch.zeros(1, 2, *Ve, dtype=torch.int64)
+            _box(e, (0, 0, 0), Zp).copy_(torch.flip(padded, [2 + a for a in m]) if m else padded)
+            ext[m], whole[m] = e, _enc0(e, W, Zp)
+        return ext[m]
+
+    for i, rg in enumerate(p["regions"]):
+        e, o = pass_of(rg["mirror"]), rg["origin"]
+        x0 = _box(whole[rg["mirror"]], o, R).clone()
+        for f in (5, 4, 3, 2, 1, 0):   # the region is a "tile" of the shared stage 0: shells r0 deep, the first in z, y, x wins
+            if not rg["faces"][f]:
+                continue
+            a, side = f >> 1, f & 1
+            assert not p["merged"][a]
+            so = list(o)
+            so[a] += (R[a] - t0[a]) if side else 0
+            shape = tuple(t0[c] if c == a else R[c] for c in range(3))
+            keep = tuple(min(shape[c], Zp[c] - so[c]) for c in range(3))
+            _put_shell(x0, _enc0(_box(e, so, shape), W, keep), a, side, p["r0"])
+        keep1 = tuple(Zp[c] // 2 if p["merged"][c] else R[c] // 2 for c in range(3))
+        region[i] = _level1(x0, W, keep1)
+    worst = 0
+    for s in p["samples"]:
+        m, org = s["mirror"], s["origin"]
+        t0_own = _enc0(_box(pass_of(m), org, P32), W)   # the tile on its own: zero padding at all six faces
+        want = _level1(t0_own, W)
+        got = [_box(v, s["origin1"], half).clone() for v in region[s["region"]]]
+        for f in (5, 4, 3, 2, 1, 0):
+            if f not in s["slabs"]:
+                continue
+            a, side = f >> 1, f & 1
+            off, shape = s["slabs"][f]
+            assert p["merged"][a] and shape[a] == 2 * t1[a]
+            src = _level1(_box(t0_own, off, shape), W)   # zero padding at the cut, the tile's own features everywhere else
+            for i, depth in enumerate((p["d1"], p["dS"])):
+                _put_shell(got[i], src[i], a, side, depth)
+        for i, name in enumerate(("enc[1]'s output", "the skip half")):
+            assert torch.equal(got[i], want[i]), f"{name} of tile {s['tile']} mirror {m}: {int((got[i] != want[i]).sum())} elements differ"
+            worst = max(worst, int(want[i].abs().max()))
+    assert 0 < worst < 2 ** 62
+
+
+@pytest.mark.parametrize("which, by", [("d1", -1), ("dS", -1)])
+def test_shallower_shells_are_not_enough(ops, which, by):
+    """The depths are tight: one layer less and some tile differs (so the exact test above is not vacuous)."""
+    volume = (41, 56, 44)
+    p = ops.level1_share_plan(volume, P32, mode=2, num_pool=2)
+    W = _weights()
+    vol = torch.randint(-3, 4, (1, 2) + volume, generator=torch.Generator().manual_seed(22))
+    depth = dict(d1=p["d1"], dS=p["dS"])
+    depth[which] += by
+    e = torch.zeros(1, 2, *p["volume"], dtype=torch.int64)
+    _box(e, (0, 0, 0), volume).copy_(vol)
+    whole = _enc0(e, W, p["padded"])
+    differs = False
+    for s in p["samples"]:
+        if s["origin"][0] != 0:   # (the tiles of the region at z = 0, whose one face inside the volume is the high z face)
+            continue
+        rg = p["regions"][s["region"]]
+        x0 = _box(whole, rg["origin"], p["region"]).clone()
+        t0, R = p["stage0_slab_thickness"], p["region"]
+        so = (R[0] - t0[0], 0, 0)
+        shape = (t0[0], R[1], R[2])
+        _put_shell(x0, _enc0(_box(e, so, shape), W, tuple(min(shape[c], p["padded"][c] - so[c]) for c in range(3))), 0, 1, p["r0"])
+        reg = _level1(x0, W, (R[0] // 2, p["padded"][1] // 2, p["padded"][2] // 2))
+        t0_own = _enc0(_box(e, s["origin"], P32), W)
+        want = _level1(t0_own, W)
+        got = [_box(v, s["origin1"], (16, 16, 16)).clone() for v in reg]
+        for f in (5, 4, 3, 2):
+            if f in s["slabs"]:
+                src = _level1(_box(t0_own, *s["slabs"][f]), W)
+                for i, k in enumerate(("d1", "dS")):
+                    _put_shell(got[i], src[i], f >> 1, f & 1, depth[k])
+        i = 0 if which == "d1" else 1
+        differs = differs or not torch.equal(got[i], want[i])
+    assert differs
