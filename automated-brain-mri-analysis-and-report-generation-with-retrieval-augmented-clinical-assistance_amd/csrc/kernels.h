@@ -37,7 +37,7 @@ int conv_weights_upload(const float *w_host, const float *bias_host, int cin, in
                         int stride, bool keep_plain, ConvWeights *out);
 void conv_weights_free(ConvWeights *w);
 
-// A per-sample view into a whole-volume tensor of the shared stage 0 (sliding_window.hip "stage-0 views"): the tile tensor [N][D][H][W][C] a
+// A per-sample view into a whole-volume tensor of the shared stage 0 (sw_share_plan.hip "stage-0 views"): the tile tensor [N][D][H][W][C] a
 // conv reads is written only inside the shells - within `depth` voxels of a tile face whose bit is set - and every other voxel of
 // sample n is read in place from `src` at smp[n].off + (z * sz + y * sy + x) voxels.  Voxel (z, y, x) of sample n comes from the tile
 // tensor iff z < depth with face bit 0, z >= D - depth with bit 1, the same for y (bits 2, 3) and x (bits 4, 5); the reader's
@@ -77,7 +77,7 @@ struct ConvCallT {
     const float *in_scale = nullptr, *in_shift = nullptr;
     int in_act = ACT_NONE;
     // [N,Do,Ho,Wo,Cout] added to the conv sum in front of bias and activation: out = act(bias + conv(in) + addend).  The shared
-    // skip half of a split concat conv (sliding_window.hip "shared skip half"); conv3_f32_wino3_kernel<3, false> only (the plain epilogue's twin), refused elsewhere.
+    // skip half of a split concat conv (sw_share_plan.hip "shared skip half"); conv3_f32_wino3_kernel<3, false> only (the plain epilogue's twin), refused elsewhere.
     const T *addend = nullptr;
     // Stage-0 views (fp32): in0 / addend hold their shells only, the rest is read through the view.  The planner never looks at
     // them - a view must not change which kernel runs -; the launcher refuses a view on a kernel that cannot read through one
@@ -158,7 +158,7 @@ struct TileDesc {  // one forward sample = one (tile, mirror)
 int extract_tiles(const float *vol, int C, int Z, int Y, int X, int padz, int pady, int padx,
                   const TileDesc *tiles_host, int n_samples, int P0, int P1, int P2, int Cpad, void *x, int dtype,
                   hipStream_t s);
-// Shared stage 0 of the sliding window (sliding_window.hip "shared stage 0"): encoder stage 0 runs once over the whole padded volume and
+// Shared stage 0 of the sliding window (sw_share_plan.hip "shared stage 0"): encoder stage 0 runs once over the whole padded volume and
 // over thin slabs at the tile faces that lie inside the volume; the tile tensor is then gathered from those results.
 constexpr int S0_MAX_SAMPLES = 64;
 struct S0Sample {   // one forward sample = one (tile, mirror), in the coordinates of its (mirrored) pass
@@ -171,7 +171,7 @@ struct S0GatherArgs {
     const float *slab[3];  // per axis a: [n_slabs][S0][S1][S2][C], S[a] = t[a], S[k] = P[k] otherwise
     float *out;            // [n_samples][P0][P1][P2][C]
     int P[3], Ve[3], t[3];
-    // Merged slabs (sliding_window.hip "merged slabs"): D[a] = extent of one slab of axis a - t[a] along a; along k != a either P[k] (the slab
+    // Merged slabs (sw_share_plan.hip "merged slabs"): D[a] = extent of one slab of axis a - t[a] along a; along k != a either P[k] (the slab
     // carries the tile's own padding: the tile starts at 0 in it) or Ve[k] (the slab spans the volume: the tile starts at its origin,
     // so[a][k] = 1).  stage0_gather_dense() fills the per-tile form: D[a][k] = P[k], so = 0.
     int D[3][3], so[3][3];
@@ -185,7 +185,7 @@ struct S0GatherArgs {
     int r2, C42;
     int n;                 // samples (set by stage0_gather)
     S0Sample smp[S0_MAX_SAMPLES];
-    // Sub-boxes (sliding_window.hip "shared level 1"; T[0] > 0): sample i is the P-sized box at sub[i] of a tile of T voxels, org
+    // Sub-boxes (sw_share_plan.hip "shared level 1"; T[0] > 0): sample i is the P-sized box at sub[i] of a tile of T voxels, org
     // its own origin in the volume; in a slab that carries the tile's own padding along k (so[a][k] = 0: D[a][k] = T[k]) it
     // starts at sub[i][k], not at 0.  T = 0 and sub = 0: the samples are the tiles.
     int T[3];

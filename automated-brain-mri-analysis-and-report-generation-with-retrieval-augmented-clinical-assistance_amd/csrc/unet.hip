@@ -116,21 +116,20 @@ int make_plan(const mi355_unet &net, int N, int D, int H, int W, Plan *pl) {
         pl->maxc[l] = std::max(pl->maxc[l], net.dtype == MI355_F16 ? net.tuh[u].cout : net.tu[u].cout);
         for (auto &L : net.dec[u]) pl->maxc[l] = std::max(pl->maxc[l], L.cout);
     }
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~size_t(255); return r; };
+    ArenaCursor c{0};
     const size_t es = net.dtype == MI355_F16 ? 2 : 4;
-    pl->x0_off = take((size_t)N * pl->vox[0] * net.cin_pad * es);
+    pl->x0_off = c.take((size_t)N * pl->vox[0] * net.cin_pad * es);
     for (int k = 0; k < 4; ++k) pl->off[k].resize(np + 1);
     for (int l = 0; l <= np; ++l)
         for (int k = 0; k < 4; ++k)
-            pl->off[k][l] = take((size_t)N * pl->vox[l] * pl->maxc[l] * es);
+            pl->off[k][l] = c.take((size_t)N * pl->vox[l] * pl->maxc[l] * es);
     pl->stats_bytes = (size_t)N * net.max_channels * 2 * sizeof(double);
-    pl->stats_off = take(pl->stats_bytes);
-    pl->scale_off = take((size_t)N * net.max_channels * sizeof(float));
-    pl->shift_off = take((size_t)N * net.max_channels * sizeof(float));
-    pl->scale2_off = take((size_t)N * net.max_channels * sizeof(float));
-    pl->shift2_off = take((size_t)N * net.max_channels * sizeof(float));
-    pl->total = o;
+    pl->stats_off = c.take(pl->stats_bytes);
+    pl->scale_off = c.take((size_t)N * net.max_channels * sizeof(float));
+    pl->shift_off = c.take((size_t)N * net.max_channels * sizeof(float));
+    pl->scale2_off = c.take((size_t)N * net.max_channels * sizeof(float));
+    pl->shift2_off = c.take((size_t)N * net.max_channels * sizeof(float));
+    pl->total = c.o;
     return MI355_OK;
 }
 
@@ -229,11 +228,12 @@ static bool can_defer_norm(const mi355_unet *net, const ConvLayer &L, const Conv
 // head_norm (round 3): when non-null and the last decoder block carries a run-time Instance/GroupNorm, that block's
 // normalisation (+ activation) is NOT applied to the returned feature map: *head_norm receives its scale / shift and the
 // caller's head kernel applies them while reading the features (head_logits / head_aggregate take a FeatNorm).
-// after_enc0 (shared stage 0): the level-0 features are already where enc[0]'s last block writes them; the pass starts at level 1.
-// skip_half (shared skip half): [N][V][cout] = the skip half of the last decoder stage's first conv, already gathered into the
-// level-0 buffer that stage leaves free; that block then runs over the upsampled tensor alone and adds it in its epilogue.
-// enc0_view / skip_half_view (stage-0 views): the level-0 features / the skip half hold their shells only; their one reader - the
-// first block of level 1 / that epilogue - takes the rest through the view.
+// lvl[l] (ForwardOpts::Level; l = 0: shared stage 0, l = 1: shared level 1, which asks for level 0 and both skip halves):
+// given: the level-l features are already where enc[l]'s last block writes them; the pass starts at level l + 1.
+// skip_half: [N][V][cout] = the skip half of the first conv of the decoder stage that reads them (the last stage; dec[np - 2]), already
+// gathered into the level-l buffer that stage leaves free; that block then runs over the upsampled tensor alone and adds it in its epilogue.
+// feat_view / half_view (stage-0 views): the level-l features / the skip half hold their shells only; their one reader - the
+// first block of level l + 1 / that epilogue - takes the rest through the view.
 int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W, const void **feat, int *feat_c, hipStream_t s,
                      const ForwardOpts &o) {
     const int np = net->num_pool;
@@ -247,7 +247,7 @@ int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W
     for (int l = 0; l <= np; ++l) {
         int Di = D >> l, Hi = H >> l, Wi = W >> l;
         bool pending = false;  // cur holds a raw conv output whose normalisation the next block applies
-        const bool given = (l == 0 && o.after_enc0) || (l == 1 && o.after_enc1);
+        const bool given = l < 2 && o.lvl[l].given;
         if (given) { cur = buf((int)((net->enc[l].size() - 1) & 1), l); curC = net->enc[l].back().cout; }
         for (size_t i = 0; i < net->enc[l].size() && !given; ++i) {
             const ConvLayer &L = net->enc[l][i];
@@ -257,16 +257,15 @@ int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W
             const bool defer = i + 1 < net->enc[l].size() && can_defer_norm(net, L, net->enc[l][i + 1], N, Di, Hi, Wi);
             BlockOpts bo;
             bo.defer_norm = defer; bo.in_norm = pending;
-            if (l == 1 && i == 0 && o.after_enc0) bo.in0_view = o.enc0_view;
-            if (l == 2 && i == 0 && o.after_enc1) bo.in0_view = o.enc1_view;
+            if (i == 0 && (l == 1 || l == 2) && o.lvl[l - 1].given) bo.in0_view = o.lvl[l - 1].feat_view;
             MI355_TRY(run_block(net, pl, L, cur, curC, nullptr, 0, N, inD, inH, inW, out, s, bo));
             pending = defer;
             cur = out; curC = L.cout;
         }
         if (l < np) { skip[l] = cur; skipC[l] = curC; }
     }
-    MI355_REQUIRE(!o.enc0_view || (o.skip_half && np >= 1), "stage-0 view of the level-0 features while the decoder reads them whole");
-    MI355_REQUIRE(!o.after_enc1 || (o.after_enc0 && o.skip_half && o.skip_half1 && np >= 2), "shared level 1 without the shared stage 0 and both skip halves");
+    MI355_REQUIRE(!o.lvl[0].feat_view || (o.lvl[0].skip_half && np >= 1), "stage-0 view of the level-0 features while the decoder reads them whole");
+    MI355_REQUIRE(!o.lvl[1].given || (o.lvl[0].given && o.lvl[0].skip_half && o.lvl[1].skip_half && np >= 2), "shared level 1 without the shared stage 0 and both skip halves");
     // decoder
     for (int u = 0; u < np; ++u) {
         const int l = np - 1 - u;
@@ -306,18 +305,12 @@ int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W
                 *feat = lg; *feat_c = net->head.ncls;
                 return MI355_OK;
             }
-            if (o.skip_half1 && l == 1 && i == 0) {
-                MI355_REQUIRE(L.split_c0 == C0 && (const void *)o.skip_half1 == freeAB && net->dec[u].size() > 1, "shared level 1: the block was not split at %d channels", C0);
+            if (i == 0 && l < 2 && o.lvl[l].skip_half) {  // the block runs over the upsampled half alone; the gathered skip half is its addend
+                const ForwardOpts::Level &gl = o.lvl[l];
+                MI355_REQUIRE(l != 1 || (L.split_c0 == C0 && (const void *)gl.skip_half == freeAB && net->dec[u].size() > 1), "shared level 1: the block was not split at %d channels", C0);
+                MI355_REQUIRE(l != 0 || (L.split_c0 == C0 && (const void *)gl.skip_half == freeAB), "shared skip half: the block was not split at %d channels", C0);
                 BlockOpts bo;
-                bo.half = &L.w_up; bo.addend = o.skip_half1; bo.half_name = " up-half"; bo.addend_view = o.skip_half1_view;
-                MI355_TRY(run_block(net, pl, L, in0, C0, nullptr, 0, N, Dl, Hl, Wl, out, s, bo));
-                in0 = out; C0 = L.cout; in1 = nullptr; C1 = 0;
-                continue;
-            }
-            if (o.skip_half && u == np - 1 && i == 0) {
-                MI355_REQUIRE(L.split_c0 == C0 && (const void *)o.skip_half == freeAB, "shared skip half: the block was not split at %d channels", C0);
-                BlockOpts bo;
-                bo.half = &L.w_up; bo.addend = o.skip_half; bo.half_name = " up-half"; bo.addend_view = o.skip_half_view;
+                bo.half = &L.w_up; bo.addend = gl.skip_half; bo.half_name = " up-half"; bo.addend_view = gl.half_view;
                 MI355_TRY(run_block(net, pl, L, in0, C0, nullptr, 0, N, Dl, Hl, Wl, out, s, bo));
                 in0 = out; C0 = L.cout; in1 = nullptr; C1 = 0;
                 continue;

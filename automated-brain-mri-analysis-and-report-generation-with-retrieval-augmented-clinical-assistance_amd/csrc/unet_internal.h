@@ -1,10 +1,12 @@
-// What the four host files behind include/mi355_nnunet.h share, and nobody else includes:
+// What the five host files behind include/mi355_nnunet.h share, and nobody else includes:
 //   runtime.hip         last-error text, bind_device, the lanes and device_scratch, the scratch test aids
 //   unet.hip            the network object, the arena plan, run_block / forward_features, create / destroy / forward / profile
-//   sliding_window.hip  tile geometry, the shared stage 0 and everything built on it, sw_accumulate, mi355_sw_*, the geometry dry runs
+//   sw_share_plan.hip   pure: tile geometry, what overlapping tiles share as one plan per window, the geometry dry runs
+//   sliding_window.hip  the device side of that plan: the shared stage 0 and level 1 passes, sw_accumulate, mi355_sw_*
 //   single_op.hip       the single-op entry points the tests drive, mi355_conv3d_plan, the wrappers around elementwise.hip
 // Types and the few functions that cross those files; a function used in one file is static there.
 #pragma once
+#include <array>
 #include <string>
 #include <vector>
 
@@ -79,6 +81,8 @@ struct Plan {
              size_t sub_in[3] = {0, 0, 0}, s_tmp = 0, s_e[3] = {0, 0, 0}, s_s[3] = {0, 0, 0}; } l1;
 };
 int make_plan(const mi355_unet &net, int N, int D, int H, int W, Plan *pl);
+// appends 256-byte-aligned regions to an arena plan: starts at Plan::total, which receives `o` when the last one is taken
+struct ArenaCursor { size_t o; size_t take(size_t bytes) { const size_t r = o; o += (bytes + 255) & ~size_t(255); return r; } };
 int ensure_arena(Plan *pl, hipStream_t s);
 
 struct ProfScope {
@@ -161,14 +165,12 @@ struct ForwardOpts {
     bool *is_logits = nullptr;
     float *logits_target = nullptr;
     FeatNorm *head_norm = nullptr;
-    bool after_enc0 = false;
-    const float *skip_half = nullptr;
-    const S0View *enc0_view = nullptr, *skip_half_view = nullptr;
-    // shared level 1: enc[1]'s output is already where its last block writes it and the pass starts at level 2; skip_half1 =
-    // the skip half of dec[np - 2][0], gathered into the level-1 buffer that stage leaves free
-    bool after_enc1 = false;
-    const float *skip_half1 = nullptr;
-    const S0View *enc1_view = nullptr, *skip_half1_view = nullptr;  // views into the regions' tensors: the tile tensors hold their shells only
+    // What the sliding window computed of encoder level l = 0 (shared stage 0) or 1 (shared level 1) before the forward:
+    struct Level {
+        bool given = false;                // enc[l]'s output is already where its last block writes it; the pass starts at level l + 1
+        const float *skip_half = nullptr;  // the skip half of the decoder conv that reads it, gathered into the level-l buffer that stage leaves free
+        const S0View *feat_view = nullptr, *half_view = nullptr;  // views into the shared tensors: the tile tensors hold their shells only
+    } lvl[2];
 };
 int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W, const void **feat, int *feat_c, hipStream_t s,
                      const ForwardOpts &o = ForwardOpts());
@@ -188,7 +190,7 @@ struct S0Placement {
     const char *label = "";        // suffix of the gather's profile entry
 };
 
-// The network side of the shared skip half (sliding_window.hip "shared skip half"): what is known of the first block of the last
+// The network side of the shared skip half (sw_share_plan.hip "shared skip half"): what is known of the first block of the last
 // decoder stage when the network is created, when a sliding window decides, and in the dry run - one description, one predicate.
 struct SkipShareNet {
     int dtype = MI355_F32;
@@ -209,6 +211,80 @@ inline SkipShareNet skip_share_net_of(int dtype, int r, int stride, int norm, in
 }
 bool skip_share_network_ok(const SkipShareNet &d);
 int stage0_blocks(const mi355_unet &net);
-int level1_share_mode();  // MI355_SHARE_LEVEL1: 0 off, 1 the default rule (unset), 2 wherever possible (sliding_window.hip "shared level 1")
+int level1_share_mode();  // MI355_SHARE_LEVEL1: 0 off, 1 the default rule (unset), 2 wherever possible (sw_share_plan.hip "shared level 1")
+
+// ---- what sw_share_plan.hip (pure) gives sliding_window.hip (the device side)
+struct SwGeom {
+    int P[3], Zp[3], pad_lo[3];
+    std::vector<TileDesc> tiles;   // origin of every tile, loop order axis0 outer .. axis2 inner
+    std::vector<int> mirrors;      // TileDesc-style masks in nnU-Net's evaluation order
+};
+int make_geom(const mi355_sw_opts &o, int Z, int Y, int X, SwGeom *g);
+void gaussian_map(const int p[3], double sigma_scale, std::vector<float> &out);
+int sw_batch_tiles(int dtype, int batch_tiles, int nm);
+
+// The switches a window obeys, read once where a window (sw_accumulate) or a dry run begins: nothing below reads the environment.
+struct SwSwitches { bool skip_conv, views, merge_slabs; int level1; };  // MI355_SHARE_SKIP_CONV, MI355_STAGE0_VIEWS, MI355_MERGE_SLABS, level1_share_mode()
+SwSwitches sw_switches();
+constexpr int CONV_TILE[3] = {4, 8, 8};  // the voxel tile of the conv kernels: volumes are extended, and slabs sized, in whole tiles
+inline int whole_conv_tiles(int v, int a) { return ceil_div(v, CONV_TILE[a]) * CONV_TILE[a]; }
+
+constexpr int S0_SLAB_GROUP = 8;  // (8 slabs of 4 x 128 x 128: 2048 tiles of the F(2x2x2,3x3x3) kernel, 8 per CU)
+struct S0Merged { int wv, side, org[3]; };  // a merged slab: its (mirrored) pass, the side of the faces it serves, its origin in that pass
+struct S0Geom {
+    bool shared = false;
+    int r = 0, rs = 0;             // rs = depth of the slab chain: r, or r + 1 with the shared skip half (one more conv behind stage 0)
+    int Ve[3] = {0, 0, 0};         // padded volume extended to whole 4 x 8 x 8 conv tiles
+    int t[3] = {0, 0, 0};          // slab thickness per axis: the smallest multiple of (4, 8, 8) that is >= 2 rs
+    int max_faces[3] = {0, 0, 0};  // most interior faces any tile has on an axis
+    std::vector<S0Sample> smp;     // [tile][mirror]; slab[f] = 0 where face f needs a slab, -1 where it is a volume face
+    // merged slabs (stage0_merge_geometry): the y- and x-slabs of ALL tiles, one per key, sorted by key
+    bool merge = false;
+    std::vector<S0Merged> merged[3];         // [1] y-slabs, [2] x-slabs ([0] stays empty: z-slabs are per tile)
+    int mdim[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // extent of one slab of each axis
+    std::vector<std::array<int, 6>> mslab;   // per sample: index of face f (2 .. 5) in merged[f >> 1], or -1
+};
+inline void slab_dims(const SwGeom &g, const S0Geom &sg, int a, int S[3]) { for (int k = 0; k < 3; ++k) S[k] = k == a ? sg.t[k] : g.P[k]; }
+// origin of the slab of face f (axis f >> 1, hi side if f & 1) of a box at org: thick[a] layers at that face, the box's extent on the other axes
+inline void face_slab_origin(const int org[3], const int extent[3], const int thick[3], int f, int b[3]) {
+    for (int k = 0; k < 3; ++k) b[k] = org[k] + (k == f >> 1 && (f & 1) ? extent[k] - thick[k] : 0);
+}
+struct L1Geom {
+    bool possible = false;
+    int r0 = 0, k1 = 0, d1 = 0, dS = 0;
+    bool merged[3] = {false, false, false};
+    int R[3] = {0, 0, 0};    // level-0 extent of a region
+    int t1[3] = {0, 0, 0};   // level-1 slab thickness (0 on a per-origin axis)
+    std::vector<S0Sample> regions;  // sorted by (mirror, origin); org in the (mirrored) pass; slab[f] = 0: face f needs stage-0 shells, -1: not
+    std::vector<S0Sample> smp;      // [tile][mirror], as S0Geom::smp; wv = its region, org = its origin in it at level 1; slab[f] = 0: face f has a level-1 slab, else -1
+};
+constexpr int L1_SLAB_GROUP = 8;  // level-1 slabs run as launches of exactly this many (the last one filled up), as the stage-0 slabs do
+inline int level1_slab_rows(int n_samples) { return ceil_div(2 * n_samples, L1_SLAB_GROUP) * L1_SLAB_GROUP; }
+
+// The network side: the last decoder stage as the shared skip half sees it, and level 1.
+struct L1ShareNet {
+    SkipShareNet last;
+    int num_pool = 0;
+    int k1 = 0, c1 = 0;      // blocks of enc[1] (its first has stride 2, the others stride 1) and their output channels
+    bool skip_is_enc1 = true;  // the second input of dec[np - 2][0] is enc[1]'s output
+    int dec_blocks = 0;      // blocks of dec[np - 2]
+    int c_up = 0, cout = 0;  // of dec[np - 2][0]: channels of the upsampled half, output channels
+};
+L1ShareNet level1_share_net(const mi355_unet &net);
+
+// Everything one window decided from the network's description, the geometry of ALL tiles and the switches - never from rank, world,
+// lane or batch size.  Built once per window by sw_share_plan, as the dry runs do; a local of the call (one handle may be driven from two lanes).
+struct SwSharePlan {
+    S0Geom sg;                // the shared stage 0, its merged slabs included
+    bool share_skip = false;  // the shared skip half (sg.rs = sg.r + 1)
+    L1Geom lg;
+    bool share_l1 = false;    // the shared level 1; implies sg.shared and share_skip
+};
+SwSharePlan sw_share_plan(const L1ShareNet &d, const SwGeom &g, const SwSwitches &sw);
+
+// Does the planner send this fp32 call (n boxes of S voxels, cin channels, run-time statistics or not) to the stride-2 kernel that takes a view (kernels.h S0View)?
+bool reader_takes_view(const ConvWeights &w, int cin, int n, const int S[3], bool stats);
+struct S0ViewChoice { bool enc0 = false, half = false; };
+S0ViewChoice stage0_views_choose(bool views, const S0Geom &sg, bool share_skip, int n_samples, const int P[3], const ConvWeights *w1, int c0, bool w1_stats);
 
 }  // namespace mi355

@@ -1,4 +1,4 @@
-"""-m gpu: the shared level 1 of the sliding window (MI355_SHARE_LEVEL1, csrc/sliding_window.hip "shared level 1").
+"""-m gpu: the shared level 1 of the sliding window (MI355_SHARE_LEVEL1, csrc/sw_share_plan.hip "shared level 1").
 
 The path needs the shared skip half, and its per-tile launch over the upsampled half of dec[np - 2][0] is the kernel with the addend
 epilogue, which the dispatch gives a single sample of the half patch only from 1024 (tile, cout block) units on: 64 -> 64 over 64^3,

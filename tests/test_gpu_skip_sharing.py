@@ -1,4 +1,4 @@
-"""-m gpu: the shared skip half of the last decoder stage's concat conv (MI355_SHARE_SKIP_CONV, csrc/sliding_window.hip "shared skip half").
+"""-m gpu: the shared skip half of the last decoder stage's concat conv (MI355_SHARE_SKIP_CONV, csrc/sw_share_plan.hip "shared skip half").
 
 Single op: conv3_f32_wino3_kernel<0, false> with the epilogue addend - its twin instantiation <3, false>, which differs from it in that
 epilogue only, so that launches without an addend run the code they ran before -, and the 64 -> 32 concat conv once as one launch and once as a

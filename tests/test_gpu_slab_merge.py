@@ -1,4 +1,4 @@
-"""-m gpu: the merged stage-0 slabs (MI355_MERGE_SLABS, csrc/sliding_window.hip "merged slabs").
+"""-m gpu: the merged stage-0 slabs (MI355_MERGE_SLABS, csrc/sw_share_plan.hip "merged slabs").
 
 * The gather in its general form (mi355_stage0_gather_merged, and its shells-only form) against a numpy model on CODED tensors:
   every element's value names its source tensor and its flat index there, all below 2^24, so the result is exact and a wrong

@@ -1,4 +1,4 @@
-"""-m gpu: the shared stage 0 of the sliding window (MI355_SHARE_STAGE0, csrc/sliding_window.hip "shared stage 0") against today's
+"""-m gpu: the shared stage 0 of the sliding window (MI355_SHARE_STAGE0, csrc/sw_share_plan.hip "shared stage 0") against today's
 per-tile path and the CPU oracle.
 
 The switch is read once per process, so each setting runs in a child process of its own (one per setting for the small cases,

@@ -1,4 +1,4 @@
-"""-m gpu: the stage-0 views (MI355_STAGE0_VIEWS, csrc/sliding_window.hip "stage-0 views"): the two readers of the gathered tile tensors take
+"""-m gpu: the stage-0 views (MI355_STAGE0_VIEWS, csrc/sw_share_plan.hip "stage-0 views"): the two readers of the gathered tile tensors take
 every voxel outside the shells in place from the whole-volume tensor, and the gather writes the shells alone.
 
 Views change where bytes are read, never which kernel runs nor in which order anything is summed, so EVERY comparison here is bit

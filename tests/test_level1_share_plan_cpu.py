@@ -1,4 +1,4 @@
-"""The shared level 1 (csrc/sliding_window.hip "shared level 1"), checked without a device through the dry run
+"""The shared level 1 (csrc/sw_share_plan.hip "shared level 1"), checked without a device through the dry run
 mi355_level1_share_plan - the geometry and the decision a forward would run on.
 
 * The plan of the bench geometry and of small geometries: merged axes, regions, shell depths, slab thickness, voxel counts.
@@ -90,6 +90,24 @@ def test_plan_takes_no_batch_or_rank(ops, amd):
     assert not {"batch_tiles", "batch_samples", "rank", "world"} & set(inspect.signature(ops.level1_share_plan).parameters)
     assert len(amd._lib.load().mi355_level1_share_plan.argtypes) == 13
     assert ops.level1_share_plan(*BENCH, mirror_axes=(0, 1, 2)) == ops.level1_share_plan(*BENCH, mirror_axes=(0, 1, 2))
+
+
+@pytest.mark.parametrize("volume, patch, axes", [BENCH + ((),), BENCH + ((0, 1, 2),), ((100, 100, 100), (64, 64, 64), ()), ((41, 57, 43), P32, ()),
+                                                 ((32, 32, 32), P32, ()), ((41, 56, 44), P32, ()), ((40, 56, 44), P32, (0, 1, 2)), ((37, 33, 68), P32, (2,))])
+def test_stage0_part_is_the_other_dry_runs(ops, volume, patch, axes):
+    """A window decides once (sw_share_plan): the stage-0 fields this dry run reports are those mi355_skip_share_plan reports for the
+    same network description and mi355_stage0_merge_plan for the r and skip half that one decided, in every mode; and the shared
+    level 1 is on only on top of the shared stage 0 and the shared skip half."""
+    for kw in ({}, {"dtype": "f16"}, {"norm": "instance"}, {"nonlin_first": True}, {"enc0_blocks": 0}, {"enc0_blocks": 1}):
+        s = ops.skip_share_plan(volume, patch, mirror_axes=axes, **kw)
+        m = ops.stage0_merge_plan(volume, patch, mirror_axes=axes, r=s["r"], skip_half=s["skip_shared"])
+        for mode in (0, 1, 2):
+            p = ops.level1_share_plan(volume, patch, mirror_axes=axes, mode=mode, num_pool=2, **kw)
+            assert (p["volume"], p["stage0_slab_thickness"], p["r0"], p["n_tiles"], p["n_mirrors"]) == \
+                   (s["volume"], s["slab_thickness"], s["r"], s["n_tiles"], s["n_mirrors"]), (kw, mode)
+            assert (p["padded"], p["volume"], p["stage0_slab_thickness"], p["r0"], p["n_tiles"], p["n_mirrors"]) == \
+                   (m["padded"], m["volume"], m["slab_thickness"], m["r"], m["n_tiles"], m["n_mirrors"]), (kw, mode)
+            assert not p["on"] or (s["skip_shared"] and s["stage0_shared"] and m["shared"]), (kw, mode)
 
 
 # ------------------------------------------------------------------ the exact model

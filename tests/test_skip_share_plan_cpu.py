@@ -1,4 +1,4 @@
-"""The shared skip half of the last decoder stage's concat conv (csrc/sliding_window.hip "shared skip half"), checked without a device through
+"""The shared skip half of the last decoder stage's concat conv (csrc/sw_share_plan.hip "shared skip half"), checked without a device through
 its dry-run entry point mi355_skip_share_plan - the decision code a real mi355_sw_predict call runs.
 
 The decision may depend on the network and on the geometry of all tiles only: every rank, lane and batch must compute a tile the

@@ -1,4 +1,4 @@
-"""The merged stage-0 slabs (MI355_MERGE_SLABS, csrc/sliding_window.hip "merged slabs"), checked without a device through the dry run
+"""The merged stage-0 slabs (MI355_MERGE_SLABS, csrc/sw_share_plan.hip "merged slabs"), checked without a device through the dry run
 mi355_stage0_merge_plan - the geometry code a real call runs.
 
 * The plan of the bench geometry and of the small geometries the GPU tests use: keys, boxes, voxel totals and, per sample, the

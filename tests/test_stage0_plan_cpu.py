@@ -35,6 +35,15 @@ def test_bench_geometry(ops):
             assert org == tuple(s["origin"][k] + ((128 - shape[k]) if (k == a and f & 1) else 0) for k in range(3))
 
 
+@pytest.mark.parametrize("step_size", [0.0, -0.5, 1.5])
+def test_step_size_outside_0_1_is_refused(ops, amd, step_size):
+    """make_geom checks the step before compute_steps divides by it: every dry run answers with an error, for a good patch and a bad one."""
+    for patch in ((128, 128, 128), (128, 0, 128)):
+        for plan in (ops.stage0_plan, ops.stage0_merge_plan, ops.skip_share_plan, ops.stage0_view_plan, ops.level1_share_plan):
+            with pytest.raises(amd._lib.Mi355Error):
+                plan((139, 172, 138), patch, step_size=step_size)
+
+
 def test_uncropped_volume(ops):
     p = ops.stage0_plan((155, 240, 240), (128, 128, 128), 0.5, (), 2)
     assert p["shared"] and p["n_tiles"] == 18 and p["volume"] == (156, 240, 240)

@@ -1,4 +1,4 @@
-"""The stage-0 views (MI355_STAGE0_VIEWS, csrc/sliding_window.hip "stage-0 views"), checked without a device: the dry-run entry point
+"""The stage-0 views (MI355_STAGE0_VIEWS, csrc/sw_share_plan.hip "stage-0 views"), checked without a device: the dry-run entry point
 mi355_stage0_view_plan - the decision and descriptor code a real mi355_sw_predict call runs - and, in numpy, the rule the readers
 implement: a voxel comes from the tile tensor iff it lies within the shell depth of a face whose bit is set, from the view otherwise.
 That rule must be SUFFICIENT: with the tile tensor poisoned everywhere else, the assembled tile equals the full gather's."""
