@@ -17,6 +17,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .volume_ops import check_volume
 
 #: columns of the per-component table (mi355_component_stats)
 COUNT, SUM0, MIN0, MAX0, SEG1 = 0, 1, 4, 7, 10
@@ -29,19 +30,12 @@ SEPARATE_DISTANCE_MM = 40
 MIN_LESION_VOLUME_CM3 = 0.1
 
 
-def _check_volume(t, dtype, what):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or t.dim() != 3:
-        raise ValueError(f"{what}: CUDA {dtype} [d0, d1, d2] tensor expected")
-    return t.contiguous()
-
-
 def label_components(mask, connectivity=1):
     """mask: CUDA uint8 [d0, d1, d2], foreground = nonzero.  connectivity 1 (6 neighbours, scipy's default structure) or 3
     (26 neighbours, ``generate_binary_structure(3, 3)``).  Returns (int32 CUDA label map, n): components numbered 1..n in
     raster order of their first voxel, exactly as ``scipy.ndimage.label`` numbers them."""
     import torch
-    mask = _check_volume(mask, torch.uint8, "label_components")
+    mask = check_volume(mask, torch.uint8, "label_components")
     labels = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
     n = C.c_int32(0)
     stream = torch.cuda.current_stream(mask.device).cuda_stream
@@ -54,7 +48,7 @@ def label_components_neighbours(mask, neighbours):
     """``label_components`` with the neighbourhood named by its size: 6, 18 (faces and edges, ``generate_binary_structure(3, 2)``:
     what ``feature_extraction/step6_normal_structures.py:66-67`` labels with) or 26."""
     import torch
-    mask = _check_volume(mask, torch.uint8, "label_components_neighbours")
+    mask = check_volume(mask, torch.uint8, "label_components_neighbours")
     labels = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
     n = C.c_int32(0)
     stream = torch.cuda.current_stream(mask.device).cuda_stream
@@ -67,10 +61,10 @@ def component_stats(labels, n, seg=None):
     """labels: the map of ``label_components``, n its component count, seg: optional CUDA uint8 map of the same shape.
     Returns int64 [n, 14]: count, coordinate sums (3), minima (3), maxima (3), voxels with seg value 1, 2, 3, 4."""
     import torch
-    labels = _check_volume(labels, torch.int32, "component_stats")
+    labels = check_volume(labels, torch.int32, "component_stats")
     seg_ptr = None
     if seg is not None:
-        seg = _check_volume(seg, torch.uint8, "component_stats")
+        seg = check_volume(seg, torch.uint8, "component_stats")
         if seg.shape != labels.shape:
             raise ValueError("component_stats: seg and labels differ in shape")
         seg_ptr = seg.data_ptr()
@@ -84,8 +78,8 @@ def component_stats(labels, n, seg=None):
 def component_filter(labels, seg, keep):
     """out[i] = seg[i] where keep[labels[i]] (or labels[i] == 0), else 0.  keep: n + 1 booleans, keep[0] ignored."""
     import torch
-    labels = _check_volume(labels, torch.int32, "component_filter")
-    seg = _check_volume(seg, torch.uint8, "component_filter")
+    labels = check_volume(labels, torch.int32, "component_filter")
+    seg = check_volume(seg, torch.uint8, "component_filter")
     if seg.shape != labels.shape:
         raise ValueError("component_filter: seg and labels differ in shape")
     keep = np.ascontiguousarray(np.asarray(keep, dtype=bool).astype(np.uint8))
@@ -246,7 +240,7 @@ def lesion_multiplicity(seg, voxel_dims, ctx=None):
     import torch
     if ctx is not None:
         seg = ctx.volumes(seg, (), "lesion_multiplicity")[0]
-    seg = _check_volume(seg, torch.uint8, "lesion_multiplicity")
+    seg = check_volume(seg, torch.uint8, "lesion_multiplicity")
     labels, n = label_components(seg, 3) if ctx is None else ctx.tumour_components  # tumour = seg > 0
     tumour = component_stats(labels, n, seg)
     labels, n = label_components(_indicator(seg, (3,)), 3)    # enhancing = seg == 3
@@ -260,7 +254,7 @@ def remove_all_but_the_largest_connected_component(seg, for_which_classes, volum
     minimum_valid_object_size ({class: size} or one number, in the unit of volume_per_voxel) is given and the object reaches
     it.  Returns (new seg, largest_removed {class: size or None}, kept_size {class: size or None})."""
     import torch
-    seg = _check_volume(seg, torch.uint8, "remove_all_but_the_largest_connected_component").clone()
+    seg = check_volume(seg, torch.uint8, "remove_all_but_the_largest_connected_component").clone()
     largest_removed, kept_size = {}, {}
     for c in for_which_classes:
         members = tuple(c) if isinstance(c, (list, tuple)) else (c,)

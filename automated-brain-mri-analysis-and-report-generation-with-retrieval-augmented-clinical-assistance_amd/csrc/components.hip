@@ -27,7 +27,7 @@
 // the lanes that hold the same component are reduced with a butterfly, the waves of a workgroup are merged where they agree,
 // and only then a row of the table in memory sees one atomic per column (a 100 000-voxel lesion would otherwise send 10^6
 // atomics to ten words, which memory-side atomics serialise).
-#include "kernels.h"
+#include "volume_common.h"
 
 namespace mi355 {
 
@@ -315,11 +315,6 @@ __global__ void ccl_filter_kernel(const int *labels, const uint8_t *seg, int64_t
     }
 }
 
-static inline unsigned stream_blocks(int64_t n, int per_block, int64_t cap) {
-    int64_t b = (n + per_block - 1) / per_block;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 }  // namespace mi355
 
 using namespace mi355;
@@ -340,16 +335,13 @@ static int label_components(const uint8_t *mask_dev, int d0, int d1, int d2, int
     const int nbx = ceil_div(d2, BX), nby = ceil_div(d1, BY), nbz = ceil_div(d0, BZ);
     const int64_t nbricks = (int64_t)nbx * nby * nbz;  // <= V < 2^31
     hipLaunchKernelGGL(ccl_local_kernel, dim3((unsigned)nbricks), dim3(256), 0, s, mask_dev, d0, d1, d2, nbx, nby, connectivity, par);
-    hipLaunchKernelGGL(ccl_seam_kernel, dim3(stream_blocks(V, 256, 16384)), dim3(256), 0, s, d0, d1, d2, connectivity, par);
+    hipLaunchKernelGGL(ccl_seam_kernel, dim3(grid_for(V, 256, 16384)), dim3(256), 0, s, d0, d1, d2, connectivity, par);
     hipLaunchKernelGGL(ccl_flatten_kernel, dim3((unsigned)nchunks), dim3(256), 0, s, par, V, counts);
     hipLaunchKernelGGL(ccl_scan_kernel, dim3(1), dim3(1024), 0, s, counts, (int)nchunks, total);
     hipLaunchKernelGGL(ccl_rank_kernel, dim3((unsigned)nchunks), dim3(256), 0, s, (const int *)par, V, (const int *)counts, labels_dev);
-    hipLaunchKernelGGL(ccl_relabel_kernel, dim3(stream_blocks(V, 256, 16384)), dim3(256), 0, s, (const int *)par, V, labels_dev);
-    hipError_t e = hipGetLastError();
+    hipLaunchKernelGGL(ccl_relabel_kernel, dim3(grid_for(V, 256, 16384)), dim3(256), 0, s, (const int *)par, V, labels_dev);
     int n = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&n, total, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(&n, total, sizeof(int), s));
     *n_components_host = n;
     return MI355_OK;
 }
@@ -383,10 +375,7 @@ extern "C" int mi355_component_stats(const int32_t *labels_dev, const uint8_t *s
     hipLaunchKernelGGL(ccl_table_init_kernel, dim3((unsigned)ceil_div(cells, 256)), dim3(256), 0, s, table, cells);
     hipLaunchKernelGGL(ccl_stats_kernel, dim3((unsigned)((V + STAT_CHUNK - 1) / STAT_CHUNK)), dim3(256), 0, s, (const int *)labels_dev, seg_dev,
                        d1, d2, V, n_components, table);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(stats_host, table, (size_t)cells * sizeof(long long), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(stats_host, table, (size_t)cells * sizeof(long long), s));
     return MI355_OK;
 }
 
@@ -399,7 +388,7 @@ extern "C" int mi355_component_filter(const int32_t *labels_dev, const uint8_t *
     uint8_t *keep = (uint8_t *)(scr + TABLE_BYTES);
     // (pageable host memory: the copy has left keep_host when this returns, and is ordered on the stream like the kernel)
     MI355_HIP(hipMemcpyAsync(keep, keep_host, (size_t)n_components + 1, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(ccl_filter_kernel, dim3(stream_blocks(n, 256, 8192)), dim3(256), 0, s, (const int *)labels_dev, seg_dev, n, (const uint8_t *)keep,
+    hipLaunchKernelGGL(ccl_filter_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, (const int *)labels_dev, seg_dev, n, (const uint8_t *)keep,
                        n_components, out_dev);
     MI355_HIP(hipGetLastError());
     return MI355_OK;

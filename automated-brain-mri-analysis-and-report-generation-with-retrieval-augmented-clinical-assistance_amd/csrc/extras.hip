@@ -3,7 +3,7 @@
 //   * confusion counts for Dice/IoU   evaluate_segmentation.py:12-49,129-195
 //   * cosine top-k retrieval          RAG_Assistant/rag_assistant.py:197-211 (DummyVectorStore.retrieve)
 // All HBM-bound streaming kernels.
-#include "kernels.h"
+#include "volume_common.h"
 
 namespace mi355 {
 
@@ -108,9 +108,7 @@ extern "C" int mi355_label_confusion(const uint8_t *pred_dev, const uint8_t *gt_
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(confusion_kernel, dim3((unsigned)blocks), dim3(256), 0, s, pred_dev, gt_dev, n, K, c);
     unsigned long long h[64];
-    hipError_t e = hipMemcpyAsync(h, c, sizeof(h), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(h, c, sizeof(h), s));
     for (int i = 0; i < K * K; ++i) counts_host[i] = h[i];
     return MI355_OK;
 }
@@ -137,10 +135,8 @@ extern "C" int mi355_cosine_topk(const float *vectors_dev, const float *query_de
         hipLaunchKernelGGL(argmax_pass_kernel, dim3(b2), dim3(256), 0, s, scores, N, taken, t, best);
         hipLaunchKernelGGL(take_best_kernel, dim3(1), dim3(1), 0, s, best, scores, taken, t, out_i, out_s);
     }
-    hipError_t e = hipMemcpyAsync(idx_host, out_i, k * sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(scores_host, out_s, k * sizeof(float), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_HIP(hipMemcpyAsync(idx_host, out_i, k * sizeof(int), hipMemcpyDeviceToHost, s));  // (the wait below covers both copies)
+    MI355_TRY(read_back(scores_host, out_s, k * sizeof(float), s));
     return k;
 }
 
@@ -231,29 +227,23 @@ extern "C" int mi355_crop_mask(const float *vol_dev, int C, int Z, int Y, int X,
     int64_t blocks = (V + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(nonzero_state_kernel, dim3((unsigned)blocks), dim3(256), 0, s, vol_dev, C, V, state);
-    hipError_t e = hipGetLastError();
+    MI355_HIP(hipGetLastError());
     bool converged = false;
-    for (int round = 0; e == hipSuccess && round < 4096; ++round) {
+    for (int round = 0; round < 4096; ++round) {
         (void)hipMemsetAsync(flags, 0, sizeof(int), s);
         for (int axis = 0; axis < 3; ++axis) {
             const int lines = axis == 0 ? Y * X : (axis == 1 ? Z * X : Z * Y);
             hipLaunchKernelGGL(fill_sweep_kernel, dim3((unsigned)((lines + 127) / 128)), dim3(128), 0, s, state, Z, Y, X, axis, flags);
         }
         int changed = 0;
-        e = hipMemcpyAsync(&changed, flags, sizeof(int), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e == hipSuccess && !changed) { converged = true; break; }
+        MI355_TRY(read_back(&changed, flags, sizeof(int), s));
+        if (!changed) { converged = true; break; }
     }
     int init[7] = {0, 1 << 30, 1 << 30, 1 << 30, -1, -1, -1};
-    if (e == hipSuccess) e = hipMemcpyAsync(flags, init, sizeof(init), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(fill_finish_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, s, state, mask_dev, Z, Y, X, flags + 1);
-        e = hipGetLastError();
-    }
+    MI355_HIP(hipMemcpyAsync(flags, init, sizeof(init), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(fill_finish_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, s, state, mask_dev, Z, Y, X, flags + 1);
     int out[7];
-    if (e == hipSuccess) e = hipMemcpyAsync(out, flags, sizeof(out), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(out, flags, sizeof(out), s));
     MI355_REQUIRE(converged, "crop_mask: the border flood fill did not converge in 4096 rounds (%dx%dx%d)", Z, Y, X);
     MI355_REQUIRE(out[4] >= 0, "volume is all zeros: nothing to segment");
     for (int k = 0; k < 3; ++k) { bbox_host[2 * k] = out[1 + k]; bbox_host[2 * k + 1] = out[4 + k] + 1; }  // [lo, hi) per axis
@@ -299,18 +289,13 @@ extern "C" int mi355_label_stats(const uint8_t *seg_dev, int d0, int d1, int d2,
     long long init[80], *dev = nullptr;
     for (int i = 0; i < 80; ++i) init[i] = (i % 10 >= 4 && i % 10 <= 6) ? (1ll << 40) : (i % 10 >= 7 ? -1 : 0);
     MI355_TRY(device_scratch(SCR_SMALL, s, 1 << 20, (void **)&dev));
-    hipError_t e = hipMemcpyAsync(dev, init, sizeof(init), hipMemcpyHostToDevice, s);
+    MI355_HIP(hipMemcpyAsync(dev, init, sizeof(init), hipMemcpyHostToDevice, s));
     const int64_t V = (int64_t)d0 * d1 * d2;
     int64_t blocks = (V + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(label_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, s, seg_dev, d0, d1, d2, K, dev);
-        e = hipGetLastError();
-    }
+    hipLaunchKernelGGL(label_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, s, seg_dev, d0, d1, d2, K, dev);
     long long h[80];
-    if (e == hipSuccess) e = hipMemcpyAsync(h, dev, sizeof(h), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(h, dev, sizeof(h), s));
     long long nonzero = 0;
     for (int l = 1; l < K; ++l) nonzero += h[l * 10];
     for (int i = 0; i < K * 10; ++i) stats_host[i] = h[i];

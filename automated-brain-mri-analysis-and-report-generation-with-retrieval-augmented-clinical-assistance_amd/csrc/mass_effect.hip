@@ -12,7 +12,7 @@
 // 16-byte load (byte loads when the pointer is not 16-byte aligned and on the last, partial group), turns them into a 16-bit
 // mask and does nothing more where the mask is zero - most of a head volume.  Counters live in LDS (axis_counts, box_counts) or
 // in registers and are flushed to global memory once per workgroup.
-#include "kernels.h"
+#include "volume_common.h"
 
 namespace mi355 {
 namespace me {
@@ -23,17 +23,6 @@ constexpr int SCAN = 256;        // block counts per segment of the scan
 constexpr int MAX_SEGMENTS = 2048;  // 2^31 voxels / TILE / SCAN
 constexpr int B_CHUNK = 2048;    // points of list b per workgroup of the pair distance
 
-__device__ __forceinline__ int wave_sum(int v) {
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
-__device__ __forceinline__ void coords(int64_t i, int d1, int d2, int &c0, int &c1, int &c2) {
-    const unsigned u = (unsigned)i;
-    const unsigned zy = u / (unsigned)d2;
-    c2 = (int)(u - zy * (unsigned)d2);
-    c0 = (int)(zy / (unsigned)d1);
-    c1 = (int)(zy - (unsigned)c0 * (unsigned)d1);
-}
 // (require and forbid share no bit: one comparison)
 __device__ __forceinline__ unsigned picked(unsigned byte, unsigned require, unsigned both) { return (byte & both) == require ? 1u : 0u; }
 
@@ -154,7 +143,7 @@ __global__ __launch_bounds__(256) void box_counts_kernel(const uint8_t *flags, u
 __global__ __launch_bounds__(256) void block_count_kernel(const uint8_t *flags, unsigned require, unsigned forbid, int64_t n, int vec, unsigned *block_count) {
     __shared__ int wred[4];
     const int64_t i = (int64_t)blockIdx.x * TILE + (int64_t)threadIdx.x * VPT;
-    const int c = wave_sum(i < n ? __popc(select16(flags, i, n, vec != 0, require, forbid)) : 0);
+    const int c = wave_sum(i < n ? (int)__popc(select16(flags, i, n, vec != 0, require, forbid)) : 0);
     if ((threadIdx.x & 63) == 0) wred[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) block_count[blockIdx.x] = (unsigned)(wred[0] + wred[1] + wred[2] + wred[3]);
@@ -317,24 +306,6 @@ __global__ __launch_bounds__(256) void masked_min_kernel(const int *values, cons
     }
 }
 
-static inline unsigned grid_for_tiles(int64_t n, int64_t cap) {
-    const int64_t b = (n + TILE - 1) / TILE;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-static inline int check_volume(const char *what, int d0, int d1, int d2, int64_t *V) {
-    MI355_REQUIRE(d0 >= 1 && d1 >= 1 && d2 >= 1, "%s: bad shape %dx%dx%d", what, d0, d1, d2);
-    *V = (int64_t)d0 * d1 * d2;
-    MI355_REQUIRE(*V < (1ll << 31), "%s: %dx%dx%d has 2^31 voxels or more", what, d0, d1, d2);
-    return MI355_OK;
-}
-static inline int check_selection(const char *what, int require, int forbid) {
-    MI355_REQUIRE(require >= 0 && require <= 255 && forbid >= 0 && forbid <= 255 && (require & forbid) == 0,
-                  "%s: require %d, forbid %d (masks of flag bits, 0..255, that share no bit)", what, require, forbid);
-    return MI355_OK;
-}
-static inline int aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-static inline size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace me
 }  // namespace mi355
 
@@ -355,12 +326,9 @@ extern "C" int mi355_axis_counts(const uint8_t *flags_dev, int require, int forb
     unsigned long long *counts = nullptr;
     MI355_TRY(device_scratch(SCR_MASS_EFFECT, s, (size_t)nh * sizeof(unsigned long long), (void **)&counts));
     MI355_HIP(hipMemsetAsync(counts, 0, (size_t)nh * sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(axis_counts_kernel, dim3(grid_for_tiles(V, 1024)), dim3(256), (size_t)nh * sizeof(unsigned), s, flags_dev, (unsigned)require,
+    hipLaunchKernelGGL(axis_counts_kernel, dim3(grid_for(V, TILE, 1024)), dim3(256), (size_t)nh * sizeof(unsigned), s, flags_dev, (unsigned)require,
                        (unsigned)forbid, d0, d1, d2, aligned16(flags_dev), counts);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(counts_host, counts, (size_t)nh * sizeof(int64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(counts_host, counts, (size_t)nh * sizeof(int64_t), s));
     return MI355_OK;
 }
 
@@ -386,12 +354,9 @@ extern "C" int mi355_box_counts(const uint8_t *flags_dev, int require, int forbi
     unsigned long long *counts = nullptr;
     MI355_TRY(device_scratch(SCR_MASS_EFFECT, s, 256, (void **)&counts));
     MI355_HIP(hipMemsetAsync(counts, 0, MI355_MAX_BOXES * sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(box_counts_kernel, dim3(grid_for_tiles(V, 1024)), dim3(256), 0, s, flags_dev, (unsigned)require, (unsigned)forbid, d0, d1, d2,
+    hipLaunchKernelGGL(box_counts_kernel, dim3(grid_for(V, TILE, 1024)), dim3(256), 0, s, flags_dev, (unsigned)require, (unsigned)forbid, d0, d1, d2,
                        aligned16(flags_dev), bx, nb, counts);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(counts_host, counts, (size_t)nb * sizeof(int64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(counts_host, counts, (size_t)nb * sizeof(int64_t), s));
     return MI355_OK;
 }
 
@@ -414,16 +379,13 @@ extern "C" int mi355_select_ranked(const uint8_t *flags_dev, int require, int fo
     hipLaunchKernelGGL(block_count_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, flags_dev, (unsigned)require, (unsigned)forbid, n, vec, block_count);
     hipLaunchKernelGGL(scan_blocks_kernel, dim3((unsigned)nseg), dim3(256), 0, s, (const unsigned *)block_count, nblocks, offset, segment_sum);
     hipLaunchKernelGGL(scan_segments_kernel, dim3(1), dim3(256), 0, s, (const unsigned *)segment_sum, nseg, segment_base);
-    hipError_t e = hipGetLastError();
     unsigned long long m = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&m, segment_base + nseg, sizeof(m), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(&m, segment_base + nseg, sizeof(m), s));
     count_host[0] = (int64_t)m;
     for (int j = 0; j < k; ++j)
         MI355_REQUIRE(ranks_host[j] >= 0 && (unsigned long long)ranks_host[j] < m, "select_ranked: rank %lld (entry %d) of %llu selected voxels",
                       (long long)ranks_host[j], j, m);
-    e = hipMemcpyAsync(ranks, ranks_host, (size_t)k * sizeof(long long), hipMemcpyHostToDevice, s);
+    hipError_t e = hipMemcpyAsync(ranks, ranks_host, (size_t)k * sizeof(long long), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(pick_kernel, dim3((unsigned)k), dim3(64), 0, s, flags_dev, (unsigned)require, (unsigned)forbid, n, vec, (const unsigned *)offset,
                            (const unsigned long long *)segment_base, nblocks, (const long long *)ranks, (long long *)index_dev);
@@ -452,10 +414,7 @@ extern "C" int mi355_min_pair_dist2(const int64_t *a_index_dev, int ka, const in
         hipLaunchKernelGGL(min_pair_kernel<unsigned>, grid, dim3(256), 0, s, a, ka, b, kb, d0, d1, d2, res);
     else
         hipLaunchKernelGGL(min_pair_kernel<unsigned long long>, grid, dim3(256), 0, s, a, ka, b, kb, d0, d1, d2, res);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h, res, sizeof(h), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(h, res, sizeof(h), s));
     MI355_REQUIRE(h[1] == 0, "min_pair_dist2: an index lies outside the %dx%dx%d volume", d0, d1, d2);
     min_host[0] = (int64_t)h[0];
     return MI355_OK;
@@ -471,12 +430,9 @@ extern "C" int mi355_masked_min_i32(const int32_t *values_dev, const uint8_t *fl
     MI355_TRY(device_scratch(SCR_MASS_EFFECT, s, 256, (void **)&res));
     MI355_HIP(hipMemsetAsync(res, 0, sizeof(unsigned long long), s));
     MI355_HIP(hipMemsetAsync(res + 1, 0xFF, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(masked_min_kernel, dim3(grid_for_tiles(n, 2048)), dim3(256), 0, s, (const int *)values_dev, flags_dev, (unsigned)require,
+    hipLaunchKernelGGL(masked_min_kernel, dim3(grid_for(n, TILE, 2048)), dim3(256), 0, s, (const int *)values_dev, flags_dev, (unsigned)require,
                        (unsigned)forbid, n, aligned16(flags_dev), res);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h, res, sizeof(h), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(h, res, sizeof(h), s));
     count_host[0] = (int64_t)h[0];
     if (h[0]) min_host[0] = (int32_t)((unsigned)(h[1] & 0xFFFFFFFFull) ^ 0x80000000u);
     return MI355_OK;

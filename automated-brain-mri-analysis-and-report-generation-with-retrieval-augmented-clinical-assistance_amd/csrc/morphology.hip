@@ -23,7 +23,7 @@
 // In all three the lanes of a wave sit on adjacent addresses of axis 2 for every global access.  Values are uint32 with
 // EDT_INF = 2^31: a finite value is at most the squared diagonal (< 2^31, checked), so EDT_INF + (i - j)^2 never wraps and
 // never wins against a finite candidate; every pass clamps to EDT_INF again.
-#include "kernels.h"
+#include "volume_common.h"
 
 namespace mi355 {
 
@@ -137,15 +137,6 @@ __global__ __launch_bounds__(256) void edt_axis2_kernel(unsigned *g, int64_t lin
 }
 
 // ------------------------------------------------------------------------------------------- reductions
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);  // a fixed tree: the same bits in every lane, every run
-    return v;
-}
-__device__ __forceinline__ long long wave_sum(long long v) {
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 // np.gradient's stencil along one axis of the signed distance sqrt(d2_in) - sqrt(d2_out): central difference / 2 inside,
 // one-sided first difference at both ends (the axis has at least 2 entries)
 __device__ __forceinline__ double signed_dist(const int *din, const int *dout, int64_t i) {
@@ -302,17 +293,6 @@ __global__ void flag_from_flags_kernel(uint8_t *flags, int bitmask, int require,
     }
 }
 
-static inline unsigned grid_for(int64_t n, int per_block, int64_t cap) {
-    int64_t b = (n + per_block - 1) / per_block;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-static inline int check_volume(const char *what, int d0, int d1, int d2, int64_t *V) {
-    MI355_REQUIRE(d0 >= 1 && d1 >= 1 && d2 >= 1, "%s: bad shape %dx%dx%d", what, d0, d1, d2);
-    *V = (int64_t)d0 * d1 * d2;
-    MI355_REQUIRE(*V < (1ll << 31), "%s: %dx%dx%d has 2^31 voxels or more", what, d0, d1, d2);
-    return MI355_OK;
-}
-
 }  // namespace mi355
 
 using namespace mi355;
@@ -354,11 +334,8 @@ extern "C" int mi355_edt_squared(const uint8_t *mask_dev, int d0, int d1, int d2
     MI355_TRY(device_scratch(SCR_MORPHOLOGY, s, 256, (void **)&count));
     MI355_HIP(hipMemsetAsync(count, 0, sizeof(unsigned), s));
     hipLaunchKernelGGL(count_background_kernel, dim3(grid_for(V, 256 * 16, 2048)), dim3(256), 0, s, mask_dev, V, count);
-    hipError_t e = hipGetLastError();
     unsigned background = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&background, count, sizeof(unsigned), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(&background, count, sizeof(unsigned), s));
     MI355_REQUIRE(background > 0, "edt_squared: the %dx%dx%d volume has no background voxel: there is no distance to measure", d0, d1, d2);
     unsigned *g = (unsigned *)dist2_dev;
     const int64_t plane = (int64_t)d1 * d2;
@@ -396,10 +373,7 @@ extern "C" int mi355_surface_gradient_stats(const int32_t *d2_in_dev, const int3
         hipLaunchKernelGGL(grad_stats_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, (const int *)d2_in_dev, (const int *)d2_out_dev, surface_dev, select,
                            d0, d1, d2, mean, partial);
         hipLaunchKernelGGL(sum_partials_kernel, dim3(3), dim3(64), 0, s, (const double *)partial, nblocks, 3, total);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h, total, sizeof(h), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        MI355_HIP(e);
+        MI355_TRY(read_back(h, total, sizeof(h), s));
         if (h[0] == 0) { stats_host[0] = stats_host[1] = stats_host[2] = 0; return MI355_OK; }
         if (pass == 0) mean = h[1] / h[0];
     }
@@ -420,10 +394,7 @@ extern "C" int mi355_mask_second_moments(const uint8_t *mask_dev, int d0, int d1
     MI355_TRY(device_scratch(SCR_MORPHOLOGY, s, 256, (void **)&out));
     MI355_HIP(hipMemsetAsync(out, 0, 10 * sizeof(unsigned long long), s));
     hipLaunchKernelGGL(second_moments_kernel, dim3((unsigned)((V + RED_CHUNK - 1) / RED_CHUNK)), dim3(256), 0, s, mask_dev, d0, d1, d2, out);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(moments_host, out, 10 * sizeof(int64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(moments_host, out, 10 * sizeof(int64_t), s));
     return MI355_OK;
 }
 
@@ -440,10 +411,7 @@ extern "C" int mi355_masked_moments(const float *vols_dev, int C, const uint8_t 
     int *counts = (int *)(scr + partial_bytes);
     hipLaunchKernelGGL(masked_moments_kernel, dim3((unsigned)chunks, (unsigned)C), dim3(256), 0, s, vols_dev, flags_dev, n, partial, counts);
     hipLaunchKernelGGL(masked_moments_finish_kernel, dim3((unsigned)C, 3 * MM_BITS), dim3(64), 0, s, (const double *)partial, (const int *)counts, chunks, C, out);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out_host, out, out_count * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(out_host, out, out_count * sizeof(double), s));
     return MI355_OK;
 }
 

@@ -19,6 +19,7 @@
 // Values are uint32 with CB_FAR = 2^30 (MI355_CITYBLOCK_FAR) for "no source anywhere": a finite distance is below d0 + d1 + d2
 // <= 2^30 (checked), run + 1 is clamped to CB_FAR, so nothing wraps.
 #include "radix_select.h"
+#include "volume_common.h"
 
 namespace mi355 {
 namespace ns {
@@ -163,16 +164,6 @@ struct NonNegativeKey {
     }
 };
 
-static inline unsigned grid_for(int64_t n, int per_block, int64_t cap) {
-    const int64_t b = (n + per_block - 1) / per_block;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-static inline int check_volume(const char *what, int d0, int d1, int d2, int64_t *V) {
-    MI355_REQUIRE(d0 >= 1 && d1 >= 1 && d2 >= 1, "%s: bad shape %dx%dx%d", what, d0, d1, d2);
-    *V = (int64_t)d0 * d1 * d2;
-    MI355_REQUIRE(*V < (1ll << 31), "%s: %dx%dx%d has 2^31 voxels or more", what, d0, d1, d2);
-    return MI355_OK;
-}
 static inline int check_flag_args(const char *what, int bit, int require, int forbid) {
     MI355_REQUIRE(bit >= 0 && bit < 8 && require >= 0 && require <= 255 && forbid >= 0 && forbid <= 255, "%s: bit %d, require %d, forbid %d", what, bit, require,
                   forbid);
@@ -251,8 +242,7 @@ extern "C" int mi355_masked_order_stats_i32(const int32_t *values_dev, int64_t n
     MI355_REQUIRE(nq >= 1 && nq <= PCT_MAX_Q, "masked_order_stats_i32: %d percentiles (1..%d per call)", nq, PCT_MAX_Q);
     for (int j = 0; j < nq; ++j)
         MI355_REQUIRE(q_host[j] >= 0.0 && q_host[j] <= 100.0, "masked_order_stats_i32: percentile %d is %g (0..100, not NaN)", j, q_host[j]);
-    MI355_REQUIRE(require >= 0 && require <= 255 && forbid >= 0 && forbid <= 255 && !(require & forbid),
-                  "masked_order_stats_i32: require %d, forbid %d (masks of flag bits, 0..255, that share no bit)", require, forbid);
+    MI355_TRY(check_selection("masked_order_stats_i32", require, forbid));
     int64_t counts[2] = {0, 0};
     unsigned below[PCT_MAX_Q], above[PCT_MAX_Q];
     MI355_TRY(radix_select<NonNegativeKey>("masked_order_stats_i32", (const unsigned *)values_dev, n, flags_dev, require, forbid, 0.0, 0.0, q_host, nq, counts, below,
@@ -272,8 +262,7 @@ extern "C" int mi355_column_count_max(const uint8_t *flags_dev, int require, int
     int64_t V = 0;
     MI355_TRY(check_volume("column_count_max", d0, d1, d2, &V));
     MI355_REQUIRE(flags_dev && out_host, "column_count_max: null pointer");
-    MI355_REQUIRE(require >= 0 && require <= 255 && forbid >= 0 && forbid <= 255 && !(require & forbid),
-                  "column_count_max: require %d, forbid %d (masks of flag bits, 0..255, that share no bit)", require, forbid);
+    MI355_TRY(check_selection("column_count_max", require, forbid));
     MI355_REQUIRE(i1_from >= 0, "column_count_max: i1_from %d (0 or more; at or above d1 = %d the slab is empty and the result 0)", i1_from, d1);
     out_host[0] = 0;
     if (i1_from >= d1) return MI355_OK;
@@ -284,10 +273,7 @@ extern "C" int mi355_column_count_max(const uint8_t *flags_dev, int require, int
     const int64_t plane = (int64_t)d1 * d2, first = (int64_t)i1_from * d2, columns = plane - first;
     hipLaunchKernelGGL(column_count_max_kernel, dim3((unsigned)((columns + 255) / 256)), dim3(256), 0, s, flags_dev, (unsigned)require, (unsigned)(require | forbid),
                        d0, plane, first, (unsigned)columns, best);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, best, sizeof(unsigned), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(&h, best, sizeof(unsigned), s));
     out_host[0] = (int64_t)h;
     return MI355_OK;
 }

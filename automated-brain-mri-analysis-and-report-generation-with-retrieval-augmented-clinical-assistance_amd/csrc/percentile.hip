@@ -209,8 +209,7 @@ extern "C" int mi355_masked_percentiles_multi(const float *const *x_dev, int nvo
         }
         MI355_REQUIRE(total <= PCT_MULTI_WORDS, "masked_percentiles_multi: pass %d wants %d counters, the table holds %d", pass, total, PCT_MULTI_WORDS);
         MI355_HIP(hipMemsetAsync(table, 0, (size_t)total * sizeof(unsigned), s));
-        hipError_t e = hipSuccess;
-        for (int l = 0; l < nl && e == hipSuccess; ++l) {
+        for (int l = 0; l < nl; ++l) {
             const size_t lds = (size_t)(args[l].bins + args[l].count) * sizeof(unsigned);
             if (lds > lds_allowed.load()) {
                 MI355_HIP(hipFuncSetAttribute((const void *)pct_hist_multi_kernel<FloatKey>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
@@ -218,12 +217,10 @@ extern "C" int mi355_masked_percentiles_multi(const float *const *x_dev, int nvo
             }
             hipLaunchKernelGGL(pct_hist_multi_kernel<FloatKey>, dim3(blocks), dim3(256), lds, s, args[l], flags_dev, n, 24 - 8 * pass, pass == 0 ? 1 : 0,
                                table + start[l]);
-            e = hipGetLastError();
+            MI355_HIP(hipGetLastError());
             ++launches;
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(h, table, (size_t)total * sizeof(unsigned), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        MI355_HIP(e);
+        MI355_TRY(read_back(h, table, (size_t)total * sizeof(unsigned), s));
         for (int v = 0; v < nvol; ++v) {
             if (!walk[v].live) continue;
             const PctMultiArgs &a = args[where[v][0]];

@@ -22,32 +22,15 @@
 // multiply-add in shell_dist would move max_dist by an ulp.
 #include <cstring>
 
-#include "kernels.h"
+#include "volume_common.h"
 
 #pragma clang fp contract(off)
 
 namespace mi355 {
 namespace qc {
 
-// (wave_sum, sum_columns_kernel, grid_for and check_volume repeat morphology.hip's: device code is not linked across files, and a
-// kernel defined in a shared header would be emitted once per file that includes it)
+// (sum_columns_kernel repeats morphology.hip's sum_partials_kernel: device code is not linked across files)
 constexpr int RED_CHUNK = 8192;  // voxels per workgroup in the fp64 reductions (32 per thread)
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);  // a fixed tree: the same bits in every lane, every run
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
-__device__ __forceinline__ void coords(int64_t i, int d1, int d2, int &c0, int &c1, int &c2) {
-    const unsigned u = (unsigned)i;
-    const unsigned zy = u / (unsigned)d2;
-    c2 = (int)(u - zy * (unsigned)d2);
-    c0 = (int)(zy / (unsigned)d1);
-    c1 = (int)(zy - (unsigned)c0 * (unsigned)d1);
-}
 
 // partial[block][ncols] -> out[k] = the sum of column k: lane l adds rows l, l + 64, ... in that order, then the wave's fixed
 // butterfly.  grid ncols, one wave each
@@ -237,18 +220,6 @@ __global__ __launch_bounds__(256) void face_slab_kernel(const float *x, int d0, 
     }
 }
 
-static inline unsigned grid_for(int64_t n, int per_block, int64_t cap) {
-    int64_t b = (n + per_block - 1) / per_block;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-static inline int check_volume(const char *what, int d0, int d1, int d2, int64_t *V) {
-    MI355_REQUIRE(d0 >= 1 && d1 >= 1 && d2 >= 1, "%s: bad shape %dx%dx%d", what, d0, d1, d2);
-    *V = (int64_t)d0 * d1 * d2;
-    MI355_REQUIRE(*V < (1ll << 31), "%s: %dx%dx%d has 2^31 voxels or more", what, d0, d1, d2);
-    return MI355_OK;
-}
-static inline size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace qc
 }  // namespace mi355
 
@@ -282,11 +253,8 @@ extern "C" int mi355_binary_fill_holes(const uint8_t *mask_dev, int d0, int d1, 
     MI355_HIP(hipMemsetAsync(mark, 0, (size_t)(n + 1) * sizeof(unsigned), s));
     hipLaunchKernelGGL(face_mark_kernel, dim3(blocks), dim3(256), 0, s, (const int *)labels, d0, d1, d2, (int)n, mark);
     hipLaunchKernelGGL(fill_write_kernel, dim3(blocks), dim3(256), 0, s, mask_dev, (const int *)labels, (const unsigned *)mark, (int)n, V, out_dev, filled);
-    hipError_t e = hipGetLastError();
     unsigned long long h = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, filled, sizeof(h), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(&h, filled, sizeof(h), s));
     *filled_host = (int64_t)h;
     return MI355_OK;
 }
@@ -306,10 +274,7 @@ extern "C" int mi355_sobel_magnitude_stats(const float *x_dev, const uint8_t *fl
     for (int pass = 0; pass < 2; ++pass) {  // pass 0: n and the mean; pass 1: the sums about that mean
         hipLaunchKernelGGL(sobel_stats_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, x_dev, flags_dev, select, d0, d1, d2, mean, partial);
         hipLaunchKernelGGL(sum_columns_kernel, dim3(3), dim3(64), 0, s, (const double *)partial, nblocks, 3, total);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h, total, sizeof(h), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        MI355_HIP(e);
+        MI355_TRY(read_back(h, total, sizeof(h), s));
         if (h[0] == 0) { stats_host[0] = stats_host[1] = stats_host[2] = 0; return MI355_OK; }
         if (pass == 0) mean = h[1] / h[0];
     }
@@ -338,10 +303,7 @@ extern "C" int mi355_radial_shell_moments(const float *x_dev, const uint8_t *fla
     for (int k = 0; k < 5; ++k) out_host[k] = 0;
     MI355_HIP(hipMemsetAsync(res, 0, 2 * sizeof(unsigned long long), s));
     hipLaunchKernelGGL(shell_max_kernel, dim3(grid_for(V, 256 * 16, 4096)), dim3(256), 0, s, flags_dev, require, d0, d1, d2, centre[0], centre[1], centre[2], res);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(hres, res, sizeof(hres), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(hres, res, sizeof(hres), s));
     if (hres[1] == 0) return MI355_OK;
     double max_dist;
     static_assert(sizeof(max_dist) == sizeof(hres[0]), "a double is 64 bits");
@@ -350,10 +312,7 @@ extern "C" int mi355_radial_shell_moments(const float *x_dev, const uint8_t *fla
     hipLaunchKernelGGL(shell_moments_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, x_dev, flags_dev, require, d0, d1, d2, centre[0], centre[1], centre[2],
                        t_in, t_out, partial);
     hipLaunchKernelGGL(sum_columns_kernel, dim3(4), dim3(64), 0, s, (const double *)partial, nblocks, 4, total);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h, total, sizeof(h), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(h, total, sizeof(h), s));
     out_host[0] = max_dist;
     for (int k = 0; k < 4; ++k) out_host[1 + k] = h[k];
     return MI355_OK;
@@ -369,9 +328,6 @@ extern "C" int mi355_face_slab_counts(const float *x_dev, int d0, int d1, int d2
     MI355_TRY(device_scratch(SCR_QUALITY, s, 256, (void **)&counts));
     MI355_HIP(hipMemsetAsync(counts, 0, 6 * sizeof(unsigned long long), s));
     hipLaunchKernelGGL(face_slab_kernel, dim3(grid_for(V, 256 * 16, 4096)), dim3(256), 0, s, x_dev, d0, d1, d2, margin, counts);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(counts_host, counts, 6 * sizeof(int64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    MI355_HIP(e);
+    MI355_TRY(read_back(counts_host, counts, 6 * sizeof(int64_t), s));
     return MI355_OK;
 }

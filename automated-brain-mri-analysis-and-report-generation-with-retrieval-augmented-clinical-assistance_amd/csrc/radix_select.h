@@ -5,7 +5,7 @@
 #pragma once
 #include <cmath>
 
-#include "kernels.h"
+#include "volume_common.h"
 
 namespace mi355 {
 
@@ -209,10 +209,7 @@ int radix_select(const char *what, const unsigned *x_dev, int64_t n, const uint8
         MI355_HIP(hipMemsetAsync(table, 0, (size_t)PCT_TABLE * sizeof(unsigned), s));
         hipLaunchKernelGGL(pct_hist_kernel<Key>, dim3(blocks), dim3(256), 0, s, x_dev, flags_dev, n, require, forbid, lo, hi, groups, shift, pass == 0 ? 1 : 0,
                            table);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h, table, (size_t)PCT_TABLE * sizeof(unsigned), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        MI355_HIP(e);
+        MI355_TRY(read_back(h, table, (size_t)PCT_TABLE * sizeof(unsigned), s));
         if (pass == 0) {
             int64_t m = 0;
             for (int d = 0; d < 256; ++d) m += h[d];

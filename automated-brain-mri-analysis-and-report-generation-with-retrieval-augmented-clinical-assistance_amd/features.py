@@ -20,17 +20,19 @@ As a command (the reference's arguments, run_all.py:503-516, and the two of ``br
 from __future__ import annotations
 
 import argparse
-import json
 import sys
 from datetime import datetime
 from pathlib import Path
 
 import numpy as np
 
-from . import percentile
-from .morphology import FLAIR, T1, T1CE, T2, _check_volume, case_id_and_paths, flag_from_flags
+from . import mass_effect, morphology, multiplicity, normal_structures, percentile, quality, sequence_findings
+from .case_io import FLAIR, MODALITIES, T1, T1CE, T2, case_id_and_paths, document, load_case, step_zooms, to_device, write_json
+from .volume_ops import check_volume, cityblock_distance, flag_from_flags, flag_from_i32
 
-STEP_KEYS = ('step1_sequence_findings', 'step2_mass_effect', 'step3_multiplicity', 'step4_morphology', 'step5_quality', 'step6_normal_structures')
+#: the records of the six steps, in order: what each one's command loads and what its file holds (``case_io.StepSpec``)
+SPECS = tuple(m.STEP_SPEC for m in (sequence_findings, mass_effect, multiplicity, morphology, quality, normal_structures))
+STEP_KEYS = tuple(spec.key for spec in SPECS)
 #: the percentiles the six steps take of a modality's positive voxels (``x[x > 0]``), per channel: utils.py:57 (5, steps 1, 2, 5, 6),
 #: step5_quality.py:194 (10), step4_morphology.py:317-320 (T1 10, T2 85, FLAIR 20)
 POSITIVE_QS = {T1: (5, 10), T1CE: (5, 10), T2: (5, 10, 85), FLAIR: (5, 10, 20)}
@@ -48,8 +50,8 @@ class CaseContext:
 
     def __init__(self, seg, t1, t1ce, t2, flair):
         import torch
-        self.seg = _check_volume(seg, torch.uint8, "CaseContext")
-        self.chans = [_check_volume(v, torch.float32, "CaseContext") for v in (t1, t1ce, t2, flair)]
+        self.seg = check_volume(seg, torch.uint8, "CaseContext")
+        self.chans = [check_volume(v, torch.float32, "CaseContext") for v in (t1, t1ce, t2, flair)]
         if any(v.shape != self.seg.shape for v in self.chans):
             raise ValueError("CaseContext: the volumes and the label map differ in shape")
         if int(self.seg.max()) > 4:
@@ -134,36 +136,26 @@ class CaseContext:
     @property
     def tumour_distance(self):
         """City-block distance to the tumour: ``<= n`` is ``binary_dilation(seg, n)``"""
-        from .normal_structures import cityblock_distance
         return self._once('tumour_distance', lambda: cityblock_distance(self.seg, True))
 
     @property
     def background_distance(self):
         """City-block distance to the tumour's background: ``> n`` is ``binary_erosion(seg, n)``"""
-        from .normal_structures import cityblock_distance
         return self._once('background_distance', lambda: cityblock_distance(self.seg, False))
 
     def dilated_into(self, flags, bit, iterations, require=0, forbid=0):
         """Bit ``bit`` of a step's flag byte = ``binary_dilation(seg, iterations)`` and the byte's ``require`` / ``forbid`` test"""
-        from .normal_structures import flag_from_i32
         return flag_from_i32(flags, bit, self.tumour_distance, 0, iterations, require=require, forbid=forbid)
 
     def eroded_into(self, flags, bit, iterations, require=0, forbid=0):
         """Bit ``bit`` of a step's flag byte = ``binary_erosion(seg, iterations)`` and the byte's ``require`` / ``forbid`` test"""
-        from .normal_structures import flag_from_i32
         return flag_from_i32(flags, bit, self.background_distance, iterations + 1, require=require, forbid=forbid)
 
 
-def _steps(ctx, zooms, zooms_step2, rng, distance):
-    """(key, thunk) per step, in order; each thunk returns what the step's own resident function returns"""
-    from . import components, mass_effect, morphology, normal_structures, quality, sequence_findings
-    seg, (t1, t1ce, t2, flair) = ctx.seg, ctx.chans
-    return ((STEP_KEYS[0], lambda: sequence_findings.sequence_findings(seg, t1, t1ce, t2, flair, zooms, ctx=ctx)),
-            (STEP_KEYS[1], lambda: mass_effect.mass_effect(seg, t1, zooms_step2, rng, distance, ctx=ctx)),
-            (STEP_KEYS[2], lambda: components.lesion_multiplicity(seg, zooms, ctx=ctx)),
-            (STEP_KEYS[3], lambda: morphology.tumor_morphology(seg, t1, t1ce, t2, flair, zooms, ctx=ctx)),
-            (STEP_KEYS[4], lambda: quality.quality_control(seg, t1, t1ce, t2, flair, zooms, ctx=ctx)),
-            (STEP_KEYS[5], lambda: normal_structures.normal_structures(seg, t1, t1ce, t2, flair, zooms, ctx=ctx)))
+def _call(spec, ctx, zooms, rng, distance):
+    """What the step's own resident function returns, on the context's tensors"""
+    args = {'rng': rng, 'distance': distance}
+    return spec.call(ctx.seg, dict(zip(MODALITIES, ctx.chans)), zooms, ctx=ctx, **{k: args[k] for k in spec.step_args})
 
 
 def extract_all(seg, t1, t1ce, t2, flair, voxel_dims, rng=None, distance='sampled'):
@@ -172,8 +164,7 @@ def extract_all(seg, t1, t1ce, t2, flair, voxel_dims, rng=None, distance='sample
     ``mass_effect`` with ``rng`` and ``distance``, ``lesion_multiplicity``, ``tumor_morphology``, ``quality_control``,
     ``normal_structures``).  Step 2 takes the voxel sizes as ``np.float32``, as its command does; the others as ``float``."""
     ctx = CaseContext(seg, t1, t1ce, t2, flair)
-    zooms = [float(v) for v in voxel_dims]
-    return {key: run() for key, run in _steps(ctx, zooms, [np.float32(v) for v in voxel_dims][:3], rng, distance)}
+    return {spec.key: _call(spec, ctx, step_zooms(spec, voxel_dims, voxel_dims), rng, distance) for spec in SPECS}
 
 
 # ---- the command ------------------------------------------------------------------------------------------------------
@@ -204,55 +195,29 @@ def run_all_steps(input_folder, segmentation_path, output_dir, rng=None, distanc
     finishes - byte for byte the file that step's own command writes - and ``comprehensive_analysis.json`` at the end.  A step
     that raises leaves the earlier files behind and the exception propagates (run_all.py:411-446).  ``report(key, result)`` is
     called after each step.  Returns the comprehensive dict."""
-    import torch
-    from . import components, mass_effect, nifti, normal_structures, quality
     out = Path(output_dir)
     out.mkdir(parents=True, exist_ok=True)
-    case_id, paths = case_id_and_paths(input_folder)
-    images = {k: nifti.load(p) for k, p in paths.items()}
-    seg_img = nifti.load(segmentation_path)
-    seg = np.ascontiguousarray(np.round(seg_img.data).astype(np.uint8))
-    dev = [torch.from_numpy(np.ascontiguousarray(images[k].data.astype(np.float32))).cuda() for k in ('t1', 't1ce', 't2', 'flair')]
-    ctx = CaseContext(torch.from_numpy(seg).cuda(), *dev)
-
-    def voxel_info(z):  # as the step commands write it
-        return {'dimensions_mm': [float(v) for v in z], 'volume_mm3': float(np.prod(z)), 'volume_cm3': float(np.prod(z) / 1000)}
-    zooms = [float(v) for v in images['t1'].zooms]
-    zooms_step2 = [np.float32(v) for v in images['t1'].zooms[:3]]        # mass_effect.analyze: header.get_zooms(), utils.py:119
-    zooms_step3 = [float(v) for v in seg_img.zooms]                      # multiplicity.analyze: the segmentation's own header
-    heads = {STEP_KEYS[0]: {'case_id': case_id, 'step': 'Step 1 - Sequence-specific findings', 'voxel_info': voxel_info(zooms)},
-             STEP_KEYS[1]: {'case_id': case_id, 'step': mass_effect.STEP, 'voxel_info': voxel_info(zooms_step2)},
-             STEP_KEYS[2]: {'case_id': Path(input_folder).name, 'step': 'Step 3 - Lesion multiplicity and distribution', 'voxel_info': voxel_info(zooms_step3)},
-             STEP_KEYS[3]: {'case_id': case_id, 'step': 'Step 4 - Tumor morphology and margins', 'voxel_info': voxel_info(zooms)},
-             STEP_KEYS[4]: {'case_id': case_id, 'step': quality.STEP},
-             STEP_KEYS[5]: {'case_id': case_id, 'step': normal_structures.STEP}}
-    tails = {STEP_KEYS[0]: {'sequences_analyzed': ['T1', 'T1ce', 'T2', 'FLAIR'], 'diffusion_available': False,
-                            'diffusion_note': 'DWI/ADC not available in standard BraTS dataset'}}  # sequence_findings.analyze
-    all_results = {'case_id': case_id, 'analysis_timestamp': datetime.now().isoformat(), 'input_folder': str(input_folder),
+    case = load_case(input_folder, segmentation_path)
+    ctx = CaseContext(to_device(case.labels, np.uint8), *[to_device(case.images[k].data, np.float32) for k in MODALITIES])
+    all_results = {'case_id': case.case_id, 'analysis_timestamp': datetime.now().isoformat(), 'input_folder': str(input_folder),
                    'segmentation_path': str(segmentation_path)}          # run_all.py:453-464
-    steps = dict(_steps(ctx, zooms, zooms_step2, rng, distance))
-    steps[STEP_KEYS[2]] = lambda: components.lesion_multiplicity(ctx.seg, zooms_step3, ctx=ctx)
-    for key in STEP_KEYS:
-        res = dict(heads[key])
-        res.update(steps[key]())
-        res.update(tails.get(key, {}))
-        with open(out / f"{key}.json", 'w') as f:
-            json.dump(res, f, indent=2)
-        all_results[key] = res
+    for spec in SPECS:
+        zooms = step_zooms(spec, case.images['t1'].zooms, case.segmentation.zooms)
+        res = document(spec, case.case_id, input_folder, zooms, _call(spec, ctx, zooms, rng, distance))
+        write_json(out / f"{spec.key}.json", res)
+        all_results[spec.key] = res
         if report:
-            report(key, res)
-    with open(out / "comprehensive_analysis.json", 'w') as f:
-        json.dump(all_results, f, indent=2)
+            report(spec.key, res)
+    write_json(out / "comprehensive_analysis.json", all_results)
     return all_results
 
 
 def main(argv=None):
-    from .mass_effect import DISTANCES
     ap = argparse.ArgumentParser(description='All six feature-extraction steps of one case (MI355X)')
     ap.add_argument('--input', required=True, help='Input folder containing MRI sequences')
     ap.add_argument('--segmentation', required=True, help='Path to segmentation mask (NIfTI)')
     ap.add_argument('--output', required=True, help='Output folder for results')
-    ap.add_argument('--distance', default='sampled', choices=DISTANCES, help='tumour-to-CSF distance of step 2: between sampled voxels as the reference, or exact')
+    ap.add_argument('--distance', default='sampled', choices=mass_effect.DISTANCES, help='tumour-to-CSF distance of step 2: between sampled voxels as the reference, or exact')
     ap.add_argument('--seed', type=int, default=None, help='seed of the generator the sampled distance draws from (default: unseeded)')
     args = ap.parse_args(argv)
     case_id = case_id_and_paths(args.input)[0]

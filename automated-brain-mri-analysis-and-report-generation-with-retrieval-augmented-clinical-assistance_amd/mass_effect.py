@@ -21,18 +21,14 @@ As a command (the reference's arguments, :755-768, and two of its own):
 """
 from __future__ import annotations
 
-import argparse
-import ctypes as C
-import json
 import sys
-from pathlib import Path
 
 import numpy as np
 
-from . import _lib
-from .morphology import (_check_volume, _mean_std, _stream, binary_dilation, case_id_and_paths, distance_transform_edt_sq, flag_from_flags,
-                         flag_from_labels, masked_moments)
+from .case_io import StepSpec, run_step, step_main
 from .percentile import masked_percentiles
+from .volume_ops import (axis_counts, binary_dilation, box_counts, check_volume, distance_transform_edt_sq, flag_from_flags, flag_from_labels, masked_min,
+                         masked_moments, mean_std, min_pair_dist2, select_ranked)
 
 #: region bits of the flag map ``mass_effect_stats`` builds (one uint8 per voxel)
 BRAIN, TUMOUR, CSF, DILATED, PERITUMORAL, DISTANT = range(6)
@@ -42,80 +38,6 @@ SHIFT_NOISE_THRESHOLD_MM = 1.0                 # :29
 DILATIONS, SAMPLES = 10, 1000                  # :373, :214 / :223
 AXIS_MAX, MAX_BOXES, MAX_POINTS = 4096, 16, 65536   # MI355_AXIS_COUNTS_MAX, MI355_MAX_BOXES, MI355_MAX_POINTS
 DISTANCES = ('sampled', 'exact')
-_I64P = C.POINTER(C.c_int64)
-
-
-# ---- thin wrappers over the entry points ------------------------------------------------------------------------------
-def _flags(t, what, dim=None):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or (dim is not None and t.dim() != dim):
-        raise ValueError(f"{what}: CUDA uint8 {'[d0, d1, d2] ' if dim == 3 else ''}tensor expected")
-    return t.contiguous()
-
-
-def axis_counts(flags, require=0, forbid=0):
-    """flags: CUDA uint8 [d0, d1, d2]; a voxel is selected when its byte has every bit of ``require`` and no bit of ``forbid``.
-    Returns three int64 arrays: the selected voxels at each index of axis 0, 1, 2 (``sel.sum(axis=(1, 2))``, ...).  No axis may
-    be longer than 4096."""
-    flags = _flags(flags, "axis_counts", 3)
-    d0, d1, d2 = flags.shape
-    out = np.zeros(d0 + d1 + d2, dtype=np.int64)
-    _lib.check(_lib.load().mi355_axis_counts(flags.data_ptr(), int(require), int(forbid), d0, d1, d2, out.ctypes.data_as(_I64P), _stream(flags)),
-               "mi355_axis_counts")
-    return out[:d0], out[d0:d0 + d1], out[d0 + d1:]
-
-
-def box_counts(flags, boxes, require=0, forbid=0):
-    """The selected voxels inside each of 1..16 boxes ``(lo0, hi0, lo1, hi1, lo2, hi2)``, half-open, inside the volume; boxes may
-    overlap, an empty one counts 0.  int64 [len(boxes)]."""
-    flags = _flags(flags, "box_counts", 3)
-    b = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 6))
-    out = np.zeros(len(b), dtype=np.int64)
-    _lib.check(_lib.load().mi355_box_counts(flags.data_ptr(), int(require), int(forbid), flags.shape[0], flags.shape[1], flags.shape[2],
-                                            b.ctypes.data_as(_lib.c_int32_p), len(b), out.ctypes.data_as(_I64P), _stream(flags)), "mi355_box_counts")
-    return out
-
-
-def select_ranked(flags, ranks, require=0, forbid=0):
-    """``np.flatnonzero(selected)[ranks]`` as a CUDA int64 tensor, and the number of selected voxels: the linear C-order indices
-    of the selected voxels of the given 0-based ranks (1..65 536 of them, any order, repeats allowed).  A rank outside the
-    selection raises and writes nothing."""
-    import torch
-    flags = _flags(flags, "select_ranked")
-    r = np.ascontiguousarray(np.asarray(ranks, dtype=np.int64).reshape(-1))
-    index = torch.empty(max(len(r), 1), dtype=torch.int64, device=flags.device)
-    count = C.c_int64(0)
-    _lib.check(_lib.load().mi355_select_ranked(flags.data_ptr(), int(require), int(forbid), flags.numel(), r.ctypes.data_as(_I64P), len(r), index.data_ptr(),
-                                               C.byref(count), _stream(flags)), "mi355_select_ranked")
-    return index[:len(r)], int(count.value)
-
-
-def min_pair_dist2(a, b, shape):
-    """a, b: CUDA int64 lists (1..65 536 entries each) of linear C-order indices into a volume of ``shape`` -> the smallest
-    squared distance, in voxel units, between a voxel of a and a voxel of b (an int)."""
-    import torch
-    for t in (a, b):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or not t.is_cuda or t.dim() != 1:
-            raise ValueError("min_pair_dist2: CUDA int64 [k] tensors expected")
-    a, b = a.contiguous(), b.contiguous()
-    out = C.c_int64(0)
-    _lib.check(_lib.load().mi355_min_pair_dist2(a.data_ptr(), a.numel(), b.data_ptr(), b.numel(), int(shape[0]), int(shape[1]), int(shape[2]), C.byref(out),
-                                                _stream(a)), "mi355_min_pair_dist2")
-    return int(out.value)
-
-
-def masked_min(values, flags, require=0, forbid=0):
-    """values: CUDA int32 tensor, flags: CUDA uint8 tensor of its shape -> (the minimum over the selected voxels or None, their
-    number)."""
-    import torch
-    flags = _flags(flags, "masked_min")
-    if not isinstance(values, torch.Tensor) or values.dtype != torch.int32 or not values.is_cuda or values.shape != flags.shape:
-        raise ValueError("masked_min: CUDA int32 values of the shape of the flags expected")
-    values = values.contiguous()
-    lowest, count = C.c_int32(0), C.c_int64(0)
-    _lib.check(_lib.load().mi355_masked_min_i32(values.data_ptr(), flags.data_ptr(), int(require), int(forbid), flags.numel(), C.byref(lowest), C.byref(count),
-                                                _stream(flags)), "mi355_masked_min_i32")
-    return (int(lowest.value) if count.value else None), int(count.value)
 
 
 # ---- step2_mass_effect.py:32-602 on the integers and sums -------------------------------------------------------------
@@ -294,7 +216,7 @@ def _sulcal_effacement(n_tumour, peritumoral, distant):  # analyze_sulcal_efface
         return {'effacement_detected': False, 'severity': 'Could not analyze', 'details': 'Could not analyze peritumoral region'}
     if distant[0] == 0:
         return {'effacement_detected': True, 'severity': 'Severe', 'details': 'Tumor occupies majority of brain volume'}
-    peritumoral_std, distant_std = _mean_std(peritumoral)[1], _mean_std(distant)[1]
+    peritumoral_std, distant_std = mean_std(peritumoral)[1], mean_std(distant)[1]
     variance_ratio = peritumoral_std / distant_std if distant_std > 0 else 1.0
     if variance_ratio < 0.6:
         effacement, severity = True, 'Moderate to Severe'
@@ -474,8 +396,8 @@ def mass_effect(seg, t1, voxel_dims, rng=None, distance='sampled', ctx=None):
             raise ValueError(f"mass_effect: distance {distance!r} (one of {', '.join(DISTANCES)})")
         seg, (t1,) = ctx.volumes(seg, (t1,), "mass_effect")
         return mass_effect_from_stats(mass_effect_stats(seg, t1, rng, distance, ctx), voxel_dims)
-    seg = _check_volume(seg, torch.uint8, "mass_effect")
-    t1 = _check_volume(t1, torch.float32, "mass_effect")
+    seg = check_volume(seg, torch.uint8, "mass_effect")
+    t1 = check_volume(t1, torch.float32, "mass_effect")
     if t1.shape != seg.shape:
         raise ValueError("mass_effect: the volume and the label map differ in shape")
     if distance not in DISTANCES:
@@ -486,36 +408,29 @@ def mass_effect(seg, t1, voxel_dims, rng=None, distance='sampled', ctx=None):
 
 
 # ---- the command ------------------------------------------------------------------------------------------------------
+def _summary(res):
+    loc, vc = res['anatomical_location'], res['ventricular_compression']
+    return (f"{loc['laterality']}, {loc['primary_lobe']}; midline shift {res['midline_shift']['severity']}; ventricles {vc['severity']}; "
+            f"sulci {res['sulcal_effacement']['severity']}; herniation risk {res['herniation_risk']['risk_level']}")
+
+
+STEP_SPEC = StepSpec(key='step2_mass_effect', title=STEP, description='Step 2: mass effect metrics (MI355X)', modalities=('t1',), zooms='t1_float32',
+                     call=lambda seg, chans, zooms, ctx=None, rng=None, distance='sampled': mass_effect(seg, chans['t1'], zooms, rng, distance, ctx=ctx),
+                     summary=_summary, step_args=('rng', 'distance'))
+
+
+def _distance_args(ap):
+    ap.add_argument('--distance', default='sampled', choices=DISTANCES, help='tumour-to-CSF distance: between sampled voxels as the reference, or exact')
+    ap.add_argument('--seed', type=int, default=None, help='seed of the generator the sampled distance draws from (default: unseeded)')
+    return lambda args: {'rng': None if args.seed is None else np.random.RandomState(args.seed), 'distance': args.distance}
+
+
 def analyze(input_folder, segmentation_path, output_path=None, rng=None, distance='sampled'):
-    import torch
-    from . import nifti
-    case_id, paths = case_id_and_paths(input_folder)
-    t1 = nifti.load(paths['t1'])
-    seg = np.ascontiguousarray(np.round(nifti.load(segmentation_path).data).astype(np.uint8))  # :674-675
-    zooms = [np.float32(v) for v in t1.zooms[:3]]  # header.get_zooms(), utils.py:119
-    res = {'case_id': case_id, 'step': STEP,
-           'voxel_info': {'dimensions_mm': [float(v) for v in zooms], 'volume_mm3': float(np.prod(zooms)), 'volume_cm3': float(np.prod(zooms) / 1000)}}
-    res.update(mass_effect(torch.from_numpy(seg).cuda(), torch.from_numpy(np.ascontiguousarray(t1.data.astype(np.float32))).cuda(), zooms, rng, distance))
-    if output_path:
-        Path(output_path).parent.mkdir(parents=True, exist_ok=True)
-        with open(output_path, 'w') as f:
-            json.dump(res, f, indent=2)
-    return res
+    return run_step(STEP_SPEC, input_folder, segmentation_path, output_path, rng=rng, distance=distance)
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description='Step 2: mass effect metrics (MI355X)')
-    ap.add_argument('--input', required=True, help='Input folder containing MRI sequences')
-    ap.add_argument('--segmentation', required=True, help='Path to segmentation mask (NIfTI)')
-    ap.add_argument('--output', default=None, help='Output path for JSON results')
-    ap.add_argument('--distance', default='sampled', choices=DISTANCES, help='tumour-to-CSF distance: between sampled voxels as the reference, or exact')
-    ap.add_argument('--seed', type=int, default=None, help='seed of the generator the sampled distance draws from (default: unseeded)')
-    args = ap.parse_args(argv)
-    res = analyze(args.input, args.segmentation, args.output, None if args.seed is None else np.random.RandomState(args.seed), args.distance)
-    loc, vc = res['anatomical_location'], res['ventricular_compression']
-    print(f"{res['case_id']}: {loc['laterality']}, {loc['primary_lobe']}; midline shift {res['midline_shift']['severity']}; ventricles {vc['severity']}; "
-          f"sulci {res['sulcal_effacement']['severity']}; herniation risk {res['herniation_risk']['risk_level']}")
-    return 0
+    return step_main(STEP_SPEC, argv, _distance_args)
 
 
 if __name__ == '__main__':

@@ -15,140 +15,20 @@ As a command (the reference's arguments, :690-703):
 """
 from __future__ import annotations
 
-import argparse
-import ctypes as C
-import json
 import sys
 from fractions import Fraction
-from pathlib import Path
 
 import numpy as np
 
-from . import _lib
+from .case_io import FLAIR, T1, T1CE, T2, StepSpec, run_step, step_main
+from .volume_ops import (NBITS, binary_dilation, binary_erosion, check_volume, distance_transform_edt_sq, flag_from_flags, flag_from_labels, masked_moments,
+                         mean_std, second_moments, surface_gradient_stats)
 
 #: region bits of the flag map ``tumor_morphology`` builds (one uint8 per voxel)
 WT, BAND, INNER, OUTER, NCR, CYSTIC = 0, 1, 2, 3, 4, 5
-#: channels of the stacked volumes
-T1, T1CE, T2, FLAIR = 0, 1, 2, 3
-NBITS = 8
-#: longest axis-1 / axis-2 line of ``distance_transform_edt_sq`` (one line per 64 KiB LDS tile)
-EDT_MAX_LINE = 1024
-
-
-def _check_volume(t, dtype, what):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or t.dim() != 3:
-        raise ValueError(f"{what}: CUDA {dtype} [d0, d1, d2] tensor expected")
-    return t.contiguous()
-
-
-def _stream(t):
-    import torch
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-# ---- thin wrappers over the entry points ------------------------------------------------------------------------------
-def _morph(mask, iterations, dilate, what):
-    import torch
-    mask = _check_volume(mask, torch.uint8, what)
-    out = torch.empty_like(mask)
-    _lib.check(_lib.load().mi355_binary_morphology(mask.data_ptr(), mask.shape[0], mask.shape[1], mask.shape[2], int(dilate), int(iterations),
-                                                   out.data_ptr(), _stream(mask)), "mi355_binary_morphology")
-    return out
-
-
-def binary_erosion(mask, iterations=1):
-    """mask: CUDA uint8 [d0, d1, d2], foreground = nonzero -> uint8 0 / 1 map, bit-equal to
-    ``scipy.ndimage.binary_erosion(mask, iterations=iterations)`` (6-neighbour cross, border_value 0); iterations >= 1."""
-    return _morph(mask, iterations, 0, "binary_erosion")
-
-
-def binary_dilation(mask, iterations=1):
-    """As ``binary_erosion`` for ``scipy.ndimage.binary_dilation``."""
-    return _morph(mask, iterations, 1, "binary_dilation")
-
-
-def distance_transform_edt_sq(mask):
-    """mask: CUDA uint8 [d0, d1, d2] -> int32 map of the squared distance, in voxels, to the nearest background voxel
-    (0 on the background): ``rint(scipy.ndimage.distance_transform_edt(mask) ** 2)`` bit for bit.  Refused: a mask without
-    background, a squared diagonal beyond int32, more than 1024 entries along axis 1 or 2."""
-    import torch
-    mask = _check_volume(mask, torch.uint8, "distance_transform_edt_sq")
-    out = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
-    _lib.check(_lib.load().mi355_edt_squared(mask.data_ptr(), mask.shape[0], mask.shape[1], mask.shape[2], out.data_ptr(), _stream(mask)),
-               "mi355_edt_squared")
-    return out
-
-
-def surface_gradient_stats(d2_in, d2_out, surface, select=255):
-    """d2_in, d2_out: the int32 maps of ``distance_transform_edt_sq`` of a mask and of its complement; surface: CUDA uint8 map,
-    a voxel counts where ``surface & select`` is nonzero.  Returns (n, mean, std) of ``|grad(sqrt(d2_in) - sqrt(d2_out))|``
-    over those voxels, the gradient being ``np.gradient``'s, the std the population one; fp64."""
-    import torch
-    d2_in = _check_volume(d2_in, torch.int32, "surface_gradient_stats")
-    d2_out = _check_volume(d2_out, torch.int32, "surface_gradient_stats")
-    surface = _check_volume(surface, torch.uint8, "surface_gradient_stats")
-    if not (d2_in.shape == d2_out.shape == surface.shape):
-        raise ValueError("surface_gradient_stats: the three maps differ in shape")
-    out = (C.c_double * 3)()
-    _lib.check(_lib.load().mi355_surface_gradient_stats(d2_in.data_ptr(), d2_out.data_ptr(), surface.data_ptr(), int(select), surface.shape[0],
-                                                        surface.shape[1], surface.shape[2], out, _stream(surface)), "mi355_surface_gradient_stats")
-    return int(out[0]), float(out[1]), float(out[2])
-
-
-def second_moments(mask):
-    """mask: CUDA uint8 [d0, d1, d2] -> int64 [10]: n, the sums of the coordinates c0 c1 c2, of their squares, and of c0 c1,
-    c0 c2, c1 c2 over the foreground.  Exact."""
-    import torch
-    mask = _check_volume(mask, torch.uint8, "second_moments")
-    out = np.zeros(10, dtype=np.int64)
-    _lib.check(_lib.load().mi355_mask_second_moments(mask.data_ptr(), mask.shape[0], mask.shape[1], mask.shape[2],
-                                                     out.ctypes.data_as(C.POINTER(C.c_int64)), _stream(mask)), "mi355_mask_second_moments")
-    return out
-
-
-def masked_moments(vols, flags):
-    """vols: CUDA float32 [C, ...], flags: CUDA uint8 of the shape of one channel, bit b = region b.  Returns float64
-    [8, C, 3]: per (bit, channel) the number of voxels with the bit, the sum and the sum of squares of the channel over them,
-    accumulated in fp64 in a fixed order."""
-    import torch
-    if not isinstance(vols, torch.Tensor) or vols.dtype != torch.float32 or not vols.is_cuda or vols.dim() < 2:
-        raise ValueError("masked_moments: CUDA float32 [C, ...] tensor expected")
-    if not isinstance(flags, torch.Tensor) or flags.dtype != torch.uint8 or not flags.is_cuda or flags.shape != vols.shape[1:]:
-        raise ValueError("masked_moments: CUDA uint8 flags of the shape of one channel expected")
-    vols, flags = vols.contiguous(), flags.contiguous()
-    out = np.zeros((NBITS, vols.shape[0], 3), dtype=np.float64)
-    _lib.check(_lib.load().mi355_masked_moments(vols.data_ptr(), vols.shape[0], flags.data_ptr(), flags.numel(),
-                                                out.ctypes.data_as(C.POINTER(C.c_double)), _stream(flags)), "mi355_masked_moments")
-    return out
-
-
-def flag_from_labels(labels, values, bit, flags):
-    """Bit ``bit`` of ``flags`` (in place) = ``labels`` takes one of ``values``; with a 0 / 1 mask and ``(1,)`` a mask becomes a bit."""
-    table = np.zeros(256, dtype=np.uint8)
-    table[list(values)] = 1
-    _lib.check(_lib.load().mi355_flag_from_labels(labels.data_ptr(), table.ctypes.data_as(C.POINTER(C.c_uint8)), int(bit), flags.data_ptr(),
-                                                  flags.numel(), _stream(flags)), "mi355_flag_from_labels")
-    return flags
-
-
-def flag_from_flags(flags, bit, require=0, forbid=0, x=None, lo=-np.inf, hi=np.inf):
-    """Bit ``bit`` of ``flags`` (in place) = all bits of the mask ``require`` set, none of ``forbid``, and ``lo < x < hi`` (fp64
-    comparison of the float32 volume ``x``, when given)."""
-    _lib.check(_lib.load().mi355_flag_from_flags(flags.data_ptr(), int(bit), int(require), int(forbid), None if x is None else x.data_ptr(),
-                                                 float(lo), float(hi), flags.numel(), _stream(flags)), "mi355_flag_from_flags")
-    return flags
 
 
 # ---- step4_morphology.py:33-541 on the integers and sums --------------------------------------------------------------
-def _mean_std(row):
-    """(mean, population std) from (n, sum, sum of squares): the difference of the two squares is taken exactly"""
-    n = int(row[0])
-    s1, s2 = Fraction(float(row[1])), Fraction(float(row[2]))
-    var = s2 / n - (s1 / n) ** 2
-    return np.float64(float(s1 / n)), np.float64(np.sqrt(float(var)) if var > 0 else 0.0)
-
-
 def _shape_descriptors(n_wt, n_surface, moments, voxel_dims):  # calculate_shape_descriptors, :483-541
     if n_wt == 0:
         return {'volume_cm3': 0, 'surface_area_mm2': 0, 'sphericity': 0, 'compactness': 0, 'elongation': 1.0, 'principal_axes_mm': [0, 0, 0]}
@@ -206,12 +86,12 @@ def _margin_definition(region):  # analyze_margin_definition, :208-290; region[b
         return {'margin_sharpness': 0, 'classification': 'No tumor', 'description': 'No tumor detected'}
     if region[BAND][0] == 0:
         return {'margin_sharpness': 0.5, 'classification': 'Could not assess', 'description': 'Insufficient peritumoral tissue for analysis'}
-    tumor_mean, _ = _mean_std(region[WT])
-    peritumoral_mean, _ = _mean_std(region[BAND])
+    tumor_mean, _ = mean_std(region[WT])
+    peritumoral_mean, _ = mean_std(region[BAND])
     contrast = abs(tumor_mean - peritumoral_mean) / peritumoral_mean if peritumoral_mean > 0 else 0
     if region[INNER][0] > 0 and region[OUTER][0] > 0:
-        inner_mean, inner_std = _mean_std(region[INNER])
-        outer_mean, outer_std = _mean_std(region[OUTER])
+        inner_mean, inner_std = mean_std(region[INNER])
+        outer_mean, outer_std = mean_std(region[OUTER])
         border_gradient_normalized = abs(inner_mean - outer_mean) / (inner_std + outer_std + 1e-6)
     else:
         border_gradient_normalized = 0
@@ -235,8 +115,8 @@ def _cystic_vs_solid(n_wt, region_moments, voxel_dims):  # analyze_cystic_vs_sol
     n_ncr = int(region_moments[NCR][T2][0])
     if n_ncr > 0:
         cystic_fraction_in_ncr = np.int64(region_moments[CYSTIC][T2][0]) / n_ncr
-        t2_mean, t2_std = _mean_std(region_moments[NCR][T2])
-        flair_mean, _ = _mean_std(region_moments[NCR][FLAIR])
+        t2_mean, t2_std = mean_std(region_moments[NCR][T2])
+        flair_mean, _ = mean_std(region_moments[NCR][FLAIR])
         t2_cv = t2_std / t2_mean if t2_mean > 0 else 0
         flair_t2_ratio = flair_mean / t2_mean if t2_mean > 0 else 1
     else:
@@ -394,8 +274,8 @@ def tumor_morphology(seg, t1, t1ce, t2, flair, voxel_dims, ctx=None):
     if ctx is not None:
         seg, chans = ctx.volumes(seg, (t1, t1ce, t2, flair), "tumor_morphology")
     else:
-        seg = _check_volume(seg, torch.uint8, "tumor_morphology")
-        chans = [_check_volume(v, torch.float32, "tumor_morphology") for v in (t1, t1ce, t2, flair)]
+        seg = check_volume(seg, torch.uint8, "tumor_morphology")
+        chans = [check_volume(v, torch.float32, "tumor_morphology") for v in (t1, t1ce, t2, flair)]
         if any(v.shape != seg.shape for v in chans):
             raise ValueError("tumor_morphology: the volumes and the label map differ in shape")
     flags = region_flags(seg, chans[T1], chans[T2], chans[FLAIR], ctx)
@@ -409,49 +289,22 @@ def tumor_morphology(seg, t1, t1ce, t2, flair, voxel_dims, ctx=None):
 
 
 # ---- the command ------------------------------------------------------------------------------------------------------
-def case_id_and_paths(input_folder):
-    """utils.py:71-114: the case id and the T1, T1ce, T2 and FLAIR files of a case folder, in either naming scheme."""
-    folder = Path(input_folder)
-    files = sorted(folder.glob("*_t1.nii.gz"))
-    if files:
-        case_id = files[0].name.split('_t1')[0]
-    else:
-        files = sorted(folder.glob("*-t1n.nii.gz"))
-        case_id = files[0].name.split('-t1')[0] if files else folder.name
-    for names in ({'t1': '_t1', 't1ce': '_t1ce', 't2': '_t2', 'flair': '_flair'}, {'t1': '-t1n', 't1ce': '-t1c', 't2': '-t2w', 'flair': '-t2f'}):
-        if (folder / f"{case_id}{names['t1']}.nii.gz").exists():
-            return case_id, {k: folder / f"{case_id}{v}.nii.gz" for k, v in names.items()}
-    raise ValueError(f"Could not find MRI files in {folder}")
+def _summary(res):
+    return (f"{res['shape_descriptors'].get('shape_classification', 'No tumor')}; {res['border_regularity']['classification']}; "
+            f"{res['margin_definition']['classification']}; {res['necrosis_pattern']['pattern']}; {res['cystic_solid_classification']['classification']}")
+
+
+STEP_SPEC = StepSpec(key='step4_morphology', title='Step 4 - Tumor morphology and margins', description='Step 4: tumor morphology and margins (MI355X)',
+                     call=lambda seg, chans, zooms, ctx=None: tumor_morphology(seg, chans['t1'], chans['t1ce'], chans['t2'], chans['flair'], zooms, ctx=ctx),
+                     summary=_summary)
 
 
 def analyze(input_folder, segmentation_path, output_path=None):
-    import torch
-    from . import nifti
-    case_id, paths = case_id_and_paths(input_folder)
-    images = {k: nifti.load(p) for k, p in paths.items()}
-    seg = np.ascontiguousarray(np.round(nifti.load(segmentation_path).data).astype(np.uint8))  # (x, y, z) as nibabel hands it over, :619-620
-    zooms = [float(v) for v in images['t1'].zooms]
-    dev = [torch.from_numpy(np.ascontiguousarray(images[k].data.astype(np.float32))).cuda() for k in ('t1', 't1ce', 't2', 'flair')]
-    res = {'case_id': case_id, 'step': 'Step 4 - Tumor morphology and margins',
-           'voxel_info': {'dimensions_mm': zooms, 'volume_mm3': float(np.prod(zooms)), 'volume_cm3': float(np.prod(zooms) / 1000)}}
-    res.update(tumor_morphology(torch.from_numpy(seg).cuda(), *dev, zooms))
-    if output_path:
-        Path(output_path).parent.mkdir(parents=True, exist_ok=True)
-        with open(output_path, 'w') as f:
-            json.dump(res, f, indent=2)
-    return res
+    return run_step(STEP_SPEC, input_folder, segmentation_path, output_path)
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description='Step 4: tumor morphology and margins (MI355X)')
-    ap.add_argument('--input', required=True, help='Input folder containing MRI sequences')
-    ap.add_argument('--segmentation', required=True, help='Path to segmentation mask (NIfTI)')
-    ap.add_argument('--output', default=None, help='Output path for JSON results')
-    args = ap.parse_args(argv)
-    res = analyze(args.input, args.segmentation, args.output)
-    print(f"{res['case_id']}: {res['shape_descriptors'].get('shape_classification', 'No tumor')}; {res['border_regularity']['classification']}; "
-          f"{res['margin_definition']['classification']}; {res['necrosis_pattern']['pattern']}; {res['cystic_solid_classification']['classification']}")
-    return 0
+    return step_main(STEP_SPEC, argv)
 
 
 if __name__ == '__main__':

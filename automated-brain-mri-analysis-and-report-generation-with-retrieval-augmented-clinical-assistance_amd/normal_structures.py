@@ -26,19 +26,14 @@ As a command (the reference's arguments, :506-519):
 """
 from __future__ import annotations
 
-import argparse
-import ctypes as C
-import json
 import sys
-from pathlib import Path
 
 import numpy as np
 
-from . import _lib
-from .mass_effect import axis_counts
-from .morphology import (_check_volume, _stream, binary_dilation, binary_erosion, case_id_and_paths, distance_transform_edt_sq, flag_from_flags,
-                         flag_from_labels, masked_moments)
+from .case_io import StepSpec, run_step, step_main
 from .percentile import masked_percentiles, percentile_from_order_stats
+from .volume_ops import (axis_counts, binary_dilation, binary_erosion, check_volume, cityblock_distance, column_count_max, distance_transform_edt_sq,
+                         flag_from_box, flag_from_flags, flag_from_i32, flag_from_labels, masked_moments, masked_order_stats_i32)
 
 #: region bits of the flag map ``normal_structures_stats`` builds (one uint8 per voxel).  VENTRICLE holds the CSF predicate until
 #: the kept components replace it; the upper four bits are reduced once (T1, FLAIR) and then reused (T1, T1ce)
@@ -49,88 +44,6 @@ STEP = 'Step 6 - Normal structures assessment'
 MIN_VENTRICLE_VOXELS = 1000                    # :70-71: "1 cm3", in voxels whatever the spacing
 CENTRAL_FRACTION = 0.3                         # :81
 OBSTRUCTION_STEPS, PERI_STEPS = 5, 10          # :152, :215 / :345
-CITYBLOCK_FAR = 1 << 30                        # MI355_CITYBLOCK_FAR
-_I32_MAX = 2 ** 31 - 1
-
-
-# ---- thin wrappers over the entry points ------------------------------------------------------------------------------
-def cityblock_distance(mask, to_foreground=True):
-    """mask: CUDA uint8 [d0, d1, d2], foreground = nonzero -> int32 map of the exact city-block (taxicab) distance.
-    ``to_foreground``: to the nearest foreground voxel (0 on the mask, ``CITYBLOCK_FAR`` = 2^30 everywhere when the mask is empty);
-    ``dist <= n`` is ``scipy.ndimage.binary_dilation(mask, iterations=n)``.  Otherwise: to the nearest background voxel, every
-    position outside the volume being background; ``dist > n`` is ``scipy.ndimage.binary_erosion(mask, iterations=n)``."""
-    import torch
-    mask = _check_volume(mask, torch.uint8, "cityblock_distance")
-    out = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
-    _lib.check(_lib.load().mi355_cityblock_distance(mask.data_ptr(), mask.shape[0], mask.shape[1], mask.shape[2], int(bool(to_foreground)), out.data_ptr(),
-                                                    _stream(mask)), "mi355_cityblock_distance")
-    return out
-
-
-def _check_values(values, flags, what):
-    import torch
-    if not isinstance(flags, torch.Tensor) or flags.dtype != torch.uint8 or not flags.is_cuda:
-        raise ValueError(f"{what}: CUDA uint8 flags expected")
-    if not isinstance(values, torch.Tensor) or values.dtype != torch.int32 or not values.is_cuda or values.shape != flags.shape:
-        raise ValueError(f"{what}: CUDA int32 values of the shape of the flags expected")
-    if not values.is_contiguous() or not flags.is_contiguous():
-        raise ValueError(f"{what}: contiguous tensors expected")
-
-
-def flag_from_i32(flags, bit, values, lo=0, hi=_I32_MAX, require=0, forbid=0):
-    """Bit ``bit`` of ``flags`` (in place) = all bits of the mask ``require`` set, none of ``forbid``, and ``lo <= values <= hi``
-    (int32 map of the shape of the flags; bounds beyond int32 are clamped, an empty range clears the bit)."""
-    _check_values(values, flags, "flag_from_i32")
-    lo, hi = max(int(lo), -_I32_MAX - 1), min(int(hi), _I32_MAX)
-    if lo > hi:
-        lo, hi = 1, 0
-    _lib.check(_lib.load().mi355_flag_from_i32(flags.data_ptr(), int(bit), int(require), int(forbid), values.data_ptr(), lo, hi, flags.numel(), _stream(flags)),
-               "mi355_flag_from_i32")
-    return flags
-
-
-def flag_from_box(flags, bit, box, require=0, forbid=0):
-    """Bit ``bit`` of ``flags`` [d0, d1, d2] (in place) = all bits of ``require`` set, none of ``forbid``, and the voxel inside the
-    half-open index box ``(lo0, hi0, lo1, hi1, lo2, hi2)``, clipped to the volume."""
-    import torch
-    if not flags.is_contiguous():
-        raise ValueError("flag_from_box: contiguous flags expected")
-    _check_volume(flags, torch.uint8, "flag_from_box")
-    b = np.ascontiguousarray(np.clip(np.asarray(box, dtype=np.int64).reshape(6), -_I32_MAX, _I32_MAX).astype(np.int32))
-    _lib.check(_lib.load().mi355_flag_from_box(flags.data_ptr(), int(bit), int(require), int(forbid), flags.shape[0], flags.shape[1], flags.shape[2],
-                                               b.ctypes.data_as(_lib.c_int32_p), _stream(flags)), "mi355_flag_from_box")
-    return flags
-
-
-def masked_order_stats_i32(values, qs, flags=None, require=0, forbid=0):
-    """values: CUDA int32 tensor with nothing below 0; flags: CUDA uint8 tensor of its shape or None.  Returns ``(count, below,
-    above)``: the number of selected voxels and per percentile the two int32 order statistics that bracket it (ranks ``floor(v)``
-    and ``min(floor(v) + 1, count - 1)``, ``v = (count - 1) * q / 100``); zeros when nothing is selected."""
-    import torch
-    if not isinstance(values, torch.Tensor) or values.dtype != torch.int32 or not values.is_cuda:
-        raise ValueError("masked_order_stats_i32: CUDA int32 tensor expected")
-    if flags is not None and (not isinstance(flags, torch.Tensor) or flags.dtype != torch.uint8 or not flags.is_cuda or flags.shape != values.shape):
-        raise ValueError("masked_order_stats_i32: CUDA uint8 flags of the shape of the values expected")
-    values = values.contiguous()
-    flags = None if flags is None else flags.contiguous()
-    q = np.ascontiguousarray(np.atleast_1d(np.asarray(qs, dtype=np.float64)))
-    count = C.c_int64(0)
-    below, above = np.zeros(q.size, dtype=np.int32), np.zeros(q.size, dtype=np.int32)
-    _lib.check(_lib.load().mi355_masked_order_stats_i32(values.data_ptr(), values.numel(), None if flags is None else flags.data_ptr(), int(require), int(forbid),
-                                                        q.ctypes.data_as(C.POINTER(C.c_double)), q.size, C.byref(count), below.ctypes.data_as(_lib.c_int32_p),
-                                                        above.ctypes.data_as(_lib.c_int32_p), _stream(values)), "mi355_masked_order_stats_i32")
-    return int(count.value), below, above
-
-
-def column_count_max(flags, i1_from, require=0, forbid=0):
-    """``np.max(np.sum(selected[:, i1_from:, :], axis=0))`` of the voxels of ``flags`` [d0, d1, d2] with every bit of ``require`` and
-    no bit of ``forbid``; 0 when that slab selects nothing."""
-    import torch
-    flags = _check_volume(flags, torch.uint8, "column_count_max")
-    out = C.c_int64(0)
-    _lib.check(_lib.load().mi355_column_count_max(flags.data_ptr(), int(require), int(forbid), flags.shape[0], flags.shape[1], flags.shape[2], int(i1_from),
-                                                  C.byref(out), _stream(flags)), "mi355_column_count_max")
-    return int(out.value)
 
 
 # ---- pure host helpers ------------------------------------------------------------------------------------------------
@@ -375,7 +288,7 @@ def normal_structures_stats(seg, chans, ctx=None):
     dist2 = distance_transform_edt_sq(components._indicator(flags, [v for v in range(256) if v & brain]))             # :206
     _, below, above = masked_order_stats_i32(dist2, (60, 40), flags, require=brain)                                   # :207, :224
     deep_threshold, cortical_threshold = percentile_from_order_stats(n_brain, (60, 40), np.sqrt(below.astype(np.float64)), np.sqrt(above.astype(np.float64)))
-    flag_from_i32(flags, DEEP, dist2, sqrt_bounds(deep_threshold)[0] + 1, _I32_MAX, require=1 << NORMAL)              # :210
+    flag_from_i32(flags, DEEP, dist2, sqrt_bounds(deep_threshold)[0] + 1, require=1 << NORMAL)                        # :210
     flag_from_i32(flags, CORTICAL, dist2, 0, sqrt_bounds(cortical_threshold)[1] - 1, require=1 << NORMAL)             # :224
     m = masked_moments(torch.stack((t1, flair)), flags)
     stats.update(n_brain=int(m[BRAIN][0][0]), n_normal=int(m[NORMAL][0][0]), n_obstructed=int(m[OBSTRUCTED][0][0]),
@@ -401,8 +314,8 @@ def normal_structures(seg, t1, t1ce, t2, flair, voxel_dims, ctx=None):
     if ctx is not None:
         seg, chans = ctx.volumes(seg, (t1, t1ce, t2, flair), "normal_structures")
         return normal_structures_from_stats(normal_structures_stats(seg, chans, ctx), voxel_dims)
-    seg = _check_volume(seg, torch.uint8, "normal_structures")
-    chans = [_check_volume(v, torch.float32, "normal_structures") for v in (t1, t1ce, t2, flair)]
+    seg = check_volume(seg, torch.uint8, "normal_structures")
+    chans = [check_volume(v, torch.float32, "normal_structures") for v in (t1, t1ce, t2, flair)]
     if any(v.shape != seg.shape for v in chans):
         raise ValueError("normal_structures: the volumes and the label map differ in shape")
     if int(seg.max()) > 4:
@@ -411,35 +324,24 @@ def normal_structures(seg, t1, t1ce, t2, flair, voxel_dims, ctx=None):
 
 
 # ---- the command ------------------------------------------------------------------------------------------------------
+def _summary(res):
+    vent, par, ves = (res[k] for k in SECTIONS)
+    return (f"ventricles {vent['size_assessment']} (VBR {vent['ventricle_brain_ratio_percent']:.1f}%), {vent['hydrocephalus_type']}; "
+            f"parenchyma {par.get('overall_assessment', par.get('assessment'))}; flow voids {ves['flow_voids']['assessment']}; "
+            f"vascular involvement {ves['vascular_involvement']['assessment']}")
+
+
+STEP_SPEC = StepSpec(key='step6_normal_structures', title=STEP, description='Step 6: normal structures assessment (MI355X)', voxel_info=False,
+                     call=lambda seg, chans, zooms, ctx=None: normal_structures(seg, chans['t1'], chans['t1ce'], chans['t2'], chans['flair'], zooms, ctx=ctx),
+                     summary=_summary)
+
+
 def analyze(input_folder, segmentation_path, output_path=None):
-    import torch
-    from . import nifti
-    case_id, paths = case_id_and_paths(input_folder)
-    images = {k: nifti.load(p) for k, p in paths.items()}
-    seg = np.ascontiguousarray(np.round(nifti.load(segmentation_path).data).astype(np.uint8))  # :443-444
-    zooms = [float(v) for v in images['t1'].zooms]
-    dev = [torch.from_numpy(np.ascontiguousarray(images[k].data.astype(np.float32))).cuda() for k in ('t1', 't1ce', 't2', 'flair')]
-    res = {'case_id': case_id, 'step': STEP}
-    res.update(normal_structures(torch.from_numpy(seg).cuda(), *dev, zooms))
-    if output_path:
-        Path(output_path).parent.mkdir(parents=True, exist_ok=True)
-        with open(output_path, 'w') as f:
-            json.dump(res, f, indent=2)
-    return res
+    return run_step(STEP_SPEC, input_folder, segmentation_path, output_path)
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description='Step 6: normal structures assessment (MI355X)')
-    ap.add_argument('--input', required=True, help='Input folder containing MRI sequences')
-    ap.add_argument('--segmentation', required=True, help='Path to segmentation mask (NIfTI)')
-    ap.add_argument('--output', default=None, help='Output path for JSON results')
-    args = ap.parse_args(argv)
-    res = analyze(args.input, args.segmentation, args.output)
-    vent, par, ves = (res[k] for k in SECTIONS)
-    print(f"{res['case_id']}: ventricles {vent['size_assessment']} (VBR {vent['ventricle_brain_ratio_percent']:.1f}%), {vent['hydrocephalus_type']}; "
-          f"parenchyma {par.get('overall_assessment', par.get('assessment'))}; flow voids {ves['flow_voids']['assessment']}; "
-          f"vascular involvement {ves['vascular_involvement']['assessment']}")
-    return 0
+    return step_main(STEP_SPEC, argv)
 
 
 if __name__ == '__main__':

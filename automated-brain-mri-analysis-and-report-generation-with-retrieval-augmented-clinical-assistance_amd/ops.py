@@ -10,11 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-
-
-def _stream(t):
-    import torch
-    return torch.cuda.current_stream(t.device).cuda_stream
+from .volume_ops import stream_of
 
 
 def _require_cuda(t, dtype, name):
@@ -36,7 +32,7 @@ def regions_to_labels(probs, order=(1, 2, 3), bbox_lo=(0, 0, 0), full_shape=None
     lo = (C.c_int32 * 3)(*[int(v) for v in bbox_lo])
     fu = (C.c_int32 * 3)(*[int(v) for v in full])
     _lib.check(_lib.load().mi355_regions_to_labels(probs.data_ptr(), c, z, y, x, order_a, lo, fu, out.data_ptr(),
-                                                   _stream(probs)), "mi355_regions_to_labels")
+                                                   stream_of(probs)), "mi355_regions_to_labels")
     return out
 
 
@@ -48,7 +44,7 @@ def label_ensemble(a, b):
     if a.shape != b.shape:
         raise ValueError("label_ensemble: shape mismatch")
     out = torch.empty_like(a)
-    _lib.check(_lib.load().mi355_label_ensemble(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), _stream(a)),
+    _lib.check(_lib.load().mi355_label_ensemble(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), stream_of(a)),
                "mi355_label_ensemble")
     return out
 
@@ -60,7 +56,7 @@ def prob_mean(a, b):
     if a.shape != b.shape:
         raise ValueError("prob_mean: shape mismatch")
     out = torch.empty_like(a)
-    _lib.check(_lib.load().mi355_prob_mean(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), _stream(a)),
+    _lib.check(_lib.load().mi355_prob_mean(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), stream_of(a)),
                "mi355_prob_mean")
     return out
 
@@ -77,7 +73,7 @@ def crop_mask(vol):
     c, z, y, x = vol.shape
     mask = torch.empty((z, y, x), dtype=torch.uint8, device=vol.device)
     box = (C.c_int32 * 6)()
-    _lib.check(_lib.load().mi355_crop_mask(vol.data_ptr(), c, z, y, x, mask.data_ptr(), box, _stream(vol)), "mi355_crop_mask")
+    _lib.check(_lib.load().mi355_crop_mask(vol.data_ptr(), c, z, y, x, mask.data_ptr(), box, stream_of(vol)), "mi355_crop_mask")
     return mask, [[int(box[0]), int(box[1])], [int(box[2]), int(box[3])], [int(box[4]), int(box[5])]]
 
 
@@ -91,7 +87,7 @@ def zscore_masked_(vol, mask):
     v = vol[0].numel()
     if mask.numel() != v:
         raise ValueError("zscore_masked_: mask shape mismatch")
-    _lib.check(_lib.load().mi355_zscore_masked(vol.data_ptr(), mask.data_ptr(), c, v, _stream(vol)),
+    _lib.check(_lib.load().mi355_zscore_masked(vol.data_ptr(), mask.data_ptr(), c, v, stream_of(vol)),
                "mi355_zscore_masked")
     return vol
 
@@ -109,7 +105,7 @@ def resize_axis(x, axis: int, n_out: int, order: int):
     outer = int(np.prod(x.shape[:axis], dtype=np.int64)) if axis > 0 else 1
     inner = int(np.prod(x.shape[axis + 1:], dtype=np.int64)) if axis + 1 < x.dim() else 1
     out = torch.empty(tuple(x.shape[:axis]) + (int(n_out),) + tuple(x.shape[axis + 1:]), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().mi355_resize_axis(x.data_ptr(), out.data_ptr(), outer, n_in, int(n_out), inner, int(order), _stream(x)),
+    _lib.check(_lib.load().mi355_resize_axis(x.data_ptr(), out.data_ptr(), outer, n_in, int(n_out), inner, int(order), stream_of(x)),
                "mi355_resize_axis")
     return out
 
@@ -124,7 +120,7 @@ def clip_to_range_of_(x, ref, group_dims: int):
         raise ValueError("clip_to_range_of_: group shapes differ")
     groups = int(np.prod(x.shape[:group_dims], dtype=np.int64)) if group_dims else 1
     _lib.check(_lib.load().mi355_clip_to_range_of(x.data_ptr(), groups, x.numel() // groups, ref.data_ptr(), ref.numel() // groups,
-                                                  _stream(x)), "mi355_clip_to_range_of")
+                                                  stream_of(x)), "mi355_clip_to_range_of")
     return x
 
 
@@ -133,7 +129,7 @@ def mask_to_float(mask):
     import torch
     mask = _require_cuda(mask, torch.uint8, "mask")
     out = torch.empty(mask.shape, dtype=torch.float32, device=mask.device)
-    _lib.check(_lib.load().mi355_mask_to_float(mask.data_ptr(), out.data_ptr(), mask.numel(), _stream(mask)), "mi355_mask_to_float")
+    _lib.check(_lib.load().mi355_mask_to_float(mask.data_ptr(), out.data_ptr(), mask.numel(), stream_of(mask)), "mi355_mask_to_float")
     return out
 
 
@@ -142,7 +138,7 @@ def threshold_ge(x, thr: float):
     import torch
     x = _require_cuda(x, torch.float32, "x")
     out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    _lib.check(_lib.load().mi355_threshold_ge(x.data_ptr(), float(thr), out.data_ptr(), x.numel(), _stream(x)), "mi355_threshold_ge")
+    _lib.check(_lib.load().mi355_threshold_ge(x.data_ptr(), float(thr), out.data_ptr(), x.numel(), stream_of(x)), "mi355_threshold_ge")
     return out
 
 
@@ -158,7 +154,7 @@ def conv3d_ndhwc(x, weight, bias=None, stride=1, act=0, slope=0.01, impl="mfma")
         do, ho, wo = (d - 1) // stride + 1, (h - 1) // stride + 1, (w - 1) // stride + 1
         y = torch.full((n, do, ho, wo, cout), float("nan"), dtype=torch.float16, device=x.device)
         _lib.check(_lib.load().mi355_conv3d_ndhwc_f16(x.data_ptr(), n, d, h, w, cin, _lib.fptr(weight), _lib.fptr(b), cout,
-                                                      stride, act, slope, y.data_ptr(), _stream(x)), "mi355_conv3d_ndhwc_f16")
+                                                      stride, act, slope, y.data_ptr(), stream_of(x)), "mi355_conv3d_ndhwc_f16")
         return y
     x = _require_cuda(x, torch.float32, "x")
     n, d, h, w, cin = x.shape
@@ -169,7 +165,7 @@ def conv3d_ndhwc(x, weight, bias=None, stride=1, act=0, slope=0.01, impl="mfma")
     y = torch.full((n, do, ho, wo, cout), float("nan"), dtype=torch.float32, device=x.device)
     _lib.check(_lib.load().mi355_conv3d_ndhwc(x.data_ptr(), n, d, h, w, cin, _lib.fptr(weight), _lib.fptr(b), cout,
                                               stride, act, slope, {"mfma": 0, "direct": 1}[impl], y.data_ptr(),
-                                              _stream(x)), "mi355_conv3d_ndhwc")
+                                              stream_of(x)), "mi355_conv3d_ndhwc")
     return y
 
 
@@ -188,7 +184,7 @@ def conv3d_sums_ndhwc(x, weight, bias=None, stride=1, act=0, slope=0.01):
     y = torch.full((n, do, ho, wo, cout), float("nan"), dtype=x.dtype, device=x.device)
     sums = torch.full((n, cout, 2), float("nan"), dtype=torch.float64, device=x.device)
     _lib.check(_lib.load().mi355_conv3d_sums_ndhwc(x.data_ptr(), 1 if f16 else 0, n, d, h, w, cin, _lib.fptr(weight), _lib.fptr(b),
-                                                   cout, stride, act, slope, y.data_ptr(), sums.data_ptr(), _stream(x)),
+                                                   cout, stride, act, slope, y.data_ptr(), sums.data_ptr(), stream_of(x)),
                "mi355_conv3d_sums_ndhwc")
     return y, sums
 
@@ -231,7 +227,7 @@ def conv3d_fused_ndhwc(x0, weight, bias=None, x1=None, in_scale=None, in_shift=N
     _lib.check(_lib.load().mi355_conv3d_fused_ndhwc(
         x0.data_ptr(), ptr(x1), 1 if f16 else 0, n, d, h, w, c0, c1, _lib.fptr(weight), _lib.fptr(b), cout, stride, act, slope,
         {"mfma": 0, "direct": 1}[impl], ptr(in_scale), ptr(in_shift), in_act, ptr(head_w), ptr(head_b), ncls,
-        out.data_ptr() if head else None, None if head else out.data_ptr(), ptr(sums), _stream(x0)), "mi355_conv3d_fused_ndhwc")
+        out.data_ptr() if head else None, None if head else out.data_ptr(), ptr(sums), stream_of(x0)), "mi355_conv3d_fused_ndhwc")
     return out, sums
 
 
@@ -360,7 +356,7 @@ def conv3d_wino3_ndhwc(x0, weight, bias=None, x1=None, addend=None, act=0, slope
     y = torch.full((n, d, h, w, cout), float("nan"), dtype=torch.float32, device=x0.device)
     _lib.check(_lib.load().mi355_conv3d_wino3_ndhwc(x0.data_ptr(), None if x1 is None else x1.data_ptr(), n, d, h, w, c0, c1,
                                                     _lib.fptr(weight), _lib.fptr(b), cout, act, slope,
-                                                    None if addend is None else addend.data_ptr(), y.data_ptr(), _stream(x0)),
+                                                    None if addend is None else addend.data_ptr(), y.data_ptr(), stream_of(x0)),
                "mi355_conv3d_wino3_ndhwc")
     return y
 
@@ -458,7 +454,7 @@ def conv3d_s2dma_view_ndhwc(x, weight, bias=None, view=None, act=0, slope=0.01, 
         raise ValueError("conv3d_s2dma_view_ndhwc: the view's source must have the input's channels")
     y = torch.full((n, (d - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1, cout), float("nan"), dtype=torch.float32, device=x.device)
     _lib.check(_lib.load().mi355_conv3d_s2dma_view_ndhwc(x.data_ptr(), None if v is None else C.byref(v), n, d, h, w, cin, _lib.fptr(weight),
-                                                         _lib.fptr(b), cout, act, slope, int(bool(force)), y.data_ptr(), _stream(x)),
+                                                         _lib.fptr(b), cout, act, slope, int(bool(force)), y.data_ptr(), stream_of(x)),
                "mi355_conv3d_s2dma_view_ndhwc")
     return y
 
@@ -481,7 +477,7 @@ def conv3d_wino3_view_ndhwc(x0, weight, bias, addend, view=None, act=0, slope=0.
         raise ValueError("conv3d_wino3_view_ndhwc: the view's source must have the addend's channels")
     y = torch.full((n, d, h, w, cout), float("nan"), dtype=torch.float32, device=x0.device)
     _lib.check(_lib.load().mi355_conv3d_wino3_view_ndhwc(x0.data_ptr(), n, d, h, w, c0, _lib.fptr(weight), _lib.fptr(b), cout, act, slope,
-                                                         addend.data_ptr(), None if v is None else C.byref(v), y.data_ptr(), _stream(x0)),
+                                                         addend.data_ptr(), None if v is None else C.byref(v), y.data_ptr(), stream_of(x0)),
                "mi355_conv3d_wino3_view_ndhwc")
     return y
 
@@ -501,7 +497,7 @@ def tconv3d_ndhwc(x, weight):
         cout = weight.shape[1]
         y = torch.full((n, 2 * d, 2 * h, 2 * w, cout), float("nan"), dtype=torch.float16, device=x.device)
         _lib.check(_lib.load().mi355_tconv3d_ndhwc_f16(x.data_ptr(), n, d, h, w, cin, _lib.fptr(weight), cout, y.data_ptr(),
-                                                       _stream(x)), "mi355_tconv3d_ndhwc_f16")
+                                                       stream_of(x)), "mi355_tconv3d_ndhwc_f16")
         return y
     x = _require_cuda(x, torch.float32, "x")
     n, d, h, w, cin = x.shape
@@ -509,7 +505,7 @@ def tconv3d_ndhwc(x, weight):
     cout = weight.shape[1]
     y = torch.full((n, 2 * d, 2 * h, 2 * w, cout), float("nan"), dtype=torch.float32, device=x.device)
     _lib.check(_lib.load().mi355_tconv3d_ndhwc(x.data_ptr(), n, d, h, w, cin, _lib.fptr(weight), cout, y.data_ptr(),
-                                               _stream(x)), "mi355_tconv3d_ndhwc")
+                                               stream_of(x)), "mi355_tconv3d_ndhwc")
     return y
 
 
@@ -556,7 +552,7 @@ def norm_finalize(stats, count, kind="instance", groups=1, eps=1e-5, gamma=None,
     shift = torch.full((n, c), float("nan"), dtype=torch.float32, device=stats.device)
     _lib.check(_lib.load().mi355_norm_finalize(stats.data_ptr(), n, c, int(count), {"instance": _lib.NORM_INSTANCE, "group": _lib.NORM_GROUP}[kind],
                                                int(groups), float(eps), _ptr(gamma), _ptr(beta), scale.data_ptr(), shift.data_ptr(),
-                                               _stream(stats)), "mi355_norm_finalize")
+                                               stream_of(stats)), "mi355_norm_finalize")
     return scale, shift
 
 
@@ -575,7 +571,7 @@ def norm_apply_(x, scale, shift, act=0, slope=0.01):
         n, v, c = x.shape
     scale, shift = _f32(scale, "scale", n * c), _f32(shift, "shift", n * c)
     _lib.check(_lib.load().mi355_norm_apply(x.data_ptr(), int(x.dtype == torch.float16), n, v, c, scale.data_ptr(), shift.data_ptr(), int(act),
-                                            float(slope), _stream(x)), "mi355_norm_apply")
+                                            float(slope), stream_of(x)), "mi355_norm_apply")
     return x
 
 
@@ -595,7 +591,7 @@ def extract_tiles(vol, pad, tiles, patch, cpad, dtype="f32"):
     out = torch.full(shape, float("nan"), dtype=torch.float16 if f16 else torch.float32, device=vol.device)
     flat = (C.c_int32 * (4 * n))(*[k for t in tiles for k in t])
     _lib.check(_lib.load().mi355_extract_tiles(vol.data_ptr(), c, z, y, x, _i3(pad), flat, n, _i3(patch), cpad, out.data_ptr(), int(f16),
-                                               _stream(vol)), "mi355_extract_tiles")
+                                               stream_of(vol)), "mi355_extract_tiles")
     return out
 
 
@@ -633,7 +629,7 @@ def head_logits(feat, weight, bias=None, scale=None, shift=None, slope=1.0):
     ncls = weight.shape[0]
     out = torch.full((n, ncls, v), float("nan"), dtype=torch.float32, device=feat.device)
     _lib.check(_lib.load().mi355_head_logits(feat.data_ptr(), int(f16), n, v, c, _lib.fptr(weight), _lib.fptr(bias), ncls, _ptr(scale),
-                                             _ptr(shift), float(slope), out.data_ptr(), _stream(feat)), "mi355_head_logits")
+                                             _ptr(shift), float(slope), out.data_ptr(), stream_of(feat)), "mi355_head_logits")
     return out
 
 
@@ -668,7 +664,7 @@ def head_aggregate_(feat, weight, bias, mirrors, patch, nonlin, agg, cnt, origin
     _lib.check(_lib.load().mi355_head_aggregate(feat.data_ptr(), int(f16), c, _lib.fptr(weight), _lib.fptr(bias), weight.shape[0], _ptr(scale),
                                                 _ptr(shift), float(slope), int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
                                                 len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss), agg.data_ptr(), _ptr(cnt), _i3(padded),
-                                                _i3(origin), _stream(feat)), "mi355_head_aggregate")
+                                                _i3(origin), stream_of(feat)), "mi355_head_aggregate")
 
 
 def logits_aggregate_(logits, mirrors, patch, nonlin, agg, cnt, origin, gauss=None, first_sample=0):
@@ -683,7 +679,7 @@ def logits_aggregate_(logits, mirrors, patch, nonlin, agg, cnt, origin, gauss=No
     from .predictor import NONLIN
     _lib.check(_lib.load().mi355_logits_aggregate(logits.data_ptr(), ncls, int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
                                                   len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss), agg.data_ptr(), _ptr(cnt), _i3(padded),
-                                                  _i3(origin), _stream(logits)), "mi355_logits_aggregate")
+                                                  _i3(origin), stream_of(logits)), "mi355_logits_aggregate")
 
 
 def logits_aggregate_tiles_(logits, mirrors, patch, nonlin, agg, cnt, origins, gauss=None, first_sample=0):
@@ -704,14 +700,14 @@ def logits_aggregate_tiles_(logits, mirrors, patch, nonlin, agg, cnt, origins, g
     from .predictor import NONLIN
     _lib.check(_lib.load().mi355_logits_aggregate_tiles(logits.data_ptr(), ncls, int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
                                                         len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss_dev), agg.data_ptr(), _ptr(cnt),
-                                                        _i3(padded), (C.c_int32 * len(flat))(*flat), len(origins), _stream(logits)),
+                                                        _i3(padded), (C.c_int32 * len(flat))(*flat), len(origins), stream_of(logits)),
                "mi355_logits_aggregate_tiles")
 
 
 def cnt_add_tile_(cnt, patch, origin, gauss=None):
     """``mi355_cnt_add_tile``: cnt [Zp, Yp, Xp] (CUDA fp32, in place) += gauss [patch] (None: 1) at origin."""
     gauss, padded, _ = _tile_operands(cnt[None], cnt, gauss, 1, patch, origin, "cnt_add_tile_")
-    _lib.check(_lib.load().mi355_cnt_add_tile(_ptr(gauss), _i3(patch), cnt.data_ptr(), _i3(padded), _i3(origin), _stream(cnt)),
+    _lib.check(_lib.load().mi355_cnt_add_tile(_ptr(gauss), _i3(patch), cnt.data_ptr(), _i3(padded), _i3(origin), stream_of(cnt)),
                "mi355_cnt_add_tile")
 
 
@@ -762,9 +758,9 @@ def stage0_gather(wv, slabs, samples, patch, r, shells_only=False, out=None):
         raise ValueError(f"stage0_gather: out must be a contiguous CUDA fp32 {shape}")
     a.out_dev = out.data_ptr()
     if shells_only:
-        _lib.check(_lib.load().mi355_stage0_gather_shells(C.byref(a), _stream(wv)), "mi355_stage0_gather_shells")
+        _lib.check(_lib.load().mi355_stage0_gather_shells(C.byref(a), stream_of(wv)), "mi355_stage0_gather_shells")
     else:
-        _lib.check(_lib.load().mi355_stage0_gather(C.byref(a), _stream(wv)), "mi355_stage0_gather")
+        _lib.check(_lib.load().mi355_stage0_gather(C.byref(a), stream_of(wv)), "mi355_stage0_gather")
     return out
 
 
@@ -853,7 +849,7 @@ def stage0_gather_merged(wv, slabs, samples, patch, r, spans, shells_only=False,
     if second is not None:
         out2 = result(second.get("out"), c2)
         m.out2_dev = out2.data_ptr()
-    _lib.check(_lib.load().mi355_stage0_gather_merged(C.byref(m), int(bool(shells_only)), _stream(wv)), "mi355_stage0_gather_merged")
+    _lib.check(_lib.load().mi355_stage0_gather_merged(C.byref(m), int(bool(shells_only)), stream_of(wv)), "mi355_stage0_gather_merged")
     return out, out2
 
 
@@ -862,7 +858,7 @@ def stage0_mask_(x, keep):
     import torch
     if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 5):
         raise ValueError("stage0_mask_: x must be a contiguous CUDA fp32 [N, Ve0, Ve1, Ve2, C]")
-    _lib.check(_lib.load().mi355_stage0_mask(x.data_ptr(), int(x.shape[0]), _i3(x.shape[1:4]), _i3(keep), int(x.shape[4]), _stream(x)),
+    _lib.check(_lib.load().mi355_stage0_mask(x.data_ptr(), int(x.shape[0]), _i3(x.shape[1:4]), _i3(keep), int(x.shape[4]), stream_of(x)),
                "mi355_stage0_mask")
     return x
 

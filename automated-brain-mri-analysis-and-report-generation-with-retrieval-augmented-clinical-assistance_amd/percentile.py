@@ -180,11 +180,11 @@ def gather_planned(results, back):
 def intensity_stats(x, flags, bit):
     """``utils.get_intensity_stats(data, mask)`` (utils.py:27-51) for the region bit ``bit`` of the flag byte: minimum, maximum,
     median and quartiles from one ``masked_percentiles`` call, mean, std and count from ``masked_moments``."""
-    from . import morphology
+    from .volume_ops import masked_moments, mean_std
     count, p = masked_percentiles(x, (0, 100, 50, 25, 75), flags, require=1 << bit)
     if count == 0:
         return {'mean': None, 'std': None, 'min': None, 'max': None, 'median': None, 'q25': None, 'q75': None, 'voxel_count': 0}
-    row = morphology.masked_moments(x.reshape((1,) + tuple(x.shape)), flags)[bit][0]
-    mean, std = morphology._mean_std(row)
+    row = masked_moments(x.reshape((1,) + tuple(x.shape)), flags)[bit][0]
+    mean, std = mean_std(row)
     return {'mean': float(mean), 'std': float(std), 'min': float(p[0]), 'max': float(p[1]), 'median': float(p[2]), 'q25': float(p[3]),
             'q75': float(p[4]), 'voxel_count': int(row[0])}

@@ -17,18 +17,14 @@ As a command (the reference's arguments, :704-717):
 """
 from __future__ import annotations
 
-import argparse
-import ctypes as C
-import json
 import sys
-from pathlib import Path
 
 import numpy as np
 
-from . import _lib
-from .morphology import (_check_volume, _mean_std, _stream, binary_erosion, case_id_and_paths, flag_from_flags, flag_from_labels, masked_moments,
-                         second_moments)
+from .case_io import StepSpec, run_step, step_main
 from .percentile import masked_percentiles
+from .volume_ops import (binary_erosion, binary_fill_holes, check_volume, face_slab_counts, flag_from_flags, flag_from_labels, masked_moments, mean_std,
+                         radial_shell_moments, second_moments, sobel_magnitude_stats)
 
 #: region bits of the flag map ``quality_control`` builds (one uint8 per voxel); BACKGROUND .. LOW are rewritten per sequence
 BRAIN, BACKGROUND, ZERO, GHOST, HIGH, LOW, EDGE, ERODED = range(8)
@@ -38,61 +34,6 @@ STEP = 'Step 5 - Quality control and confidence metrics'
 BOUNDARY_MARGIN, EDGE_MARGIN = 3, 5            # :113, :382
 INNER_FRACTION, OUTER_FRACTION = 0.3, 0.7      # :293-294
 _TINY = float(np.nextafter(0.0, 1.0))          # -_TINY < x < _TINY: x == 0
-
-
-# ---- thin wrappers over the entry points ------------------------------------------------------------------------------
-def binary_fill_holes(mask):
-    """mask: CUDA uint8 [d0, d1, d2], foreground = nonzero -> (uint8 0 / 1 map bit-equal to
-    ``scipy.ndimage.binary_fill_holes(mask)``, number of voxels added)."""
-    import torch
-    mask = _check_volume(mask, torch.uint8, "binary_fill_holes")
-    out = torch.empty_like(mask)
-    filled = C.c_int64(0)
-    _lib.check(_lib.load().mi355_binary_fill_holes(mask.data_ptr(), mask.shape[0], mask.shape[1], mask.shape[2], out.data_ptr(), C.byref(filled),
-                                                   _stream(mask)), "mi355_binary_fill_holes")
-    return out, int(filled.value)
-
-
-def sobel_magnitude_stats(x, flags, select=255):
-    """x: CUDA float32 [d0, d1, d2]; flags: CUDA uint8 map of that shape, a voxel counts where ``flags & select`` is nonzero.
-    Returns (n, mean, std) of ``sqrt(sobel(x, 0)**2 + sobel(x, 1)**2 + sobel(x, 2)**2)`` over those voxels (scipy's defaults,
-    float64, population std)."""
-    import torch
-    x = _check_volume(x, torch.float32, "sobel_magnitude_stats")
-    flags = _check_volume(flags, torch.uint8, "sobel_magnitude_stats")
-    if flags.shape != x.shape:
-        raise ValueError("sobel_magnitude_stats: the volume and the flags differ in shape")
-    out = (C.c_double * 3)()
-    _lib.check(_lib.load().mi355_sobel_magnitude_stats(x.data_ptr(), flags.data_ptr(), int(select), x.shape[0], x.shape[1], x.shape[2], out, _stream(x)),
-               "mi355_sobel_magnitude_stats")
-    return int(out[0]), float(out[1]), float(out[2])
-
-
-def radial_shell_moments(x, flags, require, centre, inner_frac=INNER_FRACTION, outer_frac=OUTER_FRACTION):
-    """Over the voxels whose flag byte has every bit of ``require``: (max_dist, n_inner, sum_inner, n_outer, sum_outer) - the
-    largest distance from ``centre`` (voxel units, numpy's float64 arithmetic bit for bit), and count and sum of ``x`` over the
-    voxels nearer than ``max_dist * inner_frac`` and over those farther than ``max_dist * outer_frac``."""
-    import torch
-    x = _check_volume(x, torch.float32, "radial_shell_moments")
-    flags = _check_volume(flags, torch.uint8, "radial_shell_moments")
-    if flags.shape != x.shape:
-        raise ValueError("radial_shell_moments: the volume and the flags differ in shape")
-    c = (C.c_double * 3)(*[float(v) for v in centre])
-    out = (C.c_double * 5)()
-    _lib.check(_lib.load().mi355_radial_shell_moments(x.data_ptr(), flags.data_ptr(), int(require), x.shape[0], x.shape[1], x.shape[2], c, float(inner_frac),
-                                                      float(outer_frac), out, _stream(x)), "mi355_radial_shell_moments")
-    return float(out[0]), int(out[1]), float(out[2]), int(out[3]), float(out[4])
-
-
-def face_slab_counts(x, margin):
-    """x: CUDA float32 [d0, d1, d2] -> int64 [6]: the voxels with ``x > 0`` in the first and in the last ``margin`` indices of
-    axis 0, 1, 2 (``x[:margin]``, ``x[-margin:]``, ``x[:, :margin]``, ...)."""
-    import torch
-    x = _check_volume(x, torch.float32, "face_slab_counts")
-    out = np.zeros(6, dtype=np.int64)
-    _lib.check(_lib.load().mi355_face_slab_counts(x.data_ptr(), x.shape[0], x.shape[1], x.shape[2], int(margin), out.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                  _stream(x)), "mi355_face_slab_counts")
-    return out
 
 
 # ---- step5_quality.py:32-545 on the integers and sums -----------------------------------------------------------------
@@ -152,9 +93,9 @@ def _image_quality(n_brain, sequences):  # assess_image_quality, :162-258
             quality_metrics[seq_name] = {'snr_estimate': 0, 'issues': seq_issues, 'quality': 'Poor'}
             continue
         s = sequences[seq_name]
-        signal_mean, brain_std = _mean_std(s['brain'])
+        signal_mean, brain_std = mean_std(s['brain'])
         if s['background'][0] > 100:
-            background_std = _mean_std(s['background'])[1]
+            background_std = mean_std(s['background'])[1]
             snr = signal_mean / background_std if background_std > 0 else 0
         else:
             snr = signal_mean / brain_std if brain_std > 0 else 0
@@ -205,7 +146,7 @@ def _artifacts(n_brain, n_wt, sequences, shell, face_counts, n_edge, edge_gradie
     for seq_name in SEQUENCES:  # :320-346
         ghost = sequences[seq_name]['ghost']
         if ghost[0] > 1000:
-            bg_mean, bg_std = _mean_std(ghost)
+            bg_mean, bg_std = mean_std(ghost)
             cv_background = bg_std / bg_mean if bg_mean > 0 else 0
             if cv_background > 0.5:
                 if 'motion_ghosting' not in artifact_details:
@@ -369,7 +310,7 @@ def quality_stats(seg, chans, ctx=None):
             stats['n_edge'] = int(m[EDGE][0])
     if n_brain:
         centre = [np.float64(int(brain_moments[1 + k])) / n_brain for k in range(3)]     # np.mean of integer coordinates, :283
-        stats['shell'] = radial_shell_moments(t1, flags, 1 << BRAIN, centre)
+        stats['shell'] = radial_shell_moments(t1, flags, 1 << BRAIN, centre, INNER_FRACTION, OUTER_FRACTION)
     stats['face_counts'] = face_slab_counts(t1, EDGE_MARGIN)
     if n_wt and stats['n_edge'] > 100:
         stats['edge_gradient'] = sobel_magnitude_stats(t1, flags, 1 << EDGE)             # :413-419
@@ -385,8 +326,8 @@ def quality_control(seg, t1, t1ce, t2, flair, voxel_dims, ctx=None):
     if ctx is not None:
         seg, chans = ctx.volumes(seg, (t1, t1ce, t2, flair), "quality_control")
         return quality_from_stats(quality_stats(seg, chans, ctx), voxel_dims)
-    seg = _check_volume(seg, torch.uint8, "quality_control")
-    chans = [_check_volume(v, torch.float32, "quality_control") for v in (t1, t1ce, t2, flair)]
+    seg = check_volume(seg, torch.uint8, "quality_control")
+    chans = [check_volume(v, torch.float32, "quality_control") for v in (t1, t1ce, t2, flair)]
     if any(v.shape != seg.shape for v in chans):
         raise ValueError("quality_control: the volumes and the label map differ in shape")
     if int(seg.max()) > 4:
@@ -395,34 +336,23 @@ def quality_control(seg, t1, t1ce, t2, flair, voxel_dims, ctx=None):
 
 
 # ---- the command ------------------------------------------------------------------------------------------------------
+def _summary(res):
+    seg, art = res['segmentation_quality'], res['artifact_detection']
+    return (f"segmentation {seg['grade']} ({seg['quality_score']}/100); image quality {res['image_quality']['overall_quality']}; "
+            f"artifacts {art['severity']} ({art['artifact_count']}); {len(res['limitations_and_caveats']['caveats'])} caveats")
+
+
+STEP_SPEC = StepSpec(key='step5_quality', title=STEP, description='Step 5: quality control and confidence assessment (MI355X)', voxel_info=False,
+                     call=lambda seg, chans, zooms, ctx=None: quality_control(seg, chans['t1'], chans['t1ce'], chans['t2'], chans['flair'], zooms, ctx=ctx),
+                     summary=_summary)
+
+
 def analyze(input_folder, segmentation_path, output_path=None):
-    import torch
-    from . import nifti
-    case_id, paths = case_id_and_paths(input_folder)
-    images = {k: nifti.load(p) for k, p in paths.items()}
-    seg = np.ascontiguousarray(np.round(nifti.load(segmentation_path).data).astype(np.uint8))  # :625-626
-    zooms = [float(v) for v in images['t1'].zooms]
-    dev = [torch.from_numpy(np.ascontiguousarray(images[k].data.astype(np.float32))).cuda() for k in ('t1', 't1ce', 't2', 'flair')]
-    res = {'case_id': case_id, 'step': STEP}
-    res.update(quality_control(torch.from_numpy(seg).cuda(), *dev, zooms))
-    if output_path:
-        Path(output_path).parent.mkdir(parents=True, exist_ok=True)
-        with open(output_path, 'w') as f:
-            json.dump(res, f, indent=2)
-    return res
+    return run_step(STEP_SPEC, input_folder, segmentation_path, output_path)
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description='Step 5: quality control and confidence assessment (MI355X)')
-    ap.add_argument('--input', required=True, help='Input folder containing MRI sequences')
-    ap.add_argument('--segmentation', required=True, help='Path to segmentation mask (NIfTI)')
-    ap.add_argument('--output', default=None, help='Output path for JSON results')
-    args = ap.parse_args(argv)
-    res = analyze(args.input, args.segmentation, args.output)
-    seg, art = res['segmentation_quality'], res['artifact_detection']
-    print(f"{res['case_id']}: segmentation {seg['grade']} ({seg['quality_score']}/100); image quality {res['image_quality']['overall_quality']}; "
-          f"artifacts {art['severity']} ({art['artifact_count']}); {len(res['limitations_and_caveats']['caveats'])} caveats")
-    return 0
+    return step_main(STEP_SPEC, argv)
 
 
 if __name__ == '__main__':

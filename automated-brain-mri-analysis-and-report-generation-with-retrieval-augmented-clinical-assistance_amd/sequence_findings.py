@@ -15,16 +15,13 @@ As a command (the reference's arguments, :552-565):
 """
 from __future__ import annotations
 
-import argparse
-import json
 import sys
-from pathlib import Path
 
 import numpy as np
 
-from .morphology import (FLAIR, NBITS, T1, T1CE, T2, _check_volume, _mean_std, binary_dilation, case_id_and_paths, flag_from_flags,
-                         flag_from_labels, masked_moments)
+from .case_io import FLAIR, T1, T1CE, T2, StepSpec, run_step, step_main
 from .percentile import masked_percentiles
+from .volume_ops import NBITS, binary_dilation, check_volume, flag_from_flags, flag_from_labels, masked_moments, mean_std
 
 #: region bits of the flag map ``sequence_findings`` builds: the three labels, the normal brain of each modality (in channel
 #: order) and the enhancing voxels within two dilations of the necrotic core
@@ -52,7 +49,7 @@ def _region_signals(region_name, rows, normal_mean):  # analyze_region_signals, 
         return None
     mean, std = {}, {}
     for c in (T1, T1CE, T2, FLAIR):
-        mean[c], std[c] = (float(v) for v in _mean_std(rows[c]))
+        mean[c], std[c] = (float(v) for v in mean_std(rows[c]))
     ratio = {c: mean[c] / normal_mean[c] if normal_mean[c] and normal_mean[c] > 0 else 1.0 for c in (T1, T1CE, T2, FLAIR)}
     label = {c: get_signal_label(ratio[c]) for c in ratio}
     enhancement_ratio = mean[T1CE] / mean[T1] if mean[T1] and mean[T1] > 0 else 1.0
@@ -66,7 +63,7 @@ def _region_signals(region_name, rows, normal_mean):  # analyze_region_signals, 
 
 
 def _all_region_signals(m):  # analyze_all_region_signals, :135-176
-    normal_mean = {c: float(_mean_std(m[NORMAL[c]][c])[0]) if m[NORMAL[c]][c][0] > 0 else None for c in (T1, T1CE, T2, FLAIR)}
+    normal_mean = {c: float(mean_std(m[NORMAL[c]][c])[0]) if m[NORMAL[c]][c][0] > 0 else None for c in (T1, T1CE, T2, FLAIR)}
     results = {'normal_brain_reference': {'methodology': 'Combined gray matter + white matter (non-tumor, non-CSF brain tissue)',
                                           'T1_mean': normal_mean[T1], 'T2_mean': normal_mean[T2], 'FLAIR_mean': normal_mean[FLAIR],
                                           'T1ce_mean': normal_mean[T1CE], 'voxel_count': int(m[NORMAL_T1][T1][0])},
@@ -191,8 +188,8 @@ def sequence_findings(seg, t1, t1ce, t2, flair, voxel_dims, ctx=None):
     if ctx is not None:
         seg, chans = ctx.volumes(seg, (t1, t1ce, t2, flair), "sequence_findings")
         return sequence_findings_from_stats(masked_moments(torch.stack(chans), region_flags(seg, chans, ctx)), voxel_dims)
-    seg = _check_volume(seg, torch.uint8, "sequence_findings")
-    chans = [_check_volume(v, torch.float32, "sequence_findings") for v in (t1, t1ce, t2, flair)]
+    seg = check_volume(seg, torch.uint8, "sequence_findings")
+    chans = [check_volume(v, torch.float32, "sequence_findings") for v in (t1, t1ce, t2, flair)]
     if any(v.shape != seg.shape for v in chans):
         raise ValueError("sequence_findings: the volumes and the label map differ in shape")
     if int(seg.max()) > 4:
@@ -202,38 +199,26 @@ def sequence_findings(seg, t1, t1ce, t2, flair, voxel_dims, ctx=None):
 
 
 # ---- the command ------------------------------------------------------------------------------------------------------
+def _summary(res):
+    ce = res['contrast_enhancement']
+    return (f"{ce['pattern']}; {ce['heterogeneity']}; {ce.get('enhancement_strength', 'no enhancement strength')}; "
+            f"T2/FLAIR mismatch {'detected' if res['t2_flair_mismatch']['mismatch_detected'] else 'not detected'}; "
+            f"{len(res['region_signal_analysis']['regions'])} regions")
+
+
+STEP_SPEC = StepSpec(key='step1_sequence_findings', title='Step 1 - Sequence-specific findings', description='Step 1: sequence-specific findings (MI355X)',
+                     call=lambda seg, chans, zooms, ctx=None: sequence_findings(seg, chans['t1'], chans['t1ce'], chans['t2'], chans['flair'], zooms, ctx=ctx),
+                     summary=_summary,
+                     tail={'sequences_analyzed': ['T1', 'T1ce', 'T2', 'FLAIR'], 'diffusion_available': False,
+                           'diffusion_note': 'DWI/ADC not available in standard BraTS dataset'})  # :531-533
+
+
 def analyze(input_folder, segmentation_path, output_path=None):
-    import torch
-    from . import nifti
-    case_id, paths = case_id_and_paths(input_folder)
-    images = {k: nifti.load(p) for k, p in paths.items()}
-    seg = np.ascontiguousarray(np.round(nifti.load(segmentation_path).data).astype(np.uint8))  # :400-401
-    zooms = [float(v) for v in images['t1'].zooms]
-    dev = [torch.from_numpy(np.ascontiguousarray(images[k].data.astype(np.float32))).cuda() for k in ('t1', 't1ce', 't2', 'flair')]
-    res = {'case_id': case_id, 'step': 'Step 1 - Sequence-specific findings',
-           'voxel_info': {'dimensions_mm': zooms, 'volume_mm3': float(np.prod(zooms)), 'volume_cm3': float(np.prod(zooms) / 1000)}}
-    res.update(sequence_findings(torch.from_numpy(seg).cuda(), *dev, zooms))
-    res.update({'sequences_analyzed': ['T1', 'T1ce', 'T2', 'FLAIR'], 'diffusion_available': False,
-                'diffusion_note': 'DWI/ADC not available in standard BraTS dataset'})  # :531-533
-    if output_path:
-        Path(output_path).parent.mkdir(parents=True, exist_ok=True)
-        with open(output_path, 'w') as f:
-            json.dump(res, f, indent=2)
-    return res
+    return run_step(STEP_SPEC, input_folder, segmentation_path, output_path)
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description='Step 1: sequence-specific findings (MI355X)')
-    ap.add_argument('--input', required=True, help='Input folder containing MRI sequences')
-    ap.add_argument('--segmentation', required=True, help='Path to segmentation mask (NIfTI)')
-    ap.add_argument('--output', default=None, help='Output path for JSON results')
-    args = ap.parse_args(argv)
-    res = analyze(args.input, args.segmentation, args.output)
-    ce = res['contrast_enhancement']
-    print(f"{res['case_id']}: {ce['pattern']}; {ce['heterogeneity']}; {ce.get('enhancement_strength', 'no enhancement strength')}; "
-          f"T2/FLAIR mismatch {'detected' if res['t2_flair_mismatch']['mismatch_detected'] else 'not detected'}; "
-          f"{len(res['region_signal_analysis']['regions'])} regions")
-    return 0
+    return step_main(STEP_SPEC, argv)
 
 
 if __name__ == '__main__':
