@@ -72,7 +72,7 @@ class UNetDesc(C.Structure):
 
 
 class SwOpts(C.Structure):
-    _fields_ = [("patch", C.c_int32 * 3), ("step_size", C.c_float), ("use_gaussian", C.c_int32),
+    _fields_ = [("patch", C.c_int32 * 3), ("step_size", C.c_double), ("use_gaussian", C.c_int32),
                 ("mirror_axes", C.c_int32), ("nonlin", C.c_int32), ("batch_tiles", C.c_int32)]
 
 
@@ -222,7 +222,7 @@ def load():
     lib.mi355_unet_flops.restype = C.c_int64
     lib.mi355_unet_forward.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.mi355_sw_predict.argtypes = [C.POINTER(vp), C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(SwOpts), vp, vp]
-    lib.mi355_compute_steps.argtypes = [C.c_int, C.c_int, C.c_float, c_int32_p, C.c_int]
+    lib.mi355_compute_steps.argtypes = [C.c_int, C.c_int, C.c_double, c_int32_p, C.c_int]
     lib.mi355_sw_partial.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(SwOpts), C.c_int, C.c_int, vp, vp, vp]
     lib.mi355_sw_finish.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, vp, vp]
     lib.mi355_sw_partial_folds.argtypes = [C.POINTER(vp), C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(SwOpts), C.c_int, C.c_int, vp, vp, vp]
@@ -245,9 +245,9 @@ def load():
     lib.mi355_conv3d_plan.argtypes = [C.c_int] * 13 + [C.POINTER(ConvPlan)]
     lib.mi355_conv_kernel_names.argtypes = [C.c_char_p, C.c_int64]
     lib.mi355_conv_kernel_names.restype = C.c_int64
-    lib.mi355_stage0_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.c_int, C.POINTER(Stage0Geom),
+    lib.mi355_stage0_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_double, C.c_int, C.c_int, C.POINTER(Stage0Geom),
                                       C.POINTER(Stage0Sample), C.c_int]
-    lib.mi355_skip_share_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.POINTER(SkipShareNet), C.c_int,
+    lib.mi355_skip_share_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_double, C.c_int, C.POINTER(SkipShareNet), C.c_int,
                                           C.c_int, C.c_int, C.POINTER(SkipShareGeom)]
     lib.mi355_conv3d_wino3_ndhwc.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
                                              C.c_int, C.c_int, C.c_float, vp, vp, vp]
@@ -305,17 +305,17 @@ def load():
     lib.mi355_cnt_add_tile.argtypes = [vp, c_int32_p, vp, c_int32_p, c_int32_p, vp]
     lib.mi355_stage0_gather.argtypes = [C.POINTER(Stage0GatherArgs), vp]
     lib.mi355_stage0_mask.argtypes = [vp, C.c_int, c_int32_p, c_int32_p, C.c_int, vp]
-    lib.mi355_stage0_merge_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(Stage0MergeGeom),
+    lib.mi355_stage0_merge_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Stage0MergeGeom),
                                             C.POINTER(Stage0MergeSlab), C.c_int, C.POINTER(Stage0MergeSample), C.c_int]
     lib.mi355_stage0_gather_merged.argtypes = [C.POINTER(Stage0GatherMergedArgs), C.c_int, vp]
     lib.mi355_stage0_gather_shells.argtypes = [C.POINTER(Stage0GatherArgs), vp]
-    lib.mi355_stage0_view_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.POINTER(SkipShareNet), C.c_int, C.c_int,
+    lib.mi355_stage0_view_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_double, C.c_int, C.POINTER(SkipShareNet), C.c_int, C.c_int,
                                            C.POINTER(Stage0ViewGeom), C.POINTER(Stage0ViewSample), C.c_int]
     lib.mi355_conv3d_s2dma_view_ndhwc.argtypes = [vp, C.POINTER(Stage0View), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
                                                   C.c_int, C.c_int, C.c_float, C.c_int, vp, vp]
     lib.mi355_conv3d_wino3_view_ndhwc.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, C.c_int, C.c_int,
                                                   C.c_float, vp, C.POINTER(Stage0View), vp, vp]
-    lib.mi355_level1_share_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_float, C.c_int, C.POINTER(Level1ShareNet), C.c_int,
+    lib.mi355_level1_share_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_double, C.c_int, C.POINTER(Level1ShareNet), C.c_int,
                                             C.POINTER(Level1ShareGeom), C.POINTER(Level1ShareRegion), C.c_int, C.POINTER(Level1ShareSample), C.c_int]
     lib.mi355_scratch_sizes.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     lib.mi355_scratch_fill.argtypes = [vp, C.c_int, C.c_uint32]

@@ -16,6 +16,8 @@ namespace mi355 {
 // ---- sliding-window helpers (nnU-Net v1)
 static std::vector<int> compute_steps(int patch, int image, double step_size) {
     // target = patch*step ; n = ceil((image-patch)/target)+1 ; actual = (image-patch)/(n-1)
+    // The step is a double from the C ABI down, as nnU-Net's is a Python float: rounded to float32, 0.3, 0.6, 0.7 and 0.9 put the ceil
+    // on the other side wherever image - patch is a multiple of the target (0.3, patch 96, image 240: 6 tiles for nnU-Net's 7).
     const double target = patch * step_size;
     const int n = (int)std::ceil((image - patch) / target) + 1;
     const int max_step = image - patch;
@@ -66,7 +68,7 @@ void gaussian_map(const int p[3], double sigma_scale, std::vector<float> &out) {
 int make_geom(const mi355_sw_opts &o, int Z, int Y, int X, SwGeom *g) {
     const int dims[3] = {Z, Y, X};
     std::vector<int> steps[3];
-    MI355_REQUIRE(o.step_size > 0.f && o.step_size <= 1.f, "step_size must be in (0, 1]");  // (before compute_steps divides by it)
+    MI355_REQUIRE(o.step_size > 0.0 && o.step_size <= 1.0, "step_size must be in (0, 1]");  // (before compute_steps divides by it)
     for (int a = 0; a < 3; ++a) {
         g->P[a] = o.patch[a];
         MI355_REQUIRE(g->P[a] > 0 && dims[a] > 0, "bad patch / volume size");
@@ -87,7 +89,7 @@ int make_geom(const mi355_sw_opts &o, int Z, int Y, int X, SwGeom *g) {
 }
 
 // the geometry of a dry run, which takes the three values of mi355_sw_opts that make_geom reads
-static int sw_geom_from_abi(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes, SwGeom *g) {
+static int sw_geom_from_abi(int z, int y, int x, const int32_t patch[3], double step_size, int mirror_axes, SwGeom *g) {
     mi355_sw_opts o;
     memset(&o, 0, sizeof(o));
     for (int a = 0; a < 3; ++a) o.patch[a] = patch[a];
@@ -442,8 +444,8 @@ SwSharePlan sw_share_plan(const L1ShareNet &d, const SwGeom &g, const SwSwitches
 
 using namespace mi355;
 
-extern "C" int mi355_compute_steps(int patch, int image, float step_size, int32_t *steps, int max_steps) {
-    MI355_REQUIRE(patch > 0 && image >= patch && step_size > 0.f && step_size <= 1.f, "compute_steps: bad arguments");
+extern "C" int mi355_compute_steps(int patch, int image, double step_size, int32_t *steps, int max_steps) {
+    MI355_REQUIRE(patch > 0 && image >= patch && step_size > 0.0 && step_size <= 1.0, "compute_steps: bad arguments");
     std::vector<int> st = compute_steps(patch, image, step_size);
     MI355_REQUIRE((int)st.size() <= max_steps, "compute_steps: %zu steps > buffer %d", st.size(), max_steps);
     for (size_t i = 0; i < st.size(); ++i) steps[i] = st[i];
@@ -451,7 +453,7 @@ extern "C" int mi355_compute_steps(int patch, int image, float step_size, int32_
 }
 
 // ---- the geometry dry runs.  The two that take a raw r / skip_half and no network ask the geometry layer directly.
-extern "C" int mi355_stage0_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes, int r,
+extern "C" int mi355_stage0_plan(int z, int y, int x, const int32_t patch[3], double step_size, int mirror_axes, int r,
                                  mi355_stage0_geom *out, mi355_stage0_sample *samples, int max_samples) {
     MI355_REQUIRE(out && patch && r >= 0 && (samples || max_samples == 0), "mi355_stage0_plan: bad argument");
     SwGeom g;
@@ -481,7 +483,7 @@ extern "C" int mi355_stage0_plan(int z, int y, int x, const int32_t patch[3], fl
     return n;
 }
 
-extern "C" int mi355_stage0_merge_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes, int r, int skip_half,
+extern "C" int mi355_stage0_merge_plan(int z, int y, int x, const int32_t patch[3], double step_size, int mirror_axes, int r, int skip_half,
                                        mi355_stage0_merge_geom *out, mi355_stage0_merge_slab *slabs, int max_slabs,
                                        mi355_stage0_merge_sample *samples, int max_samples) {
     MI355_REQUIRE(out && patch && r >= 0 && (slabs || max_slabs == 0) && (samples || max_samples == 0), "mi355_stage0_merge_plan: bad argument");
@@ -532,7 +534,7 @@ extern "C" int mi355_stage0_merge_plan(int z, int y, int x, const int32_t patch[
     return n;
 }
 
-extern "C" int mi355_skip_share_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes,
+extern "C" int mi355_skip_share_plan(int z, int y, int x, const int32_t patch[3], double step_size, int mirror_axes,
                                      const mi355_skip_share_net *nd, int batch_tiles, int rank, int world, mi355_skip_share_geom *out) {
     MI355_REQUIRE(out && patch && nd && batch_tiles >= 0 && world >= 1 && rank >= 0 && rank < world, "mi355_skip_share_plan: bad argument");
     SwGeom g;
@@ -550,7 +552,7 @@ extern "C" int mi355_skip_share_plan(int z, int y, int x, const int32_t patch[3]
     return MI355_OK;
 }
 
-extern "C" int mi355_stage0_view_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes,
+extern "C" int mi355_stage0_view_plan(int z, int y, int x, const int32_t patch[3], double step_size, int mirror_axes,
                                       const mi355_skip_share_net *nd, int c_level1, int batch_samples, mi355_stage0_view_geom *out,
                                       mi355_stage0_view_sample *samples, int max_samples) {
     MI355_REQUIRE(out && patch && nd && c_level1 > 0 && batch_samples >= 0 && (samples || max_samples == 0), "mi355_stage0_view_plan: bad argument");
@@ -589,7 +591,7 @@ extern "C" int mi355_stage0_view_plan(int z, int y, int x, const int32_t patch[3
     return n;
 }
 
-extern "C" int mi355_level1_share_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes,
+extern "C" int mi355_level1_share_plan(int z, int y, int x, const int32_t patch[3], double step_size, int mirror_axes,
                                        const mi355_level1_share_net *nd, int mode, mi355_level1_share_geom *out,
                                        mi355_level1_share_region *regions, int max_regions, mi355_level1_share_sample *samples, int max_samples) {
     MI355_REQUIRE(out && patch && nd && mode >= 0 && mode <= 2 && (regions || max_regions == 0) && (samples || max_samples == 0),

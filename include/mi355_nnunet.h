@@ -98,7 +98,7 @@ typedef struct mi355_unet *mi355_unet_t;
 
 typedef struct {
     int32_t patch[3];     /* (z,y,x), e.g. 128,128,128 */
-    float step_size;      /* 0.5 */
+    double step_size;     /* 0.5; a double, as nnU-Net forms patch * step from the Python float (4 bytes of padding before it) */
     int32_t use_gaussian; /* 1 */
     int32_t mirror_axes;  /* bit0 = z, bit1 = y, bit2 = x; 7 = 8-way TTA, 0 = no TTA */
     int32_t nonlin;       /* MI355_NONLIN_* applied to the logits of every forward */
@@ -130,7 +130,7 @@ int mi355_sw_predict(const mi355_unet_t *nets, int n_nets, const float *vol_dev,
                      const mi355_sw_opts *opts, float *probs_dev, void *stream);
 /* Host helper: the step table the predictor uses (nnU-Net v1 _compute_steps_for_sliding_window).
  * Writes at most max_steps entries, returns the count (or <0). */
-int mi355_compute_steps(int patch, int image, float step_size, int32_t *steps, int max_steps);
+int mi355_compute_steps(int patch, int image, double step_size, int32_t *steps, int max_steps);
 /* Tile-sharded variant for multi-GPU: only tiles with (index % world) == rank are evaluated;
  * agg_dev [num_classes][Zp][Yp][Xp] receives the Gaussian-weighted partial sums (to be summed
  * across ranks in rank order), cnt_dev [Zp][Yp][Xp] the full normaliser. Zp.. = max(Z, patch). */
@@ -554,7 +554,7 @@ typedef struct mi355_stage0_sample {
     int32_t slab_origin[6][3];   /* of the face's slab, in its pass (zeros for an unflagged face) */
     int32_t slab_shape[6][3];
 } mi355_stage0_sample;
-int mi355_stage0_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes, int r,
+int mi355_stage0_plan(int z, int y, int x, const int32_t patch[3], double step_size, int mirror_axes, int r,
                       mi355_stage0_geom *out, mi355_stage0_sample *samples, int max_samples);
 /* Dry run of the shared skip half (needs no device and launches nothing; the decision code mi355_sw_predict /
  * mi355_sw_partial[_folds] run).  The first block of the last decoder stage reads the concat (upsampled, skip) and is linear in
@@ -584,7 +584,7 @@ typedef struct mi355_skip_share_geom {
     int32_t volume[3];
     int32_t slab_thickness[3];  /* smallest multiple of (4, 8, 8) >= 2 (r + 1) when on, >= 2 r otherwise */
 } mi355_skip_share_geom;
-int mi355_skip_share_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes,
+int mi355_skip_share_plan(int z, int y, int x, const int32_t patch[3], double step_size, int mirror_axes,
                           const mi355_skip_share_net *net, int batch_tiles, int rank, int world, mi355_skip_share_geom *out);
 /* One stride-1 conv on conv3_f32_wino3_kernel<0, false> - with an addend its twin <3, false> - whatever the size (test aid: the dispatch sends launches of a few tiles
  * elsewhere): y = act(bias + conv(cat(x0, x1)) + addend), x1_dev / addend_dev may be NULL; d % 4 == h % 8 == w % 8 == 0,
@@ -617,7 +617,7 @@ typedef struct mi355_stage0_view_sample {
     int32_t pad_;
     int64_t shell_voxels[2];    /* voxels of the tile the gather still writes, per tensor */
 } mi355_stage0_view_sample;
-int mi355_stage0_view_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes,
+int mi355_stage0_view_plan(int z, int y, int x, const int32_t patch[3], double step_size, int mirror_axes,
                            const mi355_skip_share_net *net, int c_level1, int batch_samples, mi355_stage0_view_geom *out,
                            mi355_stage0_view_sample *samples, int max_samples);
 /* A view as the single-op entries below take it: sample i of the call is the box at samples[i].origin of volume samples[i].wv of
@@ -743,7 +743,7 @@ typedef struct mi355_stage0_merge_sample {
     int32_t slab[6];             /* z faces: 0 = the face gets a per-tile slab; y, x faces: index in that axis's list; -1: a volume face */
     int32_t offset[6][3];        /* y, x faces: where the tile's part of the slab (for a hi face its last thickness layers) starts in the slab */
 } mi355_stage0_merge_sample;
-int mi355_stage0_merge_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes, int r, int skip_half,
+int mi355_stage0_merge_plan(int z, int y, int x, const int32_t patch[3], double step_size, int mirror_axes, int r, int skip_half,
                             mi355_stage0_merge_geom *out, mi355_stage0_merge_slab *slabs, int max_slabs,
                             mi355_stage0_merge_sample *samples, int max_samples);
 /* mi355_stage0_gather / mi355_stage0_gather_shells (shells_only != 0) in their general form: the slabs of axis a are
@@ -812,7 +812,7 @@ typedef struct mi355_level1_share_sample {
     int32_t slab[6];             /* 1: face f has a level-1 slab */
     int32_t slab_offset[6][3], slab_shape[6][3];  /* the level-0 sub-box of the tile the slab is cut from */
 } mi355_level1_share_sample;
-int mi355_level1_share_plan(int z, int y, int x, const int32_t patch[3], float step_size, int mirror_axes,
+int mi355_level1_share_plan(int z, int y, int x, const int32_t patch[3], double step_size, int mirror_axes,
                             const mi355_level1_share_net *net, int mode, mi355_level1_share_geom *out,
                             mi355_level1_share_region *regions, int max_regions, mi355_level1_share_sample *samples, int max_samples);
 /* x_dev [n][volume][c] fp32: zero every voxel outside [0, keep) (c % 4 == 0, 0 < keep <= volume); the rest is not written. */

@@ -154,16 +154,15 @@ def _put_shell(dst, src, a, side, depth):
     dst[tuple(d)] = src[tuple(s)]
 
 
-@pytest.mark.parametrize("volume, axes", [((41, 56, 44), ()), ((40, 56, 44), (0, 1, 2)), ((37, 33, 68), (2,))])
-def test_assembly_equals_per_tile_exactly(ops, volume, axes):
-    """The third case: z and y per-origin with odd origins (regions with stage-0 shells on two axes and the edge between them), x
-    merged with four tiles (0, 12, 24, 36)."""
-    p = ops.level1_share_plan(volume, P32, mirror_axes=axes, mode=2, num_pool=2)
+def _assembly_equals_per_tile_exactly(ops, patch, volume, step, axes, shrink=(0, 0)):
+    """shrink: layers taken off the shell depths (d1, dS); then nothing is asserted of the tensors, and which of the two differed
+    on some sample is returned next to the plan"""
+    p = ops.level1_share_plan(volume, patch, step, mirror_axes=axes, mode=2, num_pool=2)
     assert p["possible"]
     W = _weights()
     vol = torch.randint(-3, 4, (1, 2) + tuple(volume), generator=torch.Generator().manual_seed(22))
     Zp, Ve, R, t0, t1 = p["padded"], p["volume"], p["region"], p["stage0_slab_thickness"], p["slab_thickness"]
-    half = tuple(d // 2 for d in P32)
+    half = tuple(d // 2 for d in patch)
     lo = [(Zp[a] - volume[a]) // 2 for a in range(3)]
     padded = torch.zeros(1, 2, *Zp, dtype=torch.int64)
     _box(padded, lo, volume).copy_(vol)
@@ -191,10 +190,10 @@ def test_assembly_equals_per_tile_exactly(ops, volume, axes):
             _put_shell(x0, _enc0(_box(e, so, shape), W, keep), a, side, p["r0"])
         keep1 = tuple(Zp[c] // 2 if p["merged"][c] else R[c] // 2 for c in range(3))
         region[i] = _level1(x0, W, keep1)
-    worst = 0
+    worst, differs = 0, [False, False]
     for s in p["samples"]:
         m, org = s["mirror"], s["origin"]
-        t0_own = _enc0(_box(pass_of(m), org, P32), W)   # the tile on its own: zero padding at all six faces
+        t0_own = _enc0(_box(pass_of(m), org, patch), W)   # the tile on its own: zero padding at all six faces
         want = _level1(t0_own, W)
         got = [_box(v, s["origin1"], half).clone() for v in region[s["region"]]]
         for f in (5, 4, 3, 2, 1, 0):
@@ -204,12 +203,72 @@ def test_assembly_equals_per_tile_exactly(ops, volume, axes):
             off, shape = s["slabs"][f]
             assert p["merged"][a] and shape[a] == 2 * t1[a]
             src = _level1(_box(t0_own, off, shape), W)   # zero padding at the cut, the tile's own features everywhere else
-            for i, depth in enumerate((p["d1"], p["dS"])):
+            for i, depth in enumerate((p["d1"] - shrink[0], p["dS"] - shrink[1])):
                 _put_shell(got[i], src[i], a, side, depth)
         for i, name in enumerate(("enc[1]'s output", "the skip half")):
-            assert torch.equal(got[i], want[i]), f"{name} of tile {s['tile']} mirror {m}: {int((got[i] != want[i]).sum())} elements differ"
+            differs[i] = differs[i] or not torch.equal(got[i], want[i])
+            assert any(shrink) or not differs[i], f"{name} of tile {s['tile']} mirror {m}: {int((got[i] != want[i]).sum())} elements differ"
             worst = max(worst, int(want[i].abs().max()))
     assert 0 < worst < 2 ** 62
+    return (p, differs) if any(shrink) else p
+
+
+@pytest.mark.parametrize("volume, axes", [((41, 56, 44), ()), ((40, 56, 44), (0, 1, 2)), ((37, 33, 68), (2,))])
+def test_assembly_equals_per_tile_exactly(ops, volume, axes):
+    """The third case: z and y per-origin with odd origins (regions with stage-0 shells on two axes and the edge between them), x
+    merged with four tiles (0, 12, 24, 36)."""
+    _assembly_equals_per_tile_exactly(ops, P32, volume, 0.5, axes)
+
+
+# Off the cube and off step 0.5.  The shared level 1 needs an axis on which every origin and the padded extent are even, so each
+# volume is the neighbour of an all-odd one - (41, 45, 139), (77, 55, 43), (43, 75, 67), (41, 57, 43), (37, 33, 70), for which the
+# plan rightly answers "not possible" (test_rightly_refused_geometries) - that is even on ONE axis: the others keep their odd
+# excess or deficit and stay per-origin.  merged: the axis the plan must merge; tiles: tile origins per axis.
+NONCUBIC = [((32, 48, 64), (41, 45, 128), 0.5, (), 2, (2, 1, 3)), ((64, 32, 48), (77, 56, 43), 0.5, (0, 2), 1, (2, 3, 1)),
+            ((48, 64, 32), (43, 75, 68), 0.5, (1,), 2, (1, 2, 4))]
+STEPPED = [(P32, (41, 56, 43), 0.25, (), 1, (3, 4, 3)), (P32, (37, 34, 70), 0.25, (0,), 1, (2, 2, 6)),
+           (P32, (41, 56, 43), 0.3, (2,), 1, (2, 4, 3)), (P32, (37, 34, 70), 0.3, (), 1, (2, 2, 5)),
+           (P32, (41, 57, 44), 0.75, (), 2, (2, 3, 2)), (P32, (37, 34, 70), 0.75, (), 1, (2, 2, 3)),
+           (P32, (41, 57, 44), 1.0, (), 2, (2, 2, 2)), (P32, (37, 34, 70), 1.0, (1,), 1, (2, 2, 3))]
+
+
+@pytest.mark.parametrize("patch, volume, step, axes, merged, tiles", NONCUBIC + STEPPED)
+def test_assembly_equals_per_tile_exactly_geometries(ops, patch, volume, step, axes, merged, tiles):
+    p = _assembly_equals_per_tile_exactly(ops, patch, volume, step, axes)
+    assert p["merged"] == tuple(a == merged for a in range(3))
+    assert p["region"] == tuple(p["volume"][a] if a == merged else patch[a] for a in range(3))
+    assert p["n_tiles"] == tiles[0] * tiles[1] * tiles[2] and p["n_mirrors"] == 2 ** len(axes)
+    # one region per (mirror, origin tuple on the per-origin axes)
+    assert len(p["regions"]) == p["n_mirrors"] * p["n_tiles"] // tiles[merged]
+    for s in p["samples"]:
+        assert s["origin1"] == tuple(s["origin"][a] // 2 if a == merged else 0 for a in range(3))
+        assert set(s["slabs"]) == {2 * merged + side for side in (0, 1) if s["faces"][2 * merged + side]}
+    if tiles[merged] >= 3:   # a middle tile: two level-1 slabs
+        assert any(len(s["slabs"]) == 2 for s in p["samples"])
+
+
+def test_rightly_refused_geometries(ops):
+    """A stride-2 conv commutes with even shifts only: where every axis has an odd origin or an odd padded extent no axis merges,
+    at any step and for any patch - the all-odd neighbours of the geometries above.  And a patch (32, 48, 24) on (41, 45, 48) has
+    even x origins (0, 12, 24) but half its x extent, 12, has no room for the two level-1 slabs of thickness 8 a middle tile needs."""
+    for patch, volume, step, axes in [((32, 48, 64), (41, 45, 139), 0.5, ()), ((64, 32, 48), (77, 55, 43), 0.5, (0, 2)),
+                                      ((48, 64, 32), (43, 75, 67), 0.5, (1,)), (P32, (41, 57, 43), 0.25, ()), (P32, (37, 33, 70), 0.3, ()),
+                                      (P32, (41, 57, 43), 0.75, ()), (P32, (37, 33, 70), 1.0, ())]:
+        for mode in (1, 2):
+            p = ops.level1_share_plan(volume, patch, step, mirror_axes=axes, mode=mode, num_pool=2)
+            assert p["n_tiles"] > 1 and not p["possible"] and not p["on"] and p["regions"] == [] and p["samples"] == [], (patch, volume, step)
+    assert sorted({s["origin"][2] for s in ops.stage0_plan((41, 45, 48), (32, 48, 24), 0.5, (), 2)["samples"]}) == [0, 12, 24]
+    p = ops.level1_share_plan((41, 45, 48), (32, 48, 24), 0.5, mode=2, num_pool=2)
+    assert not p["possible"] and not p["on"]
+
+
+@pytest.mark.parametrize("which", [0, 1])
+@pytest.mark.parametrize("patch, volume, step, axes, merged, tiles", NONCUBIC + STEPPED[:2])
+def test_shallower_shells_are_not_enough_geometries(ops, which, patch, volume, step, axes, merged, tiles):
+    """The depths d1 and dS are tight off the cube and at step 0.25 too: one layer less of either and that tensor differs on some tile."""
+    shrink = (1, 0) if which == 0 else (0, 1)
+    _, differs = _assembly_equals_per_tile_exactly(ops, patch, volume, step, axes, shrink)
+    assert differs[which] and not differs[1 - which]
 
 
 @pytest.mark.parametrize("which, by", [("d1", -1), ("dS", -1)])

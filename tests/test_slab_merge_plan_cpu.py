@@ -149,10 +149,8 @@ def _put_shell(dst, src, a, side, depth, patch, t):
     dst[tuple(d)] = src[tuple(s)]
 
 
-@pytest.mark.parametrize("volume, axes", [((41, 57, 43), ()), ((40, 56, 44), (0, 1, 2)), ((20, 40, 30), (1,)), ((37, 33, 70), (0, 2))])
-def test_assembly_equals_per_tile_exactly(ops, volume, axes):
-    patch = (32, 32, 32)
-    p = ops.stage0_merge_plan(volume, patch, 0.5, axes, 2, True)
+def _assembly_equals_per_tile_exactly(ops, patch, volume, step, axes):
+    p = ops.stage0_merge_plan(volume, patch, step, axes, 2, True)
     assert p["shared"]
     enc, wskip = _weights()
     g = torch.Generator().manual_seed(12)
@@ -196,3 +194,45 @@ def test_assembly_equals_per_tile_exactly(ops, volume, axes):
                 _put_shell(got[i], src[i], a, side, depth, patch, t)
         for i, name in enumerate(("skip tensor", "S")):
             assert torch.equal(got[i], want[i]), f"{name} of tile {s['tile']} mirror {m}: {int((got[i] != want[i]).sum())} elements differ"
+    return p
+
+
+@pytest.mark.parametrize("volume, axes", [((41, 57, 43), ()), ((40, 56, 44), (0, 1, 2)), ((20, 40, 30), (1,)), ((37, 33, 70), (0, 2))])
+def test_assembly_equals_per_tile_exactly(ops, volume, axes):
+    _assembly_equals_per_tile_exactly(ops, (32, 32, 32), volume, 0.5, axes)
+
+
+# Off the cube and off step 0.5 (the cases of tests/test_stage0_plan_cpu.py): three different extents in three orders, volumes with
+# a different odd excess or deficit per axis, a middle tile on one axis and a single tile on another; 32^3 at steps 0.25 (tiles i
+# and i + 2 overlap: a y key is shared by tiles of several x AND z origins), 0.3, 0.75 and 1.0.
+NONCUBIC = [((32, 48, 64), (41, 45, 139), 0.5, (), (2, 1, 4)), ((64, 32, 48), (77, 55, 43), 0.5, (0, 2), (2, 3, 1)),
+            ((48, 64, 32), (43, 75, 67), 0.5, (1,), (1, 2, 4))]
+STEPPED = [((32, 32, 32), (41, 57, 43), 0.25, (), (3, 5, 3)), ((32, 32, 32), (37, 33, 70), 0.25, (0, 2), (2, 2, 6)),
+           ((32, 32, 32), (41, 57, 43), 0.3, (1,), (2, 4, 3)), ((32, 32, 32), (37, 33, 70), 0.3, (), (2, 2, 5)),
+           ((32, 32, 32), (41, 57, 43), 0.75, (), (2, 3, 2)), ((32, 32, 32), (37, 33, 70), 0.75, (), (2, 2, 3)),
+           ((32, 32, 32), (41, 57, 43), 1.0, (), (2, 2, 2)), ((32, 32, 32), (37, 33, 70), 1.0, (2,), (2, 2, 3))]
+
+
+@pytest.mark.parametrize("patch, volume, step, axes, tiles", NONCUBIC + STEPPED)
+def test_assembly_equals_per_tile_exactly_geometries(ops, patch, volume, step, axes, tiles):
+    p = _assembly_equals_per_tile_exactly(ops, patch, volume, step, axes)
+    _check_plan(p, patch)
+    assert p["n_tiles"] == tiles[0] * tiles[1] * tiles[2] and p["n_mirrors"] == 2 ** len(axes)
+    for a in range(3):
+        assert len({s["origin"][a] for s in p["samples"] if s["mirror"] == ()}) == tiles[a]
+        if tiles[a] == 1:   # one tile along an axis: no face of it inside the volume, no slab
+            assert p["n_slabs"][a] == 0
+    # a y key is (mirror, side, y of the slab, x origin): tiles that differ in z alone share it
+    if tiles[1] > 1:
+        assert p["n_slabs"][1] == p["n_mirrors"] * 2 * (tiles[1] - 1) * tiles[2]
+
+
+def test_rightly_refused_geometries(ops):
+    """With the skip half the slab chain is r + 1 = 3 layers deep and a z slab 8 thick (two conv tiles of 4 >= 6): a patch
+    (6, 48, 64) has no room for it and is refused, while without the skip half (thickness 4) it is shared; and (30, 48, 60) under
+    (32, 48, 64) is one tile after padding, with nothing to share."""
+    thin = ops.stage0_merge_plan((11, 45, 75), (6, 48, 64), 0.5, (), 2, True)
+    assert thin["n_tiles"] > 1 and thin["slab_thickness"][0] == 8 and not thin["shared"] and thin["n_slabs"] == (0, 0, 0)
+    assert ops.stage0_merge_plan((11, 45, 75), (6, 48, 64), 0.5, (), 2, False)["shared"]
+    one = ops.stage0_merge_plan((30, 48, 60), (32, 48, 64), 0.5, (1,), 2, True)
+    assert one["n_tiles"] == 1 and not one["shared"] and one["samples"] == []

@@ -79,10 +79,9 @@ def _box(t, org, shape):
     return t[:, :, org[0]:org[0] + shape[0], org[1]:org[1] + shape[1], org[2]:org[2] + shape[2]]
 
 
-@pytest.mark.parametrize("volume, axes", [((41, 57, 43), (0, 1, 2)), ((20, 40, 30), (0, 2)), ((40, 33, 70), ())])
-def test_assembly_equals_per_tile(ops, volume, axes):
-    patch, r = (32, 32, 32), 2
-    p = ops.stage0_plan(volume, patch, 0.5, axes, r)
+def _assembly_equals_per_tile(ops, patch, volume, step, axes):
+    r = 2
+    p = ops.stage0_plan(volume, patch, step, axes, r)
     assert p["shared"]
     g = torch.Generator().manual_seed(5)
     f64 = dict(generator=g, dtype=torch.float64)
@@ -117,5 +116,43 @@ def test_assembly_equals_per_tile(ops, volume, axes):
             got[tuple(dst)] = out[tuple(src)]
         want = _enc0(_box(volm, s["origin"], patch), ws)
         worst = max(worst, float((got - want).abs().max()))
-    print(f"stage-0 assembly vs per tile, {volume} mirrors {axes}: max abs diff {worst:.2e} over {len(p['samples'])} samples")
+    print(f"stage-0 assembly vs per tile, patch {patch} on {volume} step {step} mirrors {axes}: max abs diff {worst:.2e} over {len(p['samples'])} samples")
     assert worst <= 1e-5
+    return p
+
+
+@pytest.mark.parametrize("volume, axes", [((41, 57, 43), (0, 1, 2)), ((20, 40, 30), (0, 2)), ((40, 33, 70), ())])
+def test_assembly_equals_per_tile(ops, volume, axes):
+    _assembly_equals_per_tile(ops, (32, 32, 32), volume, 0.5, axes)
+
+
+# Off the cube and off step 0.5.  A patch of three different extents and two of its permutations, so that every axis takes the
+# smallest and the largest extent once; each volume with a different odd excess (or an odd deficit: one tile, padded) per axis, one
+# axis with a middle tile.  Then 32^3 at the steps at which a voxel lies in up to 4 tiles per axis (0.25), at a step no binary
+# fraction holds (0.3), and at steps with little or no nominal overlap (0.75, 1.0).
+NONCUBIC = [((32, 48, 64), (41, 45, 139), 0.5, (), (2, 1, 4)), ((64, 32, 48), (77, 55, 43), 0.5, (0, 2), (2, 3, 1)),
+            ((48, 64, 32), (43, 75, 67), 0.5, (1,), (1, 2, 4))]
+STEPPED = [((32, 32, 32), (41, 57, 43), 0.25, (), (3, 5, 3)), ((32, 32, 32), (37, 33, 70), 0.25, (0, 2), (2, 2, 6)),
+           ((32, 32, 32), (41, 57, 43), 0.3, (1,), (2, 4, 3)), ((32, 32, 32), (37, 33, 70), 0.3, (), (2, 2, 5)),
+           ((32, 32, 32), (41, 57, 43), 0.75, (), (2, 3, 2)), ((32, 32, 32), (37, 33, 70), 0.75, (), (2, 2, 3)),
+           ((32, 32, 32), (41, 57, 43), 1.0, (), (2, 2, 2)), ((32, 32, 32), (37, 33, 70), 1.0, (2,), (2, 2, 3))]
+
+
+@pytest.mark.parametrize("patch, volume, step, axes, tiles", NONCUBIC + STEPPED)
+def test_assembly_equals_per_tile_geometries(ops, patch, volume, step, axes, tiles):
+    p = _assembly_equals_per_tile(ops, patch, volume, step, axes)
+    for a in range(3):
+        assert len({s["origin"][a] for s in p["samples"] if s["mirror"] == ()}) == tiles[a]
+    assert p["n_tiles"] == tiles[0] * tiles[1] * tiles[2]
+    if max(tiles) >= 3:   # a middle tile: both faces of one axis inside the volume
+        assert any(s["face"][2 * a] and s["face"][2 * a + 1] for s in p["samples"] for a in range(3))
+
+
+def test_rightly_refused_geometries(ops):
+    """The plan refuses where there is nothing to share or no room for a slab: (30, 48, 60) under the patch (32, 48, 64) is one
+    tile after padding; a patch (32, 48, 4) is thinner along x than the x slab of 8 (one 4 x 8 x 8 conv tile >= 2 r)."""
+    one = ops.stage0_plan((30, 48, 60), (32, 48, 64), 0.5, (0, 2), 2)
+    assert not one["shared"] and one["n_tiles"] == 1 and one["padded"] == (32, 48, 64) and one["samples"] == []
+    thin = ops.stage0_plan((41, 45, 9), (32, 48, 4), 0.5, (), 2)
+    assert thin["n_tiles"] > 1 and thin["slab_thickness"] == (4, 8, 8) and not thin["shared"]
+    assert ops.stage0_plan((41, 45, 19), (32, 48, 8), 0.5, (), 2)["shared"]
