@@ -440,6 +440,39 @@ int mi355_masked_order_stats_i32(const int32_t *values_dev, int64_t n, const uin
  * there.  Refused: i1_from < 0.  Synchronous. */
 int mi355_column_count_max(const uint8_t *flags_dev, int require, int forbid, int d0, int d1, int d2, int i1_from, int64_t *out_host, void *stream);
 
+/* ---- surface distances between two label maps (csrc/surface_distance.hip): what brats_amd.evaluate derives the 95 % Hausdorff
+ * distance, the average symmetric surface distance and the surface Dice from (MedPy's definitions, which nnU-Net v1's evaluator
+ * reports beside Dice).  Volumes are [d0][d1][d2] C-order with fewer than 2^31 voxels; a box is lo_host[3] <= index < hi_host[3]
+ * inside the volume, and a box-shaped map is dense over it, [hi0 - lo0][hi1 - lo1][hi2 - lo2].  None of the three takes device
+ * scratch: all working memory is the caller's, passed with its size, and no result depends on what it held before the call. ---- */
+#define MI355_SURFACE_EDT_MAX_LINE 512 /* longest axis 1 / axis 2 of a box of mi355_edt_to_flagged_f64: a [512][8] fp64 tile is its 32 KiB of LDS */
+#define MI355_GATHER_CHUNK 2048        /* box voxels per block count of mi355_gather_flagged_f64 */
+/* One pass over both label maps.  pred_table256_host / gt_table256_host [256]: label value -> mask of the regions (bits 0..3) the
+ * label belongs to in that map; an entry above 15 is refused.  flags_dev [d0][d1][d2] uint8 (flags_bytes >= the voxel count, must
+ * not alias a label map): bit r = the voxel is on the surface of region r of the prediction, bit 4 + r the same for the ground
+ * truth, where surface = mask & ~binary_erosion(mask) with scipy's defaults (6-neighbour cross, one iteration, border_value = 0:
+ * a position outside the volume counts as background).  Every byte is written.  Asynchronous on `stream`. */
+int mi355_region_surfaces(const uint8_t *pred_dev, const uint8_t *gt_dev, int d0, int d1, int d2, const uint8_t *pred_table256_host,
+                          const uint8_t *gt_table256_host, uint8_t *flags_dev, int64_t flags_bytes, void *stream);
+/* dist2_dev (box-shaped fp64, dist2_capacity >= the box's voxel count) = for every voxel x of the box the minimum over the sites y
+ * - the voxels of the box with flags_dev[y] & select != 0 - of ((x0-y0) s0)^2 + ((x1-y1) s1)^2 + ((x2-y2) s2)^2, s = spacing_host[3],
+ * each product, square and sum rounded once in fp64 and the terms added in this order: the square of
+ * scipy.ndimage.distance_transform_edt(~sites, sampling=spacing) on the box.  Sites outside the box are ignored.  count_dev: one
+ * 32-bit device word of working memory.  Refused before any pass is launched: a box without a site (one counting launch and a 4-byte
+ * read-back find that out, which makes the call synchronise once), axis 1 or 2 of the box longer than MI355_SURFACE_EDT_MAX_LINE
+ * (axis 0 is scanned and has no such limit), select outside 1..255, a spacing that is not finite and positive, a map that is too
+ * small.  The passes themselves are asynchronous on `stream`. */
+int mi355_edt_to_flagged_f64(const uint8_t *flags_dev, int d0, int d1, int d2, const int32_t *lo_host, const int32_t *hi_host, int select,
+                             const double *spacing_host, double *dist2_dev, int64_t dist2_capacity, uint32_t *count_dev, void *stream);
+/* out_dev[0 .. count) = values_dev (box-shaped fp64) at the voxels of the box with flags_dev & select != 0, in raster order of the
+ * box; *count_host = their number.  Order and count follow from the inputs alone: a count per MI355_GATHER_CHUNK voxels, an exclusive
+ * scan, a scatter to computed positions.  block_counts_dev: block_words >= ceil(box voxels / MI355_GATHER_CHUNK) + 1 32-bit device
+ * words of working memory.  count > capacity is an error, not a truncation: *count_host is set and nothing is written to out_dev.
+ * out_dev NULL (with capacity 0; values_dev may be NULL too): a count-only call.  Synchronises once, for the count; the scatter is asynchronous on `stream`. */
+int mi355_gather_flagged_f64(const double *values_dev, const uint8_t *flags_dev, int d0, int d1, int d2, const int32_t *lo_host,
+                             const int32_t *hi_host, int select, double *out_dev, int64_t capacity, uint32_t *block_counts_dev,
+                             int64_t block_words, int64_t *count_host, void *stream);
+
 /* Device scratch, for tests (DESIGN.md "Scratch holds no state").  Working memory lives in slots (csrc/common.h, enum ScratchSlot;
  * ops.SCRATCH_SLOTS names them in that order), one set per stream lane; the first MI355_SCRATCH_LANES distinct streams get a lane
  * each, a further stream takes over the least recently used one.  The two zero pages (slots 4 and 5) are shared by all lanes.
