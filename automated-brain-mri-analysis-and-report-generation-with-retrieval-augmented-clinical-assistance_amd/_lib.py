@@ -39,6 +39,7 @@ EXPORTS = [
     "mi355_label_components_nb", "mi355_cityblock_distance", "mi355_flag_from_i32", "mi355_flag_from_box", "mi355_masked_order_stats_i32",
     "mi355_column_count_max",
     "mi355_region_surfaces", "mi355_edt_to_flagged_f64", "mi355_gather_flagged_f64",
+    "mi355_binary_morphology_nb", "mi355_label_pair_counts", "mi355_label_lookup", "mi355_label_lookup_i32",
     "mi355_stage0_plan", "mi355_skip_share_plan", "mi355_conv3d_wino3_ndhwc",
     "mi355_norm_finalize", "mi355_norm_apply", "mi355_extract_tiles", "mi355_head_logits", "mi355_head_aggregate",
     "mi355_logits_aggregate", "mi355_cnt_add_tile", "mi355_stage0_gather", "mi355_stage0_mask",
@@ -296,6 +297,10 @@ def load():
     lib.mi355_edt_to_flagged_f64.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p, C.c_int, C.POINTER(C.c_double), vp, C.c_int64, vp, vp]
     lib.mi355_gather_flagged_f64.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p, C.c_int, vp, C.c_int64, vp, C.c_int64,
                                              C.POINTER(C.c_int64), vp]
+    lib.mi355_binary_morphology_nb.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp]
+    lib.mi355_label_pair_counts.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64), vp]
+    lib.mi355_label_lookup.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(C.c_uint8), vp, C.c_int64, vp, vp]
+    lib.mi355_label_lookup_i32.argtypes = [vp, C.c_int64, C.c_int, c_int32_p, vp, C.c_int64, vp, vp]
     lib.mi355_norm_finalize.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]
     lib.mi355_norm_apply.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int, vp, vp, C.c_int, C.c_float, vp]
     lib.mi355_extract_tiles.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p, C.c_int, c_int32_p, C.c_int, vp,

@@ -90,6 +90,59 @@ def component_filter(labels, seg, keep):
     return out
 
 
+PAIR_TABLE_MAX = 1 << 20     # MI355_PAIR_TABLE_MAX
+_LOOKUP_TABLE_OFFSET = 16    # bytes in front of the table's copy in the work buffer of mi355_label_lookup
+
+
+def pair_counts(a, n_a, b, n_b, names=("the first map", "the second map")):
+    """a, b: CUDA int32 label maps of one shape with labels 0..n_a and 0..n_b -> int64 [n_a + 1, n_b + 1], entry [i, j] = the voxels
+    with a == i and b == j (row 0 and column 0 = label 0 included; the table sums to the voxel count): ``np.add.at(t, (a, b), 1)``.
+    ValueError: a table of more than ``PAIR_TABLE_MAX`` entries.  A label outside its range is refused by the library."""
+    import torch
+    a = check_volume(a, torch.int32, "pair_counts")
+    b = check_volume(b, torch.int32, "pair_counts")
+    if a.shape != b.shape:
+        raise ValueError("pair_counts: the two label maps differ in shape")
+    n_a, n_b = int(n_a), int(n_b)
+    if n_a < 0 or n_b < 0:
+        raise ValueError(f"pair_counts: {n_a} and {n_b} labels")
+    entries = (n_a + 1) * (n_b + 1)
+    if entries > PAIR_TABLE_MAX:
+        raise ValueError(f"pair_counts: {n_a} components in {names[0]} and {n_b} in {names[1]} make a table of {entries} entries "
+                         f"({PAIR_TABLE_MAX} at most)")
+    table = torch.empty(entries + 1, dtype=torch.int64, device=a.device)
+    out = np.zeros(entries, dtype=np.int64)
+    stream = torch.cuda.current_stream(a.device).cuda_stream
+    _lib.check(_lib.load().mi355_label_pair_counts(a.data_ptr(), n_a, b.data_ptr(), n_b, a.numel(), table.data_ptr(), table.numel(),
+                                                   out.ctypes.data_as(C.POINTER(C.c_int64)), stream), "mi355_label_pair_counts")
+    return out.reshape(n_a + 1, n_b + 1)
+
+
+def lookup(labels, n, table):
+    """labels: CUDA int32 label map with labels 0..n; table: n + 1 entries of uint8 or int32 (numpy) -> ``table[labels]`` as a CUDA tensor
+    of the table's dtype; ``table[0]`` is honoured.  A label outside 0..n is refused by the library and nothing is written."""
+    import torch
+    labels = check_volume(labels, torch.int32, "lookup")
+    table = np.ascontiguousarray(table)
+    n = int(n)
+    if table.dtype not in (np.uint8, np.int32) or table.shape != (n + 1,):
+        raise ValueError(f"lookup: a uint8 or int32 table of n + 1 = {n + 1} entries expected, got {table.dtype} {table.shape}")
+    if n > MAX_COMPONENTS:
+        raise ValueError(f"lookup: {n} components, {MAX_COMPONENTS} at most")
+    wide = table.dtype == np.int32
+    out = torch.empty(labels.shape, dtype=torch.int32 if wide else torch.uint8, device=labels.device)
+    work = torch.empty(_LOOKUP_TABLE_OFFSET + table.nbytes, dtype=torch.uint8, device=labels.device)
+    stream = torch.cuda.current_stream(labels.device).cuda_stream
+    lib = _lib.load()
+    if wide:
+        _lib.check(lib.mi355_label_lookup_i32(labels.data_ptr(), labels.numel(), n, table.ctypes.data_as(_lib.c_int32_p), work.data_ptr(), work.numel(),
+                                              out.data_ptr(), stream), "mi355_label_lookup_i32")
+    else:
+        _lib.check(lib.mi355_label_lookup(labels.data_ptr(), labels.numel(), n, table.ctypes.data_as(C.POINTER(C.c_uint8)), work.data_ptr(), work.numel(),
+                                          out.data_ptr(), stream), "mi355_label_lookup")
+    return out
+
+
 def _indicator(seg, values):
     """uint8 map that is 1 where seg takes one of `values` (the remap kernel with a 0/1 table)."""
     import torch

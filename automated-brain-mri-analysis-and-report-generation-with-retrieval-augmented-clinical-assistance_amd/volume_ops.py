@@ -1,5 +1,6 @@
 """The volume primitives that belong to no single feature-extraction step: thin ctypes wrappers over the entry points of
-csrc/morphology.hip, csrc/quality.hip, csrc/mass_effect.hip and csrc/normal_structures.hip, and the tensor checks they share.
+csrc/morphology.hip, csrc/quality.hip, csrc/mass_effect.hip and csrc/normal_structures.hip (and the morphology of
+csrc/lesionwise.hip), and the tensor checks they share.
 
 A step module (``sequence_findings``, ``mass_effect``, ``morphology``, ``quality``, ``normal_structures``) and ``features`` import
 what they need from here; the primitives with one subject of their own stay in ``percentile``, ``components`` and ``evaluate``.
@@ -79,6 +80,32 @@ def binary_erosion(mask, iterations=1):
 def binary_dilation(mask, iterations=1):
     """As ``binary_erosion`` for ``scipy.ndimage.binary_dilation``."""
     return _morph(mask, iterations, 1, "binary_dilation")
+
+
+# ---- csrc/lesionwise.hip: the same two with the 6-, 18- or 26-neighbourhood -------------------------------------------------
+MORPH_NB_LDS_STEPS = 4                         # MI355_MORPH_NB_LDS_STEPS
+
+
+def _morph_nb(mask, neighbours, iterations, dilate, what):
+    import torch
+    mask = check_volume(mask, torch.uint8, what)
+    out = torch.empty_like(mask)
+    tmp = torch.empty_like(mask) if int(iterations) > MORPH_NB_LDS_STEPS else None   # the second buffer of a run of several launches
+    _lib.check(_lib.load().mi355_binary_morphology_nb(mask.data_ptr(), mask.shape[0], mask.shape[1], mask.shape[2], int(dilate), int(neighbours),
+                                                      int(iterations), out.data_ptr(), None if tmp is None else tmp.data_ptr(),
+                                                      0 if tmp is None else tmp.numel(), stream_of(mask)), "mi355_binary_morphology_nb")
+    return out
+
+
+def binary_erosion_nb(mask, neighbours, iterations=1):
+    """mask: CUDA uint8 [d0, d1, d2], foreground = nonzero -> uint8 0 / 1 map, bit-equal to ``scipy.ndimage.binary_erosion(mask,
+    generate_binary_structure(3, c), iterations)`` with c = 1, 2, 3 for ``neighbours`` = 6, 18, 26 (border_value 0); iterations >= 1."""
+    return _morph_nb(mask, neighbours, iterations, 0, "binary_erosion_nb")
+
+
+def binary_dilation_nb(mask, neighbours, iterations=1):
+    """As ``binary_erosion_nb`` for ``scipy.ndimage.binary_dilation``."""
+    return _morph_nb(mask, neighbours, iterations, 1, "binary_dilation_nb")
 
 
 def distance_transform_edt_sq(mask):

@@ -473,6 +473,43 @@ int mi355_gather_flagged_f64(const double *values_dev, const uint8_t *flags_dev,
                              const int32_t *hi_host, int select, double *out_dev, int64_t capacity, uint32_t *block_counts_dev,
                              int64_t block_words, int64_t *count_host, void *stream);
 
+/* ---- lesion-wise scoring (csrc/lesionwise.hip): the three pieces brats_amd.evaluate.lesionwise_metrics needs beside the labelling
+ * above and the surface-distance entry points - the BraTS 2023+ ranking scores a prediction per lesion (the ground truth dilated,
+ * its components grouped into lesions, predicted components matched to them).  Volumes are [d0][d1][d2] C-order with fewer than 2^31
+ * voxels.  None of the four takes device scratch: all working memory is the caller's, passed with its size, and no result depends
+ * on what it held before the call.  Integers only: two calls give bit-equal results.  A refused call writes to no output. ---- */
+#define MI355_MORPH_NB_BRICK0 8        /* output voxels of one workgroup of mi355_binary_morphology_nb along axis 0, 1, 2 */
+#define MI355_MORPH_NB_BRICK1 16
+#define MI355_MORPH_NB_BRICK2 64
+#define MI355_MORPH_NB_LDS_STEPS 4     /* steps one launch runs on bit-planes in LDS (= the halo it stages); more iterations are several launches */
+#define MI355_PAIR_TABLE_MAX 1048576   /* most entries (n_a + 1) * (n_b + 1) of mi355_label_pair_counts */
+#define MI355_PAIR_LDS_BINS 8192       /* the first so many entries of a table are counted in LDS per workgroup, the rest in global memory */
+#define MI355_LOOKUP_MAX_LABEL 65536   /* largest n of mi355_label_lookup / _i32 */
+/* scipy.ndimage.binary_erosion (dilate = 0) / binary_dilation (dilate != 0)(mask, generate_binary_structure(3, c), iterations,
+ * border_value = 0) with c = 1, 2, 3 named by `neighbours` = 6, 18, 26: out_dev [d0][d1][d2] uint8 holds 0 / 1 and is bit-equal to
+ * scipy's mask for every iterations >= 1 (a position outside the volume counts as 0 in every step).  Up to MI355_MORPH_NB_LDS_STEPS
+ * iterations are one launch and tmp_dev may be NULL; more are ceil(iterations / MI355_MORPH_NB_LDS_STEPS) launches that alternate
+ * between out_dev and tmp_dev (tmp_bytes >= the voxel count; neither may alias the other or the input).  Refused: iterations < 1,
+ * another neighbourhood, aliased buffers, a missing or short tmp_dev when it is needed.  Asynchronous on `stream`. */
+int mi355_binary_morphology_nb(const uint8_t *mask_dev, int d0, int d1, int d2, int dilate, int neighbours, int iterations, uint8_t *out_dev,
+                               uint8_t *tmp_dev, int64_t tmp_bytes, void *stream);
+/* counts_host[a * (n_b + 1) + b] = the voxels i < V with labels_a[i] == a and labels_b[i] == b, a = 0..n_a, b = 0..n_b: numpy's
+ * np.add.at(table, (labels_a, labels_b), 1), which replaces one `np.isin` / `labelled == id` pass per component.  The table sums to
+ * V.  table_dev: table_words >= (n_a + 1) * (n_b + 1) + 1 64-bit device words of working memory (cleared by the call).  Refused by
+ * return code, with counts_host untouched: a table of more than MI355_PAIR_TABLE_MAX entries (the message names n_a and n_b), too
+ * few table_words, a voxel whose label lies outside 0..n_a / 0..n_b (such a label is counted, never used as an index).  Synchronous. */
+int mi355_label_pair_counts(const int32_t *labels_a_dev, int n_a, const int32_t *labels_b_dev, int n_b, int64_t V, int64_t *table_dev,
+                            int64_t table_words, int64_t *counts_host, void *stream);
+/* out_dev[i] = table_host[labels_dev[i]] for i < V, table_host[0] included: numpy's table[labels], n + 1 entries of uint8 (_i32: of
+ * int32), n <= MI355_LOOKUP_MAX_LABEL.  work_dev: work_bytes >= 16 + (n + 1) * the entry size bytes of device working memory (a count
+ * word and the table's copy; the entry points have no other way to a device table without library-owned memory).  One launch looks
+ * for labels outside 0..n first (a 4-byte read-back: the call synchronises once); if there is one the call is refused and out_dev is
+ * untouched.  out_dev must not be labels_dev.  The lookup itself is asynchronous on `stream`. */
+int mi355_label_lookup(const int32_t *labels_dev, int64_t V, int n, const uint8_t *table_host, void *work_dev, int64_t work_bytes, uint8_t *out_dev,
+                       void *stream);
+int mi355_label_lookup_i32(const int32_t *labels_dev, int64_t V, int n, const int32_t *table_host, void *work_dev, int64_t work_bytes,
+                           int32_t *out_dev, void *stream);
+
 /* Device scratch, for tests (DESIGN.md "Scratch holds no state").  Working memory lives in slots (csrc/common.h, enum ScratchSlot;
  * ops.SCRATCH_SLOTS names them in that order), one set per stream lane; the first MI355_SCRATCH_LANES distinct streams get a lane
  * each, a further stream takes over the least recently used one.  The two zero pages (slots 4 and 5) are shared by all lanes.
