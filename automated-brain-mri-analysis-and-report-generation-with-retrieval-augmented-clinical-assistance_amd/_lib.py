@@ -47,6 +47,7 @@ EXPORTS = [
     "mi355_logits_aggregate_tiles", "mi355_stage0_merge_plan", "mi355_stage0_gather_merged",
     "mi355_scratch_sizes", "mi355_scratch_fill", "mi355_scratch_release", "mi355_scratch_zero_pages",
     "mi355_level1_share_plan",
+    "mi355_reverse_axes",
 ]
 
 
@@ -301,6 +302,7 @@ def load():
     lib.mi355_label_pair_counts.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64), vp]
     lib.mi355_label_lookup.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(C.c_uint8), vp, C.c_int64, vp, vp]
     lib.mi355_label_lookup_i32.argtypes = [vp, C.c_int64, C.c_int, c_int32_p, vp, C.c_int64, vp, vp]
+    lib.mi355_reverse_axes.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.mi355_norm_finalize.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]
     lib.mi355_norm_apply.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int, vp, vp, C.c_int, C.c_float, vp]
     lib.mi355_extract_tiles.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_int32_p, C.c_int, c_int32_p, C.c_int, vp,

@@ -232,14 +232,19 @@ def ensemble_label_files(model1_output: Path, model2_output: Path, output_folder
     return finals
 
 
-def run_both_models(model_dirs, input_folder, output_folder, folds, do_tta, step_size, dtype, label_format, cache: ModelCache):
+def run_both_models(model_dirs, input_folder, output_folder, folds, do_tta, step_size, dtype, label_format, cache: ModelCache, analyze=None):
     """What reference :263-322 produces (model 1 over all cases, model 2 over all cases, label-round ensemble of the two
     NIfTI files per case), computed in ONE pass per case: the four modalities are read, cropped and normalised once
     (the reference preprocesses per model, :89), both members predict from the same device tensor, the ensemble takes
     the two label volumes where they are - on the device - and the three NIfTI products of the case
     (``temp_model1/<case>.nii.gz``, ``temp_model2/<case>.nii.gz``, ``<case>.nii.gz``) are compressed and written by
     background threads while the next case runs.  Same files, same label values, same printed volumes; checkpoint loading of
-    both members and the copy of the inputs into ``temp_model{1,2}/temp_input`` overlap as well."""
+    both members and the copy of the inputs into ``temp_model{1,2}/temp_input`` overlap as well.
+
+    ``analyze`` (default None: nothing below changes): a callable ``analyze(raw, ens, like, case_name, n_cases, submit)`` run once per
+    case after its three label files are on their way - ``raw`` the uploaded modalities [4, Z, Y, X] (preprocessing then keeps the
+    tensor instead of freeing it), ``ens`` the ensemble's label map [Z, Y, X], both on the device, ``like`` the case's geometry,
+    ``submit(fn, *args)`` the background writer pool, joined with the label files.  ``--analyze`` hands in ``pipeline.analyze_resident``."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
     from . import evaluate
@@ -278,11 +283,17 @@ def run_both_models(model_dirs, input_folder, output_folder, folds, do_tta, step
 
     def preprocess_on_side(raw, like, plans):
         with torch.cuda.stream(side):
-            data, props = preprocessing.preprocess_case(raw, plans=plans, spacing_zyx=tuple(reversed(like.zooms)))
+            kept = None
+            if analyze is None:
+                data, props = preprocessing.preprocess_case(raw, plans=plans, spacing_zyx=tuple(reversed(like.zooms)))
+            else:
+                data, props, kept = preprocessing.preprocess_case(raw, plans=plans, spacing_zyx=tuple(reversed(like.zooms)), return_raw=True)
             ev = torch.cuda.Event()
             ev.record(side)
         data.record_stream(main_stream)
-        return data, props, ev
+        if kept is not None:
+            kept.record_stream(main_stream)   # the analysis reads it on the main stream
+        return data, props, ev, kept
 
     plans0 = models[0].folder.plans
     nxt = pool.submit(read_case, prepared[0][1])
@@ -293,7 +304,7 @@ def run_both_models(model_dirs, input_folder, output_folder, folds, do_tta, step
         t1 = time.perf_counter()
         if ci + 1 < len(prepared):
             nxt = pool.submit(read_case, prepared[ci + 1][1])  # the next case's gunzip overlaps this case's prediction
-        data, props, ev = ready
+        data, props, ev, cur_raw_dev = ready   # (this case's: `ready` is the next case's before the analysis below runs)
         cur_raw_channels, cur_like = raw.shape[0], like
         main_stream.wait_event(ev)
         print(f"Data shape after preprocessing: {tuple(data.shape)}")
@@ -336,6 +347,19 @@ def run_both_models(model_dirs, input_folder, output_folder, folds, do_tta, step
         print(f"  TC (Tumor Core):            {v['TC']:.2f} cm3")
         print(f"  WT (Whole Tumor):           {v['WT']:.2f} cm3")
         finals.append(final_output)
+        if analyze is not None:
+            # Here and not earlier: the next case's preprocessing was enqueued on `side` before the synchronise above and has
+            # finished with it, so nothing else is in flight on the device.  Hole filling, the crop mask and several feature
+            # primitives work in scratch the library owns per stream lane or per process; the analysis must not run beside `side`.
+            try:
+                analyze(cur_raw_dev, ens, cur_like, case_name, len(prepared), lambda fn, *a: writes.append(pool.submit(fn, *a)))
+            except BaseException:
+                for w in writes:   # the label files of this case and of the ones before it are complete before the error leaves
+                    w.exception()
+                mirror.exception()
+                pool.shutdown()
+                raise
+            del cur_raw_dev
     for w in writes:
         w.result()
     mirror.result()
@@ -343,10 +367,8 @@ def run_both_models(model_dirs, input_folder, output_folder, folds, do_tta, step
     return finals
 
 
-def main(argv=None, script_dir=None, model_cache: ModelCache = None):
-    """Reference :246-327.  --input/--output are the whole contract; the extra flags default to the
-    reference's hard-coded settings (5 folds, TTA on, step 0.5).  ``model_cache``: the resident worker's (models stay
-    loaded between requests); a plain process builds its own and frees it at the end."""
+def build_parser():
+    from .mass_effect import DISTANCES
     ap = argparse.ArgumentParser(description="BraTS 2021 Brain Tumor Segmentation (MI355X-native)")
     ap.add_argument("--input", type=str, required=True, help="Input directory with BraTS sample data")
     ap.add_argument("--output", type=str, required=True, help="Output directory for segmentation results")
@@ -363,7 +385,39 @@ def main(argv=None, script_dir=None, model_cache: ModelCache = None):
     ap.add_argument("--label-format", dest="label_format", choices=("nnunet", "brats2025", "brats2021"), default="nnunet",
                     help="convention of the final <case>.nii.gz; 'nnunet' (default) is what the reference writes, the others "
                          "fold convert_labels_to_brats.py:34-55 into the export")
+    ap.add_argument("--analyze", action="store_true",
+                    help="after each case's ensemble, from the tensors still on the device: <case>_brats.nii.gz (BraTS 2025 labels), the "
+                         "evaluation against a ground truth when there is one (report on stdout, <case>_evaluation.json) and the seven "
+                         "files of feature_extraction/ - what run_full_pipeline.py spawns three more programs for (brats_amd.pipeline)")
+    ap.add_argument("--gt", type=str, default=None,
+                    help="with --analyze: the ground-truth segmentation (default: <input>/<case>_seg.nii.gz, then <case>-seg.nii.gz; "
+                         "none: no evaluation).  Through the resident worker: an absolute path")
+    ap.add_argument("--lesionwise", action="store_true", help="with --analyze: the evaluator's lesion-wise scores too")
+    ap.add_argument("--distance", default="sampled", choices=DISTANCES, help="with --analyze: tumour-to-CSF distance of feature step 2, as brats_amd.features")
+    ap.add_argument("--seed", type=int, default=None, help="with --analyze: seed of the generator the sampled distance draws from (default: unseeded)")
+    return ap
+
+
+def parse_args(argv=None):
+    """The drop-in's arguments, with the combinations ``--analyze`` does not serve refused before anything touches the device."""
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if args.analyze and args.sequential:
+        ap.error("--analyze works on the tensors of the one-pass-per-case path: not with --sequential")
+    if args.analyze and args.label_format != "nnunet":
+        ap.error("--analyze converts the labels itself (<case>_brats.nii.gz): --label-format must stay nnunet")
+    if not args.analyze and (args.gt is not None or args.lesionwise):
+        ap.error("--gt and --lesionwise need --analyze")
+    if args.gt is not None and not Path(args.gt).is_file():
+        ap.error(f"--gt {args.gt}: no such file")
+    return args
+
+
+def main(argv=None, script_dir=None, model_cache: ModelCache = None):
+    """Reference :246-327.  --input/--output are the whole contract; the extra flags default to the
+    reference's hard-coded settings (5 folds, TTA on, step 0.5).  ``model_cache``: the resident worker's (models stay
+    loaded between requests); a plain process builds its own and frees it at the end."""
+    args = parse_args(argv)
     script_dir = Path(script_dir) if script_dir else Path(__file__).resolve().parent.parent
     results_folder = Path(args.results_folder or os.environ.get("MI355_RESULTS_FOLDER") or script_dir / "nnUNet_results")
     os.environ["RESULTS_FOLDER"] = str(results_folder)
@@ -383,9 +437,15 @@ def main(argv=None, script_dir=None, model_cache: ModelCache = None):
     else:
         print("\n" + "=" * 70 + f"\nMODELS: {MODEL1.split('__')[0]} + {MODEL2.split('__')[0]}\n" + "=" * 70)
         cache = model_cache or ModelCache()
+        analyze = None
+        if args.analyze:
+            import functools
+            from . import pipeline
+            analyze = functools.partial(pipeline.analyze_resident, input_folder=args.input, output_folder=output_folder, gt=args.gt,
+                                        lesionwise=args.lesionwise, distance=args.distance, seed=args.seed)
         try:
             run_both_models([base / MODEL1, base / MODEL2], args.input, output_folder, tuple(args.folds), not args.disable_tta,
-                            args.step_size, args.dtype, args.label_format, cache)
+                            args.step_size, args.dtype, args.label_format, cache, analyze)
         finally:
             if model_cache is None:
                 cache.close()

@@ -8,7 +8,8 @@ batched selects, ``masked_percentiles_multi``, where the six steps alone make 22
 statistics, the 26-neighbour labelling of the tumour, and one city-block distance transform of the tumour each way, whose
 thresholds are every dilation and erosion steps 2, 4, 5 and 6 take of it.  Each step's resident function takes the context as
 ``ctx=``; without one it runs as it always has.  ``extract_all`` runs the six through one context, ``run_all_steps`` does so from
-the files of a case folder, loading each of the five files once, and writes the reference's seven JSON files.
+the files of a case folder, loading each of the five files once, and writes the reference's seven JSON files; its running half,
+``run_steps_resident``, is what ``pipeline.analyze_resident`` calls on the tensors the inference driver holds.
 
 The reference's compiled report (``comprehensive_report``, ``llm_summary``, ``llm_ready_summary.json``, ``radiology_report.txt``)
 and the steps' ``text_summary`` / ``technique`` prose stay out: they are string templates of the reference's program text.
@@ -195,15 +196,26 @@ def run_all_steps(input_folder, segmentation_path, output_dir, rng=None, distanc
     finishes - byte for byte the file that step's own command writes - and ``comprehensive_analysis.json`` at the end.  A step
     that raises leaves the earlier files behind and the exception propagates (run_all.py:411-446).  ``report(key, result)`` is
     called after each step.  Returns the comprehensive dict."""
-    out = Path(output_dir)
-    out.mkdir(parents=True, exist_ok=True)
+    Path(output_dir).mkdir(parents=True, exist_ok=True)
     case = load_case(input_folder, segmentation_path)
     ctx = CaseContext(to_device(case.labels, np.uint8), *[to_device(case.images[k].data, np.float32) for k in MODALITIES])
-    all_results = {'case_id': case.case_id, 'analysis_timestamp': datetime.now().isoformat(), 'input_folder': str(input_folder),
+    return run_steps_resident(ctx, case.case_id, input_folder, segmentation_path, case.images['t1'].zooms, case.segmentation.zooms, output_dir,
+                              rng, distance, report)
+
+
+def run_steps_resident(ctx, case_id, input_folder, segmentation_path, t1_zooms, segmentation_zooms, output_dir, rng=None, distance='sampled',
+                       report=None):
+    """The running half of ``run_all_steps`` on a ``CaseContext`` that is already on the device, whoever put it there (the files of
+    a case folder, or ``pipeline.analyze_resident`` with the tensors the inference driver holds): the six steps in order, each
+    file written as its step finishes, ``comprehensive_analysis.json`` last.  ``input_folder`` and ``segmentation_path`` only name
+    the case in the files; ``t1_zooms`` / ``segmentation_zooms`` are the voxel sizes of the two headers the step commands read."""
+    out = Path(output_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    all_results = {'case_id': case_id, 'analysis_timestamp': datetime.now().isoformat(), 'input_folder': str(input_folder),
                    'segmentation_path': str(segmentation_path)}          # run_all.py:453-464
     for spec in SPECS:
-        zooms = step_zooms(spec, case.images['t1'].zooms, case.segmentation.zooms)
-        res = document(spec, case.case_id, input_folder, zooms, _call(spec, ctx, zooms, rng, distance))
+        zooms = step_zooms(spec, t1_zooms, segmentation_zooms)
+        res = document(spec, case_id, input_folder, zooms, _call(spec, ctx, zooms, rng, distance))
         write_json(out / f"{spec.key}.json", res)
         all_results[spec.key] = res
         if report:

@@ -155,9 +155,11 @@ def nonzero_crop_shape(raw: np.ndarray) -> Tuple[int, int, int]:
 
 
 def preprocess_case(raw: np.ndarray, device="cuda", plans: Optional[Dict] = None,
-                    spacing_zyx: Optional[Sequence[float]] = None) -> Tuple["object", Dict]:
+                    spacing_zyx: Optional[Sequence[float]] = None, return_raw: bool = False) -> Tuple["object", Dict]:
     """raw [C,Z,Y,X] (any real dtype) -> (CUDA fp32 [C,Zc,Yc,Xc] normalised, properties dict with
-    crop_bbox / original_size_of_raw_data / size_after_cropping, the fields export needs)."""
+    crop_bbox / original_size_of_raw_data / size_after_cropping, the fields export needs).  ``return_raw``: a third value, the
+    uploaded CUDA fp32 [C,Z,Y,X] tensor of the whole input as it was before the crop (``pipeline.analyze_resident`` reads the
+    modalities from it), which is otherwise freed here."""
     import torch
     from . import ops
     raw = np.asarray(raw, dtype=np.float32)
@@ -167,6 +169,9 @@ def preprocess_case(raw: np.ndarray, device="cuda", plans: Optional[Dict] = None
     sl = tuple(slice(lo, hi) for lo, hi in bbox)
     data = vol[(slice(None),) + sl].contiguous()
     mask = full_mask[sl].contiguous()
+    kept = vol if return_raw else None
+    if return_raw and data.untyped_storage().data_ptr() == vol.untyped_storage().data_ptr():
+        data = data.clone()   # a crop that keeps everything is a view: the z-score below works in place and must not reach the raw tensor
     del vol, full_mask
     size_after_cropping = tuple(int(v) for v in data.shape[1:])
     rs = check_spacing(plans, spacing_zyx, data.shape[1:])
@@ -188,6 +193,8 @@ def preprocess_case(raw: np.ndarray, device="cuda", plans: Optional[Dict] = None
         props["spacing_after_resampling"] = rs[3]
     if spacing_zyx is not None:
         props["original_spacing"] = tuple(float(v) for v in spacing_zyx)
+    if return_raw:
+        return data, props, kept
     return data, props
 
 

@@ -1,6 +1,6 @@
 """The volume primitives that belong to no single feature-extraction step: thin ctypes wrappers over the entry points of
 csrc/morphology.hip, csrc/quality.hip, csrc/mass_effect.hip and csrc/normal_structures.hip (and the morphology of
-csrc/lesionwise.hip), and the tensor checks they share.
+csrc/lesionwise.hip and the axis reversal of csrc/resident_case.hip), and the tensor checks they share.
 
 A step module (``sequence_findings``, ``mass_effect``, ``morphology``, ``quality``, ``normal_structures``) and ``features`` import
 what they need from here; the primitives with one subject of their own stay in ``percentile``, ``components`` and ``evaluate``.
@@ -59,6 +59,24 @@ def _check_values(values, flags, what):
         raise ValueError(f"{what}: CUDA int32 values of the shape of the flags expected")
     if not values.is_contiguous() or not flags.is_contiguous():
         raise ValueError(f"{what}: contiguous tensors expected")
+
+
+# ---- csrc/resident_case.hip -------------------------------------------------------------------------------------------
+def reverse_axes(t):
+    """t: contiguous CUDA uint8 or float32 tensor [d0, d1, d2] or [C, d0, d1, d2] -> a new tensor [d2, d1, d0] or [C, d2, d1, d0],
+    ``out[c, k, j, i] = t[c, i, j, k]`` bit for bit, in one launch on the current stream: a volume in file order ([Z, Y, X], what
+    the inference driver holds) becomes the (x, y, z) volume the evaluator and the feature steps take, and back."""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.float32) or t.dim() not in (3, 4):
+        raise ValueError("reverse_axes: CUDA uint8 or float32 tensor [d0, d1, d2] or [C, d0, d1, d2] expected")
+    if not t.is_contiguous():
+        raise ValueError("reverse_axes: contiguous tensor expected")
+    lead = tuple(t.shape[:-3])
+    d0, d1, d2 = (int(v) for v in t.shape[-3:])
+    out = torch.empty(lead + (d2, d1, d0), dtype=t.dtype, device=t.device)
+    _lib.check(_lib.load().mi355_reverse_axes(t.data_ptr(), out.data_ptr(), int(lead[0]) if lead else 1, d0, d1, d2, t.element_size(), stream_of(t)),
+               "mi355_reverse_axes")
+    return out
 
 
 # ---- csrc/morphology.hip ----------------------------------------------------------------------------------------------

@@ -510,6 +510,17 @@ int mi355_label_lookup(const int32_t *labels_dev, int64_t V, int n, const uint8_
 int mi355_label_lookup_i32(const int32_t *labels_dev, int64_t V, int n, const int32_t *table_host, void *work_dev, int64_t work_bytes,
                            int32_t *out_dev, void *stream);
 
+/* ---- the resident case (csrc/resident_case.hip): what brats_amd.pipeline needs to hand the case the inference driver holds - file
+ * order, [C][Z][Y][X] - to the evaluator and the feature steps, which take [x][y][z] volumes, without a trip through the host. ---- */
+#define MI355_REVERSE_AXES_MAX_ELEMENTS 2147483648ll   /* channels * d0 * d1 * d2 stays below this */
+/* dst[c][k][j][i] = src[c][i][j][k]: src_dev [channels][d0][d1][d2] -> dst_dev [channels][d2][d1][d0], both contiguous, elements of
+ * elem_bytes = 1 (label maps) or 4 (float32 volumes) bytes, moved bit for bit (NaN payloads included).  Any d0, d1, d2 >= 1; a
+ * pointer need only be aligned to its element (a slice of a larger tensor).  Takes no device scratch and is asynchronous on
+ * `stream`.  Refused (MI355_ERR_INVALID, nothing is launched, dst_dev is not written): a null pointer, a dimension below 1,
+ * another elem_bytes, MI355_REVERSE_AXES_MAX_ELEMENTS elements or more, source and destination that overlap, a pointer to 4-byte
+ * elements that is not aligned to 4 bytes. */
+int mi355_reverse_axes(const void *src_dev, void *dst_dev, int channels, int d0, int d1, int d2, int elem_bytes, void *stream);
+
 /* Device scratch, for tests (DESIGN.md "Scratch holds no state").  Working memory lives in slots (csrc/common.h, enum ScratchSlot;
  * ops.SCRATCH_SLOTS names them in that order), one set per stream lane; the first MI355_SCRATCH_LANES distinct streams get a lane
  * each, a further stream takes over the least recently used one.  The two zero pages (slots 4 and 5) are shared by all lanes.
