@@ -48,6 +48,7 @@ EXPORTS = [
     "mi355_scratch_sizes", "mi355_scratch_fill", "mi355_scratch_release", "mi355_scratch_zero_pages",
     "mi355_level1_share_plan",
     "mi355_reverse_axes",
+    "mi355_conv3d_plan_hinted", "mi355_conv3d_s2dma_hinted_ndhwc", "mi355_stage0_gather_boxes",
 ]
 
 
@@ -138,6 +139,10 @@ class Stage0MergeSample(C.Structure):
 class Stage0GatherMergedArgs(C.Structure):
     _fields_ = [("base", Stage0GatherArgs), ("slab_shape", (C.c_int32 * 3) * 3), ("spans_volume", (C.c_int32 * 3) * 3),
                 ("wv2_dev", C.c_void_p), ("slab2_dev", C.c_void_p * 3), ("out2_dev", C.c_void_p), ("r2", C.c_int32), ("channels2", C.c_int32)]
+
+
+class Stage0GatherBoxesArgs(C.Structure):
+    _fields_ = [("merged", Stage0GatherMergedArgs), ("tile", C.c_int32 * 3), ("sub", (C.c_int32 * 3) * 64)]
 
 
 class Stage0ViewGeom(C.Structure):
@@ -246,6 +251,7 @@ def load():
                                              c_float_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, C.c_int, vp, vp,
                                              C.c_int, vp, vp, vp, vp]
     lib.mi355_conv3d_plan.argtypes = [C.c_int] * 13 + [C.POINTER(ConvPlan)]
+    lib.mi355_conv3d_plan_hinted.argtypes = [C.c_int] * 14 + [C.POINTER(ConvPlan)]
     lib.mi355_conv_kernel_names.argtypes = [C.c_char_p, C.c_int64]
     lib.mi355_conv_kernel_names.restype = C.c_int64
     lib.mi355_stage0_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_double, C.c_int, C.c_int, C.POINTER(Stage0Geom),
@@ -321,10 +327,13 @@ def load():
                                             C.POINTER(Stage0MergeSlab), C.c_int, C.POINTER(Stage0MergeSample), C.c_int]
     lib.mi355_stage0_gather_merged.argtypes = [C.POINTER(Stage0GatherMergedArgs), C.c_int, vp]
     lib.mi355_stage0_gather_shells.argtypes = [C.POINTER(Stage0GatherArgs), vp]
+    lib.mi355_stage0_gather_boxes.argtypes = [C.POINTER(Stage0GatherBoxesArgs), C.c_int, C.c_int, vp]
     lib.mi355_stage0_view_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_double, C.c_int, C.POINTER(SkipShareNet), C.c_int, C.c_int,
                                            C.POINTER(Stage0ViewGeom), C.POINTER(Stage0ViewSample), C.c_int]
     lib.mi355_conv3d_s2dma_view_ndhwc.argtypes = [vp, C.POINTER(Stage0View), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
                                                   C.c_int, C.c_int, C.c_float, C.c_int, vp, vp]
+    lib.mi355_conv3d_s2dma_hinted_ndhwc.argtypes = [vp, C.POINTER(Stage0View), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
+                                                    C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp]
     lib.mi355_conv3d_wino3_view_ndhwc.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, C.c_int, C.c_int,
                                                   C.c_float, vp, C.POINTER(Stage0View), vp, vp]
     lib.mi355_level1_share_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_double, C.c_int, C.POINTER(Level1ShareNet), C.c_int,

@@ -1304,7 +1304,11 @@ bool plan_s2dma(const ConvWeights &w, const ConvCall &c, ConvPlan *p, bool force
     if (!(w.stride == 2 && w.wp_dev && w.cc == 8 && w.nf == 2 && !c.head_out)) return false;
     const int Do = (c.Di - 1) / 2 + 1, Ho = (c.Hi - 1) / 2 + 1, Wo = (c.Wi - 1) / 2 + 1;
     const bool in_fits_32bit = (long)c.Di * c.Hi * c.Wi * (c.C0 > c.C1 ? c.C0 : c.C1) < (1l << 31);
-    const int txl = Wo >= 24 ? 5 : 4;  // 2 x 2 x 32 tiles, or 2 x 4 x 16 on narrow volumes
+    int txl = Wo >= 24 ? 5 : 4;  // 2 x 2 x 32 tiles, or 2 x 4 x 16 on narrow volumes
+    if (c.s2_least_padding) {  // (opt-in: the shape that pads fewer output lanes, e.g. Wo = 72 is 80 columns of 16 and 96 of 32)
+        auto padded = [&](int l) { return (long)ceil_div(Wo, 1 << l) * (1 << l) * ceil_div(Ho, 64 >> l) * (64 >> l); };
+        txl = padded(4) < padded(5) ? 4 : 5;
+    }
     const int TX = 1 << txl, TY = 64 >> txl;
     const TileGeom g = fixed_tile(Do, Ho, Wo, 1, 6 - txl, txl, 5, 2 * TY + 1, 2 * TX + 1);
     const long tiles = g.tiles_per_n() * c.N;

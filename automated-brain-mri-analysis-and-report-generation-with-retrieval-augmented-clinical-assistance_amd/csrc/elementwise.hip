@@ -235,6 +235,21 @@ static __device__ __forceinline__ int64_t s0_slab_voxel(const S0GatherArgs &a, c
     return (((int64_t)idx * a.D[ax][0] + v[0]) * a.D[ax][1] + v[1]) * a.D[ax][2] + v[2];
 }
 
+// where voxel (z, y, x) of sample n comes from (as a pointer to its first channel quad): the first shell that holds it, z before y
+// before x, else the whole-volume tensor - stage0_gather_row's sources and precedence, per voxel
+static __device__ __forceinline__ const f32x4 *s0_voxel_source(const S0GatherArgs &a, const S0GatherSet &t, int n, int z, int y, int x) {
+    const S0Sample &sm = a.smp[n];
+    const int r = t.r;
+    const int64_t C4 = t.C4;
+    if (sm.slab[0] >= 0 && z < r) return (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, a.sub[n], 0, 0, sm.slab[0], z, y, x) * C4;
+    if (sm.slab[1] >= 0 && z >= a.P[0] - r) return (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, a.sub[n], 0, 1, sm.slab[1], z, y, x) * C4;
+    if (sm.slab[2] >= 0 && y < r) return (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, a.sub[n], 1, 0, sm.slab[2], z, y, x) * C4;
+    if (sm.slab[3] >= 0 && y >= a.P[1] - r) return (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, a.sub[n], 1, 1, sm.slab[3], z, y, x) * C4;
+    if (sm.slab[4] >= 0 && x < r) return (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, a.sub[n], 2, 0, sm.slab[4], z, y, x) * C4;
+    if (sm.slab[5] >= 0 && x >= a.P[2] - r) return (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, a.sub[n], 2, 1, sm.slab[5], z, y, x) * C4;
+    return (const f32x4 *)t.wv + ((((int64_t)sm.wv * a.Ve[0] + sm.org[0] + z) * a.Ve[1] + sm.org[1] + y) * a.Ve[2] + sm.org[2] + x) * C4;
+}
+
 static __device__ __forceinline__ void stage0_gather_row(const S0GatherArgs &a, const S0GatherSet &t, int m, int Z, int Y) {
     const int r = t.r, C4 = t.C4;
     const f32x4 *wrow = (const f32x4 *)t.wv + (((int64_t)m * a.Ve[0] + Z) * a.Ve[1] + Y) * a.Ve[2] * C4;
@@ -292,11 +307,56 @@ __global__ __launch_bounds__(256) void stage0_gather_kernel(S0GatherArgs a) {
     }
 }
 
+// The same gather with the grid over what is WRITTEN (by_box; the sub-boxes of the shared level 1): the n output boxes are one
+// contiguous run of (sample, z, y) rows of P2 * C4 quads; a workgroup takes `rows_per_wg` consecutive rows, a lane one 16-byte piece
+// at a time, four loads in flight before the first store.  The row form above walks every row of the whole volume and, per row, every
+// sample: right for tiles that cover the volume several times over, but for thin sub-boxes most of its 256-lane workgroups find
+// a 16-voxel piece or nothing.  Sources and precedence per voxel are the row form's (s0_voxel_source): bit-identical.
+__global__ __launch_bounds__(256) void stage0_gather_box_kernel(S0GatherArgs a, int rows_per_wg) {
+    const S0GatherSet t = {a.wv, {a.slab[0], a.slab[1], a.slab[2]}, a.out, a.r, a.C4};
+    const unsigned C4 = (unsigned)t.C4, rowq = (unsigned)a.P[2] * C4, plane = (unsigned)a.P[0] * (unsigned)a.P[1];
+    const unsigned rows = (unsigned)a.n * plane;  // (host: rows * rowq < 2^31)
+    const unsigned row0 = blockIdx.x * (unsigned)rows_per_wg;
+    const unsigned nrow = rows - row0 < (unsigned)rows_per_wg ? rows - row0 : (unsigned)rows_per_wg;
+    const unsigned chunk = nrow * rowq;
+    f32x4 *dst = (f32x4 *)t.out + (int64_t)row0 * rowq;
+    constexpr int U = 4;
+    for (unsigned j0 = threadIdx.x; j0 < chunk; j0 += U * 256) {
+        const f32x4 *src[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const unsigned j = j0 + u * 256;
+            if (j >= chunk) continue;
+            const unsigned rr = j / rowq, q = j - rr * rowq, row = row0 + rr;
+            const unsigned n = row / plane, zy = row - n * plane;
+            const unsigned z = zy / (unsigned)a.P[1], y = zy - z * (unsigned)a.P[1];
+            const unsigned x = q / C4, c4 = q - x * C4;
+            src[u] = s0_voxel_source(a, t, (int)n, (int)z, (int)y, (int)x) + c4;
+        }
+        f32x4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (j0 + u * 256 < chunk) v[u] = *src[u];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (j0 + u * 256 < chunk) dst[j0 + u * 256] = v[u];
+    }
+}
+
 static int stage0_gather_check(const S0GatherArgs &a, int n_samples, int *n_wv);
 static_assert(sizeof(S0GatherArgs) + sizeof(int) <= 4096, "the gather's arguments must fit the kernel-argument block");
-int stage0_gather(const S0GatherArgs &a, int n_samples, hipStream_t s) {
+int stage0_gather(const S0GatherArgs &a, int n_samples, hipStream_t s, bool by_box) {
     int n_wv = 0;
     MI355_TRY(stage0_gather_check(a, n_samples, &n_wv));
+    const int64_t rowq = (int64_t)a.P[2] * a.C4, rows = (int64_t)n_samples * a.P[0] * a.P[1];
+    if (by_box && !a.out2 && rows * rowq < (1ll << 31)) {  // (one tensor; a larger gather stays with the row form)
+        S0GatherArgs k = a;
+        k.n = n_samples;
+        const int rows_per_wg = (int)std::max<int64_t>(1, (4 * 256 + rowq - 1) / rowq);  // about one pass of the unrolled loop
+        hipLaunchKernelGGL(stage0_gather_box_kernel, dim3((unsigned)((rows + rows_per_wg - 1) / rows_per_wg)), dim3(256), 0, s, k, rows_per_wg);
+        MI355_HIP(hipGetLastError());
+        return MI355_OK;
+    }
     MI355_REQUIRE((int64_t)a.Ve[0] * a.Ve[1] < (1ll << 31), "stage0_gather: grid too large");
     S0GatherArgs k = a;
     k.n = n_samples;
@@ -361,21 +421,7 @@ __global__ __launch_bounds__(256) void stage0_gather_shell_kernel(S0GatherArgs a
         const unsigned ky = w / nx;
         y = d.lo[1] + (int)ky; x = shell_at(w - ky * nx, d.lo[2], d.hi[2]);
     }
-    const f32x4 *src;
-    if (sm.slab[0] >= 0 && z < r)
-        src = (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, a.sub[n], 0, 0, sm.slab[0], z, y, x) * C4;
-    else if (sm.slab[1] >= 0 && z >= a.P[0] - r)
-        src = (const f32x4 *)t.slab[0] + s0_slab_voxel(a, sm, a.sub[n], 0, 1, sm.slab[1], z, y, x) * C4;
-    else if (sm.slab[2] >= 0 && y < r)
-        src = (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, a.sub[n], 1, 0, sm.slab[2], z, y, x) * C4;
-    else if (sm.slab[3] >= 0 && y >= a.P[1] - r)
-        src = (const f32x4 *)t.slab[1] + s0_slab_voxel(a, sm, a.sub[n], 1, 1, sm.slab[3], z, y, x) * C4;
-    else if (sm.slab[4] >= 0 && x < r)
-        src = (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, a.sub[n], 2, 0, sm.slab[4], z, y, x) * C4;
-    else if (sm.slab[5] >= 0 && x >= a.P[2] - r)
-        src = (const f32x4 *)t.slab[2] + s0_slab_voxel(a, sm, a.sub[n], 2, 1, sm.slab[5], z, y, x) * C4;
-    else   // (not reached: every enumerated voxel lies in a shell)
-        src = (const f32x4 *)t.wv + ((((int64_t)sm.wv * a.Ve[0] + sm.org[0] + z) * a.Ve[1] + sm.org[1] + y) * a.Ve[2] + sm.org[2] + x) * C4;
+    const f32x4 *src = s0_voxel_source(a, t, n, z, y, x);  // (every enumerated voxel lies in a shell: never the whole-volume tensor)
     ((f32x4 *)t.out)[((((int64_t)n * a.P[0] + z) * a.P[1] + y) * a.P[2] + x) * C4 + c4] = src[c4];
 }
 

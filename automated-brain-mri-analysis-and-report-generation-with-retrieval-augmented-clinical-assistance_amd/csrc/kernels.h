@@ -83,6 +83,10 @@ struct ConvCallT {
     // them - a view must not change which kernel runs -; the launcher refuses a view on a kernel that cannot read through one
     // (in0_view: conv3_f32_s2dma_kernel_view, C1 == 0; addend_view: conv3_f32_wino3_kernel<3, false>).
     const S0View *in0_view = nullptr, *addend_view = nullptr;
+    // Opt-in hint to the stride-2 LDS-DMA planner (plan_s2dma, fp32): take the tile shape, 2 x 2 x 32 or 2 x 4 x 16, whose padded
+    // output columns times padded rows are fewer (ties: 2 x 2 x 32) instead of asking Wo >= 24.  Both shapes sum an output voxel
+    // in the same order, so the hint changes which lanes are wasted, never a value.  Unset, every call plans as it always did.
+    bool s2_least_padding = false;
 };
 typedef ConvCallT<float> ConvCall;
 typedef ConvCallT<_Float16> ConvCallH;
@@ -197,7 +201,9 @@ inline void stage0_gather_dense(S0GatherArgs *a) {
         for (int k = 0; k < 3; ++k) { a->D[ax][k] = k == ax ? a->t[k] : a->P[k]; a->so[ax][k] = 0; }
 }
 // fp32 NDHWC, 16 bytes per lane.  Where the shells of two or three faces meet the first face in the order above wins.
-int stage0_gather(const S0GatherArgs &a, int n_samples, hipStream_t s);
+// by_box: launched over the output boxes (stage0_gather_box_kernel: thin sub-boxes) instead of over the whole volume's rows; the
+// same values.  A gather of two tensors, or of 2^31 quads and more, takes the row form whatever by_box says.
+int stage0_gather(const S0GatherArgs &a, int n_samples, hipStream_t s, bool by_box = false);
 // The same for a tensor whose reader takes a stage-0 view (S0View): only the voxels within r of a face that has a slab are written,
 // from the sources and with the precedence of stage0_gather; the rest of the tile tensor is left as it is.  which = 0: the first
 // tensor of `a` (out, depth r), 1: the second (out2, depth r2).

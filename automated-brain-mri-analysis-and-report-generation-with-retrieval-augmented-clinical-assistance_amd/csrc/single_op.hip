@@ -201,7 +201,7 @@ extern "C" int mi355_conv3d_fused_ndhwc(const void *x0_dev, const void *x1_dev, 
 // What mi355_conv3d_fused_ndhwc would do with a call of this shape, without a device: the same route through the stem
 // shortcut, the pack layout and the planner, with stand-in pointers where the planners test for null.
 static int conv3d_plan_impl(int dtype, int n, int d, int h, int w, int c0, int c1, int cout, int stride, int impl, bool stats,
-                            bool in_norm, int head_ncls, mi355_conv_plan *out) {
+                            bool in_norm, int head_ncls, bool s2_least_padding, mi355_conv_plan *out) {
     MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_F16, "unknown dtype %d", dtype);
     MI355_REQUIRE(n > 0 && d > 0 && h > 0 && w > 0 && c0 > 0 && c1 >= 0 && cout > 0 && head_ncls >= 0, "bad conv shape");
     static float stand_in[2];
@@ -234,7 +234,8 @@ static int conv3d_plan_impl(int dtype, int n, int d, int h, int w, int c0, int c
         ConvPackLayout l;
         MI355_TRY(conv_pack_layout(cin, cin, cout, stride, &l));
         const ConvWeights cw = stand_in_conv_weights(l, cin, cout, stride, impl == 1);
-        const ConvCall c = make_call<float>(stand_in, cin, n, d, h, w, y, sums, ACT_NONE, 0.f, f);
+        ConvCall c = make_call<float>(stand_in, cin, n, d, h, w, y, sums, ACT_NONE, 0.f, f);
+        c.s2_least_padding = s2_least_padding;
         out->fuses_in_norm = impl == 0 && cw.wp3_dev && conv3d_wino3_fuses_input_norm(cw, make_call<float>(stand_in, cin, n, d, h, w, y, sums, ACT_NONE, 0.f, plain));
         MI355_REQUIRE(!sums || impl != 1, "the direct cross-check kernel carries no statistics epilogue");
         if (impl == 1) { MI355_TRY(plan_conv_direct(cw, c)); name = "conv3_direct_kernel"; }
@@ -251,13 +252,17 @@ static int conv3d_plan_impl(int dtype, int n, int d, int h, int w, int c0, int c
     return MI355_OK;
 }
 
-extern "C" int mi355_conv3d_plan(int dtype, int n, int d, int h, int w, int c0, int c1, int cout, int stride, int impl, int has_stats,
-                                 int has_in_norm, int head_ncls, mi355_conv_plan *out) {
+extern "C" int mi355_conv3d_plan_hinted(int dtype, int n, int d, int h, int w, int c0, int c1, int cout, int stride, int impl, int has_stats,
+                                        int has_in_norm, int head_ncls, int s2_least_padding, mi355_conv_plan *out) {
     MI355_REQUIRE(out != nullptr, "mi355_conv3d_plan: out is null");
     memset(out, 0, sizeof(*out));
     out->splitk = 1;
-    out->rc = conv3d_plan_impl(dtype, n, d, h, w, c0, c1, cout, stride, impl, has_stats != 0, has_in_norm != 0, head_ncls, out);
+    out->rc = conv3d_plan_impl(dtype, n, d, h, w, c0, c1, cout, stride, impl, has_stats != 0, has_in_norm != 0, head_ncls, s2_least_padding != 0, out);
     return out->rc;
+}
+extern "C" int mi355_conv3d_plan(int dtype, int n, int d, int h, int w, int c0, int c1, int cout, int stride, int impl, int has_stats,
+                                 int has_in_norm, int head_ncls, mi355_conv_plan *out) {
+    return mi355_conv3d_plan_hinted(dtype, n, d, h, w, c0, c1, cout, stride, impl, has_stats, has_in_norm, head_ncls, 0, out);
 }
 
 extern "C" int64_t mi355_conv_kernel_names(char *buf, int64_t buf_bytes) {
@@ -304,9 +309,9 @@ static int view_from_abi(const mi355_stage0_view *v, int n, int d, int h, int w,
     return stage0_view_make(v->src_dev, v->n_wv, Ve, P, c, v->depth, smp.data(), n, out);
 }
 
-extern "C" int mi355_conv3d_s2dma_view_ndhwc(const float *x_dev, const mi355_stage0_view *view, int n, int d, int h, int w, int cin,
-                                             const float *weight_host, const float *bias_host, int cout, int act, float slope, int force,
-                                             float *y_dev, void *stream) {
+extern "C" int mi355_conv3d_s2dma_hinted_ndhwc(const float *x_dev, const mi355_stage0_view *view, int n, int d, int h, int w, int cin,
+                                               const float *weight_host, const float *bias_host, int cout, int act, float slope, int force,
+                                               int s2_least_padding, float *y_dev, void *stream) {
     MI355_REQUIRE(x_dev && y_dev && weight_host && cin > 0 && cout > 0, "mi355_conv3d_s2dma_view_ndhwc: bad argument");
     MI355_REQUIRE(act != ACT_LRELU || (slope >= 0.f && slope <= 1.f), "LeakyReLU slope %g outside [0, 1]", (double)slope);
     S0View sv;
@@ -317,10 +322,16 @@ extern "C" int mi355_conv3d_s2dma_view_ndhwc(const float *x_dev, const mi355_sta
     MI355_TRY(conv_weights_upload(weight_host, bias_host, cin, cin, cout, 2, false, &cw.w));
     ConvCall c = make_call<float>(x_dev, cin, n, d, h, w, y_dev, nullptr, act, slope);
     if (view) c.in0_view = &sv;
+    c.s2_least_padding = s2_least_padding != 0;
     const char *kname = nullptr;
     const int rc = conv3d_s2dma_f32(cw.w, c, force != 0, s, &kname);
     g_last_conv_kernel = kname ? kname : "";
     return synced(rc, s, "conv");
+}
+extern "C" int mi355_conv3d_s2dma_view_ndhwc(const float *x_dev, const mi355_stage0_view *view, int n, int d, int h, int w, int cin,
+                                             const float *weight_host, const float *bias_host, int cout, int act, float slope, int force,
+                                             float *y_dev, void *stream) {
+    return mi355_conv3d_s2dma_hinted_ndhwc(x_dev, view, n, d, h, w, cin, weight_host, bias_host, cout, act, slope, force, 0, y_dev, stream);
 }
 
 extern "C" int mi355_conv3d_wino3_view_ndhwc(const float *x0_dev, int n, int d, int h, int w, int c0, const float *weight_host,
@@ -508,7 +519,9 @@ static int stage0_gather_abi(const mi355_stage0_gather_args *a, void *stream, bo
 extern "C" int mi355_stage0_gather(const mi355_stage0_gather_args *a, void *stream) { return stage0_gather_abi(a, stream, false); }
 extern "C" int mi355_stage0_gather_shells(const mi355_stage0_gather_args *a, void *stream) { return stage0_gather_abi(a, stream, true); }
 
-extern "C" int mi355_stage0_gather_merged(const mi355_stage0_gather_merged_args *m, int shells_only, void *stream) {
+// boxes (null: the samples are the tiles): the sub-box form; by_box: the dense gather runs over the boxes
+static int stage0_gather_general(const mi355_stage0_gather_merged_args *m, const mi355_stage0_gather_boxes_args *boxes, int shells_only, bool by_box,
+                                 void *stream) {
     MI355_REQUIRE(m, "mi355_stage0_gather_merged: bad argument");
     const mi355_stage0_gather_args *a = &m->base;
     MI355_REQUIRE(a->wv_dev && a->out_dev && a->channels > 0 && a->channels % 4 == 0, "mi355_stage0_gather_merged: bad argument");
@@ -541,11 +554,23 @@ extern "C" int mi355_stage0_gather_merged(const mi355_stage0_gather_merged_args 
                           "mi355_stage0_gather_merged: sample %d: face %d without a slab tensor", i, f);
         }
     }
+    if (boxes)
+        for (int k = 0; k < 3; ++k) {
+            ga.T[k] = boxes->tile[k];
+            for (int i = 0; i < a->n_samples; ++i) ga.sub[i][k] = boxes->sub[i][k];
+        }
     hipStream_t s = (hipStream_t)stream;
-    if (!shells_only) return synced(stage0_gather(ga, a->n_samples, s), s, "stage0_gather");
+    if (!shells_only) return synced(stage0_gather(ga, a->n_samples, s, by_box), s, "stage0_gather");
     MI355_TRY(stage0_gather_shells(ga, a->n_samples, 0, s));
     if (ga.out2) MI355_TRY(stage0_gather_shells(ga, a->n_samples, 1, s));
     return synced(MI355_OK, s, "stage0_gather_shells");
+}
+extern "C" int mi355_stage0_gather_merged(const mi355_stage0_gather_merged_args *m, int shells_only, void *stream) {
+    return stage0_gather_general(m, nullptr, shells_only, false, stream);
+}
+extern "C" int mi355_stage0_gather_boxes(const mi355_stage0_gather_boxes_args *b, int shells_only, int by_box, void *stream) {
+    MI355_REQUIRE(b && b->tile[0] > 0 && b->tile[1] > 0 && b->tile[2] > 0, "mi355_stage0_gather_boxes: bad argument");
+    return stage0_gather_general(&b->merged, b, shells_only, by_box != 0, stream);
 }
 
 extern "C" int mi355_stage0_mask(float *x_dev, int n, const int32_t volume[3], const int32_t keep[3], int c, void *stream) {

@@ -159,9 +159,10 @@ static S0ViewChoice views_decide(const mi355_unet &net, int l, bool views, const
 // ---- the hand-off of one level to the forward: the features of n samples (C channels) and the skip half of the decoder conv that reads
 // them (C2 channels, 0 = none), gathered from the n_wv shared tensors and the slabs `ga` names.  A tensor whose reader takes a view (want)
 // is gathered in its shells alone and *out receives the view (src = null: none, the tensor is dense; so too where no view can be built).
+// sw: how it is launched - a dense gather of sub-boxes runs over the boxes (subbox_gather).
 struct LevelHandOff { S0View feat_view, half_view; };
-static int handoff_gather(mi355_unet *net, const S0GatherArgs &ga, int n, int n_wv, int C, int C2, S0ViewChoice want, const char *label, LevelHandOff *out,
-                          hipStream_t s) {
+static int handoff_gather(mi355_unet *net, const S0GatherArgs &ga, int n, int n_wv, int C, int C2, S0ViewChoice want, const SwSwitches &sw, const char *label,
+                          LevelHandOff *out, hipStream_t s) {
     const bool v0 = want.enc0 && stage0_view_make(ga.wv, n_wv, ga.Ve, ga.P, C, ga.r, ga.smp, n, &out->feat_view) == MI355_OK;
     const bool v1 = want.half && C2 && stage0_view_make(ga.wv2, n_wv, ga.Ve, ga.P, C2, ga.r2, ga.smp, n, &out->half_view) == MI355_OK;
     const double pv = (double)n * ga.P[0] * ga.P[1] * ga.P[2];
@@ -172,12 +173,13 @@ static int handoff_gather(mi355_unet *net, const S0GatherArgs &ga, int n, int n_
     }
     // (one profile entry, as before the views; its bytes are what is moved: read + written)
     ProfScope ps(net, s, label, 0.0, 2.0 * 4.0 * ((v0 ? shell0 : pv) * C + (v1 ? shell1 : pv) * C2));
-    if (!v0 && !v1) return stage0_gather(ga, n, s);
+    const bool by_box = sw.subbox_gather && ga.T[0] > 0;
+    if (!v0 && !v1) return stage0_gather(ga, n, s, by_box);
     if (v0) MI355_TRY(stage0_gather_shells(ga, n, 0, s));
     else {  // the features whole, alone
         S0GatherArgs g0 = ga;
         g0.out2 = nullptr; g0.wv2 = nullptr;
-        MI355_TRY(stage0_gather(g0, n, s));
+        MI355_TRY(stage0_gather(g0, n, s, by_box));
     }
     if (!C2) return MI355_OK;
     if (v1) return stage0_gather_shells(ga, n, 1, s);
@@ -185,14 +187,14 @@ static int handoff_gather(mi355_unet *net, const S0GatherArgs &ga, int n, int n_
     g1.wv = ga.wv2; g1.out = ga.out2; g1.r = ga.r2; g1.C4 = ga.C42;
     for (int a = 0; a < 3; ++a) g1.slab[a] = ga.slab2[a];
     g1.out2 = nullptr; g1.wv2 = nullptr;
-    return stage0_gather(g1, n, s);
+    return stage0_gather(g1, n, s, by_box);
 }
 
 // the slabs of one batch of samples (indices into sg.smp), then the hand-off of the batch's tile tensors.  want: which tensors'
 // readers will take a view.  out->ga: the gather's arguments (shared level 1: the sources of the batch's sub-boxes).
 struct S0TilesOut { LevelHandOff h; S0GatherArgs ga; };
 static int stage0_tiles(mi355_unet *net, const Plan &pl, const SwVolume &v, const SwGeom &g, const S0Geom &sg, const std::vector<int> &samples,
-                        S0ViewChoice want, S0TilesOut *out, hipStream_t s) {
+                        S0ViewChoice want, const SwSwitches &sw, S0TilesOut *out, hipStream_t s) {
     const int n = (int)samples.size();
     MI355_REQUIRE(n <= S0_MAX_SAMPLES, "shared stage 0: %d samples per forward (max %d)", n, S0_MAX_SAMPLES);
     const int C = net->enc[0].back().cout;
@@ -235,7 +237,7 @@ static int stage0_tiles(mi355_unet *net, const Plan &pl, const SwVolume &v, cons
         ga.r2 = sg.rs; ga.C42 = C2 / 4;
     } else
         for (int a = 0; a < 3; ++a) ga.slab2[a] = nullptr;
-    return handoff_gather(net, ga, n, (int)g.mirrors.size(), C, C2, want, "stage0_gather_kernel", &out->h, s);
+    return handoff_gather(net, ga, n, (int)g.mirrors.size(), C, C2, want, sw, "stage0_gather_kernel", &out->h, s);
 }
 
 // ---- shared level 1 (sw_share_plan.hip "shared level 1"): the region pass and the per-forward slabs
@@ -276,9 +278,10 @@ static void level1_plan(const mi355_unet &net, const SwGeom &g, const S0Geom &sg
 }
 
 // enc[1] (its first block through in0_view when given) and the skip half of dec[np - 2][0] over n boxes of S level-0 voxels:
-// x0 -> e_out (through tmp, and e_out itself, in turns) and s_out; keep1: zeros restored outside it behind every block
-static int level1_chain(mi355_unet *net, const Plan &pl, const void *x0, const S0View *view, int n, const int S[3], const int *keep1, void *tmp,
-                        void *e_out, void *s_out, hipStream_t s) {
+// x0 -> e_out (through tmp, and e_out itself, in turns) and s_out; keep1: zeros restored outside it behind every block;
+// least_padding: the stride-2 block plans with ConvCall::s2_least_padding (whoever asked the planner about a view asked with it too)
+static int level1_chain(mi355_unet *net, const Plan &pl, const void *x0, const S0View *view, bool least_padding, int n, const int S[3], const int *keep1,
+                        void *tmp, void *e_out, void *s_out, hipStream_t s) {
     const std::vector<ConvLayer> &e1 = net->enc[1];
     const int S1[3] = {S[0] / 2, S[1] / 2, S[2] / 2};
     const void *cur = x0;
@@ -286,7 +289,7 @@ static int level1_chain(mi355_unet *net, const Plan &pl, const void *x0, const S
     for (size_t i = 0; i < e1.size(); ++i) {
         void *out = ((e1.size() - 1 - i) & 1) ? tmp : e_out;  // (the last block writes e_out)
         BlockOpts bo;
-        if (i == 0) bo.in0_view = view;
+        if (i == 0) { bo.in0_view = view; bo.s2_least_padding = least_padding; }
         MI355_TRY(run_block(net, pl, e1[i], cur, curC, nullptr, 0, n, i ? S1[0] : S[0], i ? S1[1] : S[1], i ? S1[2] : S[2], out, s, bo));
         if (keep1) MI355_TRY(mask_outside(net, out, n, S1, keep1, e1[i].cout, s));
         cur = out; curC = e1[i].cout;
@@ -299,7 +302,8 @@ static int level1_chain(mi355_unet *net, const Plan &pl, const void *x0, const S
 
 // region pass, once per volume behind the whole-volume pass: the stage-0 slabs at the regions' faces on per-origin axes, the
 // regions' level-0 shells, then enc[1] and the skip half over the regions, their level-0 input read in place through a view
-static int level1_regions(mi355_unet *net, const Plan &pl, const SwVolume &v, const SwGeom &g, const S0Geom &sg, const L1Geom &lg, hipStream_t s) {
+static int level1_regions(mi355_unet *net, const Plan &pl, const SwVolume &v, const SwGeom &g, const S0Geom &sg, const L1Geom &lg, const SwSwitches &sw,
+                          hipStream_t s) {
     const int nreg = (int)lg.regions.size();
     const int c0 = net->enc[0].back().cout;
     MI355_REQUIRE(nreg > 0 && nreg <= S0_VIEW_MAX_SAMPLES, "shared level 1: %d regions (max %d)", nreg, S0_VIEW_MAX_SAMPLES);
@@ -337,7 +341,7 @@ static int level1_regions(mi355_unet *net, const Plan &pl, const SwVolume &v, co
     int keep1[3];
     for (int k = 0; k < 3; ++k) keep1[k] = lg.merged[k] ? g.Zp[k] / 2 : lg.R[k] / 2;
     const int last = (int)((net->enc[1].size() - 1) & 1);
-    return level1_chain(net, pl, ga.out, &view, nreg, lg.R, keep1, pl.arena + pl.l1.r_e[last ^ 1], pl.arena + pl.l1.r_e[last],
+    return level1_chain(net, pl, ga.out, &view, sw.s2_least_padding, nreg, lg.R, keep1, pl.arena + pl.l1.r_e[last ^ 1], pl.arena + pl.l1.r_e[last],
                         pl.arena + pl.l1.r_s, s);
 }
 
@@ -346,7 +350,7 @@ static int level1_regions(mi355_unet *net, const Plan &pl, const SwVolume &v, co
 // fin->smp[i].slab (0 where face f of sample i has a level-1 slab) receives the row of that slab.  Out: gs, the gather of the sub-boxes
 // (gs.smp[0 .. *n_out), a multiple of L1_SLAB_GROUP; gs.P their extent); *viewed: the chain's first conv reads enc[0]'s whole-volume
 // result through a view, gs.out holds the shells alone.
-static int level1_sub_boxes(mi355_unet *net, const Plan &pl, const SwGeom &g, const L1Geom &lg, const S0GatherArgs &ga0, int n, int a, bool views,
+static int level1_sub_boxes(mi355_unet *net, const Plan &pl, const SwGeom &g, const L1Geom &lg, const S0GatherArgs &ga0, int n, int a, const SwSwitches &sw,
                             S0GatherArgs *fin, S0GatherArgs &gs, int *n_out, bool *viewed, hipStream_t s) {
     const int c0 = net->enc[0].back().cout;
     gs = ga0;
@@ -373,21 +377,21 @@ static int level1_sub_boxes(mi355_unet *net, const Plan &pl, const SwGeom &g, co
     // where a launch of L1_SLAB_GROUP sub-boxes goes to the stride-2 kernel that takes a view, it reads enc[0]'s whole-volume
     // result in place and the gather writes the sub-boxes' shells alone (bit-identical: a view changes where bytes are read)
     S0ViewChoice want;
-    want.enc0 = views && reader_takes_view(net->enc[1][0].w, c0, L1_SLAB_GROUP, gs.P, false);
+    want.enc0 = sw.views && reader_takes_view(net->enc[1][0].w, c0, L1_SLAB_GROUP, gs.P, false, sw.s2_least_padding);
     LevelHandOff probe;  // (of all ns: step 2 builds a view per launch; where none can be built the gather is dense)
-    const int rc = handoff_gather(net, gs, ns, (int)g.mirrors.size(), c0, 0, want, "stage0_gather_kernel sub-boxes", &probe, s);
+    const int rc = handoff_gather(net, gs, ns, (int)g.mirrors.size(), c0, 0, want, sw, "stage0_gather_kernel sub-boxes", &probe, s);
     *viewed = probe.feat_view.src != nullptr;
     return rc;
 }
 
 // step 2: enc[1] and the skip half over the sub-boxes, in launches of exactly L1_SLAB_GROUP
-static int level1_slabs(mi355_unet *net, const Plan &pl, const SwGeom &g, const S0GatherArgs &gs, int n, bool viewed, int a, hipStream_t s) {
+static int level1_slabs(mi355_unet *net, const Plan &pl, const SwGeom &g, const S0GatherArgs &gs, int n, bool viewed, bool least_padding, int a, hipStream_t s) {
     const size_t c0 = net->enc[0].back().cout, c1 = net->enc[1].back().cout, cS = net->dec[net->num_pool - 2][0].cout;
     const size_t sv0 = (size_t)gs.P[0] * gs.P[1] * gs.P[2], sv1 = sv0 / 8;
     for (int g0 = 0; g0 < n; g0 += L1_SLAB_GROUP) {
         S0View view;
         if (viewed) MI355_TRY(stage0_view_make(gs.wv, (int)g.mirrors.size(), gs.Ve, gs.P, (int)c0, gs.r, gs.smp + g0, L1_SLAB_GROUP, &view));
-        MI355_TRY(level1_chain(net, pl, pl.arena + pl.l1.sub_in[a] + g0 * sv0 * c0 * 4, viewed ? &view : nullptr, L1_SLAB_GROUP, gs.P, nullptr,
+        MI355_TRY(level1_chain(net, pl, pl.arena + pl.l1.sub_in[a] + g0 * sv0 * c0 * 4, viewed ? &view : nullptr, least_padding, L1_SLAB_GROUP, gs.P, nullptr,
                                pl.arena + pl.l1.s_tmp, pl.arena + pl.l1.s_e[a] + g0 * sv1 * c1 * 4, pl.arena + pl.l1.s_s[a] + g0 * sv1 * cS * 4, s));
     }
     return MI355_OK;
@@ -395,7 +399,7 @@ static int level1_slabs(mi355_unet *net, const Plan &pl, const SwGeom &g, const 
 
 // per forward: the level-1 slabs of the batch's samples (indices into lg.smp; ga0 = the stage-0 gather of the same batch), then
 // step 3, the hand-off of the two level-1 tile tensors from the regions and the slabs
-static int level1_tiles(mi355_unet *net, const Plan &pl, const SwGeom &g, const SwSharePlan &p, bool views, const S0GatherArgs &ga0,
+static int level1_tiles(mi355_unet *net, const Plan &pl, const SwGeom &g, const SwSharePlan &p, const SwSwitches &sw, const S0GatherArgs &ga0,
                         const std::vector<int> &samples, LevelHandOff *out, hipStream_t s) {
     const L1Geom &lg = p.lg;
     const int n = (int)samples.size();
@@ -410,8 +414,8 @@ static int level1_tiles(mi355_unet *net, const Plan &pl, const SwGeom &g, const 
         fin.t[a] = lg.merged[a] ? lg.t1[a] : whole_conv_tiles(2 * lg.dS, a);  // (a per-origin axis has no slab; the gather asks for a thickness all the same)
         if (!lg.merged[a]) continue;
         S0GatherArgs gs; int ns; bool viewed;
-        MI355_TRY(level1_sub_boxes(net, pl, g, lg, ga0, n, a, views, &fin, gs, &ns, &viewed, s));
-        MI355_TRY(level1_slabs(net, pl, g, gs, ns, viewed, a, s));
+        MI355_TRY(level1_sub_boxes(net, pl, g, lg, ga0, n, a, sw, &fin, gs, &ns, &viewed, s));
+        MI355_TRY(level1_slabs(net, pl, g, gs, ns, viewed, sw.s2_least_padding, a, s));
     }
     const int last = (int)((net->enc[1].size() - 1) & 1);
     fin.wv = (const float *)(pl.arena + pl.l1.r_e[last]);
@@ -422,7 +426,7 @@ static int level1_tiles(mi355_unet *net, const Plan &pl, const SwGeom &g, const 
     stage0_gather_dense(&fin);
     fin.r = lg.d1; fin.C4 = c1 / 4; fin.r2 = lg.dS; fin.C42 = cS / 4;
     // the two readers take views where they can, and the gather then writes the shells alone
-    return handoff_gather(net, fin, n, (int)lg.regions.size(), c1, cS, views_decide(*net, 1, views, p, n, fin.P), "stage0_gather_kernel level 1", out, s);
+    return handoff_gather(net, fin, n, (int)lg.regions.size(), c1, cS, views_decide(*net, 1, sw.views, p, n, fin.P), sw, "stage0_gather_kernel level 1", out, s);
 }
 
 // Evaluates the tiles with (index % world) == rank of one net; adds into agg (and cnt if non-null,
@@ -455,7 +459,7 @@ static int sw_accumulate(mi355_unet *net, const SwVolume &v, const mi355_sw_opts
     if (mine.empty()) return MI355_OK;
     if (sg.shared) MI355_TRY(stage0_whole(net, pl, v, g, sg, s));
     if (sg.merge) MI355_TRY(stage0_merged(net, pl, v, g, sg, s));
-    if (p.share_l1) MI355_TRY(level1_regions(net, pl, v, g, sg, p.lg, s));
+    if (p.share_l1) MI355_TRY(level1_regions(net, pl, v, g, sg, p.lg, sw, s));
     for (size_t b0 = 0; b0 < mine.size(); b0 += bt) {
         const int nb = (int)std::min<size_t>(bt, mine.size() - b0);
         std::vector<TileDesc> samples;
@@ -481,10 +485,10 @@ static int sw_accumulate(mi355_unet *net, const SwVolume &v, const mi355_sw_opts
         };
         S0TilesOut t0; LevelHandOff h1;
         if (sg.shared) {
-            MI355_TRY(stage0_tiles(net, pl, v, g, sg, sample_ids, views_decide(*net, 0, sw.views, p, (int)samples.size(), g.P), &t0, s));
+            MI355_TRY(stage0_tiles(net, pl, v, g, sg, sample_ids, views_decide(*net, 0, sw.views, p, (int)samples.size(), g.P), sw, &t0, s));
             give(0, t0.h, p.share_skip);
             if (p.share_l1) {
-                MI355_TRY(level1_tiles(net, pl, g, p, sw.views, t0.ga, sample_ids, &h1, s));
+                MI355_TRY(level1_tiles(net, pl, g, p, sw, t0.ga, sample_ids, &h1, s));
                 give(1, h1, true);
             }
         } else {

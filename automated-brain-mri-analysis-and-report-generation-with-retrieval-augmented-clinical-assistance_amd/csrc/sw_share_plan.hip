@@ -208,7 +208,8 @@ int stage0_blocks(const mi355_unet &net) {
 }
 
 SwSwitches sw_switches() {
-    return SwSwitches{env_switch("MI355_SHARE_SKIP_CONV"), env_switch("MI355_STAGE0_VIEWS"), env_switch("MI355_MERGE_SLABS"), level1_share_mode()};
+    return SwSwitches{env_switch("MI355_SHARE_SKIP_CONV"), env_switch("MI355_STAGE0_VIEWS"), env_switch("MI355_MERGE_SLABS"), level1_share_mode(),
+                      env_switch("MI355_S2_LEAST_PADDING"), env_switch("MI355_SUBBOX_GATHER")};
 }
 
 // ---- shared skip half.  The first block of the last decoder stage reads the virtual concat (upsampled, skip) and is linear in
@@ -289,9 +290,10 @@ static SkipShareNet skip_share_net_from_abi(const mi355_skip_share_net *nd) {
 //     first, for exactly this call - sends enc[1][0] to conv3_f32_s2dma_kernel; the launch then runs conv3_f32_s2dma_kernel_view;
 //   * S: the shared skip half is on (its reader is then always conv3_f32_wino3_kernel<3, false>).
 // A view that cannot be built (stage0_view_make: offsets beyond 32 bits) falls back to the full gather for that tensor.
-bool reader_takes_view(const ConvWeights &w, int cin, int n, const int S[3], bool stats) {
+bool reader_takes_view(const ConvWeights &w, int cin, int n, const int S[3], bool stats, bool least_padding) {
     static float stand_in[2];
-    const ConvCall c = make_call<float>(stand_in, cin, n, S[0], S[1], S[2], stand_in, stats ? (double *)stand_in : nullptr, ACT_LRELU, 0.01f);
+    ConvCall c = make_call<float>(stand_in, cin, n, S[0], S[1], S[2], stand_in, stats ? (double *)stand_in : nullptr, ACT_LRELU, 0.01f);
+    c.s2_least_padding = least_padding;
     ConvPlan p;
     return plan_conv_f32(w, c, &p) == MI355_OK && p.family == FAM_S2DMA;
 }
@@ -392,7 +394,7 @@ static bool level1_share_rule(const L1ShareNet &d, const SwGeom &g, const SwSwit
     if ((int)lg.regions.size() > S0_VIEW_MAX_SAMPLES) return false;
     ConvPackLayout l1;
     if (conv_pack_layout(d.last.c_skip, d.last.c_skip, d.c1, 2, &l1) != MI355_OK || !l1.mfma) return false;
-    if (!reader_takes_view(stand_in_conv_weights(l1, d.last.c_skip, d.c1, 2), d.last.c_skip, (int)lg.regions.size(), lg.R, false)) return false;
+    if (!reader_takes_view(stand_in_conv_weights(l1, d.last.c_skip, d.c1, 2), d.last.c_skip, (int)lg.regions.size(), lg.R, false, sw.s2_least_padding)) return false;
     if (sw.level1 == 1)
         for (int a = 0; a < 3; ++a) {
             if (!lg.merged[a]) continue;

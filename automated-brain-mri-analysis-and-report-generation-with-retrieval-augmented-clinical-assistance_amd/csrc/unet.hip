@@ -182,6 +182,7 @@ int run_block(mi355_unet *net, const Plan &pl, const ConvLayer &L, const void *i
             ConvCall c = make_call<float>(in0, C0 + C1, N, Di, Hi, Wi, out, stats_arg, o.half && !o.addend ? ACT_NONE : act, net->slope, f);
             c.addend = o.addend;
             c.in0_view = o.in0_view; c.addend_view = o.addend_view;  // (stage-0 views: the caller asked the planner first)
+            c.s2_least_padding = o.s2_least_padding;
             const ConvWeights &W = o.half ? *o.half : L.w;
             ProfScope ps(net, s, "conv3_direct_kernel", flops, bytes);  // (renamed to the instantiation the MFMA dispatch picks)
             if (W.wp_dev) MI355_TRY(conv3d_mfma_f32(W, c, s, &kname));

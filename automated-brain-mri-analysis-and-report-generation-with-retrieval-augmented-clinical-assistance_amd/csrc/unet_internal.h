@@ -156,6 +156,7 @@ struct BlockOpts {
     const float *addend = nullptr;
     const char *half_name = "";
     const S0View *in0_view = nullptr, *addend_view = nullptr;  // stage-0 views of in0 / of the addend (the caller asked the planner first)
+    bool s2_least_padding = false;  // ConvCall::s2_least_padding of the launch (fp32; the shared level 1 sets it on enc[1][0])
 };
 int run_block(mi355_unet *net, const Plan &pl, const ConvLayer &L, const void *in0, int C0, const void *in1, int C1, int N, int Di, int Hi,
               int Wi, void *out, hipStream_t s, const BlockOpts &o = BlockOpts());
@@ -224,7 +225,12 @@ void gaussian_map(const int p[3], double sigma_scale, std::vector<float> &out);
 int sw_batch_tiles(int dtype, int batch_tiles, int nm);
 
 // The switches a window obeys, read once where a window (sw_accumulate) or a dry run begins: nothing below reads the environment.
-struct SwSwitches { bool skip_conv, views, merge_slabs; int level1; };  // MI355_SHARE_SKIP_CONV, MI355_STAGE0_VIEWS, MI355_MERGE_SLABS, level1_share_mode()
+struct SwSwitches {
+    bool skip_conv, views, merge_slabs; int level1;  // MI355_SHARE_SKIP_CONV, MI355_STAGE0_VIEWS, MI355_MERGE_SLABS, level1_share_mode()
+    // how two pieces of the shared level 1 are launched, never what they compute (0 = as before them):
+    bool s2_least_padding;  // MI355_S2_LEAST_PADDING: enc[1][0] over the regions and sub-boxes plans with ConvCall::s2_least_padding
+    bool subbox_gather;     // MI355_SUBBOX_GATHER: a dense gather of sub-boxes runs stage0_gather_box_kernel
+};
 SwSwitches sw_switches();
 constexpr int CONV_TILE[3] = {4, 8, 8};  // the voxel tile of the conv kernels: volumes are extended, and slabs sized, in whole tiles
 inline int whole_conv_tiles(int v, int a) { return ceil_div(v, CONV_TILE[a]) * CONV_TILE[a]; }
@@ -283,7 +289,8 @@ struct SwSharePlan {
 SwSharePlan sw_share_plan(const L1ShareNet &d, const SwGeom &g, const SwSwitches &sw);
 
 // Does the planner send this fp32 call (n boxes of S voxels, cin channels, run-time statistics or not) to the stride-2 kernel that takes a view (kernels.h S0View)?
-bool reader_takes_view(const ConvWeights &w, int cin, int n, const int S[3], bool stats);
+// least_padding: the call carries ConvCall::s2_least_padding (the launch it is asked about must carry it too)
+bool reader_takes_view(const ConvWeights &w, int cin, int n, const int S[3], bool stats, bool least_padding = false);
 struct S0ViewChoice { bool enc0 = false, half = false; };
 S0ViewChoice stage0_views_choose(bool views, const S0Geom &sg, bool share_skip, int n_samples, const int P[3], const ConvWeights *w1, int c0, bool w1_stats);
 

@@ -231,15 +231,17 @@ def conv3d_fused_ndhwc(x0, weight, bias=None, x1=None, in_scale=None, in_shift=N
     return out, sums
 
 
-def conv3d_plan(dtype, shape, c0, cout, c1=0, stride=1, impl="mfma", stats=False, in_norm=False, head_ncls=0):
+def conv3d_plan(dtype, shape, c0, cout, c1=0, stride=1, impl="mfma", stats=False, in_norm=False, head_ncls=0, s2_least_padding=False):
     """Dry run of ``conv3d_fused_ndhwc`` (test aid, ``mi355_conv3d_plan``; no GPU needed): the kernel a call of ``shape`` =
     (N, D, H, W) with C0 (+ C1) input channels would be dispatched to.  dtype: "f32" | "f16".  Returns a dict (rc, kernel, grid,
-    lds_bytes, splitk, tile, fuses_in_norm, error); a refused call has rc < 0 and the dispatcher's message in ``error``."""
+    lds_bytes, splitk, tile, fuses_in_norm, error); a refused call has rc < 0 and the dispatcher's message in ``error``.
+    s2_least_padding: the call carries the stride-2 planner's least-padding hint (``mi355_conv3d_plan_hinted``)."""
     p = _lib.ConvPlan()
     n, d, h, w = (int(v) for v in shape)
     lib = _lib.load()
-    rc = lib.mi355_conv3d_plan({"f32": 0, "f16": 1}[dtype], n, d, h, w, int(c0), int(c1), int(cout), int(stride),
-                               {"mfma": 0, "direct": 1}[impl], int(bool(stats)), int(bool(in_norm)), int(head_ncls), C.byref(p))
+    args = ({"f32": 0, "f16": 1}[dtype], n, d, h, w, int(c0), int(c1), int(cout), int(stride),
+            {"mfma": 0, "direct": 1}[impl], int(bool(stats)), int(bool(in_norm)), int(head_ncls))
+    rc = lib.mi355_conv3d_plan_hinted(*args, 1, C.byref(p)) if s2_least_padding else lib.mi355_conv3d_plan(*args, C.byref(p))
     return {"rc": rc, "kernel": p.kernel.decode(), "grid": tuple(p.grid), "lds_bytes": int(p.lds_bytes), "splitk": int(p.splitk),
             "tile": tuple(p.tile), "fuses_in_norm": bool(p.fuses_in_norm), "error": (lib.mi355_last_error() or b"").decode() if rc < 0 else ""}
 
@@ -439,10 +441,11 @@ def _stage0_view(src, samples, depth):
     return v, src
 
 
-def conv3d_s2dma_view_ndhwc(x, weight, bias=None, view=None, act=0, slope=0.01, force=True):
+def conv3d_s2dma_view_ndhwc(x, weight, bias=None, view=None, act=0, slope=0.01, force=True, s2_least_padding=False):
     """One stride-2 conv on ``conv3_f32_s2dma_kernel`` or, with ``view`` = (src, samples, depth), on its view twin (test entry point,
     ``mi355_conv3d_s2dma_view_ndhwc``).  x: CUDA fp32 [N,D,H,W,Cin], the dense tile tensor - with a view only its shell voxels are
-    read; src: CUDA fp32 [n_wv,Ve0,Ve1,Ve2,Cin]; samples: one dict {wv, origin, faces} per sample of x; weight: numpy [Cout,Cin,3,3,3]."""
+    read; src: CUDA fp32 [n_wv,Ve0,Ve1,Ve2,Cin]; samples: one dict {wv, origin, faces} per sample of x; weight: numpy [Cout,Cin,3,3,3].
+    s2_least_padding: the call carries the planner's least-padding hint (``mi355_conv3d_s2dma_hinted_ndhwc``)."""
     import torch
     x = _require_cuda(x, torch.float32, "x")
     n, d, h, w, cin = x.shape
@@ -453,9 +456,11 @@ def conv3d_s2dma_view_ndhwc(x, weight, bias=None, view=None, act=0, slope=0.01, 
     if keep is not None and keep.shape[4] != cin:
         raise ValueError("conv3d_s2dma_view_ndhwc: the view's source must have the input's channels")
     y = torch.full((n, (d - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1, cout), float("nan"), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().mi355_conv3d_s2dma_view_ndhwc(x.data_ptr(), None if v is None else C.byref(v), n, d, h, w, cin, _lib.fptr(weight),
-                                                         _lib.fptr(b), cout, act, slope, int(bool(force)), y.data_ptr(), stream_of(x)),
-               "mi355_conv3d_s2dma_view_ndhwc")
+    head = (x.data_ptr(), None if v is None else C.byref(v), n, d, h, w, cin, _lib.fptr(weight), _lib.fptr(b), cout, act, slope, int(bool(force)))
+    if s2_least_padding:
+        _lib.check(_lib.load().mi355_conv3d_s2dma_hinted_ndhwc(*head, 1, y.data_ptr(), stream_of(x)), "mi355_conv3d_s2dma_hinted_ndhwc")
+    else:
+        _lib.check(_lib.load().mi355_conv3d_s2dma_view_ndhwc(*head, y.data_ptr(), stream_of(x)), "mi355_conv3d_s2dma_view_ndhwc")
     return y
 
 
@@ -764,16 +769,21 @@ def stage0_gather(wv, slabs, samples, patch, r, shells_only=False, out=None):
     return out
 
 
-def stage0_gather_merged(wv, slabs, samples, patch, r, spans, shells_only=False, out=None, second=None):
+def stage0_gather_merged(wv, slabs, samples, patch, r, spans, shells_only=False, out=None, second=None, tile=None, by_box=False):
     """``mi355_stage0_gather_merged``: ``stage0_gather`` with slabs that may span the volume.  slabs[a]: CUDA fp32 [n, S0, S1, S2, C] or
     None; spans[a][k] truthy: the slabs of axis a span the volume along k (S[k] = volume[k], the tile at its origin) instead of
     holding the tile's extent (S[k] = patch[k]).  second: None or a dict wv, slabs, r and optionally out - a second tensor gathered
-    for the same samples.  Returns (out, out2); out / out2 given are written in place (shells_only: the shell voxels alone)."""
+    for the same samples.  Returns (out, out2); out / out2 given are written in place (shells_only: the shell voxels alone).
+    tile: ``mi355_stage0_gather_boxes`` - the samples are sub-boxes (each dict also has ``sub``, its offset in its tile) of tiles of
+    ``tile`` voxels, which is what a slab holds along an axis it does not span; by_box: the dense gather of one tensor is launched
+    over the boxes (``stage0_gather_box_kernel``) instead of over the whole volume's rows."""
     import torch
     wv = _require_cuda(wv, torch.float32, "wv")
     nwv = int(wv.shape[0])
     patch = [int(p) for p in patch]
-    m = _lib.Stage0GatherMergedArgs()
+    boxes = _lib.Stage0GatherBoxesArgs() if tile is not None else None
+    m = _lib.Stage0GatherMergedArgs() if boxes is None else boxes.merged
+    held = patch if tile is None else [int(t) for t in tile]  # what a slab holds along an axis it does not span
     a = m.base
     keep = [wv]
     vol = [int(wv.shape[1 + k]) for k in range(3)]
@@ -790,7 +800,7 @@ def stage0_gather_merged(wv, slabs, samples, patch, r, spans, shells_only=False,
             sl = _require_cuda(sl, torch.float32, f"{name} slabs[{k}]")
             keep.append(sl)
             thick = int(sl.shape[1 + k])
-            want = [thick if j == k else (vol[j] if spans[k][j] else patch[j]) for j in range(3)]
+            want = [thick if j == k else (vol[j] if spans[k][j] else held[j]) for j in range(3)]
             if sl.dim() != 5 or list(sl.shape[1:4]) != want or sl.shape[4] != c or (counts[k] and counts[k] != sl.shape[0]):
                 raise ValueError(f"{name} slabs[{k}]: shape {tuple(sl.shape)}, expected [n, {want}, {c}]")
             if a.slab_thickness[k] not in (0, thick):
@@ -820,7 +830,7 @@ def stage0_gather_merged(wv, slabs, samples, patch, r, spans, shells_only=False,
         if ptrs[k] is None:   # an axis without slabs: the per-tile form, never indexed
             a.slab_thickness[k] = 2 * int(second["r"] if second is not None else r)
             for j in range(3):
-                m.slab_shape[k][j], m.spans_volume[k][j] = (a.slab_thickness[k] if j == k else patch[j]), 0
+                m.slab_shape[k][j], m.spans_volume[k][j] = (a.slab_thickness[k] if j == k else held[j]), 0
     if len(samples) > 64:
         raise ValueError("stage0_gather_merged: more than 64 samples")
     for i, sm in enumerate(samples):
@@ -834,6 +844,9 @@ def stage0_gather_merged(wv, slabs, samples, patch, r, spans, shells_only=False,
             if idx >= counts[f >> 1]:
                 raise ValueError(f"stage0_gather_merged: sample {i}: face {f} has no slab {idx}")
             a.samples[i].slab[f] = idx
+        if boxes is not None:
+            for k in range(3):
+                boxes.sub[i][k] = int(sm["sub"][k])
 
     def result(given, ch):
         shape = (max(len(samples), 1), patch[0], patch[1], patch[2], ch)
@@ -849,7 +862,15 @@ def stage0_gather_merged(wv, slabs, samples, patch, r, spans, shells_only=False,
     if second is not None:
         out2 = result(second.get("out"), c2)
         m.out2_dev = out2.data_ptr()
-    _lib.check(_lib.load().mi355_stage0_gather_merged(C.byref(m), int(bool(shells_only)), stream_of(wv)), "mi355_stage0_gather_merged")
+    if boxes is not None:
+        for k in range(3):
+            boxes.tile[k] = held[k]
+        _lib.check(_lib.load().mi355_stage0_gather_boxes(C.byref(boxes), int(bool(shells_only)), int(bool(by_box)), stream_of(wv)),
+                   "mi355_stage0_gather_boxes")
+    elif by_box:
+        raise ValueError("stage0_gather_merged: by_box needs the sub-box form (tile)")
+    else:
+        _lib.check(_lib.load().mi355_stage0_gather_merged(C.byref(m), int(bool(shells_only)), stream_of(wv)), "mi355_stage0_gather_merged")
     return out, out2
 
 

@@ -604,6 +604,12 @@ typedef struct mi355_conv_plan {
 } mi355_conv_plan;
 int mi355_conv3d_plan(int dtype, int n, int d, int h, int w, int c0, int c1, int cout, int stride, int impl, int has_stats,
                       int has_in_norm, int head_ncls, mi355_conv_plan *out);
+/* The same for a call that carries the least-padding hint of the stride-2 LDS-DMA planner (s2_least_padding != 0; MI355_S2_LEAST_PADDING,
+ * csrc/kernels.h ConvCall::s2_least_padding): where conv3_f32_s2dma_kernel takes the call, the tile shape - 2 x 2 x 32 or 2 x 4 x 16 -
+ * whose padded output columns times padded rows are fewer, ties to 2 x 2 x 32.  Only enc[1][0] of the shared level 1 sets the hint;
+ * with s2_least_padding = 0 this is mi355_conv3d_plan. */
+int mi355_conv3d_plan_hinted(int dtype, int n, int d, int h, int w, int c0, int c1, int cout, int stride, int impl, int has_stats,
+                             int has_in_norm, int head_ncls, int s2_least_padding, mi355_conv_plan *out);
 /* The kernel instantiations the 3x3x3 conv dispatch can launch (test aid; needs no device and launches nothing): one
  * "table | name\n" line per row of the four row tables (f32_rows, wino3_rows, f16_rows, s2h_rows), name as mi355_conv3d_plan and
  * mi355_last_conv_kernel spell it (without the " split-K" suffix).  Writes at most buf_bytes bytes, NUL-terminated, and returns
@@ -720,6 +726,10 @@ typedef struct mi355_stage0_view {
 int mi355_conv3d_s2dma_view_ndhwc(const float *x_dev, const mi355_stage0_view *view, int n, int d, int h, int w, int cin,
                                   const float *weight_host, const float *bias_host, int cout, int act, float slope, int force,
                                   float *y_dev, void *stream);
+/* The same with the least-padding hint (mi355_conv3d_plan_hinted) on the call; s2_least_padding = 0: mi355_conv3d_s2dma_view_ndhwc. */
+int mi355_conv3d_s2dma_hinted_ndhwc(const float *x_dev, const mi355_stage0_view *view, int n, int d, int h, int w, int cin,
+                                    const float *weight_host, const float *bias_host, int cout, int act, float slope, int force,
+                                    int s2_least_padding, float *y_dev, void *stream);
 /* mi355_conv3d_wino3_ndhwc with an addend (conv3_f32_wino3_kernel<3, false>) that is read through a view: addend_dev [n,d,h,w,cout]
  * the dense tile tensor; view (channels = cout) may be NULL. */
 int mi355_conv3d_wino3_view_ndhwc(const float *x0_dev, int n, int d, int h, int w, int c0, const float *weight_host,
@@ -840,6 +850,17 @@ typedef struct mi355_stage0_gather_merged_args {
     int32_t r2, channels2;
 } mi355_stage0_gather_merged_args;
 int mi355_stage0_gather_merged(const mi355_stage0_gather_merged_args *args, int shells_only, void *stream);
+/* The same for SUB-BOXES (shared level 1): sample i is the base.patch-sized box at sub[i] of a tile of `tile` voxels, origin[] its
+ * own origin in the volume; a slab that does not span the volume along k holds the TILE's extent there (slab_shape[a][k] = tile[k])
+ * and the box starts at sub[i][k] in it.  A face of a box that takes a shell must be a face of its tile.  by_box != 0: the launch of
+ * MI355_SUBBOX_GATHER - a dense gather of one tensor runs over the boxes (stage0_gather_box_kernel) instead of over the whole
+ * volume's rows; the same bytes.  (The shells-only form has one launch form.) */
+typedef struct mi355_stage0_gather_boxes_args {
+    mi355_stage0_gather_merged_args merged;
+    int32_t tile[3];
+    int32_t sub[64][3];
+} mi355_stage0_gather_boxes_args;
+int mi355_stage0_gather_boxes(const mi355_stage0_gather_boxes_args *args, int shells_only, int by_box, void *stream);
 /* ---- shared level 1 (MI355_SHARE_LEVEL1: 0 off, unset the default rule, 2 wherever possible; csrc/sliding_window.hip "shared
  * level 1"): the geometry and the decision mi355_sw_predict / mi355_sw_partial[_folds] run, as a dry run (no device; nothing is
  * launched).  A stride-2 conv commutes with shifts by an even number of voxels, so along
