@@ -49,6 +49,8 @@ EXPORTS = [
     "mi355_level1_share_plan",
     "mi355_reverse_axes",
     "mi355_conv3d_plan_hinted", "mi355_conv3d_s2dma_hinted_ndhwc", "mi355_stage0_gather_boxes",
+    "mi355_sw_partial_folds_moments", "mi355_sw_finish_moments", "mi355_logits_aggregate_m2", "mi355_logits_aggregate_tiles_m2",
+    "mi355_head_aggregate_m2", "mi355_uncertainty_maps", "mi355_uncertainty_stats",
 ]
 
 
@@ -320,6 +322,17 @@ def load():
                                            c_int32_p, vp]
     lib.mi355_logits_aggregate_tiles.argtypes = [vp, C.c_int, C.c_int, c_int32_p, C.c_int, c_int32_p, C.c_int, vp, vp, vp, c_int32_p,
                                                  c_int32_p, C.c_int, vp]
+    lib.mi355_head_aggregate_m2.argtypes = [vp, C.c_int, C.c_int, c_float_p, c_float_p, C.c_int, vp, vp, C.c_float, C.c_int, c_int32_p,
+                                            C.c_int, c_int32_p, C.c_int, vp, vp, vp, vp, c_int32_p, c_int32_p, vp]
+    lib.mi355_logits_aggregate_m2.argtypes = [vp, C.c_int, C.c_int, c_int32_p, C.c_int, c_int32_p, C.c_int, vp, vp, vp, vp, c_int32_p,
+                                              c_int32_p, vp]
+    lib.mi355_logits_aggregate_tiles_m2.argtypes = [vp, C.c_int, C.c_int, c_int32_p, C.c_int, c_int32_p, C.c_int, vp, vp, vp, vp, c_int32_p,
+                                                    c_int32_p, C.c_int, vp]
+    lib.mi355_sw_partial_folds_moments.argtypes = [C.POINTER(vp), C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(SwOpts), C.c_int, C.c_int,
+                                                   vp, vp, vp, vp]
+    lib.mi355_sw_finish_moments.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, C.c_int, vp, vp, vp]
+    lib.mi355_uncertainty_maps.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, c_int32_p, c_int32_p, vp, vp, vp]
+    lib.mi355_uncertainty_stats.argtypes = [vp, vp, vp, C.c_int, C.c_int64, c_float_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double), vp]
     lib.mi355_cnt_add_tile.argtypes = [vp, c_int32_p, vp, c_int32_p, c_int32_p, vp]
     lib.mi355_stage0_gather.argtypes = [C.POINTER(Stage0GatherArgs), vp]
     lib.mi355_stage0_mask.argtypes = [vp, C.c_int, c_int32_p, c_int32_p, C.c_int, vp]

@@ -742,10 +742,13 @@ struct MirrorList {
 // NM: compile-time mirror count (8 = the reference's full TTA; 0 = run time).  With the loop unrolled the feature loads of all
 // mirrors are independent of the sigmoid / softmax arithmetic between them and go out together: this kernel is a stream
 // of 16-B loads (32 per voxel for 32 channels x 8 mirrors), and as a run-time loop it had one mirror's four in flight.
-template <typename T, bool NORM, int NM = 0>
+// M2 (compile time; false = the kernel as it was, agg2 unused): the second moment rides along - res2 = sum_m mult * p * p beside
+// res = sum_m mult * p, agg2[:, tile] += res2 * gaussian - so that var = agg2 / cnt - (agg / cnt)^2 is the spread of the samples
+// whose mean the predictor keeps.  agg and cnt receive the same operations in the same order either way.
+template <typename T, bool NORM, int NM = 0, bool M2 = false>
 __global__ void head_aggregate_kernel(const T *feat, const float *w, const float *b, int C, int ncls,
                                       MirrorList ml, int P0, int P1, int P2, int nonlin, const float *gauss,
-                                      float *agg, float *cnt, int Zp, int Yp, int Xp, int z0, int y0, int x0, FeatNorm fn) {
+                                      float *agg, float *cnt, int Zp, int Yp, int Xp, int z0, int y0, int x0, FeatNorm fn, float *agg2) {
     const int64_t PV = (int64_t)P0 * P1 * P2;
     const int64_t ZYXp = (int64_t)Zp * Yp * Xp;
     const float mult = 1.0f / (float)ml.n;
@@ -754,8 +757,13 @@ __global__ void head_aggregate_kernel(const T *feat, const float *w, const float
         const int py = (int)((v / P2) % P1);
         const int pz = (int)(v / ((int64_t)P2 * P1));
         float res[HEAD_MAX_CLS];
+        float res2[M2 ? HEAD_MAX_CLS : 1];
 #pragma unroll
         for (int k = 0; k < HEAD_MAX_CLS; ++k) res[k] = 0.f;
+        if constexpr (M2) {
+#pragma unroll
+            for (int k = 0; k < HEAD_MAX_CLS; ++k) res2[k] = 0.f;
+        }
         const int nm = NM ? NM : ml.n;
 #pragma unroll
         for (int mi = 0; mi < (NM ? NM : 8); ++mi) {
@@ -784,12 +792,21 @@ __global__ void head_aggregate_kernel(const T *feat, const float *w, const float
             }
 #pragma unroll
             for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) res[k] += mult * lg[k];
+            if constexpr (M2) {
+#pragma unroll
+                for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) res2[k] += mult * lg[k] * lg[k];
+            }
         }
         const float g = gauss ? gauss[v] : 1.0f;
         const int64_t gi = ((int64_t)(z0 + pz) * Yp + (y0 + py)) * Xp + (x0 + px);
 #pragma unroll
         for (int k = 0; k < HEAD_MAX_CLS; ++k)
             if (k < ncls) agg[k * ZYXp + gi] += res[k] * g;
+        if constexpr (M2) {
+#pragma unroll
+            for (int k = 0; k < HEAD_MAX_CLS; ++k)
+                if (k < ncls) agg2[k * ZYXp + gi] += res2[k] * g;
+        }
         if (cnt) cnt[gi] += g;
     }
 }
@@ -797,21 +814,24 @@ __global__ void head_aggregate_kernel(const T *feat, const float *w, const float
 template <typename T>
 static void launch_head_aggregate(const HeadWeights &w, const T *feat, const MirrorList &ml, int P0, int P1, int P2, int nonlin,
                                   const float *gauss, float *agg, float *cnt, int Zp, int Yp, int Xp, int z0, int y0, int x0,
-                                  const FeatNorm &fn, hipStream_t s) {
+                                  const FeatNorm &fn, hipStream_t s, float *agg2) {
     const int64_t PV = (int64_t)P0 * P1 * P2;
     int64_t blocks = (PV + 255) / 256;
     if (blocks > 16384) blocks = 16384;
-#define MI355_HA_LAUNCH(NORM_, NM_) hipLaunchKernelGGL((head_aggregate_kernel<T, NORM_, NM_>), dim3((unsigned)blocks), dim3(256), 0, s, feat, w.w_dev, w.b_dev, \
-                                                      w.cin, w.ncls, ml, P0, P1, P2, nonlin, gauss, agg, cnt, Zp, Yp, Xp, z0, y0, x0, fn)
-    if (fn.scale) { if (ml.n == 8) MI355_HA_LAUNCH(true, 8); else MI355_HA_LAUNCH(true, 0); }
-    else { if (ml.n == 8) MI355_HA_LAUNCH(false, 8); else MI355_HA_LAUNCH(false, 0); }
+#define MI355_HA_LAUNCH(NORM_, NM_, M2_) hipLaunchKernelGGL((head_aggregate_kernel<T, NORM_, NM_, M2_>), dim3((unsigned)blocks), dim3(256), 0, s, feat, w.w_dev, w.b_dev, \
+                                                           w.cin, w.ncls, ml, P0, P1, P2, nonlin, gauss, agg, cnt, Zp, Yp, Xp, z0, y0, x0, fn, agg2)
+#define MI355_HA_MIRRORS(NORM_, M2_) do { if (ml.n == 8) MI355_HA_LAUNCH(NORM_, 8, M2_); else MI355_HA_LAUNCH(NORM_, 0, M2_); } while (0)
+    if (agg2) { if (fn.scale) MI355_HA_MIRRORS(true, true); else MI355_HA_MIRRORS(false, true); }
+    else { if (fn.scale) MI355_HA_MIRRORS(true, false); else MI355_HA_MIRRORS(false, false); }
+#undef MI355_HA_MIRRORS
 #undef MI355_HA_LAUNCH
 }
 
 int head_aggregate(const HeadWeights &w, const void *feat, int dtype, int first_sample, const int *mirrors_host,
                    int n_mirrors, int P0, int P1, int P2, int nonlin, const float *gauss, float *agg,
-                   float *cnt, int Zp, int Yp, int Xp, int z0, int y0, int x0, hipStream_t s, const FeatNorm &fn_all) {
+                   float *cnt, int Zp, int Yp, int Xp, int z0, int y0, int x0, hipStream_t s, const FeatNorm &fn_all, float *agg2) {
     MI355_REQUIRE(n_mirrors >= 1 && n_mirrors <= 8, "head_aggregate: %d mirrors", n_mirrors);
+    MI355_REQUIRE(!agg2 || nonlin != MI355_NONLIN_IDENTITY, "head_aggregate: the second moment needs probabilities (nonlin identity has none)");
     MirrorList ml;
     ml.n = n_mirrors;
     for (int i = 0; i < 8; ++i) ml.m[i] = i < n_mirrors ? mirrors_host[i] : 0;
@@ -820,23 +840,31 @@ int head_aggregate(const HeadWeights &w, const void *feat, int dtype, int first_
     if (fn.scale) { fn.scale += (size_t)first_sample * w.cin; fn.shift += (size_t)first_sample * w.cin; }
     if (dtype == MI355_F16)
         launch_head_aggregate<_Float16>(w, (const _Float16 *)feat + (size_t)first_sample * PV * w.cin, ml, P0, P1, P2, nonlin, gauss, agg,
-                                        cnt, Zp, Yp, Xp, z0, y0, x0, fn, s);
+                                        cnt, Zp, Yp, Xp, z0, y0, x0, fn, s, agg2);
     else
         launch_head_aggregate<float>(w, (const float *)feat + (size_t)first_sample * PV * w.cin, ml, P0, P1, P2, nonlin, gauss, agg, cnt,
-                                     Zp, Yp, Xp, z0, y0, x0, fn, s);
+                                     Zp, Yp, Xp, z0, y0, x0, fn, s, agg2);
     MI355_HIP(hipGetLastError());
     return MI355_OK;
 }
 
 // One tile's term of a voxel, from the logits [n_mirrors][ncls][PV] of that tile: acc[k] += (sum_m mult * nonlin(logits_m))[k] * g and
 // c += g at the tile's voxel (pz, py, px).  The one expression of both kernels below, so that they cannot drift by a rounding.
+// M2: acc2[k] += (sum_m mult * nonlin(logits_m)^2)[k] * g as well (acc2 is not touched without it); acc and c are the same either way.
+template <bool M2>
 static __device__ __forceinline__ void logits_tile_term(const float *logits, int ncls, const MirrorList &ml, int P0, int P1, int P2, int nonlin,
-                                                        const float *gauss, int pz, int py, int px, float acc[HEAD_MAX_CLS], float &c) {
+                                                        const float *gauss, int pz, int py, int px, float acc[HEAD_MAX_CLS], float &c,
+                                                        float *acc2) {
     const int64_t PV = (int64_t)P0 * P1 * P2;
     const float mult = 1.0f / (float)ml.n;
     float res[HEAD_MAX_CLS];
+    float res2[M2 ? HEAD_MAX_CLS : 1];
 #pragma unroll
     for (int k = 0; k < HEAD_MAX_CLS; ++k) res[k] = 0.f;
+    if constexpr (M2) {
+#pragma unroll
+        for (int k = 0; k < HEAD_MAX_CLS; ++k) res2[k] = 0.f;
+    }
     for (int mi = 0; mi < ml.n; ++mi) {
         const int m = ml.m[mi];
         const int sz = (m & 1) ? P0 - 1 - pz : pz;
@@ -861,18 +889,28 @@ static __device__ __forceinline__ void logits_tile_term(const float *logits, int
         }
 #pragma unroll
         for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) res[k] += mult * lg[k];
+        if constexpr (M2) {
+#pragma unroll
+            for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) res2[k] += mult * lg[k] * lg[k];
+        }
     }
     const float g = gauss ? gauss[((int64_t)pz * P1 + py) * P2 + px] : 1.0f;
 #pragma unroll
     for (int k = 0; k < HEAD_MAX_CLS; ++k)
         if (k < ncls) acc[k] += res[k] * g;
+    if constexpr (M2) {
+#pragma unroll
+        for (int k = 0; k < HEAD_MAX_CLS; ++k)
+            if (k < ncls) acc2[k] += res2[k] * g;
+    }
     c += g;
 }
 
 // Same as head_aggregate_kernel when the last conv already applied the head (logits [n_mirrors][ncls][PV] of this tile).
+template <bool M2 = false>
 __global__ void logits_aggregate_kernel(const float *logits, int ncls, MirrorList ml, int P0, int P1, int P2, int nonlin,
                                         const float *gauss, float *agg, float *cnt, int Zp, int Yp, int Xp, int z0, int y0,
-                                        int x0) {
+                                        int x0, float *agg2) {
     const int64_t PV = (int64_t)P0 * P1 * P2;
     const int64_t ZYXp = (int64_t)Zp * Yp * Xp;
     for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < PV; v += (int64_t)gridDim.x * blockDim.x) {
@@ -883,28 +921,44 @@ __global__ void logits_aggregate_kernel(const float *logits, int ncls, MirrorLis
         float acc[HEAD_MAX_CLS];
 #pragma unroll
         for (int k = 0; k < HEAD_MAX_CLS; ++k) acc[k] = (k < ncls) ? agg[k * ZYXp + gi] : 0.f;
+        float acc2[M2 ? HEAD_MAX_CLS : 1];
+        if constexpr (M2) {
+#pragma unroll
+            for (int k = 0; k < HEAD_MAX_CLS; ++k) acc2[k] = (k < ncls) ? agg2[k * ZYXp + gi] : 0.f;
+        }
         float c = cnt ? cnt[gi] : 0.f;
-        logits_tile_term(logits, ncls, ml, P0, P1, P2, nonlin, gauss, pz, py, px, acc, c);
+        logits_tile_term<M2>(logits, ncls, ml, P0, P1, P2, nonlin, gauss, pz, py, px, acc, c, acc2);
 #pragma unroll
         for (int k = 0; k < HEAD_MAX_CLS; ++k)
             if (k < ncls) agg[k * ZYXp + gi] = acc[k];
+        if constexpr (M2) {
+#pragma unroll
+            for (int k = 0; k < HEAD_MAX_CLS; ++k)
+                if (k < ncls) agg2[k * ZYXp + gi] = acc2[k];
+        }
         if (cnt) cnt[gi] = c;
     }
 }
 
 int logits_aggregate(const float *logits, int ncls, int first_sample, const int *mirrors_host, int n_mirrors, int P0, int P1,
                      int P2, int nonlin, const float *gauss, float *agg, float *cnt, int Zp, int Yp, int Xp, int z0, int y0,
-                     int x0, hipStream_t s) {
+                     int x0, hipStream_t s, float *agg2) {
     MI355_REQUIRE(n_mirrors >= 1 && n_mirrors <= 8 && ncls >= 1 && ncls <= HEAD_MAX_CLS, "logits_aggregate: bad arguments");
+    MI355_REQUIRE(!agg2 || nonlin != MI355_NONLIN_IDENTITY, "logits_aggregate: the second moment needs probabilities (nonlin identity has none)");
     MirrorList ml;
     ml.n = n_mirrors;
     for (int i = 0; i < 8; ++i) ml.m[i] = i < n_mirrors ? mirrors_host[i] : 0;
     const int64_t PV = (int64_t)P0 * P1 * P2;
     int64_t blocks = (PV + 255) / 256;
     if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(logits_aggregate_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
-                       logits + (size_t)first_sample * ncls * PV, ncls, ml, P0, P1, P2, nonlin, gauss, agg, cnt, Zp, Yp, Xp, z0, y0,
-                       x0);
+    if (agg2)
+        hipLaunchKernelGGL(logits_aggregate_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s,
+                           logits + (size_t)first_sample * ncls * PV, ncls, ml, P0, P1, P2, nonlin, gauss, agg, cnt, Zp, Yp, Xp, z0, y0,
+                           x0, agg2);
+    else
+        hipLaunchKernelGGL(logits_aggregate_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s,
+                           logits + (size_t)first_sample * ncls * PV, ncls, ml, P0, P1, P2, nonlin, gauss, agg, cnt, Zp, Yp, Xp, z0, y0,
+                           x0, agg2);
     MI355_HIP(hipGetLastError());
     return MI355_OK;
 }
@@ -918,9 +972,10 @@ struct AggTileList {
     int n;
     int org[LOGITS_AGG_MAX_TILES][3];
 };
+template <bool M2 = false>
 __global__ __launch_bounds__(256) void logits_aggregate_tiles_kernel(const float *logits, int ncls, MirrorList ml, int P0, int P1, int P2, int nonlin,
                                                                      const float *gauss, float *agg, float *cnt, int Zp, int Yp, int Xp, AggTileList tl,
-                                                                     int lo0, int lo1, int lo2, int B0, int B1, int B2) {
+                                                                     int lo0, int lo1, int lo2, int B0, int B1, int B2, float *agg2) {
     const int64_t PV = (int64_t)P0 * P1 * P2;
     const int64_t ZYXp = (int64_t)Zp * Yp * Xp;
     const int64_t BV = (int64_t)B0 * B1 * B2;
@@ -930,6 +985,7 @@ __global__ __launch_bounds__(256) void logits_aggregate_tiles_kernel(const float
         const int z = lo0 + (int)(v / ((int64_t)B2 * B1));
         const int64_t gi = ((int64_t)z * Yp + y) * Xp + x;
         float acc[HEAD_MAX_CLS];
+        float acc2[M2 ? HEAD_MAX_CLS : 1];
         float c = 0.f;
         bool held = false;
         for (int i = 0; i < tl.n; ++i) {
@@ -938,15 +994,24 @@ __global__ __launch_bounds__(256) void logits_aggregate_tiles_kernel(const float
             if (!held) {
 #pragma unroll
                 for (int k = 0; k < HEAD_MAX_CLS; ++k) acc[k] = (k < ncls) ? agg[k * ZYXp + gi] : 0.f;
+                if constexpr (M2) {
+#pragma unroll
+                    for (int k = 0; k < HEAD_MAX_CLS; ++k) acc2[k] = (k < ncls) ? agg2[k * ZYXp + gi] : 0.f;
+                }
                 c = cnt ? cnt[gi] : 0.f;
                 held = true;
             }
-            logits_tile_term(logits + (int64_t)i * ml.n * ncls * PV, ncls, ml, P0, P1, P2, nonlin, gauss, pz, py, px, acc, c);
+            logits_tile_term<M2>(logits + (int64_t)i * ml.n * ncls * PV, ncls, ml, P0, P1, P2, nonlin, gauss, pz, py, px, acc, c, acc2);
         }
         if (!held) continue;
 #pragma unroll
         for (int k = 0; k < HEAD_MAX_CLS; ++k)
             if (k < ncls) agg[k * ZYXp + gi] = acc[k];
+        if constexpr (M2) {
+#pragma unroll
+            for (int k = 0; k < HEAD_MAX_CLS; ++k)
+                if (k < ncls) agg2[k * ZYXp + gi] = acc2[k];
+        }
         if (cnt) cnt[gi] = c;
     }
 }
@@ -955,8 +1020,9 @@ __global__ __launch_bounds__(256) void logits_aggregate_tiles_kernel(const float
 // launches in order, each over the bounding box of its own tiles.
 int logits_aggregate_tiles(const float *logits, int ncls, int first_sample, const int *mirrors_host, int n_mirrors, int P0, int P1, int P2,
                            int nonlin, const float *gauss, float *agg, float *cnt, int Zp, int Yp, int Xp, const int *origins_host, int n_tiles,
-                           hipStream_t s) {
+                           hipStream_t s, float *agg2) {
     MI355_REQUIRE(n_mirrors >= 1 && n_mirrors <= 8 && ncls >= 1 && ncls <= HEAD_MAX_CLS && n_tiles >= 1, "logits_aggregate_tiles: bad arguments");
+    MI355_REQUIRE(!agg2 || nonlin != MI355_NONLIN_IDENTITY, "logits_aggregate_tiles: the second moment needs probabilities (nonlin identity has none)");
     MirrorList ml;
     ml.n = n_mirrors;
     for (int i = 0; i < 8; ++i) ml.m[i] = i < n_mirrors ? mirrors_host[i] : 0;
@@ -976,9 +1042,14 @@ int logits_aggregate_tiles(const float *logits, int ncls, int first_sample, cons
         const int64_t BV = (int64_t)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
         int64_t blocks = (BV + 255) / 256;
         if (blocks > 65536) blocks = 65536;
-        hipLaunchKernelGGL(logits_aggregate_tiles_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
-                           logits + ((size_t)first_sample + (size_t)t0 * n_mirrors) * ncls * PV, ncls, ml, P0, P1, P2, nonlin, gauss, agg, cnt, Zp, Yp,
-                           Xp, tl, lo[0], lo[1], lo[2], hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]);
+        if (agg2)
+            hipLaunchKernelGGL(logits_aggregate_tiles_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s,
+                               logits + ((size_t)first_sample + (size_t)t0 * n_mirrors) * ncls * PV, ncls, ml, P0, P1, P2, nonlin, gauss, agg, cnt, Zp, Yp,
+                               Xp, tl, lo[0], lo[1], lo[2], hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2], agg2);
+        else
+            hipLaunchKernelGGL(logits_aggregate_tiles_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s,
+                               logits + ((size_t)first_sample + (size_t)t0 * n_mirrors) * ncls * PV, ncls, ml, P0, P1, P2, nonlin, gauss, agg, cnt, Zp, Yp,
+                               Xp, tl, lo[0], lo[1], lo[2], hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2], agg2);
         MI355_HIP(hipGetLastError());
     }
     return MI355_OK;
@@ -1011,6 +1082,37 @@ int finish_probs(const float *agg, const float *cnt, int C, int Z, int Y, int X,
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(finish_probs_kernel, dim3((unsigned)blocks), dim3(256), 0, s, agg, cnt, C, Z, Y, X, Zp, Yp,
                        Xp, pz, py, px, probs, accumulate);
+    MI355_HIP(hipGetLastError());
+    return MI355_OK;
+}
+
+// Both moments of one ensemble member, cropped back from the padded grid: mean = agg / cnt / n_folds with the two divisions of
+// finish_probs_kernel followed by scale_kernel (x / 1.0f is x: the same bits as without the second division), m2 likewise from agg2.
+__global__ void finish_moments_kernel(const float *agg, const float *agg2, const float *cnt, int C, int Z, int Y, int X, int Zp, int Yp, int Xp,
+                                      int pz, int py, int px, float n_folds, float *mean, float *m2) {
+    const int64_t ZYX = (int64_t)Z * Y * X, ZYXp = (int64_t)Zp * Yp * Xp;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < ZYX; v += (int64_t)gridDim.x * blockDim.x) {
+        const int x = (int)(v % X);
+        const int y = (int)((v / X) % Y);
+        const int z = (int)(v / ((int64_t)X * Y));
+        const int64_t gi = ((int64_t)(z + pz) * Yp + (y + py)) * Xp + (x + px);
+        const float c = cnt[gi];
+        for (int k = 0; k < C; ++k) {
+            const float p = agg[k * ZYXp + gi] / c;
+            const float q = agg2[k * ZYXp + gi] / c;
+            mean[k * ZYX + v] = p / n_folds;
+            m2[k * ZYX + v] = q / n_folds;
+        }
+    }
+}
+
+int finish_moments(const float *agg, const float *agg2, const float *cnt, int C, int Z, int Y, int X, int Zp, int Yp, int Xp, int pz, int py, int px,
+                   int n_folds, float *mean, float *m2, hipStream_t s) {
+    const int64_t ZYX = (int64_t)Z * Y * X;
+    int64_t blocks = (ZYX + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(finish_moments_kernel, dim3((unsigned)blocks), dim3(256), 0, s, agg, agg2, cnt, C, Z, Y, X, Zp, Yp, Xp, pz, py, px, (float)n_folds,
+                       mean, m2);
     MI355_HIP(hipGetLastError());
     return MI355_OK;
 }

@@ -242,23 +242,29 @@ int head_logits(const HeadWeights &w, const void *feat, int dtype, int N, int64_
                 const FeatNorm &fn = FeatNorm());
 // One tile: result = sum_m (1/n_mirrors) * flip_back(nonlin(head(feat[first_sample+m])));
 // agg[c][tile] += result * gauss ; cnt[tile] += gauss (cnt may be null).
+// agg2 (here and in the two below; null: not kept): agg2[c][tile] += (sum_m (1/n_mirrors) * p^2) * gauss, the second moment of the
+// same samples; agg and cnt come out bit-identical with and without it.  nonlin identity is refused with agg2.
 int head_aggregate(const HeadWeights &w, const void *feat, int dtype, int first_sample, const int *mirrors_host,
                    int n_mirrors, int P0, int P1, int P2, int nonlin, const float *gauss, float *agg,
-                   float *cnt, int Zp, int Yp, int Xp, int z0, int y0, int x0, hipStream_t s, const FeatNorm &fn = FeatNorm());
+                   float *cnt, int Zp, int Yp, int Xp, int z0, int y0, int x0, hipStream_t s, const FeatNorm &fn = FeatNorm(),
+                   float *agg2 = nullptr);
 // same as head_aggregate for forwards whose last conv already produced logits [n_samples][ncls][PV]
 int logits_aggregate(const float *logits, int ncls, int first_sample, const int *mirrors_host, int n_mirrors, int P0, int P1,
                      int P2, int nonlin, const float *gauss, float *agg, float *cnt, int Zp, int Yp, int Xp, int z0, int y0,
-                     int x0, hipStream_t s);
+                     int x0, hipStream_t s, float *agg2 = nullptr);
 // The same for n_tiles tiles of one forward in one launch (per LOGITS_AGG_MAX_TILES tiles): tile i's logits are samples
 // first_sample + i * n_mirrors .., its origin origins_host[3 i ..]; bit-identical to logits_aggregate called tile by tile in order.
 constexpr int LOGITS_AGG_MAX_TILES = 64;
 int logits_aggregate_tiles(const float *logits, int ncls, int first_sample, const int *mirrors_host, int n_mirrors, int P0, int P1, int P2,
                            int nonlin, const float *gauss, float *agg, float *cnt, int Zp, int Yp, int Xp, const int *origins_host, int n_tiles,
-                           hipStream_t s);
+                           hipStream_t s, float *agg2 = nullptr);
 // probs[c][z][y][x] (+)= agg[c][z+pz][y+py][x+px] / cnt[...]; then optional scale (fold mean)
 int finish_probs(const float *agg, const float *cnt, int C, int Z, int Y, int X, int Zp, int Yp, int Xp,
                  int pz, int py, int px, float *probs, int accumulate, hipStream_t s);
 int scale_inplace(float *x, int64_t n, float divisor, hipStream_t s);
+// mean[c][z][y][x] = agg / cnt / n_folds (the bits of finish_probs then scale_inplace), m2 the same from agg2
+int finish_moments(const float *agg, const float *agg2, const float *cnt, int C, int Z, int Y, int X, int Zp, int Yp, int Xp, int pz, int py, int px,
+                   int n_folds, float *mean, float *m2, hipStream_t s);
 // cnt[tile] += gauss (or 1): the normaliser of a tile this rank does not evaluate itself
 int cnt_add_tile(const float *gauss, int P0, int P1, int P2, float *cnt, int Yp, int Xp, int z0, int y0, int x0,
                  hipStream_t s);

@@ -482,6 +482,60 @@ extern "C" int mi355_logits_aggregate_tiles(const float *logits_dev, int ncls, i
                   s, "logits_aggregate_tiles");
 }
 
+// ---- the same three with the second moment kept (agg2_dev, laid out as agg_dev): agg_dev / cnt_dev come out as from the plain calls
+extern "C" int mi355_head_aggregate_m2(const void *feat_dev, int dtype, int cin, const float *weight_host, const float *bias_host, int ncls,
+                                       const float *scale_dev, const float *shift_dev, float slope, int first_sample, const int32_t *mirrors_host,
+                                       int n_mirrors, const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *agg2_dev,
+                                       float *cnt_dev, const int32_t padded[3], const int32_t origin[3], void *stream) {
+    MI355_REQUIRE(feat_dev && weight_host && mirrors_host && patch && agg_dev && agg2_dev && padded && origin && first_sample >= 0,
+                  "mi355_head_aggregate_m2: bad argument");
+    MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_F16, "unknown dtype %d", dtype);
+    MI355_REQUIRE(!scale_dev == !shift_dev, "scale and shift come together");
+    MI355_REQUIRE(nonlin != MI355_NONLIN_IDENTITY, "mi355_head_aggregate_m2: nonlin identity has no probabilities to take moments of");
+    MI355_REQUIRE(tile_in_grid(patch, padded, origin), "mi355_head_aggregate_m2: the tile leaves the padded grid");
+    MI355_TRY(require_device());
+    TmpWeights<HeadWeights, head_weights_free> hw;
+    MI355_TRY(head_weights_upload(weight_host, bias_host, cin, ncls, &hw.w));
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> mirrors(mirrors_host, mirrors_host + std::max(n_mirrors, 0));
+    return synced(head_aggregate(hw.w, feat_dev, dtype, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev, agg_dev,
+                                 cnt_dev, padded[0], padded[1], padded[2], origin[0], origin[1], origin[2], s, feat_norm(scale_dev, shift_dev, slope),
+                                 agg2_dev),
+                  s, "head_aggregate m2");
+}
+
+extern "C" int mi355_logits_aggregate_m2(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
+                                         const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *agg2_dev, float *cnt_dev,
+                                         const int32_t padded[3], const int32_t origin[3], void *stream) {
+    MI355_REQUIRE(logits_dev && mirrors_host && patch && agg_dev && agg2_dev && padded && origin && first_sample >= 0,
+                  "mi355_logits_aggregate_m2: bad argument");
+    MI355_REQUIRE(nonlin != MI355_NONLIN_IDENTITY, "mi355_logits_aggregate_m2: nonlin identity has no probabilities to take moments of");
+    MI355_REQUIRE(tile_in_grid(patch, padded, origin), "mi355_logits_aggregate_m2: the tile leaves the padded grid");
+    MI355_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> mirrors(mirrors_host, mirrors_host + std::max(n_mirrors, 0));
+    return synced(logits_aggregate(logits_dev, ncls, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev, agg_dev,
+                                   cnt_dev, padded[0], padded[1], padded[2], origin[0], origin[1], origin[2], s, agg2_dev),
+                  s, "logits_aggregate m2");
+}
+
+extern "C" int mi355_logits_aggregate_tiles_m2(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
+                                               const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *agg2_dev,
+                                               float *cnt_dev, const int32_t padded[3], const int32_t *origins, int n_tiles, void *stream) {
+    MI355_REQUIRE(logits_dev && mirrors_host && patch && agg_dev && agg2_dev && padded && origins && first_sample >= 0 && n_tiles >= 1,
+                  "mi355_logits_aggregate_tiles_m2: bad argument");
+    MI355_REQUIRE(nonlin != MI355_NONLIN_IDENTITY, "mi355_logits_aggregate_tiles_m2: nonlin identity has no probabilities to take moments of");
+    for (int i = 0; i < n_tiles; ++i)
+        MI355_REQUIRE(tile_in_grid(patch, padded, origins + 3 * (size_t)i), "mi355_logits_aggregate_tiles_m2: tile %d leaves the padded grid", i);
+    MI355_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> mirrors(mirrors_host, mirrors_host + std::max(n_mirrors, 0));
+    std::vector<int> org(origins, origins + 3 * (size_t)n_tiles);
+    return synced(logits_aggregate_tiles(logits_dev, ncls, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev,
+                                         agg_dev, cnt_dev, padded[0], padded[1], padded[2], org.data(), n_tiles, s, agg2_dev),
+                  s, "logits_aggregate_tiles m2");
+}
+
 extern "C" int mi355_cnt_add_tile(const float *gauss_dev, const int32_t patch[3], float *cnt_dev, const int32_t padded[3],
                                   const int32_t origin[3], void *stream) {
     MI355_REQUIRE(patch && cnt_dev && padded && origin, "mi355_cnt_add_tile: bad argument");

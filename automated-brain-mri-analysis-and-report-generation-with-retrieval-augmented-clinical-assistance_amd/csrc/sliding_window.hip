@@ -433,8 +433,10 @@ static int level1_tiles(mi355_unet *net, const Plan &pl, const SwGeom &g, const 
 // for ALL tiles so that every rank holds the full normaliser).
 // `first_item`: index of this net's tile 0 in the caller's work list (fold f of a fold list: f * tiles): the work items
 // (fold, tile) are dealt round-robin over the ranks as ONE list, so 5 folds x 8 tiles on 3 ranks still balance.
+// agg2 (null: not kept): the second moment of the same samples, handed to whichever aggregation the forward ends in; agg and cnt
+// are the same bits with and without it.
 static int sw_accumulate(mi355_unet *net, const SwVolume &v, const mi355_sw_opts &o, const SwGeom &g, int rank, int world, float *agg, float *cnt,
-                         hipStream_t s, long first_item = 0) {
+                         hipStream_t s, long first_item = 0, float *agg2 = nullptr) {
     const int nm = (int)g.mirrors.size();
     const bool use_gauss = o.use_gaussian && g.tiles.size() > 1;
     if (use_gauss) MI355_TRY(ensure_gaussian(net, g.P));
@@ -513,20 +515,21 @@ static int sw_accumulate(mi355_unet *net, const SwVolume &v, const mi355_sw_opts
                 }
             }
             const double pv = (double)g.P[0] * g.P[1] * g.P[2], box = (double)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
-            ProfScope ps(net, s, "logits_aggregate_tiles_kernel", 0.0, 4.0 * (nb * pv * (nm * net->num_classes + 1.0) + box * (2.0 * net->num_classes + 2.0)));
+            ProfScope ps(net, s, agg2 ? "logits_aggregate_tiles_kernel m2" : "logits_aggregate_tiles_kernel", 0.0,
+                         4.0 * (nb * pv * (nm * net->num_classes + 1.0) + box * (2.0 * net->num_classes + 2.0) + (agg2 ? box * 2.0 * net->num_classes : 0.0)));
             MI355_TRY(logits_aggregate_tiles((const float *)feat, net->num_classes, 0, g.mirrors.data(), nm, g.P[0], g.P[1], g.P[2], o.nonlin,
                                              use_gauss ? net->gauss_dev : nullptr, agg, (cnt && world == 1) ? cnt : nullptr, g.Zp[0], g.Zp[1],
-                                             g.Zp[2], origins.data(), nb, s));
+                                             g.Zp[2], origins.data(), nb, s, agg2));
             continue;
         }
         for (int i = 0; i < nb; ++i) {
             const TileDesc &td = g.tiles[mine[b0 + i]];
             const double pv = (double)g.P[0] * g.P[1] * g.P[2];
-            ProfScope ps(net, s, "head_aggregate_kernel", 2.0 * pv * nm * fc * net->num_classes,
-                         pv * ((net->dtype == MI355_F16 ? 2.0 : 4.0) * nm * fc + 4.0 * (2.0 * net->num_classes + 3.0)));
+            ProfScope ps(net, s, agg2 ? "head_aggregate_kernel m2" : "head_aggregate_kernel", 2.0 * pv * nm * fc * net->num_classes,
+                         pv * ((net->dtype == MI355_F16 ? 2.0 : 4.0) * nm * fc + 4.0 * (2.0 * net->num_classes + 3.0 + (agg2 ? 2.0 * net->num_classes : 0.0))));
             MI355_TRY(head_aggregate(net->head, feat, net->dtype, i * nm, g.mirrors.data(), nm, g.P[0], g.P[1], g.P[2], o.nonlin,
                                      use_gauss ? net->gauss_dev : nullptr, agg, (cnt && world == 1) ? cnt : nullptr,
-                                     g.Zp[0], g.Zp[1], g.Zp[2], td.z0, td.y0, td.x0, s, head_norm));
+                                     g.Zp[0], g.Zp[1], g.Zp[2], td.z0, td.y0, td.x0, s, head_norm, agg2));
         }
     }
     return MI355_OK;
@@ -540,8 +543,8 @@ using namespace mi355;
 // :112-128): the work list is (fold, tile), item f * tiles + t, dealt round-robin over the ranks; agg_dev receives
 // sum over this rank's items of the Gaussian-weighted, mirror-averaged probabilities - the fold mean is linear in the
 // per-fold aggregates (mean_f(agg_f / cnt) = (sum_f agg_f) / cnt / n_folds), so ONE exchange per ensemble member suffices.
-extern "C" int mi355_sw_partial_folds(const mi355_unet_t *nets, int n_nets, const float *vol_dev, int Z, int Y, int X,
-                                      const mi355_sw_opts *opts, int rank, int world, float *agg_dev, float *cnt_dev, void *stream) {
+static int sw_partial_folds(const mi355_unet_t *nets, int n_nets, const float *vol_dev, int Z, int Y, int X, const mi355_sw_opts *opts, int rank, int world,
+                            float *agg_dev, float *agg2_dev, float *cnt_dev, void *stream) {
     MI355_REQUIRE(nets && n_nets >= 1 && vol_dev && opts && agg_dev && world >= 1 && rank >= 0 && rank < world, "bad argument");
     for (int f = 0; f < n_nets; ++f) {
         MI355_REQUIRE(nets[f] != nullptr, "fold %d: null handle", f);
@@ -553,6 +556,7 @@ extern "C" int mi355_sw_partial_folds(const mi355_unet_t *nets, int n_nets, cons
     MI355_TRY(make_geom(*opts, Z, Y, X, &g));
     const size_t ZYXp = (size_t)g.Zp[0] * g.Zp[1] * g.Zp[2];
     MI355_HIP(hipMemsetAsync(agg_dev, 0, ZYXp * nets[0]->num_classes * sizeof(float), s));
+    if (agg2_dev) MI355_HIP(hipMemsetAsync(agg2_dev, 0, ZYXp * nets[0]->num_classes * sizeof(float), s));
     if (cnt_dev) MI355_HIP(hipMemsetAsync(cnt_dev, 0, ZYXp * sizeof(float), s));
     if (cnt_dev && world > 1) {
         // full normaliser of ONE fold on every rank: cnt[tile] += gaussian for ALL tiles, in tile order (no exchange needed)
@@ -565,8 +569,24 @@ extern "C" int mi355_sw_partial_folds(const mi355_unet_t *nets, int n_nets, cons
     // (world == 1: the first fold's aggregation kernels add the normaliser themselves, exactly as mi355_sw_predict does)
     for (int f = 0; f < n_nets; ++f)
         MI355_TRY(sw_accumulate(nets[f], SwVolume{vol_dev, Z, Y, X}, *opts, g, rank, world, agg_dev, f == 0 ? cnt_dev : nullptr, s,
-                                (long)f * (long)g.tiles.size()));
+                                (long)f * (long)g.tiles.size(), agg2_dev));
     return MI355_OK;
+}
+
+extern "C" int mi355_sw_partial_folds(const mi355_unet_t *nets, int n_nets, const float *vol_dev, int Z, int Y, int X,
+                                      const mi355_sw_opts *opts, int rank, int world, float *agg_dev, float *cnt_dev, void *stream) {
+    return sw_partial_folds(nets, n_nets, vol_dev, Z, Y, X, opts, rank, world, agg_dev, nullptr, cnt_dev, stream);
+}
+
+// The same with the second moment kept: agg2_dev receives sum over this rank's items of gaussian * mean over mirrors of p^2, linear in
+// the per-tile terms exactly as agg_dev is, so it splits over ranks and sums in rank order the same way.  Extends the fold mean of
+// run_brats2021_inference_singlethread.py:97-128, which keeps the first moment alone.
+extern "C" int mi355_sw_partial_folds_moments(const mi355_unet_t *nets, int n_nets, const float *vol_dev, int Z, int Y, int X,
+                                              const mi355_sw_opts *opts, int rank, int world, float *agg_dev, float *agg2_dev, float *cnt_dev,
+                                              void *stream) {
+    MI355_REQUIRE(agg2_dev && opts, "mi355_sw_partial_folds_moments: bad argument");
+    MI355_REQUIRE(opts->nonlin != MI355_NONLIN_IDENTITY, "mi355_sw_partial_folds_moments: nonlin identity has no probabilities to take moments of");
+    return sw_partial_folds(nets, n_nets, vol_dev, Z, Y, X, opts, rank, world, agg_dev, agg2_dev, cnt_dev, stream);
 }
 
 extern "C" int mi355_sw_partial(mi355_unet_t net, const float *vol_dev, int Z, int Y, int X, const mi355_sw_opts *opts,
@@ -583,6 +603,16 @@ extern "C" int mi355_sw_finish_folds(const float *agg_dev, const float *cnt_dev,
                            probs_dev, 0, (hipStream_t)stream));
     if (n_folds > 1) MI355_TRY(scale_inplace(probs_dev, (int64_t)num_classes * Z * Y * X, (float)n_folds, (hipStream_t)stream));
     return MI355_OK;
+}
+
+extern "C" int mi355_sw_finish_moments(const float *agg_dev, const float *agg2_dev, const float *cnt_dev, int num_classes, int Z, int Y, int X,
+                                       const int32_t patch[3], int n_folds, float *mean_dev, float *m2_dev, void *stream) {
+    MI355_REQUIRE(agg_dev && agg2_dev && cnt_dev && mean_dev && m2_dev && patch && n_folds >= 1 && num_classes >= 1 && Z >= 1 && Y >= 1 && X >= 1,
+                  "mi355_sw_finish_moments: bad argument");
+    MI355_TRY(bind_device());
+    const int Zp = std::max(Z, patch[0]), Yp = std::max(Y, patch[1]), Xp = std::max(X, patch[2]);
+    return finish_moments(agg_dev, agg2_dev, cnt_dev, num_classes, Z, Y, X, Zp, Yp, Xp, (Zp - Z) / 2, (Yp - Y) / 2, (Xp - X) / 2, n_folds, mean_dev, m2_dev,
+                          (hipStream_t)stream);
 }
 
 extern "C" int mi355_sw_finish(const float *agg_dev, const float *cnt_dev, int num_classes, int Z, int Y, int X,

@@ -232,7 +232,43 @@ def ensemble_label_files(model1_output: Path, model2_output: Path, output_folder
     return finals
 
 
+def uncertainty_products(moments, segs, models, props, like, do_tta):
+    """``--uncertainty``: from the two members' (mean, m2) - resampled for export, on the device - the ensemble's two reduced maps
+    [Z, Y, X] (device, full volume) and the dict behind ``<case>_uncertainty.json``."""
+    from . import uncertainty
+    model = models[0]
+    k = moments[0][0].shape[0]
+    names = list(uncertainty.REGION_NAMES) if model.folder.regions and k == 3 else [f"class_{i}" for i in range(k)]
+    lo = [b[0] for b in props["crop_bbox"]]
+    voxel_mm3 = float(np.prod(like.zooms))
+    blocks, reduced = {}, None
+    for tag, args in (("ensemble", moments[0] + moments[1]), ("member_1", moments[0]), ("member_2", moments[1])):
+        m = uncertainty.maps(*args, nonlin=model.nonlin, bbox_lo=lo, full_shape=props["original_size_of_raw_data"])
+        mean = ops.prob_mean(moments[0][0], moments[1][0]) if tag == "ensemble" else args[0]
+        counts, sums = uncertainty.region_stats(mean, m["std"] * m["std"], m["entropy"], uncertainty.THRESHOLDS)
+        blocks[tag] = uncertainty.summarize(counts, sums, voxel_mm3, names, uncertainty.THRESHOLDS)
+        if tag == "ensemble":
+            reduced = (m["entropy_max"], m["std_max"])
+    agreement = uncertainty.member_agreement(segs[0], segs[1], (1, 2, 3), names) if model.folder.regions and k == 3 else None
+    doc = {"thresholds": list(uncertainty.THRESHOLDS), "regions": names, "ensemble": blocks["ensemble"],
+           "members": [blocks["member_1"], blocks["member_2"]], "member_agreement": agreement,
+           "samples": {"folds": [len(m.nets) for m in models], "mirrors": 8 if do_tta else 1, "models": len(models)}}
+    return reduced, doc
+
+
+def _write_json(path, doc):
+    import json
+    with open(path, "w", encoding="utf-8") as f:
+        json.dump(doc, f, indent=2)
+
+
 def run_both_models(model_dirs, input_folder, output_folder, folds, do_tta, step_size, dtype, label_format, cache: ModelCache, analyze=None):
+    """``run_cases`` without its later options: the signature callers know."""
+    return run_cases(model_dirs, input_folder, output_folder, folds, do_tta, step_size, dtype, label_format, cache, analyze)
+
+
+def run_cases(model_dirs, input_folder, output_folder, folds, do_tta, step_size, dtype, label_format, cache: ModelCache, analyze=None,
+              uncertainty=False):
     """What reference :263-322 produces (model 1 over all cases, model 2 over all cases, label-round ensemble of the two
     NIfTI files per case), computed in ONE pass per case: the four modalities are read, cropped and normalised once
     (the reference preprocesses per model, :89), both members predict from the same device tensor, the ensemble takes
@@ -244,7 +280,11 @@ def run_both_models(model_dirs, input_folder, output_folder, folds, do_tta, step
     ``analyze`` (default None: nothing below changes): a callable ``analyze(raw, ens, like, case_name, n_cases, submit)`` run once per
     case after its three label files are on their way - ``raw`` the uploaded modalities [4, Z, Y, X] (preprocessing then keeps the
     tensor instead of freeing it), ``ens`` the ensemble's label map [Z, Y, X], both on the device, ``like`` the case's geometry,
-    ``submit(fn, *args)`` the background writer pool, joined with the label files.  ``--analyze`` hands in ``pipeline.analyze_resident``."""
+    ``submit(fn, *args)`` the background writer pool, joined with the label files.  ``--analyze`` hands in ``pipeline.analyze_resident``.
+
+    ``uncertainty`` (default False: nothing below changes): each member predicts through ``predict_folds_moments`` - its mean is
+    ``predict_folds`` bit for bit, so every label file stays what it was - and the case gets ``<case>_entropy.nii.gz``,
+    ``<case>_std.nii.gz`` (float32, the input's geometry) and ``<case>_uncertainty.json`` (``uncertainty_products``)."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
     from . import evaluate
@@ -267,6 +307,10 @@ def run_both_models(model_dirs, input_folder, output_folder, folds, do_tta, step
     mirror = pool.submit(prepare_input, input_folder, outs[1] / "temp_input", True)
     models = [f.result() for f in loaders]
     print(f"Loaded {sum(len(m.nets) for m in models)} fold checkpoints of {len(models)} models in {time.perf_counter() - t0:.2f} s")
+    if uncertainty and (len({m.nets[0].topology.num_classes for m in models}) != 1 or len({m.nonlin for m in models}) != 1):
+        mirror.result()
+        pool.shutdown()
+        raise ValueError("--uncertainty: the ensemble members have different class counts or nonlinearities; their moments cannot be pooled")
     if not prepared:
         print("[ERROR] No valid cases found!")
         mirror.result()
@@ -310,6 +354,7 @@ def run_both_models(model_dirs, input_folder, output_folder, folds, do_tta, step
         print(f"Data shape after preprocessing: {tuple(data.shape)}")
         t2 = time.perf_counter()
         segs = [None] * len(models)
+        moments = [None] * len(models)
         # (the larger member first: the process-wide activation arena is then allocated once at its final size instead of
         #  being freed and re-allocated when the second member turns out to need more - a 20-50 GB hipMalloc each time)
         order = sorted(range(len(models)), key=lambda i: -sum(int(np.prod(v.shape)) for v in models[i].folder.fold_state_dicts[0].values()))
@@ -323,11 +368,21 @@ def run_both_models(model_dirs, input_folder, output_folder, folds, do_tta, step
                         preprocessing.check_spacing(plans0, zyx, props["size_after_cropping"]):
                     raise preprocessing.UnsupportedPlansError("the two ensemble members' plans resample this case to different grids")
             print(f"Predicting {case_name} with model {mi + 1} ({len(model.nets)} folds)")
-            probs = predictor.predict_folds(model.nets, data, model.patch_size, step_size, do_tta, (0, 1, 2), True, model.nonlin)
+            if uncertainty:   # the same mean, bit for bit, and the second moment of the same samples beside it
+                probs, m2 = predictor.predict_folds_moments(model.nets, data, model.patch_size, step_size, do_tta, (0, 1, 2), True, model.nonlin)
+                m2 = preprocessing.resample_probabilities_for_export(m2, props)
+            else:
+                probs = predictor.predict_folds(model.nets, data, model.patch_size, step_size, do_tta, (0, 1, 2), True, model.nonlin)
             probs = preprocessing.resample_probabilities_for_export(probs, props)   # (a no-op unless preprocessing resampled)
+            if uncertainty:
+                moments[mi] = (probs, m2)
             lo = [b[0] for b in props["crop_bbox"]]
             segs[mi] = ops.regions_to_labels(probs, (1, 2, 3) if model.folder.regions else None, lo, props["original_size_of_raw_data"])
         ens = evaluate.convert_labels(ops.label_ensemble(segs[0], segs[1]), label_format)
+        unc_maps = unc_doc = None
+        if uncertainty:   # (before the next case's preprocessing is enqueued: region_stats reads back, and works in per-lane scratch)
+            unc_maps, unc_doc = uncertainty_products(moments, segs, models, props, cur_like, do_tta)
+            moments = [None] * len(models)
         if ci + 1 < len(prepared):  # the forwards above are only enqueued: preprocess the next case beside them
             raw, like = nxt.result()
             ready = preprocess_on_side(raw, like, plans0)
@@ -338,6 +393,12 @@ def run_both_models(model_dirs, input_folder, output_folder, folds, do_tta, step
         for arr, path in zip(host, (outs[0] / f"{case_name}.nii.gz", outs[1] / f"{case_name}.nii.gz", final_output)):
             # label volumes are written (x, y, z); the reference's ensemble saves with seg1's header = the input geometry
             writes.append(pool.submit(nifti.save_like, path, np.ascontiguousarray(arr.transpose(2, 1, 0)), cur_like))
+        if uncertainty:
+            for t, tag in zip(unc_maps, ("entropy", "std")):
+                writes.append(pool.submit(nifti.save_like, output_folder / f"{case_name}_{tag}.nii.gz",
+                                          np.ascontiguousarray(t.cpu().numpy().transpose(2, 1, 0)), cur_like))
+            writes.append(pool.submit(_write_json, output_folder / f"{case_name}_uncertainty.json", dict(unc_doc, case=case_name)))
+            del unc_maps
         v = volumes_of(host[2], cur_like.zooms)
         print(f"[OK] Completed: {final_output}  (wait for input {t2 - t1:.2f} s, predict {t3 - t2:.2f} s)")
         print(f"\nTumor Volume Analysis for {case_name}:")
@@ -389,6 +450,11 @@ def build_parser():
                     help="after each case's ensemble, from the tensors still on the device: <case>_brats.nii.gz (BraTS 2025 labels), the "
                          "evaluation against a ground truth when there is one (report on stdout, <case>_evaluation.json) and the seven "
                          "files of feature_extraction/ - what run_full_pipeline.py spawns three more programs for (brats_amd.pipeline)")
+    # (argparse.SUPPRESS: without the flag the parsed arguments are what they were before it existed - no new key)
+    ap.add_argument("--uncertainty", action="store_true", default=argparse.SUPPRESS,
+                    help="keep the spread of the samples (fold, tile, mirror) the predictor averages: <case>_entropy.nii.gz and "
+                         "<case>_std.nii.gz (float32 maps of the ensemble) and <case>_uncertainty.json (volume intervals, mean confidence, "
+                         "boundary share and member agreement per region); every other product stays byte-identical")
     ap.add_argument("--gt", type=str, default=None,
                     help="with --analyze: the ground-truth segmentation (default: <input>/<case>_seg.nii.gz, then <case>-seg.nii.gz; "
                          "none: no evaluation).  Through the resident worker: an absolute path")
@@ -404,6 +470,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.analyze and args.sequential:
         ap.error("--analyze works on the tensors of the one-pass-per-case path: not with --sequential")
+    if getattr(args, "uncertainty", False) and args.sequential:
+        ap.error("--uncertainty works on the tensors of the one-pass-per-case path: not with --sequential")
     if args.analyze and args.label_format != "nnunet":
         ap.error("--analyze converts the labels itself (<case>_brats.nii.gz): --label-format must stay nnunet")
     if not args.analyze and (args.gt is not None or args.lesionwise):
@@ -444,8 +512,12 @@ def main(argv=None, script_dir=None, model_cache: ModelCache = None):
             analyze = functools.partial(pipeline.analyze_resident, input_folder=args.input, output_folder=output_folder, gt=args.gt,
                                         lesionwise=args.lesionwise, distance=args.distance, seed=args.seed)
         try:
-            run_both_models([base / MODEL1, base / MODEL2], args.input, output_folder, tuple(args.folds), not args.disable_tta,
-                            args.step_size, args.dtype, args.label_format, cache, analyze)
+            if getattr(args, "uncertainty", False):
+                run_cases([base / MODEL1, base / MODEL2], args.input, output_folder, tuple(args.folds), not args.disable_tta,
+                          args.step_size, args.dtype, args.label_format, cache, analyze, uncertainty=True)
+            else:
+                run_both_models([base / MODEL1, base / MODEL2], args.input, output_folder, tuple(args.folds), not args.disable_tta,
+                                args.step_size, args.dtype, args.label_format, cache, analyze)
         finally:
             if model_cache is None:
                 cache.close()

@@ -709,6 +709,73 @@ def logits_aggregate_tiles_(logits, mirrors, patch, nonlin, agg, cnt, origins, g
                "mi355_logits_aggregate_tiles")
 
 
+def _agg2_operand(agg, agg2, name):
+    import torch
+    if agg2 is None or not agg2.is_cuda or agg2.dtype != torch.float32 or not agg2.is_contiguous() or agg2.shape != agg.shape:
+        raise ValueError(f"{name}: agg2 must be a contiguous CUDA fp32 tensor of agg's shape")
+    if agg2.data_ptr() == agg.data_ptr():
+        raise ValueError(f"{name}: agg2 must not be agg")
+    return agg2
+
+
+def head_aggregate_m2_(feat, weight, bias, mirrors, patch, nonlin, agg, agg2, cnt, origin, gauss=None, first_sample=0, scale=None, shift=None,
+                       slope=1.0):
+    """``mi355_head_aggregate_m2``: ``head_aggregate_`` that also adds the tile's second moment (mean over the mirrors of p^2, times
+    gauss) into agg2 [ncls, Zp, Yp, Xp]; agg and cnt receive what the plain call gives them, bit for bit.  "identity" is refused."""
+    f16, n, v, c = _feat_dims(feat)
+    weight, bias = _head_operands(weight, bias, c)
+    mirrors = [int(m) for m in mirrors]
+    gauss, padded, pv = _tile_operands(agg, cnt, gauss, weight.shape[0], patch, origin, "head_aggregate_m2_")
+    agg2 = _agg2_operand(agg, agg2, "head_aggregate_m2_")
+    if v != pv or first_sample < 0 or first_sample + len(mirrors) > n:
+        raise ValueError("head_aggregate_m2_: feat does not hold the tile's samples")
+    scale, shift = _f32(scale, "scale", n * c), _f32(shift, "shift", n * c)
+    from .predictor import NONLIN
+    _lib.check(_lib.load().mi355_head_aggregate_m2(feat.data_ptr(), int(f16), c, _lib.fptr(weight), _lib.fptr(bias), weight.shape[0], _ptr(scale),
+                                                   _ptr(shift), float(slope), int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
+                                                   len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss), agg.data_ptr(), agg2.data_ptr(),
+                                                   _ptr(cnt), _i3(padded), _i3(origin), stream_of(feat)), "mi355_head_aggregate_m2")
+
+
+def logits_aggregate_m2_(logits, mirrors, patch, nonlin, agg, agg2, cnt, origin, gauss=None, first_sample=0):
+    """``mi355_logits_aggregate_m2``: as ``head_aggregate_m2_`` from logits CUDA fp32 [S, ncls, PV]."""
+    import torch
+    logits = _require_cuda(logits, torch.float32, "logits")
+    n, ncls, v = logits.shape
+    mirrors = [int(m) for m in mirrors]
+    gauss, padded, pv = _tile_operands(agg, cnt, gauss, ncls, patch, origin, "logits_aggregate_m2_")
+    agg2 = _agg2_operand(agg, agg2, "logits_aggregate_m2_")
+    if v != pv or first_sample < 0 or first_sample + len(mirrors) > n:
+        raise ValueError("logits_aggregate_m2_: logits do not hold the tile's samples")
+    from .predictor import NONLIN
+    _lib.check(_lib.load().mi355_logits_aggregate_m2(logits.data_ptr(), ncls, int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
+                                                     len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss), agg.data_ptr(), agg2.data_ptr(),
+                                                     _ptr(cnt), _i3(padded), _i3(origin), stream_of(logits)), "mi355_logits_aggregate_m2")
+
+
+def logits_aggregate_tiles_m2_(logits, mirrors, patch, nonlin, agg, agg2, cnt, origins, gauss=None, first_sample=0):
+    """``mi355_logits_aggregate_tiles_m2``: the tiles at ``origins`` in one launch with the second moment kept; agg2 is bit-identical to
+    ``logits_aggregate_m2_`` tile by tile in that order, and a voxel no tile covers is not written."""
+    import torch
+    logits = _require_cuda(logits, torch.float32, "logits")
+    n, ncls, v = logits.shape
+    mirrors = [int(m) for m in mirrors]
+    origins = [[int(k) for k in o] for o in origins]
+    if not origins:
+        raise ValueError("logits_aggregate_tiles_m2_: no tile")
+    for o in origins:
+        gauss_dev, padded, pv = _tile_operands(agg, cnt, gauss, ncls, patch, o, "logits_aggregate_tiles_m2_")
+    agg2 = _agg2_operand(agg, agg2, "logits_aggregate_tiles_m2_")
+    if v != pv or first_sample < 0 or first_sample + len(origins) * len(mirrors) > n:
+        raise ValueError("logits_aggregate_tiles_m2_: logits do not hold the tiles' samples")
+    flat = [k for o in origins for k in o]
+    from .predictor import NONLIN
+    _lib.check(_lib.load().mi355_logits_aggregate_tiles_m2(logits.data_ptr(), ncls, int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
+                                                           len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss_dev), agg.data_ptr(), agg2.data_ptr(),
+                                                           _ptr(cnt), _i3(padded), (C.c_int32 * len(flat))(*flat), len(origins), stream_of(logits)),
+               "mi355_logits_aggregate_tiles_m2")
+
+
 def cnt_add_tile_(cnt, patch, origin, gauss=None):
     """``mi355_cnt_add_tile``: cnt [Zp, Yp, Xp] (CUDA fp32, in place) += gauss [patch] (None: 1) at origin."""
     gauss, padded, _ = _tile_operands(cnt[None], cnt, gauss, 1, patch, origin, "cnt_add_tile_")

@@ -195,11 +195,13 @@ def predict_preprocessed_data_return_seg_and_softmax(net: UNet, data, do_mirrori
 
 def predict_tile_sharded(net, data, rank: int, world: int, patch_size=(128, 128, 128), step_size=0.5,
                          do_mirroring=True, mirror_axes=(0, 1, 2), use_gaussian=True, nonlin="sigmoid",
-                         batch_tiles=0, device="cuda", want_cnt=True):
+                         batch_tiles=0, device="cuda", want_cnt=True, want_m2=False):
     """This rank's share of one volume: returns (agg [K,Zp,Yp,Xp], cnt [Zp,Yp,Xp]); ``finish_sharded`` turns the
     rank-ordered sum into probabilities.  ``net`` is one network (tiles with index % world == rank) or the FOLD LIST of
     one ensemble member (driver :161, :112-128): then the work list is (fold, tile), item ``f * tiles + t`` goes to rank
-    ``item % world``, and ``agg`` is the sum of this rank's items over all folds (``mi355_sw_partial_folds``)."""
+    ``item % world``, and ``agg`` is the sum of this rank's items over all folds (``mi355_sw_partial_folds``).
+    ``want_m2``: returns (agg, cnt, agg2) with ``agg2`` the second moment of the same samples (``mi355_sw_partial_folds_moments``);
+    agg and cnt are the same bits either way."""
     import torch
     nets = list(net) if isinstance(net, (list, tuple)) else [net]
     if len(nets) == 0:
@@ -213,6 +215,12 @@ def predict_tile_sharded(net, data, rank: int, world: int, patch_size=(128, 128,
     opts = _opts(patch_size, step_size, use_gaussian, do_mirroring, mirror_axes, nonlin, batch_tiles)
     handles = (C.c_void_p * len(nets))(*[n.handle for n in nets])
     stream = torch.cuda.current_stream(data.device).cuda_stream
+    if want_m2:
+        agg2 = torch.empty_like(agg)
+        _lib.check(_lib.load().mi355_sw_partial_folds_moments(handles, len(nets), data.data_ptr(), z, y, x, C.byref(opts), rank, world,
+                                                              agg.data_ptr(), agg2.data_ptr(), cnt.data_ptr() if want_cnt else None, stream),
+                   "mi355_sw_partial_folds_moments")
+        return agg, cnt, agg2
     _lib.check(_lib.load().mi355_sw_partial_folds(handles, len(nets), data.data_ptr(), z, y, x, C.byref(opts), rank, world,
                                                   agg.data_ptr(), cnt.data_ptr() if want_cnt else None, stream), "mi355_sw_partial_folds")
     return agg, cnt
@@ -229,3 +237,73 @@ def finish_sharded(agg, cnt, vol_shape, patch_size, n_folds=1):
     _lib.check(_lib.load().mi355_sw_finish_folds(agg.data_ptr(), cnt.data_ptr(), k, z, y, x, p, int(n_folds), probs.data_ptr(),
                                                  stream), "mi355_sw_finish_folds")
     return probs
+
+
+def finish_sharded_moments(agg, agg2, cnt, vol_shape, patch_size, n_folds=1):
+    """(mean, m2) = (agg, agg2) / cnt / n_folds, cropped to the unpadded volume; ``mean`` is bit-equal to ``finish_sharded``."""
+    import torch
+    k = agg.shape[0]
+    z, y, x = vol_shape
+    mean = torch.empty((k, z, y, x), dtype=torch.float32, device=agg.device)
+    m2 = torch.empty_like(mean)
+    p = (C.c_int32 * 3)(*[int(v) for v in patch_size])
+    stream = torch.cuda.current_stream(agg.device).cuda_stream
+    _lib.check(_lib.load().mi355_sw_finish_moments(agg.data_ptr(), agg2.data_ptr(), cnt.data_ptr(), k, z, y, x, p, int(n_folds),
+                                                   mean.data_ptr(), m2.data_ptr(), stream), "mi355_sw_finish_moments")
+    return mean, m2
+
+
+def predict_folds_moments(nets: Sequence[UNet], data, patch_size=(128, 128, 128), step_size=0.5, do_mirroring=True,
+                          mirror_axes=(0, 1, 2), use_gaussian=True, nonlin="sigmoid", batch_tiles=0, device="cuda", lanes=None):
+    """``(mean, m2)``, both ``[K, Z, Y, X]`` CUDA fp32: ``mean`` is ``predict_folds(...)`` bit for bit (same lane decision, same
+    operations in the same order) and ``m2`` the weighted mean of p^2 over the same samples - fold, covering tile, mirror, with
+    the weights of the mean - so that ``max(m2 - mean^2, 0)`` is the variance of what the ensemble member averaged.
+
+    On the lanes every lane keeps an ``agg2`` beside its ``agg`` and both are summed in lane order.  On one lane ``predict_folds``
+    is ``mi355_sw_predict``, which normalises fold by fold and adds the folds' probabilities; this does the same - one
+    ``mi355_sw_partial_folds_moments`` call at world 1 and one finish per fold, the sum in fold order, one division - because the
+    sum of the folds' aggregates divided once would differ from it by a rounding."""
+    import torch
+    if len(nets) == 0:
+        raise ValueError("no networks given")
+    if nonlin == "identity":
+        raise ValueError("predict_folds_moments: nonlin 'identity' has no probabilities to take moments of")
+    data = _to_device(data, device)
+    if data.dim() != 4 or data.shape[0] != nets[0].topology.in_channels:
+        raise ValueError(f"data must be [C={nets[0].topology.in_channels}, Z, Y, X]")
+    _, z, y, x = data.shape
+    lanes = default_lanes() if lanes is None else int(lanes)
+    args = (patch_size, step_size, do_mirroring, mirror_axes, use_gaussian, nonlin, batch_tiles, data.device)
+    n_mirrors = 2 ** len(set(mirror_axes)) if do_mirroring else 1
+    if lanes > 1 and _n_items(nets, (z, y, x), patch_size, step_size) * n_mirrors >= 32 * lanes:
+        cur = torch.cuda.current_stream(data.device)
+        ready = cur.record_event()
+        parts = []
+        for r, st in enumerate(_lane_streams(data.device, lanes)):
+            st.wait_event(ready)
+            with torch.cuda.stream(st):
+                part = predict_tile_sharded(list(nets), data, r, lanes, *args, want_cnt=(r == 0), want_m2=True)
+            for t in part:
+                if t is not None:
+                    t.record_stream(cur)
+            parts.append(part)
+            cur.wait_stream(st)
+        total, total2 = parts[0][0], parts[0][2]
+        for agg, _, agg2 in parts[1:]:
+            total += agg    # lane order: deterministic
+            total2 += agg2
+        return finish_sharded_moments(total, total2, parts[0][1], (z, y, x), patch_size, len(nets))
+    mean = m2 = None
+    for net in nets:
+        agg, cnt, agg2 = predict_tile_sharded([net], data, 0, 1, *args, want_m2=True)
+        mf, m2f = finish_sharded_moments(agg, agg2, cnt, (z, y, x), patch_size, 1)
+        if mean is None:
+            mean, m2 = mf, m2f
+        else:
+            mean += mf
+            m2 += m2f
+    if len(nets) > 1:
+        # the one division of mi355_sw_predict's fold mean, by the library's own kernel: (sum / 1) / n over an unpadded grid
+        one = torch.ones((z, y, x), dtype=torch.float32, device=data.device)
+        mean, m2 = finish_sharded_moments(mean, m2, one, (z, y, x), (1, 1, 1), len(nets))
+    return mean, m2

@@ -151,6 +151,36 @@ int mi355_sw_partial_folds(const mi355_unet_t *nets, int n_nets, const float *vo
                            void *stream);
 int mi355_sw_finish_folds(const float *agg_dev, const float *cnt_dev, int num_classes, int Z, int Y, int X,
                           const int32_t patch[3], int n_folds, float *probs_dev, void *stream);
+/* Ensemble uncertainty.  run_brats2021_inference_singlethread.py:97-128 keeps the weighted mean of the samples (fold, covering tile,
+ * mirror) of a voxel and nothing of their spread; these two keep the second moment beside it.  agg2_dev [num_classes][padded]
+ * receives sum over this rank's items of gauss * (1 / n_mirrors) * sum_m p^2 - agg with p^2 in place of p, linear in the per-tile
+ * terms, so it is summed over ranks exactly as agg is; agg_dev and cnt_dev are bit-identical to mi355_sw_partial_folds.
+ * nonlin = identity has no probabilities: refused with MI355_ERR_INVALID. */
+int mi355_sw_partial_folds_moments(const mi355_unet_t *nets, int n_nets, const float *vol_dev, int Z, int Y, int X,
+                                   const mi355_sw_opts *opts, int rank, int world, float *agg_dev, float *agg2_dev,
+                                   float *cnt_dev, void *stream);
+/* mean_dev = agg / cnt / n_folds - bit-equal to mi355_sw_finish_folds - and m2_dev = agg2 / cnt / n_folds, both
+ * [num_classes][Z][Y][X], cropped from the padded grid.  var = max(m2 - mean^2, 0) is derived by mi355_uncertainty_maps, after any
+ * resampling of the two moments (an interpolation with non-negative weights keeps m2 >= mean^2 up to rounding). */
+int mi355_sw_finish_moments(const float *agg_dev, const float *agg2_dev, const float *cnt_dev, int num_classes, int Z, int Y, int X,
+                            const int32_t patch[3], int n_folds, float *mean_dev, float *m2_dev, void *stream);
+/* Maps of one ensemble member (mean_b = m2_b = NULL) or of two with equal weight (mean = (a + b) / 2, m2 likewise: the moments over
+ * the union of both members' samples); all inputs [C][Z][Y][X] fp32, C <= 8.  std = sqrt(max(m2 - mean^2, 0)); entropy in bits in
+ * [0, 1] with 0 log 0 = 0: nonlin sigmoid - per channel -m log2 m - (1 - m) log2 (1 - m); nonlin softmax - per voxel
+ * -sum_k m_k log2 m_k / log2 C, the same value in every channel.  std_dev / entropy_dev [C][Z][Y][X] (either may be NULL) receive the
+ * per-channel maps; std_max_dev / entropy_max_dev [full] (either may be NULL) the maximum over channels, pasted at bbox_lo into a
+ * zeroed volume as mi355_regions_to_labels pastes labels.  These replace, as a measurement, the literals of
+ * feature_extraction/step5_quality.py:457-500 (calculate_measurement_confidence), which depend on nothing. */
+int mi355_uncertainty_maps(const float *mean_a, const float *m2_a, const float *mean_b, const float *m2_b, int C, int Z, int Y, int X,
+                           int nonlin, float *std_dev, float *entropy_dev, const int32_t bbox_lo[3], const int32_t full[3],
+                           float *std_max_dev, float *entropy_max_dev, void *stream);
+/* Per channel of mean_dev / var_dev / entropy_dev [C][n] (C <= 8) and n_thr <= 8 thresholds: counts_host [C][n_thr + 1] =
+ * #{mean > t} per threshold (strict, as mi355_regions_to_labels), then |F| with F = {mean > 0.5}; sums_host [C][7] = the sums of
+ * mean, var, entropy over all voxels, the same three over F, and max var.  fp64 sums in a fixed order (block partials, then an
+ * ordered second stage; no atomics): bit-reproducible run to run.  Synchronises `stream`.  The numbers behind a volume interval and
+ * a mean confidence where step5_quality.py:457-500 returns 'High' / 'Moderate'. */
+int mi355_uncertainty_stats(const float *mean_dev, const float *var_dev, const float *entropy_dev, int C, int64_t n,
+                            const float *thresholds_host, int n_thr, int64_t *counts_host, double *sums_host, void *stream);
 
 /* seg = 0; for i in 0..C-1: seg[probs[i] > 0.5] = order[i]; pasted at bbox_lo into a zeroed
  * [full_z][full_y][full_x] uint8 volume.  order == NULL: seg = argmax over the C channels (first maximum wins), what
@@ -779,6 +809,19 @@ int mi355_logits_aggregate(const float *logits_dev, int ncls, int first_sample, 
 int mi355_logits_aggregate_tiles(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
                                  const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *cnt_dev,
                                  const int32_t padded[3], const int32_t *origins, int n_tiles, void *stream);
+/* The three above with the second moment kept (the fold mean of run_brats2021_inference_singlethread.py:97-128 extended by its
+ * spread): agg2_dev [ncls][padded] += (sum over the mirrors of (1 / n_mirrors) * p^2) * gauss, read and written as agg_dev is;
+ * agg_dev and cnt_dev come out bit-identical to the plain call.  nonlin = identity is refused. */
+int mi355_head_aggregate_m2(const void *feat_dev, int dtype, int cin, const float *weight_host, const float *bias_host, int ncls,
+                            const float *scale_dev, const float *shift_dev, float slope, int first_sample, const int32_t *mirrors_host,
+                            int n_mirrors, const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *agg2_dev,
+                            float *cnt_dev, const int32_t padded[3], const int32_t origin[3], void *stream);
+int mi355_logits_aggregate_m2(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
+                              const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *agg2_dev, float *cnt_dev,
+                              const int32_t padded[3], const int32_t origin[3], void *stream);
+int mi355_logits_aggregate_tiles_m2(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
+                                    const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *agg2_dev,
+                                    float *cnt_dev, const int32_t padded[3], const int32_t *origins, int n_tiles, void *stream);
 /* cnt_dev [padded] += gauss_dev [patch] (NULL: 1) at origin[]: the normaliser of a tile another rank evaluates. */
 int mi355_cnt_add_tile(const float *gauss_dev, const int32_t patch[3], float *cnt_dev, const int32_t padded[3],
                        const int32_t origin[3], void *stream);
