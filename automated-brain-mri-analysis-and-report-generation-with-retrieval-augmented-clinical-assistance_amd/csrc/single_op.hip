@@ -362,10 +362,13 @@ extern "C" int mi355_tconv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, i
     MI355_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
     const int64_t Vi = (int64_t)d * h * w;
-    TmpBuf xb, yb;
+    const size_t ybytes = (size_t)n * Vi * 8 * cout * 2, guard = guard_bytes((size_t)Vi * 8 * cout * 2);
+    TmpBuf xb, ybuf;  // ybuf: guard band, the kernel's output, guard band (guards_intact)
     MI355_HIP(hipMalloc(&xb.p, (size_t)n * Vi * cin * 2));
-    MI355_HIP(hipMalloc(&yb.p, (size_t)n * Vi * 8 * cout * 2));
-    MI355_HIP(hipMemsetAsync(yb.p, 0xFF, (size_t)n * Vi * 8 * cout * 2, s));  // all-NaN: an unstored voxel cannot pass for a result
+    MI355_HIP(hipMalloc(&ybuf.p, ybytes + 2 * guard));
+    struct { void *p; } yb = {(char *)ybuf.p + guard};
+    MI355_HIP(hipMemsetAsync(ybuf.p, GUARD_BYTE, ybytes + 2 * guard, s));
+    MI355_HIP(hipMemsetAsync(yb.p, 0xFF, ybytes, s));  // all-NaN: an unstored voxel cannot pass for a result
     TmpWeights<TConvWeightsH, tconv_weights_free_f16> tw;
     MI355_TRY(tconv_weights_upload_f16(weight_host, cin, cout, &tw.w));
     int rc = ndhwc_to_b8((const _Float16 *)x_dev, n, cin, Vi, (_Float16 *)xb.p, s);
@@ -373,7 +376,8 @@ extern "C" int mi355_tconv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, i
     if (rc == MI355_OK) rc = tconv2_mfma_f16(tw.w, (const _Float16 *)xb.p, n, d, h, w, (_Float16 *)yb.p, s, &tname);
     g_last_conv_kernel = tname ? tname : "";
     if (rc == MI355_OK) rc = b8_to_ndhwc((const _Float16 *)yb.p, n, cout, Vi * 8, (_Float16 *)y_dev, s);
-    return synced(rc, s, "tconv");
+    rc = synced(rc, s, "tconv");
+    return rc == MI355_OK ? guards_intact(ybuf.p, guard, ybytes, g_last_conv_kernel.c_str()) : rc;
 }
 
 // ---- single-op entry points of the kernels around the convolutions (csrc/elementwise.hip): each binds the device, calls the

@@ -105,8 +105,9 @@ def _integer_run(amd, dev, c):
     return ran, numel, float(np.abs(y2).max() / 2), guarded
 
 
-def run_case(amd, dev, c, check_kernel):
-    """one entry: (a), then (b) and (c); prints the entry's line"""
+def run_case(amd, dev, c, check_kernel, tag="CONV ROW"):
+    """one entry: (a), then (b) and (c); prints the entry's line (`tag`: what the line starts with; test_gpu_tconv_stem.py runs
+    the stem cases through here)"""
     t0 = time.time()
     ran_a = _gates_of_test_gpu_ops(amd, dev, c)
     if check_kernel:
@@ -114,7 +115,7 @@ def run_case(amd, dev, c, check_kernel):
     ran_b, numel, top, guarded = _integer_run(amd, dev, c)
     if check_kernel:
         assert ran_b == c.kernel, (c.name, ran_b)
-    print(f"CONV ROW {c.name} [{U.env_key(c.env)}] gates of test_gpu_ops on {ran_a} | integers: {numel} outputs of {ran_b} equal the int64 conv "
+    print(f"{tag} {c.name} [{U.env_key(c.env)}] gates of test_gpu_ops on {ran_a} | integers: {numel} outputs of {ran_b} equal the int64 conv "
           f"(max |y| {top:g}), {guarded} | {'ragged' if c.ragged else 'whole tiles'}"
           f"{', statistics' if c.stats else ''} | {time.time() - t0:.1f} s", flush=True)
 
