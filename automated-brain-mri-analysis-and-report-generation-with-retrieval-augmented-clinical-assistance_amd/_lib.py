@@ -51,6 +51,7 @@ EXPORTS = [
     "mi355_conv3d_plan_hinted", "mi355_conv3d_s2dma_hinted_ndhwc", "mi355_stage0_gather_boxes",
     "mi355_sw_partial_folds_moments", "mi355_sw_finish_moments", "mi355_logits_aggregate_m2", "mi355_logits_aggregate_tiles_m2",
     "mi355_head_aggregate_m2", "mi355_uncertainty_maps", "mi355_uncertainty_stats",
+    "mi355_live_allocations",
 ]
 
 
@@ -356,6 +357,7 @@ def load():
     lib.mi355_scratch_fill.restype = C.c_int64
     lib.mi355_scratch_release.argtypes = [vp]
     lib.mi355_scratch_zero_pages.argtypes = [C.POINTER(C.c_int64)]
+    lib.mi355_live_allocations.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.mi355_profile_enable.argtypes = [vp, C.c_int]
     lib.mi355_profile_read.argtypes = [vp, C.POINTER(ProfEntry), C.c_int]
     _lib = lib

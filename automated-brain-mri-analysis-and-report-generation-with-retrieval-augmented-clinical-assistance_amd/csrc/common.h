@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <type_traits>
+#include <vector>
 
 #include "../../include/mi355_nnunet.h"
 
@@ -27,7 +28,31 @@ enum ScratchSlot { SCR_ARENA = 0, SCR_SW_AGG, SCR_SPLITK_F32, SCR_SPLITK_F16, SC
                    SCR_CROP, SCR_ZSCORE, SCR_RESAMPLE, SCR_RESAMPLE_MM, SCR_COMPONENTS, SCR_MORPHOLOGY, SCR_QUALITY, SCR_MASS_EFFECT, SCR_COUNT };
 int device_scratch(int slot, hipStream_t stream, size_t bytes, void **out, bool zeroed = false);
 
-#define MI355_HIP(expr)                                                                    \
+// The one owner of device memory that outlives a launch and is not scratch: weights, the Gaussian map, the buffers of a single-op
+// call.  A network handle, or an entry point on its stack, holds one; what it allocated is freed, newest first, by release() or
+// when it goes out of scope - so an error return between two allocations leaves nothing behind.  The weight structs of kernels.h
+// are plain copyable views of its memory and free nothing themselves.  Every allocation and release is counted process-wide
+// (mi355_live_allocations).  Not thread-safe: one owner is filled by one thread at a time.  Defined in runtime.hip.
+class DeviceAllocs {
+  public:
+    DeviceAllocs() = default;
+    DeviceAllocs(const DeviceAllocs &) = delete;
+    DeviceAllocs &operator=(const DeviceAllocs &) = delete;
+    ~DeviceAllocs() { release(); }
+    int alloc(size_t bytes, void **dev);                                  // hipMalloc, recorded before anything else can fail
+    int upload(const void *host, size_t bytes, void **dev);               // alloc + copy from the host
+    int upload_or_zero(const void *host_or_null, size_t bytes, void **dev);  // ... or zeros when there is nothing to copy (a bias)
+    template <typename T> int alloc(size_t bytes, T **dev) { return alloc(bytes, (void **)dev); }
+    template <typename T> int upload(const void *host, size_t bytes, T **dev) { return upload(host, bytes, (void **)dev); }
+    template <typename T> int upload_or_zero(const void *host, size_t bytes, T **dev) { return upload_or_zero(host, bytes, (void **)dev); }
+    void release();  // the caller has made sure that no launch still uses the memory
+
+  private:
+    std::vector<void *> ptrs_;
+    size_t bytes_ = 0;
+};
+
+#define MI355_HIP(expr)                                                               \
     do {                                                                                   \
         hipError_t e__ = (expr);                                                           \
         if (e__ != hipSuccess) {                                                           \

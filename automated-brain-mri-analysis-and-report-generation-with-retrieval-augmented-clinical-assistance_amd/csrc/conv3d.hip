@@ -1212,18 +1212,14 @@ int conv_pack_layout(int cin, int cin_pad, int cout, int stride, ConvPackLayout 
     return MI355_OK;
 }
 
-int conv_weights_upload(const float *w_host, const float *bias_host, int cin, int cin_pad, int cout,
+int conv_weights_upload(DeviceAllocs &mem, const float *w_host, const float *bias_host, int cin, int cin_pad, int cout,
                         int stride, bool keep_plain, ConvWeights *out) {
     ConvPackLayout l;
     MI355_TRY(conv_pack_layout(cin, cin_pad, cout, stride, &l));
     ConvWeights cw;
     cw.cin = cin; cw.cin_pad = cin_pad; cw.cout = cout; cw.stride = stride;
     cw.cc = l.cc; cw.nf = l.nf; cw.pipe = l.pipe;
-    auto upload_pack = [](const std::vector<float> &packed, float **dev) -> int {
-        MI355_HIP(hipMalloc(dev, packed.size() * sizeof(float)));
-        MI355_HIP(hipMemcpy(*dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-        return MI355_OK;
-    };
+    auto upload_pack = [&mem](const std::vector<float> &packed, float **dev) { return mem.upload(packed.data(), packed.size() * sizeof(float), dev); };
     if (l.mfma) {
         std::vector<float> packed;
         pack_conv_weights_f32(w_host, cin, cin_pad, cout, cw.cc, cw.nf, packed);
@@ -1249,26 +1245,11 @@ int conv_weights_upload(const float *w_host, const float *bias_host, int cin, in
             for (int ci = 0; ci < cin; ++ci)
                 memcpy(&plain[((size_t)co * cin_pad + ci) * 27], &w_host[((size_t)co * cin + ci) * 27],
                        27 * sizeof(float));
-        MI355_HIP(hipMalloc(&cw.w_plain_dev, plain.size() * sizeof(float)));
-        MI355_HIP(hipMemcpy(cw.w_plain_dev, plain.data(), plain.size() * sizeof(float), hipMemcpyHostToDevice));
+        MI355_TRY(upload_pack(plain, &cw.w_plain_dev));
     }
-    MI355_HIP(hipMalloc(&cw.bias_dev, cout * sizeof(float)));
-    if (bias_host)
-        MI355_HIP(hipMemcpy(cw.bias_dev, bias_host, cout * sizeof(float), hipMemcpyHostToDevice));
-    else
-        MI355_HIP(hipMemset(cw.bias_dev, 0, cout * sizeof(float)));
+    MI355_TRY(mem.upload_or_zero(bias_host, cout * sizeof(float), &cw.bias_dev));
     *out = cw;
     return MI355_OK;
-}
-
-void conv_weights_free(ConvWeights *w) {
-    if (w->wp_dev) (void)hipFree(w->wp_dev);
-    if (w->wp16_dev) (void)hipFree(w->wp16_dev);
-    if (w->wpw_dev) (void)hipFree(w->wpw_dev);
-    if (w->wp3_dev) (void)hipFree(w->wp3_dev);
-    if (w->bias_dev) (void)hipFree(w->bias_dev);
-    if (w->w_plain_dev) (void)hipFree(w->w_plain_dev);
-    *w = ConvWeights();
 }
 
 // Every instantiation conv3d_mfma_f32 launches from this file (the F(2x2x2,3x3x3) kernel's rows are in conv3d_wino3.hip).

@@ -1233,7 +1233,7 @@ int conv_pack_layout_f16(int cin, int cin_pad, int cout, int stride, int *nf) {
     return MI355_OK;
 }
 
-int conv_weights_upload_f16(const float *w_host, const float *bias_host, int cin, int cin_pad, int cout, int stride,
+int conv_weights_upload_f16(DeviceAllocs &mem, const float *w_host, const float *bias_host, int cin, int cin_pad, int cout, int stride,
                             ConvWeightsH *out) {
     ConvWeightsH cw;
     cw.cin = cin; cw.cin_pad = cin_pad; cw.cout = cout; cw.stride = stride;
@@ -1251,19 +1251,10 @@ int conv_weights_upload_f16(const float *w_host, const float *bias_host, int cin
                             const int ci = ch * 16 + (lane >> 5) * 8 + j;
                             packed[o] = (half_t)((ci < cin) ? w_host[((size_t)co * cin + ci) * 27 + tap] : 0.f);
                         }
-    MI355_HIP(hipMalloc(&cw.wp_dev, packed.size() * sizeof(half_t)));
-    MI355_HIP(hipMemcpy(cw.wp_dev, packed.data(), packed.size() * sizeof(half_t), hipMemcpyHostToDevice));
-    MI355_HIP(hipMalloc(&cw.bias_dev, cout * sizeof(float)));
-    if (bias_host) MI355_HIP(hipMemcpy(cw.bias_dev, bias_host, cout * sizeof(float), hipMemcpyHostToDevice));
-    else MI355_HIP(hipMemset(cw.bias_dev, 0, cout * sizeof(float)));
+    MI355_TRY(mem.upload(packed.data(), packed.size() * sizeof(half_t), &cw.wp_dev));
+    MI355_TRY(mem.upload_or_zero(bias_host, cout * sizeof(float), &cw.bias_dev));
     *out = cw;
     return MI355_OK;
-}
-
-void conv_weights_free_f16(ConvWeightsH *w) {
-    if (w->wp_dev) (void)hipFree(w->wp_dev);
-    if (w->bias_dev) (void)hipFree(w->bias_dev);
-    *w = ConvWeightsH();
 }
 
 // Every instantiation conv3d_mfma_f16 launches from this file (the stride-2 LDS-DMA kernel's rows are in conv3d_f16_s2.hip).

@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256, 3) void conv3_stem_f16_kernel(StemArgs p) {
 }
 
 // ---------------------------------------------------------------- host
-int stem_weights_upload(const float *w_host, const float *bias_host, int cin, int cout, int dtype, StemWeights *out) {
+int stem_weights_upload(DeviceAllocs &mem, const float *w_host, const float *bias_host, int cin, int cout, int dtype, StemWeights *out) {
     MI355_REQUIRE(cin >= 1 && cin <= 4 && cout % 32 == 0, "stem conv: need cin <= 4 and cout %% 32 == 0 (got %d -> %d)", cin, cout);
     StemWeights sw;
     sw.cin = cin; sw.cout = cout; sw.dtype = dtype;
@@ -281,8 +281,7 @@ int stem_weights_upload(const float *w_host, const float *bias_host, int cin, in
                         const int k = 8 * h + j, dx = k >> 2, c = k & 3;
                         packed[o] = (_Float16)(dx < 3 ? W(co, c, zy * 3 + dx) : 0.f);
                     }
-        MI355_HIP(hipMalloc(&sw.wp_dev, packed.size() * sizeof(_Float16)));
-        MI355_HIP(hipMemcpy(sw.wp_dev, packed.data(), packed.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+        MI355_TRY(mem.upload(packed.data(), packed.size() * sizeof(_Float16), &sw.wp_dev));
     } else {
         std::vector<float> packed((size_t)nblk * 27 * 64 * 2);
         size_t o = 0;
@@ -293,20 +292,11 @@ int stem_weights_upload(const float *w_host, const float *bias_host, int cin, in
                         const int co = b * 32 + (lane & 31), h = lane >> 5;
                         packed[o] = W(co, 2 * h + j, tap);
                     }
-        MI355_HIP(hipMalloc(&sw.wp_dev, packed.size() * sizeof(float)));
-        MI355_HIP(hipMemcpy(sw.wp_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+        MI355_TRY(mem.upload(packed.data(), packed.size() * sizeof(float), &sw.wp_dev));
     }
-    MI355_HIP(hipMalloc(&sw.bias_dev, cout * sizeof(float)));
-    if (bias_host) MI355_HIP(hipMemcpy(sw.bias_dev, bias_host, cout * sizeof(float), hipMemcpyHostToDevice));
-    else MI355_HIP(hipMemset(sw.bias_dev, 0, cout * sizeof(float)));
+    MI355_TRY(mem.upload_or_zero(bias_host, cout * sizeof(float), &sw.bias_dev));
     *out = sw;
     return MI355_OK;
-}
-
-void stem_weights_free(StemWeights *w) {
-    if (w->wp_dev) (void)hipFree(w->wp_dev);
-    if (w->bias_dev) (void)hipFree(w->bias_dev);
-    *w = StemWeights();
 }
 
 int conv3d_stem(const StemWeights &w, const void *in, int N, int D, int H, int W, void *out, double *stats, int act,

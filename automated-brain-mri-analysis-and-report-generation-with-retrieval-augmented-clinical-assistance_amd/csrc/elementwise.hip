@@ -609,25 +609,17 @@ int b8_to_ndhwc(const _Float16 *x, int N, int C, int64_t V, _Float16 *y, hipStre
 }
 
 // ------------------------------------------------------------------ segmentation head
-int head_weights_upload(const float *w_host, const float *b_host, int cin, int ncls, HeadWeights *out) {
+int head_weights_upload(DeviceAllocs &mem, const float *w_host, const float *b_host, int cin, int ncls, HeadWeights *out) {
     MI355_REQUIRE(ncls >= 1 && ncls <= 8, "head: %d classes unsupported (max 8)", ncls);
     MI355_REQUIRE(cin % 8 == 0, "head: cin %d not a multiple of 8", cin);
     HeadWeights h;
     h.cin = cin; h.ncls = ncls;
-    MI355_HIP(hipMalloc(&h.w_dev, (size_t)ncls * cin * sizeof(float)));
-    MI355_HIP(hipMemcpy(h.w_dev, w_host, (size_t)ncls * cin * sizeof(float), hipMemcpyHostToDevice));
-    MI355_HIP(hipMalloc(&h.b_dev, 8 * sizeof(float)));
-    MI355_HIP(hipMemset(h.b_dev, 0, 8 * sizeof(float)));
-    if (b_host)
-        MI355_HIP(hipMemcpy(h.b_dev, b_host, ncls * sizeof(float), hipMemcpyHostToDevice));
+    MI355_TRY(mem.upload(w_host, (size_t)ncls * cin * sizeof(float), &h.w_dev));
+    float bias[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // [8] on the device whatever ncls is
+    if (b_host) std::copy(b_host, b_host + ncls, bias);
+    MI355_TRY(mem.upload(bias, sizeof(bias), &h.b_dev));
     *out = h;
     return MI355_OK;
-}
-
-void head_weights_free(HeadWeights *w) {
-    if (w->w_dev) (void)hipFree(w->w_dev);
-    if (w->b_dev) (void)hipFree(w->b_dev);
-    *w = HeadWeights();
 }
 
 constexpr int HEAD_MAX_CLS = 8;

@@ -25,7 +25,8 @@ struct ConvWeights {
 };
 
 // Which packs a layer gets, or why the layer is refused (pure: conv_weights_upload follows it; a plan can be computed from it
-// without uploading anything).
+// without uploading anything).  Every *_weights_upload allocates in the DeviceAllocs it is given (common.h) and nowhere else: the
+// weight structs are views of that owner's memory, and what a refused or failed upload had allocated goes with the owner.
 struct ConvPackLayout {
     bool mfma = false;  // the MFMA pack exists (cout % 32 == 0, cin_pad % 8 == 0); otherwise the layer runs on the direct kernel
     int cc = 0, nf = 1;
@@ -33,9 +34,8 @@ struct ConvPackLayout {
     bool c16 = false, wino2 = false, wino3 = false;  // the second 16-channel-chunk pack, the F(2x2,3x3) and F(2x2x2,3x3x3) packs
 };
 int conv_pack_layout(int cin, int cin_pad, int cout, int stride, ConvPackLayout *out);
-int conv_weights_upload(const float *w_host, const float *bias_host, int cin, int cin_pad, int cout,
+int conv_weights_upload(DeviceAllocs &mem, const float *w_host, const float *bias_host, int cin, int cin_pad, int cout,
                         int stride, bool keep_plain, ConvWeights *out);
-void conv_weights_free(ConvWeights *w);
 
 // A per-sample view into a whole-volume tensor of the shared stage 0 (sw_share_plan.hip "stage-0 views"): the tile tensor [N][D][H][W][C] a
 // conv reads is written only inside the shells - within `depth` voxels of a tile face whose bit is set - and every other voxel of
@@ -107,8 +107,7 @@ struct StemWeights {
     void *wp_dev = nullptr;
     float *bias_dev = nullptr;
 };
-int stem_weights_upload(const float *w_host, const float *bias_host, int cin, int cout, int dtype, StemWeights *out);
-void stem_weights_free(StemWeights *w);
+int stem_weights_upload(DeviceAllocs &mem, const float *w_host, const float *bias_host, int cin, int cout, int dtype, StemWeights *out);
 int conv3d_stem(const StemWeights &w, const void *in, int N, int D, int H, int W, void *out, double *stats, int act,
                 float slope, hipStream_t s);
 
@@ -119,30 +118,20 @@ struct ConvWeightsH {
     float *bias_dev = nullptr;
 };
 int conv_pack_layout_f16(int cin, int cin_pad, int cout, int stride, int *nf);  // as conv_pack_layout: the refusals and nf
-int conv_weights_upload_f16(const float *w_host, const float *bias_host, int cin, int cin_pad, int cout, int stride,
+int conv_weights_upload_f16(DeviceAllocs &mem, const float *w_host, const float *bias_host, int cin, int cin_pad, int cout, int stride,
                             ConvWeightsH *out);
-void conv_weights_free_f16(ConvWeightsH *w);
 bool conv3d_f16_fuses_input_norm(const ConvWeightsH &w, const ConvCallH &c);
 int conv3d_mfma_f16(const ConvWeightsH &w, const ConvCallH &c, hipStream_t s, const char **kernel_name = nullptr);
 
 // ---------------------------------------------------------------- transposed conv k=2 s=2
 struct TConvWeights {
-    int cin = 0, cout = 0;
-    float *wp_dev = nullptr;
+    int cin = 0, cout = 0, dtype = 0;
+    void *wp_dev = nullptr;  // packed float (MI355_F32) or _Float16 (MI355_F16)
 };
-int tconv_weights_upload(const float *w_host, int cin, int cout, TConvWeights *out);
-void tconv_weights_free(TConvWeights *w);
-// in [N,D,H,W,Cin] -> out [N,2D,2H,2W,Cout]
-int tconv2_mfma_f32(const TConvWeights &w, const float *in, int N, int D, int H, int W, float *out,
-                    hipStream_t s, const char **kernel_name = nullptr);
-struct TConvWeightsH {
-    int cin = 0, cout = 0;
-    _Float16 *wp_dev = nullptr;
-};
-int tconv_weights_upload_f16(const float *w_host, int cin, int cout, TConvWeightsH *out);
-void tconv_weights_free_f16(TConvWeightsH *w);
-int tconv2_mfma_f16(const TConvWeightsH &w, const _Float16 *in, int N, int D, int H, int W, _Float16 *out,
-                    hipStream_t s, const char **kernel_name = nullptr);
+int tconv_weights_upload(DeviceAllocs &mem, const float *w_host, int cin, int cout, int dtype, TConvWeights *out);
+// in [N,D,H,W,Cin] -> out [N,2D,2H,2W,Cout], elements of w.dtype (fp16: channel-blocked)
+int tconv2_mfma(const TConvWeights &w, const void *in, int N, int D, int H, int W, void *out, hipStream_t s,
+                const char **kernel_name = nullptr);
 
 // ---------------------------------------------------------------- normalisation
 // stats [N][C][2] doubles -> scale/shift [N][C] so that y = x*scale + shift.
@@ -228,8 +217,7 @@ struct HeadWeights {
     float *w_dev = nullptr;  // [ncls][cin]
     float *b_dev = nullptr;  // [ncls]
 };
-int head_weights_upload(const float *w_host, const float *b_host, int cin, int ncls, HeadWeights *out);
-void head_weights_free(HeadWeights *w);
+int head_weights_upload(DeviceAllocs &mem, const float *w_host, const float *b_host, int cin, int ncls, HeadWeights *out);
 // The feature map handed to the head may be the RAW output of the last decoder conv: then scale / shift [N][C] (fp32) hold
 // its Instance/GroupNorm affine and the head applies act(x * scale + shift) per channel while it reads the features
 // (slope = 1: no activation).  scale == nullptr: the features are final.

@@ -1,5 +1,7 @@
 // The process runtime behind every entry point (host side): the last-error text, the one-GPU-per-process binding, the lanes and
-// the device scratch they own, and the test aids that look at that scratch (include/mi355_nnunet.h, "Device scratch, for tests").
+// the device scratch they own, the test aids that look at that scratch (include/mi355_nnunet.h, "Device scratch, for tests"), and
+// DeviceAllocs, the owner of every other device allocation (common.h).
+#include <atomic>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -96,6 +98,41 @@ int device_scratch(int slot, hipStream_t stream, size_t bytes, void **out, bool 
         if (zeroed) MI355_HIP(hipMemset(b.p, 0, bytes));
     }
     *out = b.p;
+    return MI355_OK;
+}
+
+// DeviceAllocs (common.h).  The counters are process-wide: the driver loads two models from two threads.
+static std::atomic<int64_t> g_live_allocs{0}, g_live_bytes{0};
+
+int DeviceAllocs::alloc(size_t bytes, void **dev) {
+    *dev = nullptr;
+    ptrs_.reserve(ptrs_.size() + 1);  // (so that recording the pointer cannot fail once the memory exists)
+    MI355_HIP(hipMalloc(dev, bytes));
+    ptrs_.push_back(*dev);
+    bytes_ += bytes;
+    g_live_allocs += 1; g_live_bytes += (int64_t)bytes;
+    return MI355_OK;
+}
+int DeviceAllocs::upload(const void *host, size_t bytes, void **dev) {
+    MI355_TRY(alloc(bytes, dev));
+    MI355_HIP(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
+    return MI355_OK;
+}
+int DeviceAllocs::upload_or_zero(const void *host_or_null, size_t bytes, void **dev) {
+    if (host_or_null) return upload(host_or_null, bytes, dev);
+    MI355_TRY(alloc(bytes, dev));
+    MI355_HIP(hipMemset(*dev, 0, bytes));
+    return MI355_OK;
+}
+void DeviceAllocs::release() {
+    for (size_t i = ptrs_.size(); i-- > 0;) (void)hipFree(ptrs_[i]);
+    g_live_allocs -= (int64_t)ptrs_.size(); g_live_bytes -= (int64_t)bytes_;
+    ptrs_.clear(); bytes_ = 0;
+}
+
+extern "C" int mi355_live_allocations(int64_t *count, int64_t *bytes) {
+    MI355_REQUIRE(count && bytes, "mi355_live_allocations: null output");
+    *count = g_live_allocs.load(); *bytes = g_live_bytes.load();
     return MI355_OK;
 }
 

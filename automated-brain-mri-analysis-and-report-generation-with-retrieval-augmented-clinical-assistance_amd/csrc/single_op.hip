@@ -13,19 +13,8 @@ static thread_local std::string g_last_conv_kernel;  // mi355_last_conv_kernel()
 extern "C" const char *mi355_last_conv_kernel(void) { return g_last_conv_kernel.c_str(); }
 
 // The single-op fp16 entry points take and return PLAIN NDHWC tensors (include/mi355_nnunet.h); the kernels work on
-// channel-blocked ones (common.h), so the operands pass through ndhwc_to_b8 / b8_to_ndhwc here.
-namespace {
-struct TmpBuf {
-    void *p = nullptr;
-    ~TmpBuf() { if (p) (void)hipFree(p); }
-};
-// the uploaded weights of a single-op call, freed on every exit
-template <typename W, void (*FREE)(W *)>
-struct TmpWeights {
-    W w;
-    ~TmpWeights() { FREE(&w); }
-};
-}  // namespace
+// channel-blocked ones (common.h), so the operands pass through ndhwc_to_b8 / b8_to_ndhwc here.  Every entry point that uploads
+// weights or needs such a copy has one DeviceAllocs `mem` on its stack: freed on every exit, after the call has synchronised.
 
 // the network's first-layer kernel instead of the generic dispatch (plain NDHW4 input)
 static bool single_op_stem(int cin, int stride, int impl, int cout, const FusedOps &f) {
@@ -44,7 +33,7 @@ static int synced(int rc, hipStream_t s, const char *what) {
 constexpr unsigned char GUARD_BYTE = 0xA5;
 static size_t guard_bytes(size_t sample_bytes) {
     const size_t g = sample_bytes < 4096 ? 4096 : (sample_bytes > (4u << 20) ? (4u << 20) : sample_bytes);
-    return (g + 255) / 256 * 256;  // (the buffer between the bands keeps hipMalloc's alignment to 256 B)
+    return (g + 255) / 256 * 256;  // (the buffer between the bands keeps the allocation's alignment to 256 B)
 }
 static int guards_intact(const void *buf, size_t guard, size_t bytes, const char *kernel) {
     std::vector<unsigned char> host(2 * guard);
@@ -74,18 +63,19 @@ static int conv3d_ndhwc_f32_impl(const float *x_dev, int n, int d, int h, int w,
     MI355_REQUIRE(f.c1 >= 0 && f.c1 < cin && (f.c1 == 0) == (f.x1 == nullptr), "bad concat split %d of %d channels", f.c1, cin);
     hipStream_t s = (hipStream_t)stream;
     if (sums) MI355_HIP(hipMemsetAsync(sums, 0, (size_t)n * cout * 2 * sizeof(double), s));
+    DeviceAllocs mem;
     if (single_op_stem(cin, stride, impl, cout, f)) {
-        TmpWeights<StemWeights, stem_weights_free> sw;
-        MI355_TRY(stem_weights_upload(weight_host, bias_host, cin, cout, MI355_F32, &sw.w));
+        StemWeights sw;
+        MI355_TRY(stem_weights_upload(mem, weight_host, bias_host, cin, cout, MI355_F32, &sw));
         g_last_conv_kernel = "conv3_stem_f32_kernel";
-        return synced(conv3d_stem(sw.w, x_dev, n, d, h, w, y_dev, sums, act, slope, s), s, "stem conv");
+        return synced(conv3d_stem(sw, x_dev, n, d, h, w, y_dev, sums, act, slope, s), s, "stem conv");
     }
-    TmpWeights<ConvWeights, conv_weights_free> cw;
-    MI355_TRY(conv_weights_upload(weight_host, bias_host, cin, cin, cout, stride, impl == 1, &cw.w));
+    ConvWeights cw;
+    MI355_TRY(conv_weights_upload(mem, weight_host, bias_host, cin, cin, cout, stride, impl == 1, &cw));
     const ConvCall c = make_call<float>(x_dev, cin, n, d, h, w, y_dev, sums, act, slope, f);
     MI355_REQUIRE(!sums || impl != 1, "the direct cross-check kernel carries no statistics epilogue");
     const char *kname = "conv3_direct_kernel";
-    const int rc = (impl == 1) ? conv3d_direct_f32(cw.w, c, s) : conv3d_mfma_f32(cw.w, c, s, &kname);
+    const int rc = (impl == 1) ? conv3d_direct_f32(cw, c, s) : conv3d_mfma_f32(cw, c, s, &kname);
     g_last_conv_kernel = kname ? kname : "";
     return synced(rc, s, "conv");
 }
@@ -99,10 +89,11 @@ extern "C" int mi355_conv3d_ndhwc(const float *x_dev, int n, int d, int h, int w
 extern "C" int mi355_tconv3d_ndhwc(const float *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
                                    int cout, float *y_dev, void *stream) {
     MI355_TRY(require_device());
-    TmpWeights<TConvWeights, tconv_weights_free> tw;
-    MI355_TRY(tconv_weights_upload(weight_host, cin, cout, &tw.w));
+    DeviceAllocs mem;
+    TConvWeights tw;
+    MI355_TRY(tconv_weights_upload(mem, weight_host, cin, cout, MI355_F32, &tw));
     const char *tname = "tconv2_f32_mfma_v2_kernel";
-    const int rc = tconv2_mfma_f32(tw.w, x_dev, n, d, h, w, y_dev, (hipStream_t)stream, &tname);
+    const int rc = tconv2_mfma(tw, x_dev, n, d, h, w, y_dev, (hipStream_t)stream, &tname);
     g_last_conv_kernel = tname;
     return synced(rc, (hipStream_t)stream, "tconv");
 }
@@ -120,42 +111,43 @@ static int conv3d_ndhwc_f16_impl(const void *x_dev, int n, int d, int h, int w, 
     const int64_t Vo = (int64_t)((d - 1) / stride + 1) * ((h - 1) / stride + 1) * ((w - 1) / stride + 1);
     MI355_REQUIRE(cout % 8 == 0, "fp16 conv needs cout %% 8 == 0 (got %d)", cout);
     const size_t ybytes = (size_t)n * Vo * cout * 2, guard = guard_bytes((size_t)Vo * cout * 2);
-    TmpBuf ybuf;  // guard band, the kernel's output, guard band (guards_intact)
-    MI355_HIP(hipMalloc(&ybuf.p, ybytes + 2 * guard));
-    struct { void *p; } yb = {(char *)ybuf.p + guard};
-    MI355_HIP(hipMemsetAsync(ybuf.p, GUARD_BYTE, ybytes + 2 * guard, s));
+    DeviceAllocs mem;
+    void *ybuf = nullptr;  // guard band, the kernel's output, guard band (guards_intact)
+    MI355_TRY(mem.alloc(ybytes + 2 * guard, &ybuf));
+    void *const yb = (char *)ybuf + guard;
+    MI355_HIP(hipMemsetAsync(ybuf, GUARD_BYTE, ybytes + 2 * guard, s));
     // all-NaN (0xFFFF) before the launch: a voxel the kernel fails to store cannot pass for a result
-    MI355_HIP(hipMemsetAsync(yb.p, 0xFF, ybytes, s));
+    MI355_HIP(hipMemsetAsync(yb, 0xFF, ybytes, s));
     int rc;
     if (single_op_stem(cin, stride, 0, cout, f)) {
-        TmpWeights<StemWeights, stem_weights_free> sw;
-        MI355_TRY(stem_weights_upload(weight_host, bias_host, cin, cout, MI355_F16, &sw.w));
-        rc = conv3d_stem(sw.w, x_dev, n, d, h, w, yb.p, sums, act, slope, s);
+        StemWeights sw;
+        MI355_TRY(stem_weights_upload(mem, weight_host, bias_host, cin, cout, MI355_F16, &sw));
+        rc = conv3d_stem(sw, x_dev, n, d, h, w, yb, sums, act, slope, s);
         g_last_conv_kernel = "conv3_stem_f16_kernel";
-        if (rc == MI355_OK) rc = b8_to_ndhwc((const _Float16 *)yb.p, n, cout, Vo, (_Float16 *)y_dev, s);
+        if (rc == MI355_OK) rc = b8_to_ndhwc((const _Float16 *)yb, n, cout, Vo, (_Float16 *)y_dev, s);
         rc = synced(rc, s, "stem conv");
-        return rc == MI355_OK ? guards_intact(ybuf.p, guard, ybytes, g_last_conv_kernel.c_str()) : rc;
+        return rc == MI355_OK ? guards_intact(ybuf, guard, ybytes, g_last_conv_kernel.c_str()) : rc;
     }
     MI355_REQUIRE(cin % 8 == 0 && f.c1 % 8 == 0, "fp16 conv needs cin %% 8 == 0 on both inputs (got %d, %d)", cin - f.c1, f.c1);
     const int c0 = cin - f.c1;
-    TmpBuf xb, x1b;
-    MI355_HIP(hipMalloc(&xb.p, (size_t)n * Vi * c0 * 2));
-    MI355_TRY(ndhwc_to_b8((const _Float16 *)x_dev, n, c0, Vi, (_Float16 *)xb.p, s));
+    void *xb = nullptr, *x1b = nullptr;  // the channel-blocked copies of x0 and x1
+    MI355_TRY(mem.alloc((size_t)n * Vi * c0 * 2, &xb));
+    MI355_TRY(ndhwc_to_b8((const _Float16 *)x_dev, n, c0, Vi, (_Float16 *)xb, s));
     if (f.x1) {
-        MI355_HIP(hipMalloc(&x1b.p, (size_t)n * Vi * f.c1 * 2));
-        MI355_TRY(ndhwc_to_b8((const _Float16 *)f.x1, n, f.c1, Vi, (_Float16 *)x1b.p, s));
+        MI355_TRY(mem.alloc((size_t)n * Vi * f.c1 * 2, &x1b));
+        MI355_TRY(ndhwc_to_b8((const _Float16 *)f.x1, n, f.c1, Vi, (_Float16 *)x1b, s));
     }
-    TmpWeights<ConvWeightsH, conv_weights_free_f16> cw;
-    MI355_TRY(conv_weights_upload_f16(weight_host, bias_host, cin, cin, cout, stride, &cw.w));
-    FusedOps fb = f;  // (the channel-blocked copy of x1)
-    fb.x1 = x1b.p;
+    ConvWeightsH cw;
+    MI355_TRY(conv_weights_upload_f16(mem, weight_host, bias_host, cin, cin, cout, stride, &cw));
+    FusedOps fb = f;
+    fb.x1 = x1b;
     const char *kname = nullptr;
     // head mode stores logits only (run_block)
-    rc = conv3d_mfma_f16(cw.w, make_call<_Float16>(xb.p, cin, n, d, h, w, f.head_out ? nullptr : yb.p, sums, act, slope, fb), s, &kname);
+    rc = conv3d_mfma_f16(cw, make_call<_Float16>(xb, cin, n, d, h, w, f.head_out ? nullptr : yb, sums, act, slope, fb), s, &kname);
     g_last_conv_kernel = kname ? kname : "";
-    if (rc == MI355_OK && !f.head_out) rc = b8_to_ndhwc((const _Float16 *)yb.p, n, cout, Vo, (_Float16 *)y_dev, s);
+    if (rc == MI355_OK && !f.head_out) rc = b8_to_ndhwc((const _Float16 *)yb, n, cout, Vo, (_Float16 *)y_dev, s);
     rc = synced(rc, s, "conv");
-    return rc == MI355_OK ? guards_intact(ybuf.p, guard, ybytes, g_last_conv_kernel.c_str()) : rc;
+    return rc == MI355_OK ? guards_intact(ybuf, guard, ybytes, g_last_conv_kernel.c_str()) : rc;
 }
 
 extern "C" int mi355_conv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
@@ -280,19 +272,20 @@ extern "C" int mi355_conv3d_wino3_ndhwc(const float *x0_dev, const float *x1_dev
     MI355_REQUIRE(act != ACT_LRELU || (slope >= 0.f && slope <= 1.f), "LeakyReLU slope %g outside [0, 1]", (double)slope);
     MI355_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
-    TmpWeights<ConvWeights, conv_weights_free> cw;
-    MI355_TRY(conv_weights_upload(weight_host, bias_host, c0 + c1, c0 + c1, cout, 1, false, &cw.w));
+    DeviceAllocs mem;
+    ConvWeights cw;
+    MI355_TRY(conv_weights_upload(mem, weight_host, bias_host, c0 + c1, c0 + c1, cout, 1, false, &cw));
     FusedOps f;
     f.x1 = x1_dev; f.c1 = c1;
     ConvCall c = make_call<float>(x0_dev, c0 + c1, n, d, h, w, y_dev, nullptr, act, slope, f);
     c.addend = addend_dev;
     ConvPlan p;
-    if (!plan_wino3(cw.w, c, &p, true)) {
+    if (!plan_wino3(cw, c, &p, true)) {
         set_error("mi355_conv3d_wino3_ndhwc: %dx%dx%dx%d, %d+%d -> %d is not a call of the F(2x2x2,3x3x3) kernel", n, d, h, w, c0, c1, cout);
         return MI355_ERR_UNSUPPORTED;
     }
     g_last_conv_kernel = p.name;
-    return synced(launch_wino3(cw.w, c, p, s), s, "conv");
+    return synced(launch_wino3(cw, c, p, s), s, "conv");
 }
 
 // the C-ABI description of a view -> S0View (refused where stage0_view_make refuses)
@@ -318,13 +311,14 @@ extern "C" int mi355_conv3d_s2dma_hinted_ndhwc(const float *x_dev, const mi355_s
     if (view) MI355_TRY(view_from_abi(view, n, d, h, w, cin, &sv));  // (before anything touches the device: a bad view launches nothing)
     MI355_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
-    TmpWeights<ConvWeights, conv_weights_free> cw;
-    MI355_TRY(conv_weights_upload(weight_host, bias_host, cin, cin, cout, 2, false, &cw.w));
+    DeviceAllocs mem;
+    ConvWeights cw;
+    MI355_TRY(conv_weights_upload(mem, weight_host, bias_host, cin, cin, cout, 2, false, &cw));
     ConvCall c = make_call<float>(x_dev, cin, n, d, h, w, y_dev, nullptr, act, slope);
     if (view) c.in0_view = &sv;
     c.s2_least_padding = s2_least_padding != 0;
     const char *kname = nullptr;
-    const int rc = conv3d_s2dma_f32(cw.w, c, force != 0, s, &kname);
+    const int rc = conv3d_s2dma_f32(cw, c, force != 0, s, &kname);
     g_last_conv_kernel = kname ? kname : "";
     return synced(rc, s, "conv");
 }
@@ -343,18 +337,19 @@ extern "C" int mi355_conv3d_wino3_view_ndhwc(const float *x0_dev, int n, int d, 
     if (view) MI355_TRY(view_from_abi(view, n, d, h, w, cout, &sv));
     MI355_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
-    TmpWeights<ConvWeights, conv_weights_free> cw;
-    MI355_TRY(conv_weights_upload(weight_host, bias_host, c0, c0, cout, 1, false, &cw.w));
+    DeviceAllocs mem;
+    ConvWeights cw;
+    MI355_TRY(conv_weights_upload(mem, weight_host, bias_host, c0, c0, cout, 1, false, &cw));
     ConvCall c = make_call<float>(x0_dev, c0, n, d, h, w, y_dev, nullptr, act, slope);
     c.addend = addend_dev;
     if (view) c.addend_view = &sv;
     ConvPlan p;
-    if (!plan_wino3(cw.w, c, &p, true)) {
+    if (!plan_wino3(cw, c, &p, true)) {
         set_error("mi355_conv3d_wino3_view_ndhwc: %dx%dx%dx%d, %d -> %d is not a call of the F(2x2x2,3x3x3) kernel", n, d, h, w, c0, cout);
         return MI355_ERR_UNSUPPORTED;
     }
     g_last_conv_kernel = p.name;
-    return synced(launch_wino3(cw.w, c, p, s), s, "conv");
+    return synced(launch_wino3(cw, c, p, s), s, "conv");
 }
 
 extern "C" int mi355_tconv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, int w, int cin, const float *weight_host,
@@ -363,21 +358,22 @@ extern "C" int mi355_tconv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, i
     hipStream_t s = (hipStream_t)stream;
     const int64_t Vi = (int64_t)d * h * w;
     const size_t ybytes = (size_t)n * Vi * 8 * cout * 2, guard = guard_bytes((size_t)Vi * 8 * cout * 2);
-    TmpBuf xb, ybuf;  // ybuf: guard band, the kernel's output, guard band (guards_intact)
-    MI355_HIP(hipMalloc(&xb.p, (size_t)n * Vi * cin * 2));
-    MI355_HIP(hipMalloc(&ybuf.p, ybytes + 2 * guard));
-    struct { void *p; } yb = {(char *)ybuf.p + guard};
-    MI355_HIP(hipMemsetAsync(ybuf.p, GUARD_BYTE, ybytes + 2 * guard, s));
-    MI355_HIP(hipMemsetAsync(yb.p, 0xFF, ybytes, s));  // all-NaN: an unstored voxel cannot pass for a result
-    TmpWeights<TConvWeightsH, tconv_weights_free_f16> tw;
-    MI355_TRY(tconv_weights_upload_f16(weight_host, cin, cout, &tw.w));
-    int rc = ndhwc_to_b8((const _Float16 *)x_dev, n, cin, Vi, (_Float16 *)xb.p, s);
+    DeviceAllocs mem;
+    void *xb = nullptr, *ybuf = nullptr;  // ybuf: guard band, the kernel's output, guard band (guards_intact)
+    MI355_TRY(mem.alloc((size_t)n * Vi * cin * 2, &xb));
+    MI355_TRY(mem.alloc(ybytes + 2 * guard, &ybuf));
+    void *const yb = (char *)ybuf + guard;
+    MI355_HIP(hipMemsetAsync(ybuf, GUARD_BYTE, ybytes + 2 * guard, s));
+    MI355_HIP(hipMemsetAsync(yb, 0xFF, ybytes, s));  // all-NaN: an unstored voxel cannot pass for a result
+    TConvWeights tw;
+    MI355_TRY(tconv_weights_upload(mem, weight_host, cin, cout, MI355_F16, &tw));
+    int rc = ndhwc_to_b8((const _Float16 *)x_dev, n, cin, Vi, (_Float16 *)xb, s);
     const char *tname = nullptr;
-    if (rc == MI355_OK) rc = tconv2_mfma_f16(tw.w, (const _Float16 *)xb.p, n, d, h, w, (_Float16 *)yb.p, s, &tname);
+    if (rc == MI355_OK) rc = tconv2_mfma(tw, xb, n, d, h, w, yb, s, &tname);
     g_last_conv_kernel = tname ? tname : "";
-    if (rc == MI355_OK) rc = b8_to_ndhwc((const _Float16 *)yb.p, n, cout, Vi * 8, (_Float16 *)y_dev, s);
+    if (rc == MI355_OK) rc = b8_to_ndhwc((const _Float16 *)yb, n, cout, Vi * 8, (_Float16 *)y_dev, s);
     rc = synced(rc, s, "tconv");
-    return rc == MI355_OK ? guards_intact(ybuf.p, guard, ybytes, g_last_conv_kernel.c_str()) : rc;
+    return rc == MI355_OK ? guards_intact(ybuf, guard, ybytes, g_last_conv_kernel.c_str()) : rc;
 }
 
 // ---- single-op entry points of the kernels around the convolutions (csrc/elementwise.hip): each binds the device, calls the
@@ -433,10 +429,11 @@ extern "C" int mi355_head_logits(const void *feat_dev, int dtype, int n, int64_t
     MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_F16, "unknown dtype %d", dtype);
     MI355_REQUIRE(!scale_dev == !shift_dev, "scale and shift come together");
     MI355_TRY(require_device());
-    TmpWeights<HeadWeights, head_weights_free> hw;
-    MI355_TRY(head_weights_upload(weight_host, bias_host, cin, ncls, &hw.w));
+    DeviceAllocs mem;
+    HeadWeights hw;
+    MI355_TRY(head_weights_upload(mem, weight_host, bias_host, cin, ncls, &hw));
     hipStream_t s = (hipStream_t)stream;
-    return synced(head_logits(hw.w, feat_dev, dtype, n, v, logits_dev, s, feat_norm(scale_dev, shift_dev, slope)), s, "head_logits");
+    return synced(head_logits(hw, feat_dev, dtype, n, v, logits_dev, s, feat_norm(scale_dev, shift_dev, slope)), s, "head_logits");
 }
 
 extern "C" int mi355_head_aggregate(const void *feat_dev, int dtype, int cin, const float *weight_host, const float *bias_host, int ncls,
@@ -448,11 +445,12 @@ extern "C" int mi355_head_aggregate(const void *feat_dev, int dtype, int cin, co
     MI355_REQUIRE(!scale_dev == !shift_dev, "scale and shift come together");
     MI355_REQUIRE(tile_in_grid(patch, padded, origin), "mi355_head_aggregate: the tile leaves the padded grid");
     MI355_TRY(require_device());
-    TmpWeights<HeadWeights, head_weights_free> hw;
-    MI355_TRY(head_weights_upload(weight_host, bias_host, cin, ncls, &hw.w));
+    DeviceAllocs mem;
+    HeadWeights hw;
+    MI355_TRY(head_weights_upload(mem, weight_host, bias_host, cin, ncls, &hw));
     hipStream_t s = (hipStream_t)stream;
     std::vector<int> mirrors(mirrors_host, mirrors_host + std::max(n_mirrors, 0));
-    return synced(head_aggregate(hw.w, feat_dev, dtype, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev, agg_dev,
+    return synced(head_aggregate(hw, feat_dev, dtype, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev, agg_dev,
                                  cnt_dev, padded[0], padded[1], padded[2], origin[0], origin[1], origin[2], s, feat_norm(scale_dev, shift_dev, slope)),
                   s, "head_aggregate");
 }
@@ -498,11 +496,12 @@ extern "C" int mi355_head_aggregate_m2(const void *feat_dev, int dtype, int cin,
     MI355_REQUIRE(nonlin != MI355_NONLIN_IDENTITY, "mi355_head_aggregate_m2: nonlin identity has no probabilities to take moments of");
     MI355_REQUIRE(tile_in_grid(patch, padded, origin), "mi355_head_aggregate_m2: the tile leaves the padded grid");
     MI355_TRY(require_device());
-    TmpWeights<HeadWeights, head_weights_free> hw;
-    MI355_TRY(head_weights_upload(weight_host, bias_host, cin, ncls, &hw.w));
+    DeviceAllocs mem;
+    HeadWeights hw;
+    MI355_TRY(head_weights_upload(mem, weight_host, bias_host, cin, ncls, &hw));
     hipStream_t s = (hipStream_t)stream;
     std::vector<int> mirrors(mirrors_host, mirrors_host + std::max(n_mirrors, 0));
-    return synced(head_aggregate(hw.w, feat_dev, dtype, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev, agg_dev,
+    return synced(head_aggregate(hw, feat_dev, dtype, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev, agg_dev,
                                  cnt_dev, padded[0], padded[1], padded[2], origin[0], origin[1], origin[2], s, feat_norm(scale_dev, shift_dev, slope),
                                  agg2_dev),
                   s, "head_aggregate m2");

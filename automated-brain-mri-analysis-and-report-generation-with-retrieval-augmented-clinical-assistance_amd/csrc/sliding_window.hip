@@ -13,10 +13,11 @@ static int ensure_gaussian(mi355_unet *net, const int p[3]) {
     std::lock_guard<std::mutex> lk(g_gauss_mu);  // (one handle may be driven from two lanes)
     if (net->gauss_dev && net->gauss_p[0] == p[0] && net->gauss_p[1] == p[1] && net->gauss_p[2] == p[2])
         return MI355_OK;
-    if (net->gauss_dev) { MI355_HIP(hipDeviceSynchronize()); MI355_HIP(hipFree(net->gauss_dev)); net->gauss_dev = nullptr; }
+    if (net->gauss_dev) { MI355_HIP(hipDeviceSynchronize()); net->gauss_mem.release(); net->gauss_dev = nullptr; }
     std::vector<float> g;
     gaussian_map(p, 1.0 / 8.0, g);
-    MI355_TRY(upload(g.data(), g.size(), &net->gauss_dev));
+    const int rc = net->gauss_mem.upload(g.data(), g.size() * sizeof(float), &net->gauss_dev);
+    if (rc != MI355_OK) { net->gauss_mem.release(); net->gauss_dev = nullptr; return rc; }  // (nothing has been launched on it)
     net->gauss_p[0] = p[0]; net->gauss_p[1] = p[1]; net->gauss_p[2] = p[2];
     return MI355_OK;
 }
@@ -630,7 +631,7 @@ extern "C" int mi355_sw_predict(const mi355_unet_t *nets, int n_nets, const floa
     const int C = nets[0]->num_classes;
     const size_t ZYXp = (size_t)g.Zp[0] * g.Zp[1] * g.Zp[2];
     // aggregation scratch: process-wide like the activation arena, grown on demand, never freed per call - a
-    // hipMalloc / synchronise / hipFree round trip per volume costs more than the small kernels of a step
+    // allocate / synchronise / free round trip per volume costs more than the small kernels of a step
     void *scratch = nullptr;
     MI355_TRY(device_scratch(SCR_SW_AGG, s, ZYXp * (size_t)(C + 1) * sizeof(float), &scratch));
     float *agg = (float *)scratch, *cnt = agg + ZYXp * C;

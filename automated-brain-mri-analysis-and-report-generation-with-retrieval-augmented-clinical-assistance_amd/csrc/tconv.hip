@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256, G <= 8 ? 2 : 1) void tconv2_f32_mfma_v3_kernel
 }
 
 // pack: [pos = a*4+b*2+c][cout block][g][lane][j]; cout = nb*32 + (lane&31), cin = g*8 + (lane>>5)*4 + j
-int tconv_weights_upload(const float *w_host, int cin, int cout, TConvWeights *out) {
+static int tconv_weights_upload_f32(DeviceAllocs &mem, const float *w_host, int cin, int cout, TConvWeights *out) {
     MI355_REQUIRE(cin % 8 == 0 && cout % 32 == 0, "tconv %d->%d: need cin %% 8 == 0 and cout %% 32 == 0", cin, cout);
     const int G = cin / 8, nblk = cout / 32;
     std::vector<float> packed((size_t)8 * nblk * G * 256);
@@ -228,20 +228,22 @@ int tconv_weights_upload(const float *w_host, int cin, int cout, TConvWeights *o
                         packed[o] = w_host[((size_t)ci * cout + co) * 8 + pos];
                     }
     TConvWeights tw;
-    tw.cin = cin; tw.cout = cout;
-    MI355_HIP(hipMalloc(&tw.wp_dev, packed.size() * sizeof(float)));
-    MI355_HIP(hipMemcpy(tw.wp_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+    tw.cin = cin; tw.cout = cout; tw.dtype = MI355_F32;
+    MI355_TRY(mem.upload(packed.data(), packed.size() * sizeof(float), &tw.wp_dev));
     *out = tw;
     return MI355_OK;
 }
 
-void tconv_weights_free(TConvWeights *w) {
-    if (w->wp_dev) (void)hipFree(w->wp_dev);
-    *w = TConvWeights();
-}
+// the weights as a launcher of element type T reads them
+template <typename T>
+struct TConvPack {
+    int cin, cout;
+    const T *wp_dev;
+    explicit TConvPack(const TConvWeights &w) : cin(w.cin), cout(w.cout), wp_dev((const T *)w.wp_dev) {}
+};
 
-int tconv2_mfma_f32(const TConvWeights &w, const float *in, int N, int D, int H, int W, float *out,
-                    hipStream_t s, const char **kernel_name) {
+static int tconv2_mfma_f32(const TConvPack<float> &w, const float *in, int N, int D, int H, int W, float *out,
+                           hipStream_t s, const char **kernel_name) {
     const long M = (long)N * D * H * W;
     MI355_REQUIRE(M > 0 && M < (1l << 30), "tconv: %ld voxels out of range", M);
     const bool v3 = env_switch("MI355_TCONV_V3");
@@ -462,7 +464,7 @@ __global__ __launch_bounds__(256, 2) void tconv2_f16_mfma_v3_kernel(const _Float
 }
 
 // pack: [pos][cout block][g][lane][j 0..7]; cout = nb*32 + (lane&31), cin = g*16 + (lane>>5)*8 + j
-int tconv_weights_upload_f16(const float *w_host, int cin, int cout, TConvWeightsH *out) {
+static int tconv_weights_upload_f16(DeviceAllocs &mem, const float *w_host, int cin, int cout, TConvWeights *out) {
     MI355_REQUIRE(cin % 16 == 0 && cout % 32 == 0, "fp16 tconv %d->%d: need cin %% 16 == 0 and cout %% 32 == 0", cin, cout);
     const int G = cin / 16, nblk = cout / 32;
     std::vector<_Float16> packed((size_t)8 * nblk * G * 512);
@@ -476,21 +478,15 @@ int tconv_weights_upload_f16(const float *w_host, int cin, int cout, TConvWeight
                         const int ci = g * 16 + (lane >> 5) * 8 + j;
                         packed[o] = (_Float16)w_host[((size_t)ci * cout + co) * 8 + pos];
                     }
-    TConvWeightsH tw;
-    tw.cin = cin; tw.cout = cout;
-    MI355_HIP(hipMalloc(&tw.wp_dev, packed.size() * sizeof(_Float16)));
-    MI355_HIP(hipMemcpy(tw.wp_dev, packed.data(), packed.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    TConvWeights tw;
+    tw.cin = cin; tw.cout = cout; tw.dtype = MI355_F16;
+    MI355_TRY(mem.upload(packed.data(), packed.size() * sizeof(_Float16), &tw.wp_dev));
     *out = tw;
     return MI355_OK;
 }
 
-void tconv_weights_free_f16(TConvWeightsH *w) {
-    if (w->wp_dev) (void)hipFree(w->wp_dev);
-    *w = TConvWeightsH();
-}
-
-int tconv2_mfma_f16(const TConvWeightsH &w, const _Float16 *in, int N, int D, int H, int W, _Float16 *out,
-                    hipStream_t s, const char **kernel_name) {
+static int tconv2_mfma_f16(const TConvPack<_Float16> &w, const _Float16 *in, int N, int D, int H, int W, _Float16 *out,
+                           hipStream_t s, const char **kernel_name) {
     if (kernel_name) *kernel_name = "tconv2_f16_mfma_v2_kernel";
     const long M = (long)N * D * H * W;
     MI355_REQUIRE(M > 0 && M < (1l << 30), "tconv: %ld voxels out of range", M);
@@ -515,6 +511,15 @@ int tconv2_mfma_f16(const TConvWeightsH &w, const _Float16 *in, int N, int D, in
                        W, make_fastdiv(W), make_fastdiv(H), make_fastdiv(D));
     MI355_HIP(hipGetLastError());
     return MI355_OK;
+}
+
+int tconv_weights_upload(DeviceAllocs &mem, const float *w_host, int cin, int cout, int dtype, TConvWeights *out) {
+    return dtype == MI355_F16 ? tconv_weights_upload_f16(mem, w_host, cin, cout, out) : tconv_weights_upload_f32(mem, w_host, cin, cout, out);
+}
+
+int tconv2_mfma(const TConvWeights &w, const void *in, int N, int D, int H, int W, void *out, hipStream_t s, const char **kernel_name) {
+    if (w.dtype == MI355_F16) return tconv2_mfma_f16(TConvPack<_Float16>(w), (const _Float16 *)in, N, D, H, W, (_Float16 *)out, s, kernel_name);
+    return tconv2_mfma_f32(TConvPack<float>(w), (const float *)in, N, D, H, W, (float *)out, s, kernel_name);
 }
 
 }  // namespace mi355

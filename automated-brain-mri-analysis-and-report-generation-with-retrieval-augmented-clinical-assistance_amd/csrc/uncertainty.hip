@@ -201,8 +201,9 @@ extern "C" int mi355_uncertainty_stats(const float *mean_dev, const float *var_d
     const size_t b_osum = (size_t)C * (UNC_NSUM + 1) * sizeof(double), b_ocnt = (size_t)C * UNC_NCNT * sizeof(long long);
     // working memory of its own for the length of the call (a few hundred KiB; the call ends in a read-back anyway): the library's
     // scratch slots belong to the entry points that had them, and nothing here outlives the call
+    DeviceAllocs mem;  // (freed on every exit: the read-back below has synchronised the stream by then)
     char *scr = nullptr;
-    MI355_HIP(hipMalloc((void **)&scr, b_psum + b_pcnt + b_pmax + b_osum + b_ocnt));
+    MI355_TRY(mem.alloc(b_psum + b_pcnt + b_pmax + b_osum + b_ocnt, &scr));
     double *psum = (double *)scr;
     long long *pcnt = (long long *)(scr + b_psum);
     float *pmax = (float *)(scr + b_psum + b_pcnt);
@@ -213,9 +214,7 @@ extern "C" int mi355_uncertainty_stats(const float *mean_dev, const float *var_d
                        (const long long *)pcnt, (const float *)pmax, blocks, osum, ocnt);
     // one read-back: the sums [C][7] and the counts [C][9] lie next to each other
     std::vector<char> host(b_osum + b_ocnt);
-    const int rc = read_back(host.data(), osum, b_osum + b_ocnt, s);   // (synchronises the stream: the kernels are done with scr)
-    (void)hipFree(scr);
-    MI355_TRY(rc);
+    MI355_TRY(read_back(host.data(), osum, b_osum + b_ocnt, s));   // (synchronises the stream: the kernels are done with scr)
     memcpy(sums_host, host.data(), b_osum);
     const long long *cnt = (const long long *)(host.data() + b_osum);
     for (int c = 0; c < C; ++c) {  // thresholds first, then |F|

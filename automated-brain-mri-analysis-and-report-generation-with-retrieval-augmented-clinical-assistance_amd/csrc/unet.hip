@@ -17,8 +17,9 @@ namespace mi355 {
 // half != nullptr (the first block of the last decoder stage, which reads the virtual concat (upsampled, skip)): when the network
 // qualifies for the shared skip half (skip_share_network_ok, the predicate the sliding window decides by) the block also gets the
 // packs of its two halves, each through conv_weights_upload and so through conv_pack_layout like any layer: the same fp64
-// Winograd transform, rounded once.
-static int build_conv(const mi355_unet &net, const mi355_conv_desc &d, int cin_phys, ConvLayer *out, bool stem = false, const SkipShareNet *half = nullptr) {
+// Winograd transform, rounded once.  Everything is uploaded straight into net.mem: a refusal part-way through a layer leaves
+// nothing behind once the handle goes.
+static int build_conv(mi355_unet &net, const mi355_conv_desc &d, int cin_phys, ConvLayer *out, bool stem = false, const SkipShareNet *half = nullptr) {
     MI355_REQUIRE(d.weight != nullptr, "conv %d->%d: null weight", d.cin, d.cout);
     MI355_REQUIRE(d.cin > 0 && d.cout > 0 && cin_phys >= d.cin, "conv: bad channel counts %d->%d (phys %d)", d.cin, d.cout, cin_phys);
     ConvLayer L;
@@ -46,20 +47,20 @@ static int build_conv(const mi355_unet &net, const mi355_conv_desc &d, int cin_p
             }
         } else {
             L.post_affine = true;
-            MI355_TRY(upload(sc.data(), d.cout, &L.gamma_dev));
-            MI355_TRY(upload(sh.data(), d.cout, &L.beta_dev));
+            MI355_TRY(net.mem.upload(sc.data(), d.cout * sizeof(float), &L.gamma_dev));
+            MI355_TRY(net.mem.upload(sh.data(), d.cout * sizeof(float), &L.beta_dev));
         }
     } else if (net.norm == MI355_NORM_INSTANCE || net.norm == MI355_NORM_GROUP) {
         L.runtime_norm = true;
         std::vector<float> g(d.cout, 1.f), be(d.cout, 0.f);
         if (d.gamma) g.assign(d.gamma, d.gamma + d.cout);
         if (d.beta) be.assign(d.beta, d.beta + d.cout);
-        MI355_TRY(upload(g.data(), d.cout, &L.gamma_dev));
-        MI355_TRY(upload(be.data(), d.cout, &L.beta_dev));
+        MI355_TRY(net.mem.upload(g.data(), d.cout * sizeof(float), &L.gamma_dev));
+        MI355_TRY(net.mem.upload(be.data(), d.cout * sizeof(float), &L.beta_dev));
     }
-    if (stem) { L.is_stem = true; MI355_TRY(stem_weights_upload(w.data(), b.data(), d.cin, d.cout, net.dtype, &L.stem)); }
-    else if (net.dtype == MI355_F16) MI355_TRY(conv_weights_upload_f16(w.data(), b.data(), d.cin, cin_phys, d.cout, d.stride, &L.wh));
-    else MI355_TRY(conv_weights_upload(w.data(), b.data(), d.cin, cin_phys, d.cout, d.stride, false, &L.w));
+    if (stem) { L.is_stem = true; MI355_TRY(stem_weights_upload(net.mem, w.data(), b.data(), d.cin, d.cout, net.dtype, &L.stem)); }
+    else if (net.dtype == MI355_F16) MI355_TRY(conv_weights_upload_f16(net.mem, w.data(), b.data(), d.cin, cin_phys, d.cout, d.stride, &L.wh));
+    else MI355_TRY(conv_weights_upload(net.mem, w.data(), b.data(), d.cin, cin_phys, d.cout, d.stride, false, &L.w));
     if (half && !stem && cin_phys == d.cin && half->c_up + half->c_skip == d.cin && skip_share_network_ok(*half)) {
         const int split_c0 = half->c_up, c_skip = half->c_skip;
         {
@@ -69,8 +70,8 @@ static int build_conv(const mi355_unet &net, const mi355_conv_desc &d, int cin_p
                 std::copy(src, src + (size_t)split_c0 * 27, &wu[(size_t)co * split_c0 * 27]);
                 std::copy(src + (size_t)split_c0 * 27, src + (size_t)d.cin * 27, &ws[(size_t)co * c_skip * 27]);
             }
-            MI355_TRY(conv_weights_upload(wu.data(), b.data(), split_c0, split_c0, d.cout, 1, false, &L.w_up));
-            MI355_TRY(conv_weights_upload(ws.data(), nullptr, c_skip, c_skip, d.cout, 1, false, &L.w_skip));
+            MI355_TRY(conv_weights_upload(net.mem, wu.data(), b.data(), split_c0, split_c0, d.cout, 1, false, &L.w_up));
+            MI355_TRY(conv_weights_upload(net.mem, ws.data(), nullptr, c_skip, c_skip, d.cout, 1, false, &L.w_skip));
             L.split_c0 = split_c0;
         }
     }
@@ -78,24 +79,8 @@ static int build_conv(const mi355_unet &net, const mi355_conv_desc &d, int cin_p
     return MI355_OK;
 }
 
-static void free_conv(ConvLayer *L) {
-    conv_weights_free(&L->w);
-    conv_weights_free(&L->w_up);
-    conv_weights_free(&L->w_skip);
-    conv_weights_free_f16(&L->wh);
-    stem_weights_free(&L->stem);
-    if (L->gamma_dev) (void)hipFree(L->gamma_dev);
-    if (L->beta_dev) (void)hipFree(L->beta_dev);
-}
-
-static void destroy(mi355_unet *net) {
+static void destroy(mi355_unet *net) {  // (device memory goes with net->mem and net->gauss_mem)
     if (!net) return;
-    for (auto &st : net->enc) for (auto &L : st) free_conv(&L);
-    for (auto &st : net->dec) for (auto &L : st) free_conv(&L);
-    for (auto &t : net->tu) tconv_weights_free(&t);
-    for (auto &t : net->tuh) tconv_weights_free_f16(&t);
-    head_weights_free(&net->head);
-    if (net->gauss_dev) (void)hipFree(net->gauss_dev);
     for (auto &r : net->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (hipEvent_t e : net->event_pool) (void)hipEventDestroy(e);
     delete net;
@@ -113,7 +98,7 @@ int make_plan(const mi355_unet &net, int N, int D, int H, int W, Plan *pl) {
     }
     for (int u = 0; u < np; ++u) {
         const int l = np - 1 - u;
-        pl->maxc[l] = std::max(pl->maxc[l], net.dtype == MI355_F16 ? net.tuh[u].cout : net.tu[u].cout);
+        pl->maxc[l] = std::max(pl->maxc[l], net.tu[u].cout);
         for (auto &L : net.dec[u]) pl->maxc[l] = std::max(pl->maxc[l], L.cout);
     }
     ArenaCursor c{0};
@@ -272,7 +257,7 @@ int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W
         const int l = np - 1 - u;
         const int Dl = D >> l, Hl = H >> l, Wl = W >> l;
         void *up = buf(2, l);
-        const int tcin = f16 ? net->tuh[u].cin : net->tu[u].cin, tcout = f16 ? net->tuh[u].cout : net->tu[u].cout;
+        const int tcin = net->tu[u].cin, tcout = net->tu[u].cout;
         MI355_REQUIRE(tcin == curC, "tu.%d expects %d channels, got %d", u, tcin, curC);
         {
             const double es = f16 ? 2.0 : 4.0;
@@ -280,8 +265,8 @@ int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W
             ProfScope ps(net, s, f16 ? "tconv2_f16_mfma_v2_kernel" : "tconv2_f32_mfma_v2_kernel", 2.0 * vin * tcin * tcout * 8.0,
                          es * (vin * tcin + 8.0 * vin * tcout + 8.0 * tcin * tcout));
             const char *tname = nullptr;
-            if (f16) { MI355_TRY(tconv2_mfma_f16(net->tuh[u], (const _Float16 *)cur, N, Dl / 2, Hl / 2, Wl / 2, (_Float16 *)up, s, &tname)); ps.rename(tname); }
-            else { MI355_TRY(tconv2_mfma_f32(net->tu[u], (const float *)cur, N, Dl / 2, Hl / 2, Wl / 2, (float *)up, s, &tname)); ps.rename(tname); }
+            MI355_TRY(tconv2_mfma(net->tu[u], cur, N, Dl / 2, Hl / 2, Wl / 2, up, s, &tname));
+            ps.rename(tname);
         }
         // concat order (upsampled, skip): generic_UNet.py:438 - never materialised
         const void *in0 = up, *in1 = skip[l];
@@ -363,7 +348,7 @@ extern "C" int mi355_unet_create(const mi355_unet_desc *d, mi355_unet_t *out) {
     int prevC = net->cin_pad;
     net->enc.resize(d->num_pool + 1);
     net->dec.resize(d->num_pool);
-    if (d->dtype == MI355_F16) net->tuh.resize(d->num_pool); else net->tu.resize(d->num_pool);
+    net->tu.resize(d->num_pool);
     std::vector<int> skipC(d->num_pool, 0);
     auto fail = [&](int code) { destroy(net); return code; };
     for (int l = 0; l <= d->num_pool && rc == MI355_OK; ++l) {
@@ -388,8 +373,7 @@ extern "C" int mi355_unet_create(const mi355_unet_desc *d, mi355_unet_t *out) {
         const int l = d->num_pool - 1 - u;
         const mi355_tconv_desc &td = d->tconvs[u];
         if (td.cin != prevC) { set_error("tu.%d: cin %d, expected %d", u, td.cin, prevC); return fail(MI355_ERR_INVALID); }
-        rc = d->dtype == MI355_F16 ? tconv_weights_upload_f16(td.weight, td.cin, td.cout, &net->tuh[u])
-                                   : tconv_weights_upload(td.weight, td.cin, td.cout, &net->tu[u]);
+        rc = tconv_weights_upload(net->mem, td.weight, td.cin, td.cout, d->dtype, &net->tu[u]);
         if (rc != MI355_OK) return fail(rc);
         net->max_channels = std::max(net->max_channels, td.cout);
         int inC = td.cout + skipC[l];
@@ -415,7 +399,7 @@ extern "C" int mi355_unet_create(const mi355_unet_desc *d, mi355_unet_t *out) {
     }
     if (ci != d->n_convs) { set_error("%d convs given, topology uses %d", d->n_convs, ci); return fail(MI355_ERR_INVALID); }
     if (d->head.cin != prevC || d->head.num_classes != d->num_classes) { set_error("head: cin %d classes %d, expected %d / %d", d->head.cin, d->head.num_classes, prevC, d->num_classes); return fail(MI355_ERR_INVALID); }
-    rc = head_weights_upload(d->head.weight, d->head.bias, d->head.cin, d->head.num_classes, &net->head);
+    rc = head_weights_upload(net->mem, d->head.weight, d->head.bias, d->head.cin, d->head.num_classes, &net->head);
     if (rc != MI355_OK) return fail(rc);
     *out = net;
     return MI355_OK;
@@ -435,7 +419,7 @@ extern "C" int64_t mi355_unet_flops(mi355_unet_t net, int d, int h, int w) {
         for (auto &L : net->enc[l]) total += 2 * vox(l) * L.cout * L.cin * 27;
     for (int u = 0; u < np; ++u) {
         const int l = np - 1 - u;
-        total += 2 * vox(l + 1) * (net->dtype == MI355_F16 ? (int64_t)net->tuh[u].cin * net->tuh[u].cout : (int64_t)net->tu[u].cin * net->tu[u].cout) * 8;
+        total += 2 * vox(l + 1) * ((int64_t)net->tu[u].cin * net->tu[u].cout) * 8;
         for (auto &L : net->dec[u]) total += 2 * vox(l) * L.cout * L.cin * 27;
     }
     total += 2 * vox(0) * net->head.cin * net->head.ncls;

@@ -1,5 +1,5 @@
 // What the five host files behind include/mi355_nnunet.h share, and nobody else includes:
-//   runtime.hip         last-error text, bind_device, the lanes and device_scratch, the scratch test aids
+//   runtime.hip         last-error text, bind_device, the lanes and device_scratch, the scratch test aids, DeviceAllocs
 //   unet.hip            the network object, the arena plan, run_block / forward_features, create / destroy / forward / profile
 //   sw_share_plan.hip   pure: tile geometry, what overlapping tiles share as one plan per window, the geometry dry runs
 //   sliding_window.hip  the device side of that plan: the shared stage 0 and level 1 passes, sw_accumulate, mi355_sw_*
@@ -38,11 +38,12 @@ struct mi355_unet {
     std::vector<std::vector<mi355::ConvLayer>> enc;  // num_pool + 1 stages
     std::vector<std::vector<mi355::ConvLayer>> dec;  // num_pool stages
     std::vector<mi355::TConvWeights> tu;
-    std::vector<mi355::TConvWeightsH> tuh;
     mi355::HeadWeights head;
+    mi355::DeviceAllocs mem;  // owns every weight above (the structs are views of it); freed with the handle
     // (the activation arena is not the handle's: one per LANE = per stream the caller launches on, shared by every handle that
     //  runs on that stream - device_scratch(SCR_ARENA, stream); a forward carries its pointer in its Plan)
-    // gaussian importance map cache
+    // gaussian importance map cache (an owner of its own: ensure_gaussian releases it when the patch changes)
+    mi355::DeviceAllocs gauss_mem;
     float *gauss_dev = nullptr;
     int gauss_p[3] = {0, 0, 0};
     int max_channels = 0;
@@ -56,12 +57,6 @@ struct mi355_unet {
 namespace mi355 {
 
 inline int require_device() { return bind_device(); }
-
-inline int upload(const float *host, size_t n, float **dev) {
-    MI355_HIP(hipMalloc(dev, n * sizeof(float)));
-    MI355_HIP(hipMemcpy(*dev, host, n * sizeof(float), hipMemcpyHostToDevice));
-    return MI355_OK;
-}
 
 // ---- arena layout for one (N, D, H, W): per level four activation buffers + norm scratch
 struct Plan {

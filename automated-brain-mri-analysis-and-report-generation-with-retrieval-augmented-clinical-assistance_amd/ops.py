@@ -1005,3 +1005,11 @@ def scratch_zero_pages() -> tuple:
     out = (C.c_int64 * 2)()
     _lib.check(_lib.load().mi355_scratch_zero_pages(out), "mi355_scratch_zero_pages")
     return int(out[0]), int(out[1])
+
+
+def live_allocations() -> tuple:
+    """(count, bytes) of the device memory the library's owners hold now: weights and Gaussian maps of live handles, the buffers
+    of a single-op call while it runs; scratch is not counted (host code: needs no GPU)."""
+    count, nbytes = C.c_int64(), C.c_int64()
+    _lib.check(_lib.load().mi355_live_allocations(C.byref(count), C.byref(nbytes)), "mi355_live_allocations")
+    return int(count.value), int(nbytes.value)

@@ -568,6 +568,11 @@ int mi355_scratch_release(void *stream);
 /* nonzero_bytes[0], [1] = the number of non-zero bytes in the two shared zero pages (0 for a page that does not exist yet),
  * after a device synchronise. */
 int mi355_scratch_zero_pages(int64_t *nonzero_bytes);
+/* Device memory that is not scratch - the weights of every live handle, their Gaussian maps, and for the length of a call the
+ * buffers and weights of a single-op entry point - has one owner per handle or call; *count / *bytes = the allocations and bytes
+ * all owners of this process hold now.  A handle that was destroyed, a create that was refused and a call that has returned hold
+ * none.  Host code, needs no device. */
+int mi355_live_allocations(int64_t *count, int64_t *bytes);
 
 /* Per-kernel timing with HIP events on the stream the kernels are launched on (bench.py's
  * roofline). flops / bytes are the ALGORITHMIC work of the recorded launches. */
