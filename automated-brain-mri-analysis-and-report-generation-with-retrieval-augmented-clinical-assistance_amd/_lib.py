@@ -52,6 +52,7 @@ EXPORTS = [
     "mi355_sw_partial_folds_moments", "mi355_sw_finish_moments", "mi355_logits_aggregate_m2", "mi355_logits_aggregate_tiles_m2",
     "mi355_head_aggregate_m2", "mi355_uncertainty_maps", "mi355_uncertainty_stats",
     "mi355_live_allocations",
+    "mi355_tconv3d_plan",
 ]
 
 
@@ -255,6 +256,7 @@ def load():
                                              C.c_int, vp, vp, vp, vp]
     lib.mi355_conv3d_plan.argtypes = [C.c_int] * 13 + [C.POINTER(ConvPlan)]
     lib.mi355_conv3d_plan_hinted.argtypes = [C.c_int] * 14 + [C.POINTER(ConvPlan)]
+    lib.mi355_tconv3d_plan.argtypes = [C.c_int] * 7 + [C.POINTER(ConvPlan)]
     lib.mi355_conv_kernel_names.argtypes = [C.c_char_p, C.c_int64]
     lib.mi355_conv_kernel_names.restype = C.c_int64
     lib.mi355_stage0_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_double, C.c_int, C.c_int, C.POINTER(Stage0Geom),

@@ -181,4 +181,15 @@ bool plan_f16_s2dma(const ConvWeightsH &w, const ConvCallH &c, ConvPlan *p);  //
 int launch_wino3(const ConvWeights &w, const ConvCall &c, const ConvPlan &p, hipStream_t s);
 int launch_f16_s2dma(const ConvWeightsH &w, const ConvCallH &c, const ConvPlan &p, hipStream_t s);
 
+// The transposed conv's plan for M = N*D*H*W input voxels (tconv.hip): a row of tconv_rows, its grid and its static LDS; or
+// the refusal of a shape the kernels do not take.  tconv2_mfma is plan_tconv + launch_tconv.
+struct TconvPlan {
+    KernelRow *row = nullptr;
+    bool persistent = false;  // version 3: grid.x workgroups stride over the voxel tiles
+    unsigned gx = 0, gy = 1;
+    size_t lds_bytes = 0;
+};
+int plan_tconv(int dtype, int cin, int cout, long M, TconvPlan *p);
+int launch_tconv(const TConvWeights &w, const TconvPlan &p, const void *in, int N, int D, int H, int W, void *out, hipStream_t s);
+
 }  // namespace mi355

@@ -92,9 +92,9 @@ extern "C" int mi355_tconv3d_ndhwc(const float *x_dev, int n, int d, int h, int 
     DeviceAllocs mem;
     TConvWeights tw;
     MI355_TRY(tconv_weights_upload(mem, weight_host, cin, cout, MI355_F32, &tw));
-    const char *tname = "tconv2_f32_mfma_v2_kernel";
+    const char *tname = nullptr;
     const int rc = tconv2_mfma(tw, x_dev, n, d, h, w, y_dev, (hipStream_t)stream, &tname);
-    g_last_conv_kernel = tname;
+    g_last_conv_kernel = tname ? tname : "";
     return synced(rc, (hipStream_t)stream, "tconv");
 }
 
@@ -255,6 +255,24 @@ extern "C" int mi355_conv3d_plan_hinted(int dtype, int n, int d, int h, int w, i
 extern "C" int mi355_conv3d_plan(int dtype, int n, int d, int h, int w, int c0, int c1, int cout, int stride, int impl, int has_stats,
                                  int has_in_norm, int head_ncls, mi355_conv_plan *out) {
     return mi355_conv3d_plan_hinted(dtype, n, d, h, w, c0, c1, cout, stride, impl, has_stats, has_in_norm, head_ncls, 0, out);
+}
+
+static int tconv3d_plan_impl(int dtype, int n, int d, int h, int w, int cin, int cout, mi355_conv_plan *out) {
+    MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_F16, "unknown dtype %d", dtype);
+    MI355_REQUIRE(n > 0 && d > 0 && h > 0 && w > 0, "bad tconv shape");
+    TconvPlan p;
+    MI355_TRY(plan_tconv(dtype, cin, cout, (long)n * d * h * w, &p));
+    out->grid[0] = (int32_t)p.gx; out->grid[1] = (int32_t)p.gy; out->grid[2] = 1;
+    out->lds_bytes = (int64_t)p.lds_bytes;
+    snprintf(out->kernel, sizeof(out->kernel), "%s", p.row->name);
+    return MI355_OK;
+}
+extern "C" int mi355_tconv3d_plan(int dtype, int n, int d, int h, int w, int cin, int cout, mi355_conv_plan *out) {
+    MI355_REQUIRE(out != nullptr, "mi355_tconv3d_plan: out is null");
+    memset(out, 0, sizeof(*out));
+    out->splitk = 1;
+    out->rc = tconv3d_plan_impl(dtype, n, d, h, w, cin, cout, out);
+    return out->rc;
 }
 
 extern "C" int64_t mi355_conv_kernel_names(char *buf, int64_t buf_bytes) {

@@ -262,11 +262,10 @@ int forward_features(mi355_unet *net, const Plan &pl, int N, int D, int H, int W
         {
             const double es = f16 ? 2.0 : 4.0;
             const double vin = (double)N * (Dl / 2) * (Hl / 2) * (Wl / 2);
-            ProfScope ps(net, s, f16 ? "tconv2_f16_mfma_v2_kernel" : "tconv2_f32_mfma_v2_kernel", 2.0 * vin * tcin * tcout * 8.0,
-                         es * (vin * tcin + 8.0 * vin * tcout + 8.0 * tcin * tcout));
-            const char *tname = nullptr;
-            MI355_TRY(tconv2_mfma(net->tu[u], cur, N, Dl / 2, Hl / 2, Wl / 2, up, s, &tname));
-            ps.rename(tname);
+            TconvPlan tp;
+            MI355_TRY(plan_tconv(net->tu[u].dtype, tcin, tcout, (long)N * (Dl / 2) * (Hl / 2) * (Wl / 2), &tp));
+            ProfScope ps(net, s, tp.row->name, 2.0 * vin * tcin * tcout * 8.0, es * (vin * tcin + 8.0 * vin * tcout + 8.0 * tcin * tcout));
+            MI355_TRY(launch_tconv(net->tu[u], tp, cur, N, Dl / 2, Hl / 2, Wl / 2, up, s));
         }
         // concat order (upsampled, skip): generic_UNet.py:438 - never materialised
         const void *in0 = up, *in1 = skip[l];

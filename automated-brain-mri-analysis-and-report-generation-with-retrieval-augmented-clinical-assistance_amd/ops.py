@@ -246,6 +246,17 @@ def conv3d_plan(dtype, shape, c0, cout, c1=0, stride=1, impl="mfma", stats=False
             "tile": tuple(p.tile), "fuses_in_norm": bool(p.fuses_in_norm), "error": (lib.mi355_last_error() or b"").decode() if rc < 0 else ""}
 
 
+def tconv_plan(dtype, shape, cin, cout):
+    """Dry run of ``tconv3d_ndhwc`` (test aid, ``mi355_tconv3d_plan``; no GPU needed): the transposed-conv kernel a call of
+    ``shape`` = (N, D, H, W) input voxels with Cin -> Cout channels is sent to.  dtype: "f32" | "f16".  Returns a dict (rc, kernel,
+    grid, lds_bytes, error); a refused call has rc < 0 and the launcher's message in ``error``."""
+    p = _lib.ConvPlan()
+    lib = _lib.load()
+    rc = lib.mi355_tconv3d_plan({"f32": 0, "f16": 1}[dtype], *(int(v) for v in shape), int(cin), int(cout), C.byref(p))
+    return {"rc": rc, "kernel": p.kernel.decode(), "grid": tuple(p.grid), "lds_bytes": int(p.lds_bytes),
+            "error": (lib.mi355_last_error() or b"").decode() if rc < 0 else ""}
+
+
 def conv_kernel_names():
     """Every kernel instantiation the 3x3x3 conv dispatch can launch (test aid, ``mi355_conv_kernel_names``; no GPU needed): a list
     of (table, name), one per row of the four row tables, names as ``conv3d_plan`` reports them (without " split-K")."""

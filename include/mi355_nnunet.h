@@ -650,6 +650,12 @@ int mi355_conv3d_plan_hinted(int dtype, int n, int d, int h, int w, int c0, int 
  * mi355_last_conv_kernel spell it (without the " split-K" suffix).  Writes at most buf_bytes bytes, NUL-terminated, and returns
  * the bytes the whole list needs (buf may be NULL when buf_bytes is 0).  No reference counterpart. */
 int64_t mi355_conv_kernel_names(char *buf, int64_t buf_bytes);
+/* Dry run of mi355_tconv3d_ndhwc / mi355_tconv3d_ndhwc_f16 (test aid; needs no device and launches nothing): the transposed-conv
+ * kernel a call of this shape is sent to, by the planner a real call and the network run.  Fills rc, kernel, grid and lds_bytes
+ * (the kernel's static LDS); splitk stays 1, tile and fuses_in_norm 0.  A shape the kernels do not take (cin, cout, 2^30 voxels
+ * or more) returns its error code (also in out->rc) and leaves the launcher's message in mi355_last_error.  No reference
+ * counterpart. */
+int mi355_tconv3d_plan(int dtype, int n, int d, int h, int w, int cin, int cout, mi355_conv_plan *out);
 /* Dry run of the shared stage 0 of the sliding window (needs no device and launches nothing; the same code mi355_sw_predict /
  * mi355_sw_partial[_folds] run).  An fp32 network whose encoder stage 0 is r stride-1 blocks without run-time statistics
  * (BatchNorm folded or no norm) computes that stage once per mirror over the whole padded volume, and per (tile, mirror) over

@@ -1,9 +1,11 @@
-"""GPU cases for the two families of matrix-core kernels that sit in no conv row table (plain data: no GPU import).
+"""GPU cases for the two families of matrix-core kernels outside the 3x3x3 conv row tables (plain data: no GPU import).
 
 conv_rows_util.py covers the 3x3x3 row tables.  The first conv of every network (conv_stem.hip: conv3_stem_f32_kernel,
-conv3_stem_f16_kernel<false|true>) and every decoder up-sampling (tconv.hip: tconv2_f32_mfma_v2_kernel,
-tconv2_f32_mfma_v3_kernel<8>, tconv2_f16_mfma_v2_kernel, tconv2_f16_mfma_v3_kernel<2|4|8>) are launched by rules of their own,
-written out here (expected_tconv_kernel; the stem takes every Cin = 4, stride-1 call).  STEM_CASES and TCONV_CASES hold, per
+conv3_stem_f16_kernel<false|true>) and every decoder up-sampling (tconv.hip, the rows of tconv_rows: tconv2_f32_mfma_v2_kernel,
+tconv2_f32_mfma_v3_kernel<8>, tconv2_f16_mfma_v2_kernel, tconv2_f16_mfma_v3_kernel<2|4|8>) are launched by rules of their own.
+The stem takes every Cin = 4, stride-1 call.  The transposed conv's rule, plan_tconv, is written out here once more as
+expected_tconv_kernel; tests/test_tconv_plan_cpu.py compares the two on the CPU through the dry run mi355_tconv3d_plan, and
+TCONV_KERNELS with the table.  STEM_CASES and TCONV_CASES hold, per
 instantiation, ragged, whole-tile and sample-straddling shapes; tests/test_tconv_stem_cpu.py keeps that set closed and checks
 the references, tests/test_gpu_tconv_stem.py runs every case on exact integers, between sentinels.
 
@@ -76,7 +78,7 @@ def tconv_straddles(shape):
 
 
 def expected_tconv_kernel(dtype, cin, m):
-    """the dispatch rule of tconv2_mfma_f32 / tconv2_mfma_f16 (tconv.hip) under the default MI355_TCONV_V3: the persistent
+    """the rule of plan_tconv (tconv.hip) under the default MI355_TCONV_V3: the persistent
     kernels take >= 1024 tiles of 128 voxels at Cin = 64 (fp32) or Cin = 32, 64, 128 (fp16); everything else is version 2"""
     many = tconv_tiles(m) >= V3_MIN_TILES
     if dtype == "f32":

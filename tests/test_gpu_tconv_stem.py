@@ -148,6 +148,8 @@ def test_tconv_case(amd, gpu, case):
     ran_b, numel, top, guarded = tconv_integer_run(amd, gpu, case)
     if check_kernel:
         assert ran_b == case.kernel, (case.name, ran_b)
+    # the dry run names what ran (whatever the switch: both read it in this process)
+    assert amd.ops.tconv_plan(case.dtype, case.shape, case.cin, case.cout)["kernel"] == ran_b == ran_a, (case.name, ran_a, ran_b)
     print(f"TCONV CASE {case.name} gates of test_gpu_ops on {ran_a}{per_element} | integers: {numel} outputs of {ran_b} equal the integer tconv "
           f"(max |y| {top}), {guarded} | {_describe(case)} | {time.time() - t0:.1f} s", flush=True)
 

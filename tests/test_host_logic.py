@@ -219,6 +219,13 @@ def test_isa_gate_flags_the_hazards_it_is_there_for(amd):
     assert gate.check_asm_text(_GATE_KERNEL % (waited, 0, 0)) == []
     f = gate.check_asm_text(_GATE_KERNEL % ("\ts_nop 0", 12, 2))
     assert len(f) == 1 and f[0].startswith("R "), f
+    # the transposed convs (NO_SPILL): judged by their metadata alone - clean as they are, refused with scratch or a spilled VGPR
+    tconv = _GATE_KERNEL.replace("_ZN5mi35520conv3_f16_dma_kernelILb0ELb0EEEvNS_9ConvArgsHE",
+                                 "_ZN5mi35525tconv2_f16_mfma_v3_kernelILi8EEEvPKDF16_S2_PDF16_iiiiiNS_7FastDivES4_S4_")
+    assert gate.check_asm_text(tconv % ("\ts_nop 0", 0, 0)) == []
+    for scratch, spilled in ((24, 5), (8, 0), (0, 1)):
+        f = gate.check_asm_text(tconv % ("\ts_nop 0", scratch, spilled))
+        assert len(f) == 1 and f[0].startswith("R ") and "tconv2_f16_mfma_v3_kernel" in f[0] and "must not spill" in f[0], f
 
 
 def test_built_library_passes_the_isa_gate(amd):
@@ -235,3 +242,5 @@ def test_built_library_passes_the_isa_gate(amd):
     # the gate knows the hand-counted kernels by name: a rename must not silently drop one out of the scratch check
     for prefix in ("conv3_f32_wino3_kernel", "conv3_f32_wino2_kernel", "conv3_f32_s2dma_kernel", "conv3_f16_dma_kernel", "conv3_f16_s2dma_kernel"):
         assert any(prefix in n for n in names), prefix
+    for prefix in gate.NO_SPILL:  # (likewise the kernels that must not spill)
+        assert sum(prefix in n for n in names) >= 2, prefix
