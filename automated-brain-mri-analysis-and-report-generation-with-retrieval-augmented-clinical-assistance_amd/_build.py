@@ -26,7 +26,7 @@ CSRC = PKG_DIR / "csrc"
 LIB_DIR = Path(os.environ["MI355_LIB_DIR"]).resolve() if os.environ.get("MI355_LIB_DIR") else PKG_DIR.parent / "lib"
 OBJ_DIR = LIB_DIR / "obj"
 LIB_PATH = LIB_DIR / "libmi355_nnunet.so"
-SOURCES = ["conv3d.hip", "conv3d_wino3.hip", "conv3d_f16.hip", "conv3d_f16_s2.hip", "conv_stem.hip", "tconv.hip", "elementwise.hip", "extras.hip", "resample.hip", "components.hip", "morphology.hip", "percentile.hip", "runtime.hip", "unet.hip", "sw_share_plan.hip", "sliding_window.hip", "single_op.hip", "quality.hip", "mass_effect.hip", "normal_structures.hip", "surface_distance.hip", "lesionwise.hip", "resident_case.hip", "uncertainty.hip"]
+SOURCES = ["conv3d.hip", "conv3d_wino3.hip", "conv3d_f16.hip", "conv3d_f16_s2.hip", "conv_stem.hip", "tconv.hip", "elementwise.hip", "stage0_gather.hip", "aggregate.hip", "extras.hip", "resample.hip", "components.hip", "morphology.hip", "percentile.hip", "runtime.hip", "unet.hip", "sw_share_plan.hip", "sliding_window.hip", "single_op.hip", "quality.hip", "mass_effect.hip", "normal_structures.hip", "surface_distance.hip", "lesionwise.hip", "resident_case.hip", "uncertainty.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", "-Wno-pass-failed"]
 
 

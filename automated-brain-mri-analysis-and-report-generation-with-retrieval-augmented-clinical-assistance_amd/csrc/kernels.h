@@ -133,7 +133,7 @@ int tconv_weights_upload(DeviceAllocs &mem, const float *w_host, int cin, int co
 int tconv2_mfma(const TConvWeights &w, const void *in, int N, int D, int H, int W, void *out, hipStream_t s,
                 const char **kernel_name = nullptr);
 
-// ---------------------------------------------------------------- normalisation
+// ---------------------------------------------------------------- elementwise.hip: normalisation, tile extraction, layouts
 // stats [N][C][2] doubles -> scale/shift [N][C] so that y = x*scale + shift.
 int norm_finalize(const double *stats, int N, int C, int64_t count, int kind, int groups, float eps,
                   const float *gamma, const float *beta, float *scale, float *shift, hipStream_t s);
@@ -141,7 +141,6 @@ int norm_finalize(const double *stats, int N, int C, int64_t count, int kind, in
 int norm_apply(void *x, int dtype, int N, int64_t V, int C, const float *scale, const float *shift, int act,
                float slope, hipStream_t s);
 
-// ---------------------------------------------------------------- tiles / head / aggregate
 struct TileDesc {  // one forward sample = one (tile, mirror)
     int z0, y0, x0;  // origin in the padded volume
     int mirror;      // bit0 flip z, bit1 flip y, bit2 flip x
@@ -151,6 +150,13 @@ struct TileDesc {  // one forward sample = one (tile, mirror)
 int extract_tiles(const float *vol, int C, int Z, int Y, int X, int padz, int pady, int padx,
                   const TileDesc *tiles_host, int n_samples, int P0, int P1, int P2, int Cpad, void *x, int dtype,
                   hipStream_t s);
+// plain NDHWC <-> channel-blocked [N][C / 8][V][8] fp16 (common.h)
+int ndhwc_to_b8(const _Float16 *x, int N, int C, int64_t V, _Float16 *y, hipStream_t s);
+int b8_to_ndhwc(const _Float16 *x, int N, int C, int64_t V, _Float16 *y, hipStream_t s);
+// NCDHW -> NDHWC(Cpad) for the plain forward API
+int nchw_to_ndhwc(const float *x, int N, int C, int64_t V, int Cpad, void *y, int dtype, hipStream_t s);
+
+// ---------------------------------------------------------------- stage0_gather.hip: the shared stage 0's tile tensors
 // Shared stage 0 of the sliding window (sw_share_plan.hip "shared stage 0"): encoder stage 0 runs once over the whole padded volume and
 // over thin slabs at the tile faces that lie inside the volume; the tile tensor is then gathered from those results.
 constexpr int S0_MAX_SAMPLES = 64;
@@ -206,12 +212,8 @@ int64_t stage0_shell_voxels(const int P[3], int r, const int faces[6]);
 int stage0_view_make(const float *src, int n_wv, const int Ve[3], const int P[3], int C, int depth, const S0Sample *smp, int n, S0View *out);
 // x [N][Ve0][Ve1][Ve2][C] fp32: zero every voxel outside [0, Zp) (C % 4 == 0)
 int stage0_mask(float *x, int N, const int Ve[3], const int Zp[3], int C, hipStream_t s);
-// plain NDHWC <-> channel-blocked [N][C / 8][V][8] fp16 (common.h)
-int ndhwc_to_b8(const _Float16 *x, int N, int C, int64_t V, _Float16 *y, hipStream_t s);
-int b8_to_ndhwc(const _Float16 *x, int N, int C, int64_t V, _Float16 *y, hipStream_t s);
-// NCDHW -> NDHWC(Cpad) for the plain forward API
-int nchw_to_ndhwc(const float *x, int N, int C, int64_t V, int Cpad, void *y, int dtype, hipStream_t s);
 
+// ---------------------------------------------------------------- aggregate.hip: segmentation head, sliding-window aggregation
 struct HeadWeights {
     int cin = 0, ncls = 0;
     float *w_dev = nullptr;  // [ncls][cin]
@@ -228,34 +230,45 @@ struct FeatNorm {
 // feat [N][V][C] -> logits [N][ncls][V]
 int head_logits(const HeadWeights &w, const void *feat, int dtype, int N, int64_t V, float *logits, hipStream_t s,
                 const FeatNorm &fn = FeatNorm());
-// One tile: result = sum_m (1/n_mirrors) * flip_back(nonlin(head(feat[first_sample+m])));
-// agg[c][tile] += result * gauss ; cnt[tile] += gauss (cnt may be null).
-// agg2 (here and in the two below; null: not kept): agg2[c][tile] += (sum_m (1/n_mirrors) * p^2) * gauss, the second moment of the
+
+// The operands of the aggregation by name; passed by value inside the kernel arguments.
+struct MirrorList {  // the mirror masks of a tile's samples, in sample order (bit0 flip z, bit1 flip y, bit2 flip x)
+    int n;
+    int m[8];
+};
+int make_mirrors(const char *what, const int *mirrors_host, int n, MirrorList *out);  // refuses n outside 1 .. 8 ("<what>: n mirrors")
+struct AggTile {         // what every tile of a forward shares
+    int P[3];            // patch
+    int nonlin;          // MI355_NONLIN_*
+    const float *gauss;  // [P0][P1][P2] weights, or null: 1
+    MirrorList ml;
+};
+struct AggGrid {  // the padded grid the tiles are added into
+    float *agg;   // [ncls][Zp0][Zp1][Zp2]
+    float *agg2;  // the same shape: the second moment, or null: not kept
+    float *cnt;   // [Zp0][Zp1][Zp2] normaliser, or null (the aggregation kernels only)
+    int Zp[3];
+};
+// One tile at org: result = sum_m (1/n_mirrors) * flip_back(nonlin(head(feat[first_sample+m])));
+// agg[c][tile] += result * gauss ; cnt[tile] += gauss.
+// agg2 (here and in the two below): agg2[c][tile] += (sum_m (1/n_mirrors) * p^2) * gauss, the second moment of the
 // same samples; agg and cnt come out bit-identical with and without it.  nonlin identity is refused with agg2.
-int head_aggregate(const HeadWeights &w, const void *feat, int dtype, int first_sample, const int *mirrors_host,
-                   int n_mirrors, int P0, int P1, int P2, int nonlin, const float *gauss, float *agg,
-                   float *cnt, int Zp, int Yp, int Xp, int z0, int y0, int x0, hipStream_t s, const FeatNorm &fn = FeatNorm(),
-                   float *agg2 = nullptr);
-// same as head_aggregate for forwards whose last conv already produced logits [n_samples][ncls][PV]
-int logits_aggregate(const float *logits, int ncls, int first_sample, const int *mirrors_host, int n_mirrors, int P0, int P1,
-                     int P2, int nonlin, const float *gauss, float *agg, float *cnt, int Zp, int Yp, int Xp, int z0, int y0,
-                     int x0, hipStream_t s, float *agg2 = nullptr);
+int head_aggregate(const HeadWeights &w, const void *feat, int dtype, int first_sample, const AggTile &t, const AggGrid &g, const int org[3],
+                   hipStream_t s, const FeatNorm &fn = FeatNorm());
+// same as head_aggregate for forwards whose last conv already produced logits [n_samples][ncls][PV]; bit-identical to
+// head_aggregate of the features behind those logits
+int logits_aggregate(const float *logits, int ncls, int first_sample, const AggTile &t, const AggGrid &g, const int org[3], hipStream_t s);
 // The same for n_tiles tiles of one forward in one launch (per LOGITS_AGG_MAX_TILES tiles): tile i's logits are samples
 // first_sample + i * n_mirrors .., its origin origins_host[3 i ..]; bit-identical to logits_aggregate called tile by tile in order.
 constexpr int LOGITS_AGG_MAX_TILES = 64;
-int logits_aggregate_tiles(const float *logits, int ncls, int first_sample, const int *mirrors_host, int n_mirrors, int P0, int P1, int P2,
-                           int nonlin, const float *gauss, float *agg, float *cnt, int Zp, int Yp, int Xp, const int *origins_host, int n_tiles,
-                           hipStream_t s, float *agg2 = nullptr);
-// probs[c][z][y][x] (+)= agg[c][z+pz][y+py][x+px] / cnt[...]; then optional scale (fold mean)
-int finish_probs(const float *agg, const float *cnt, int C, int Z, int Y, int X, int Zp, int Yp, int Xp,
-                 int pz, int py, int px, float *probs, int accumulate, hipStream_t s);
+int logits_aggregate_tiles(const float *logits, int ncls, int first_sample, const AggTile &t, const AggGrid &g, const int *origins_host, int n_tiles,
+                           hipStream_t s);
+// cnt[tile] += gauss (or 1): the normaliser of a tile this rank does not evaluate itself
+int cnt_add_tile(const AggTile &t, const AggGrid &g, const int org[3], hipStream_t s);
+// probs[c][z][y][x] (+)= agg[c][z+pad0][y+pad1][x+pad2] / cnt[...] over the volume vol = (Z, Y, X); then optional scale (fold mean)
+int finish_probs(const AggGrid &g, int C, const int vol[3], const int pad[3], float *probs, int accumulate, hipStream_t s);
 int scale_inplace(float *x, int64_t n, float divisor, hipStream_t s);
 // mean[c][z][y][x] = agg / cnt / n_folds (the bits of finish_probs then scale_inplace), m2 the same from agg2
-int finish_moments(const float *agg, const float *agg2, const float *cnt, int C, int Z, int Y, int X, int Zp, int Yp, int Xp, int pz, int py, int px,
-                   int n_folds, float *mean, float *m2, hipStream_t s);
-// cnt[tile] += gauss (or 1): the normaliser of a tile this rank does not evaluate itself
-int cnt_add_tile(const float *gauss, int P0, int P1, int P2, float *cnt, int Yp, int Xp, int z0, int y0, int x0,
-                 hipStream_t s);
-// in place: x = act(x*scale + shift), scale/shift [C] shared by every sample (un-folded BN)
+int finish_moments(const AggGrid &g, int C, const int vol[3], const int pad[3], int n_folds, float *mean, float *m2, hipStream_t s);
 
 }  // namespace mi355

@@ -1,6 +1,7 @@
 // Single-op entry points (host side; include/mi355_nnunet.h): one kernel family per call, driven by the tests and by nothing in
 // the product - convs and transposed convs in both dtypes with their guard bands, the F(2x2x2,3x3x3) and stride-2 view entries,
-// mi355_conv3d_plan (what a conv call would launch, without a device) and the wrappers around the launchers of elementwise.hip.
+// mi355_conv3d_plan (what a conv call would launch, without a device) and the wrappers around the launchers of elementwise.hip,
+// stage0_gather.hip and aggregate.hip.
 #include <cstring>
 #include <string>
 #include <vector>
@@ -394,7 +395,7 @@ extern "C" int mi355_tconv3d_ndhwc_f16(const void *x_dev, int n, int d, int h, i
     return rc == MI355_OK ? guards_intact(ybuf, guard, ybytes, g_last_conv_kernel.c_str()) : rc;
 }
 
-// ---- single-op entry points of the kernels around the convolutions (csrc/elementwise.hip): each binds the device, calls the
+// ---- single-op entry points of the kernels around the convolutions (csrc/elementwise.hip, stage0_gather.hip, aggregate.hip): each binds the device, calls the
 // launcher the network calls and waits for the stream.  Test aids; tensors are taken in the layout the launcher takes.
 static bool tile_in_grid(const int32_t patch[3], const int32_t padded[3], const int32_t origin[3]) {
     for (int a = 0; a < 3; ++a)
@@ -454,107 +455,107 @@ extern "C" int mi355_head_logits(const void *feat_dev, int dtype, int n, int64_t
     return synced(head_logits(hw, feat_dev, dtype, n, v, logits_dev, s, feat_norm(scale_dev, shift_dev, slope)), s, "head_logits");
 }
 
+// ---- the aggregation entry points and their _m2 twins, which keep the second moment (agg2_dev, laid out as agg_dev; agg_dev / cnt_dev
+// come out as from the plain calls): one implementation per pair.  m2: the call is the twin - agg2_dev is required and nonlin identity
+// refused here; name: the entry point, for its messages.
+static int agg_operands(const char *what, const int32_t *mirrors_host, int n_mirrors, const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev,
+                        float *agg2_dev, float *cnt_dev, const int32_t padded[3], AggTile *t, AggGrid *g) {
+    *t = AggTile{{patch[0], patch[1], patch[2]}, nonlin, gauss_dev, {}};
+    *g = AggGrid{agg_dev, agg2_dev, cnt_dev, {padded[0], padded[1], padded[2]}};
+    return make_mirrors(what, mirrors_host, n_mirrors, &t->ml);
+}
+
+static int head_aggregate_abi(const char *name, bool m2, const void *feat_dev, int dtype, int cin, const float *weight_host, const float *bias_host,
+                              int ncls, const float *scale_dev, const float *shift_dev, float slope, int first_sample, const int32_t *mirrors_host,
+                              int n_mirrors, const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *agg2_dev,
+                              float *cnt_dev, const int32_t padded[3], const int32_t origin[3], void *stream) {
+    MI355_REQUIRE(feat_dev && weight_host && mirrors_host && patch && agg_dev && (agg2_dev || !m2) && padded && origin && first_sample >= 0,
+                  "%s: bad argument", name);
+    MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_F16, "unknown dtype %d", dtype);
+    MI355_REQUIRE(!scale_dev == !shift_dev, "scale and shift come together");
+    MI355_REQUIRE(!m2 || nonlin != MI355_NONLIN_IDENTITY, "%s: nonlin identity has no probabilities to take moments of", name);
+    MI355_REQUIRE(tile_in_grid(patch, padded, origin), "%s: the tile leaves the padded grid", name);
+    MI355_TRY(require_device());
+    DeviceAllocs mem;
+    HeadWeights hw;
+    MI355_TRY(head_weights_upload(mem, weight_host, bias_host, cin, ncls, &hw));
+    hipStream_t s = (hipStream_t)stream;
+    AggTile t;
+    AggGrid g;
+    MI355_TRY(agg_operands("head_aggregate", mirrors_host, n_mirrors, patch, nonlin, gauss_dev, agg_dev, agg2_dev, cnt_dev, padded, &t, &g));
+    return synced(head_aggregate(hw, feat_dev, dtype, first_sample, t, g, origin, s, feat_norm(scale_dev, shift_dev, slope)), s,
+                  m2 ? "head_aggregate m2" : "head_aggregate");
+}
+
+static int logits_aggregate_abi(const char *name, bool m2, const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host,
+                                int n_mirrors, const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *agg2_dev,
+                                float *cnt_dev, const int32_t padded[3], const int32_t origin[3], void *stream) {
+    MI355_REQUIRE(logits_dev && mirrors_host && patch && agg_dev && (agg2_dev || !m2) && padded && origin && first_sample >= 0, "%s: bad argument",
+                  name);
+    MI355_REQUIRE(!m2 || nonlin != MI355_NONLIN_IDENTITY, "%s: nonlin identity has no probabilities to take moments of", name);
+    MI355_REQUIRE(tile_in_grid(patch, padded, origin), "%s: the tile leaves the padded grid", name);
+    MI355_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    AggTile t;
+    AggGrid g;
+    MI355_TRY(agg_operands("logits_aggregate", mirrors_host, n_mirrors, patch, nonlin, gauss_dev, agg_dev, agg2_dev, cnt_dev, padded, &t, &g));
+    return synced(logits_aggregate(logits_dev, ncls, first_sample, t, g, origin, s), s, m2 ? "logits_aggregate m2" : "logits_aggregate");
+}
+
+static int logits_aggregate_tiles_abi(const char *name, bool m2, const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host,
+                                      int n_mirrors, const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *agg2_dev,
+                                      float *cnt_dev, const int32_t padded[3], const int32_t *origins, int n_tiles, void *stream) {
+    MI355_REQUIRE(logits_dev && mirrors_host && patch && agg_dev && (agg2_dev || !m2) && padded && origins && first_sample >= 0 && n_tiles >= 1,
+                  "%s: bad argument", name);
+    MI355_REQUIRE(!m2 || nonlin != MI355_NONLIN_IDENTITY, "%s: nonlin identity has no probabilities to take moments of", name);
+    for (int i = 0; i < n_tiles; ++i)
+        MI355_REQUIRE(tile_in_grid(patch, padded, origins + 3 * (size_t)i), "%s: tile %d leaves the padded grid", name, i);
+    MI355_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    AggTile t;
+    AggGrid g;
+    MI355_TRY(agg_operands("logits_aggregate_tiles", mirrors_host, n_mirrors, patch, nonlin, gauss_dev, agg_dev, agg2_dev, cnt_dev, padded, &t, &g));
+    return synced(logits_aggregate_tiles(logits_dev, ncls, first_sample, t, g, origins, n_tiles, s), s,
+                  m2 ? "logits_aggregate_tiles m2" : "logits_aggregate_tiles");
+}
+
 extern "C" int mi355_head_aggregate(const void *feat_dev, int dtype, int cin, const float *weight_host, const float *bias_host, int ncls,
                                     const float *scale_dev, const float *shift_dev, float slope, int first_sample, const int32_t *mirrors_host,
                                     int n_mirrors, const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *cnt_dev,
                                     const int32_t padded[3], const int32_t origin[3], void *stream) {
-    MI355_REQUIRE(feat_dev && weight_host && mirrors_host && patch && agg_dev && padded && origin && first_sample >= 0, "mi355_head_aggregate: bad argument");
-    MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_F16, "unknown dtype %d", dtype);
-    MI355_REQUIRE(!scale_dev == !shift_dev, "scale and shift come together");
-    MI355_REQUIRE(tile_in_grid(patch, padded, origin), "mi355_head_aggregate: the tile leaves the padded grid");
-    MI355_TRY(require_device());
-    DeviceAllocs mem;
-    HeadWeights hw;
-    MI355_TRY(head_weights_upload(mem, weight_host, bias_host, cin, ncls, &hw));
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<int> mirrors(mirrors_host, mirrors_host + std::max(n_mirrors, 0));
-    return synced(head_aggregate(hw, feat_dev, dtype, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev, agg_dev,
-                                 cnt_dev, padded[0], padded[1], padded[2], origin[0], origin[1], origin[2], s, feat_norm(scale_dev, shift_dev, slope)),
-                  s, "head_aggregate");
+    return head_aggregate_abi("mi355_head_aggregate", false, feat_dev, dtype, cin, weight_host, bias_host, ncls, scale_dev, shift_dev, slope, first_sample,
+                              mirrors_host, n_mirrors, patch, nonlin, gauss_dev, agg_dev, nullptr, cnt_dev, padded, origin, stream);
 }
-
-extern "C" int mi355_logits_aggregate(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
-                                      const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *cnt_dev,
-                                      const int32_t padded[3], const int32_t origin[3], void *stream) {
-    MI355_REQUIRE(logits_dev && mirrors_host && patch && agg_dev && padded && origin && first_sample >= 0, "mi355_logits_aggregate: bad argument");
-    MI355_REQUIRE(tile_in_grid(patch, padded, origin), "mi355_logits_aggregate: the tile leaves the padded grid");
-    MI355_TRY(require_device());
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<int> mirrors(mirrors_host, mirrors_host + std::max(n_mirrors, 0));
-    return synced(logits_aggregate(logits_dev, ncls, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev, agg_dev,
-                                   cnt_dev, padded[0], padded[1], padded[2], origin[0], origin[1], origin[2], s),
-                  s, "logits_aggregate");
-}
-
-extern "C" int mi355_logits_aggregate_tiles(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
-                                            const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *cnt_dev,
-                                            const int32_t padded[3], const int32_t *origins, int n_tiles, void *stream) {
-    MI355_REQUIRE(logits_dev && mirrors_host && patch && agg_dev && padded && origins && first_sample >= 0 && n_tiles >= 1,
-                  "mi355_logits_aggregate_tiles: bad argument");
-    for (int i = 0; i < n_tiles; ++i)
-        MI355_REQUIRE(tile_in_grid(patch, padded, origins + 3 * (size_t)i), "mi355_logits_aggregate_tiles: tile %d leaves the padded grid", i);
-    MI355_TRY(require_device());
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<int> mirrors(mirrors_host, mirrors_host + std::max(n_mirrors, 0));
-    std::vector<int> org(origins, origins + 3 * (size_t)n_tiles);
-    return synced(logits_aggregate_tiles(logits_dev, ncls, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev,
-                                         agg_dev, cnt_dev, padded[0], padded[1], padded[2], org.data(), n_tiles, s),
-                  s, "logits_aggregate_tiles");
-}
-
-// ---- the same three with the second moment kept (agg2_dev, laid out as agg_dev): agg_dev / cnt_dev come out as from the plain calls
 extern "C" int mi355_head_aggregate_m2(const void *feat_dev, int dtype, int cin, const float *weight_host, const float *bias_host, int ncls,
                                        const float *scale_dev, const float *shift_dev, float slope, int first_sample, const int32_t *mirrors_host,
                                        int n_mirrors, const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *agg2_dev,
                                        float *cnt_dev, const int32_t padded[3], const int32_t origin[3], void *stream) {
-    MI355_REQUIRE(feat_dev && weight_host && mirrors_host && patch && agg_dev && agg2_dev && padded && origin && first_sample >= 0,
-                  "mi355_head_aggregate_m2: bad argument");
-    MI355_REQUIRE(dtype == MI355_F32 || dtype == MI355_F16, "unknown dtype %d", dtype);
-    MI355_REQUIRE(!scale_dev == !shift_dev, "scale and shift come together");
-    MI355_REQUIRE(nonlin != MI355_NONLIN_IDENTITY, "mi355_head_aggregate_m2: nonlin identity has no probabilities to take moments of");
-    MI355_REQUIRE(tile_in_grid(patch, padded, origin), "mi355_head_aggregate_m2: the tile leaves the padded grid");
-    MI355_TRY(require_device());
-    DeviceAllocs mem;
-    HeadWeights hw;
-    MI355_TRY(head_weights_upload(mem, weight_host, bias_host, cin, ncls, &hw));
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<int> mirrors(mirrors_host, mirrors_host + std::max(n_mirrors, 0));
-    return synced(head_aggregate(hw, feat_dev, dtype, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev, agg_dev,
-                                 cnt_dev, padded[0], padded[1], padded[2], origin[0], origin[1], origin[2], s, feat_norm(scale_dev, shift_dev, slope),
-                                 agg2_dev),
-                  s, "head_aggregate m2");
+    return head_aggregate_abi("mi355_head_aggregate_m2", true, feat_dev, dtype, cin, weight_host, bias_host, ncls, scale_dev, shift_dev, slope,
+                              first_sample, mirrors_host, n_mirrors, patch, nonlin, gauss_dev, agg_dev, agg2_dev, cnt_dev, padded, origin, stream);
 }
-
+extern "C" int mi355_logits_aggregate(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
+                                      const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *cnt_dev,
+                                      const int32_t padded[3], const int32_t origin[3], void *stream) {
+    return logits_aggregate_abi("mi355_logits_aggregate", false, logits_dev, ncls, first_sample, mirrors_host, n_mirrors, patch, nonlin, gauss_dev, agg_dev,
+                                nullptr, cnt_dev, padded, origin, stream);
+}
 extern "C" int mi355_logits_aggregate_m2(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
                                          const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *agg2_dev, float *cnt_dev,
                                          const int32_t padded[3], const int32_t origin[3], void *stream) {
-    MI355_REQUIRE(logits_dev && mirrors_host && patch && agg_dev && agg2_dev && padded && origin && first_sample >= 0,
-                  "mi355_logits_aggregate_m2: bad argument");
-    MI355_REQUIRE(nonlin != MI355_NONLIN_IDENTITY, "mi355_logits_aggregate_m2: nonlin identity has no probabilities to take moments of");
-    MI355_REQUIRE(tile_in_grid(patch, padded, origin), "mi355_logits_aggregate_m2: the tile leaves the padded grid");
-    MI355_TRY(require_device());
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<int> mirrors(mirrors_host, mirrors_host + std::max(n_mirrors, 0));
-    return synced(logits_aggregate(logits_dev, ncls, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev, agg_dev,
-                                   cnt_dev, padded[0], padded[1], padded[2], origin[0], origin[1], origin[2], s, agg2_dev),
-                  s, "logits_aggregate m2");
+    return logits_aggregate_abi("mi355_logits_aggregate_m2", true, logits_dev, ncls, first_sample, mirrors_host, n_mirrors, patch, nonlin, gauss_dev,
+                                agg_dev, agg2_dev, cnt_dev, padded, origin, stream);
 }
-
+extern "C" int mi355_logits_aggregate_tiles(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
+                                            const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *cnt_dev,
+                                            const int32_t padded[3], const int32_t *origins, int n_tiles, void *stream) {
+    return logits_aggregate_tiles_abi("mi355_logits_aggregate_tiles", false, logits_dev, ncls, first_sample, mirrors_host, n_mirrors, patch, nonlin,
+                                      gauss_dev, agg_dev, nullptr, cnt_dev, padded, origins, n_tiles, stream);
+}
 extern "C" int mi355_logits_aggregate_tiles_m2(const float *logits_dev, int ncls, int first_sample, const int32_t *mirrors_host, int n_mirrors,
                                                const int32_t patch[3], int nonlin, const float *gauss_dev, float *agg_dev, float *agg2_dev,
                                                float *cnt_dev, const int32_t padded[3], const int32_t *origins, int n_tiles, void *stream) {
-    MI355_REQUIRE(logits_dev && mirrors_host && patch && agg_dev && agg2_dev && padded && origins && first_sample >= 0 && n_tiles >= 1,
-                  "mi355_logits_aggregate_tiles_m2: bad argument");
-    MI355_REQUIRE(nonlin != MI355_NONLIN_IDENTITY, "mi355_logits_aggregate_tiles_m2: nonlin identity has no probabilities to take moments of");
-    for (int i = 0; i < n_tiles; ++i)
-        MI355_REQUIRE(tile_in_grid(patch, padded, origins + 3 * (size_t)i), "mi355_logits_aggregate_tiles_m2: tile %d leaves the padded grid", i);
-    MI355_TRY(require_device());
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<int> mirrors(mirrors_host, mirrors_host + std::max(n_mirrors, 0));
-    std::vector<int> org(origins, origins + 3 * (size_t)n_tiles);
-    return synced(logits_aggregate_tiles(logits_dev, ncls, first_sample, mirrors.data(), n_mirrors, patch[0], patch[1], patch[2], nonlin, gauss_dev,
-                                         agg_dev, cnt_dev, padded[0], padded[1], padded[2], org.data(), n_tiles, s, agg2_dev),
-                  s, "logits_aggregate_tiles m2");
+    return logits_aggregate_tiles_abi("mi355_logits_aggregate_tiles_m2", true, logits_dev, ncls, first_sample, mirrors_host, n_mirrors, patch, nonlin,
+                                      gauss_dev, agg_dev, agg2_dev, cnt_dev, padded, origins, n_tiles, stream);
 }
 
 extern "C" int mi355_cnt_add_tile(const float *gauss_dev, const int32_t patch[3], float *cnt_dev, const int32_t padded[3],
@@ -563,70 +564,46 @@ extern "C" int mi355_cnt_add_tile(const float *gauss_dev, const int32_t patch[3]
     MI355_REQUIRE(tile_in_grid(patch, padded, origin), "mi355_cnt_add_tile: the tile leaves the padded grid");
     MI355_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
-    return synced(cnt_add_tile(gauss_dev, patch[0], patch[1], patch[2], cnt_dev, padded[1], padded[2], origin[0], origin[1], origin[2], s), s,
-                  "cnt_add_tile");
+    const AggTile t = {{patch[0], patch[1], patch[2]}, MI355_NONLIN_IDENTITY, gauss_dev, {}};
+    const AggGrid g = {nullptr, nullptr, cnt_dev, {padded[0], padded[1], padded[2]}};
+    return synced(cnt_add_tile(t, g, origin, s), s, "cnt_add_tile");
 }
 
-static int stage0_gather_abi(const mi355_stage0_gather_args *a, void *stream, bool shells_only) {
-    MI355_REQUIRE(a && a->wv_dev && a->out_dev && a->channels > 0 && a->channels % 4 == 0, "mi355_stage0_gather: bad argument");
-    MI355_REQUIRE(a->n_samples > 0 && a->n_samples <= S0_MAX_SAMPLES, "mi355_stage0_gather: %d samples (max %d)", a->n_samples, S0_MAX_SAMPLES);
+// The four stage-0 gather entry points.  a: the samples and the first tensor; m (null: the slabs have the tile's extent across their
+// axis, stage0_gather_dense, and there is one tensor): the merged-slab geometry and the second tensor; boxes (null: the samples are the
+// tiles): the sub-box form; by_box: the dense gather runs over the boxes; name: the entry point, for its messages.
+static int stage0_gather_general(const char *name, const mi355_stage0_gather_args *a, const mi355_stage0_gather_merged_args *m,
+                                 const mi355_stage0_gather_boxes_args *boxes, int shells_only, bool by_box, void *stream) {
+    MI355_REQUIRE(a && a->wv_dev && a->out_dev && a->channels > 0 && a->channels % 4 == 0, "%s: bad argument", name);
+    MI355_REQUIRE(a->n_samples > 0 && a->n_samples <= S0_MAX_SAMPLES, "%s: %d samples (max %d)", name, a->n_samples, S0_MAX_SAMPLES);
+    const bool second = m && m->out2_dev;
+    MI355_REQUIRE(!second || (m->wv2_dev && m->channels2 > 0 && m->channels2 % 4 == 0), "%s: bad second tensor", name);
     MI355_TRY(require_device());
     S0GatherArgs ga;
     memset(&ga, 0, sizeof(ga));
     ga.wv = a->wv_dev; ga.out = a->out_dev;
     for (int k = 0; k < 3; ++k) { ga.slab[k] = a->slab_dev[k]; ga.P[k] = a->patch[k]; ga.Ve[k] = a->volume[k]; ga.t[k] = a->slab_thickness[k]; }
     ga.r = a->r; ga.C4 = a->channels / 4;
-    stage0_gather_dense(&ga);
-    for (int i = 0; i < a->n_samples; ++i) {
-        S0Sample &sm = ga.smp[i];
-        sm.wv = a->samples[i].wv;
-        MI355_REQUIRE(sm.wv >= 0, "mi355_stage0_gather: sample %d: whole-volume index %d", i, sm.wv);
-        for (int k = 0; k < 3; ++k) sm.org[k] = a->samples[i].origin[k];
-        for (int f = 0; f < 6; ++f) {
-            sm.slab[f] = a->samples[i].slab[f];
-            MI355_REQUIRE(sm.slab[f] < 0 || a->slab_dev[f >> 1], "mi355_stage0_gather: sample %d: face %d without a slab tensor", i, f);
-        }
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (shells_only) return synced(stage0_gather_shells(ga, a->n_samples, 0, s), s, "stage0_gather_shells");
-    return synced(stage0_gather(ga, a->n_samples, s), s, "stage0_gather");
-}
-extern "C" int mi355_stage0_gather(const mi355_stage0_gather_args *a, void *stream) { return stage0_gather_abi(a, stream, false); }
-extern "C" int mi355_stage0_gather_shells(const mi355_stage0_gather_args *a, void *stream) { return stage0_gather_abi(a, stream, true); }
-
-// boxes (null: the samples are the tiles): the sub-box form; by_box: the dense gather runs over the boxes
-static int stage0_gather_general(const mi355_stage0_gather_merged_args *m, const mi355_stage0_gather_boxes_args *boxes, int shells_only, bool by_box,
-                                 void *stream) {
-    MI355_REQUIRE(m, "mi355_stage0_gather_merged: bad argument");
-    const mi355_stage0_gather_args *a = &m->base;
-    MI355_REQUIRE(a->wv_dev && a->out_dev && a->channels > 0 && a->channels % 4 == 0, "mi355_stage0_gather_merged: bad argument");
-    MI355_REQUIRE(a->n_samples > 0 && a->n_samples <= S0_MAX_SAMPLES, "mi355_stage0_gather_merged: %d samples (max %d)", a->n_samples, S0_MAX_SAMPLES);
-    MI355_REQUIRE(!m->out2_dev || (m->wv2_dev && m->channels2 > 0 && m->channels2 % 4 == 0), "mi355_stage0_gather_merged: bad second tensor");
-    MI355_TRY(require_device());
-    S0GatherArgs ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.wv = a->wv_dev; ga.out = a->out_dev;
-    for (int k = 0; k < 3; ++k) { ga.slab[k] = a->slab_dev[k]; ga.P[k] = a->patch[k]; ga.Ve[k] = a->volume[k]; ga.t[k] = a->slab_thickness[k]; }
-    ga.r = a->r; ga.C4 = a->channels / 4;
-    if (m->out2_dev) {
+    if (second) {
         ga.wv2 = m->wv2_dev; ga.out2 = m->out2_dev; ga.r2 = m->r2; ga.C42 = m->channels2 / 4;
         for (int k = 0; k < 3; ++k) ga.slab2[k] = m->slab2_dev[k];
     }
-    for (int ax = 0; ax < 3; ++ax)
+    if (!m) stage0_gather_dense(&ga);
+    for (int ax = 0; m && ax < 3; ++ax)
         for (int k = 0; k < 3; ++k) {
             ga.D[ax][k] = m->slab_shape[ax][k];
-            MI355_REQUIRE(m->spans_volume[ax][k] == 0 || m->spans_volume[ax][k] == 1, "mi355_stage0_gather_merged: spans_volume[%d][%d]", ax, k);
+            MI355_REQUIRE(m->spans_volume[ax][k] == 0 || m->spans_volume[ax][k] == 1, "%s: spans_volume[%d][%d]", name, ax, k);
             ga.so[ax][k] = m->spans_volume[ax][k];
         }
     for (int i = 0; i < a->n_samples; ++i) {
         S0Sample &sm = ga.smp[i];
         sm.wv = a->samples[i].wv;
-        MI355_REQUIRE(sm.wv >= 0, "mi355_stage0_gather_merged: sample %d: whole-volume index %d", i, sm.wv);
+        MI355_REQUIRE(sm.wv >= 0, "%s: sample %d: whole-volume index %d", name, i, sm.wv);
         for (int k = 0; k < 3; ++k) sm.org[k] = a->samples[i].origin[k];
         for (int f = 0; f < 6; ++f) {
             sm.slab[f] = a->samples[i].slab[f];
-            MI355_REQUIRE(sm.slab[f] < 0 || (a->slab_dev[f >> 1] && (!m->out2_dev || m->slab2_dev[f >> 1])),
-                          "mi355_stage0_gather_merged: sample %d: face %d without a slab tensor", i, f);
+            MI355_REQUIRE(sm.slab[f] < 0 || (a->slab_dev[f >> 1] && (!second || m->slab2_dev[f >> 1])), "%s: sample %d: face %d without a slab tensor",
+                          name, i, f);
         }
     }
     if (boxes)
@@ -640,12 +617,19 @@ static int stage0_gather_general(const mi355_stage0_gather_merged_args *m, const
     if (ga.out2) MI355_TRY(stage0_gather_shells(ga, a->n_samples, 1, s));
     return synced(MI355_OK, s, "stage0_gather_shells");
 }
+extern "C" int mi355_stage0_gather(const mi355_stage0_gather_args *a, void *stream) {
+    return stage0_gather_general("mi355_stage0_gather", a, nullptr, nullptr, 0, false, stream);
+}
+extern "C" int mi355_stage0_gather_shells(const mi355_stage0_gather_args *a, void *stream) {
+    return stage0_gather_general("mi355_stage0_gather", a, nullptr, nullptr, 1, false, stream);
+}
 extern "C" int mi355_stage0_gather_merged(const mi355_stage0_gather_merged_args *m, int shells_only, void *stream) {
-    return stage0_gather_general(m, nullptr, shells_only, false, stream);
+    MI355_REQUIRE(m, "mi355_stage0_gather_merged: bad argument");
+    return stage0_gather_general("mi355_stage0_gather_merged", &m->base, m, nullptr, shells_only, false, stream);
 }
 extern "C" int mi355_stage0_gather_boxes(const mi355_stage0_gather_boxes_args *b, int shells_only, int by_box, void *stream) {
     MI355_REQUIRE(b && b->tile[0] > 0 && b->tile[1] > 0 && b->tile[2] > 0, "mi355_stage0_gather_boxes: bad argument");
-    return stage0_gather_general(&b->merged, b, shells_only, by_box != 0, stream);
+    return stage0_gather_general("mi355_stage0_gather_merged", &b->merged.base, &b->merged, b, shells_only, by_box != 0, stream);
 }
 
 extern "C" int mi355_stage0_mask(float *x_dev, int n, const int32_t volume[3], const int32_t keep[3], int c, void *stream) {

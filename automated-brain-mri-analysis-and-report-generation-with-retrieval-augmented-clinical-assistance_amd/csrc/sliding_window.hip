@@ -441,6 +441,10 @@ static int sw_accumulate(mi355_unet *net, const SwVolume &v, const mi355_sw_opts
     const int nm = (int)g.mirrors.size();
     const bool use_gauss = o.use_gaussian && g.tiles.size() > 1;
     if (use_gauss) MI355_TRY(ensure_gaussian(net, g.P));
+    // the aggregation's operands, the same for every tile (cnt: for ALL tiles when every rank adds its own, else cnt_add_tile has)
+    AggTile tile = {{g.P[0], g.P[1], g.P[2]}, o.nonlin, use_gauss ? net->gauss_dev : nullptr, {}};
+    MI355_TRY(make_mirrors("sliding window", g.mirrors.data(), nm, &tile.ml));
+    const AggGrid grid = {agg, agg2, (cnt && world == 1) ? cnt : nullptr, {g.Zp[0], g.Zp[1], g.Zp[2]}};
     std::vector<int> mine;
     for (size_t t = 0; t < g.tiles.size(); ++t) if ((int)((first_item + (long)t) % world) == rank) mine.push_back((int)t);
     int bt = sw_batch_tiles(net->dtype, o.batch_tiles, nm);
@@ -518,9 +522,7 @@ static int sw_accumulate(mi355_unet *net, const SwVolume &v, const mi355_sw_opts
             const double pv = (double)g.P[0] * g.P[1] * g.P[2], box = (double)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
             ProfScope ps(net, s, agg2 ? "logits_aggregate_tiles_kernel m2" : "logits_aggregate_tiles_kernel", 0.0,
                          4.0 * (nb * pv * (nm * net->num_classes + 1.0) + box * (2.0 * net->num_classes + 2.0) + (agg2 ? box * 2.0 * net->num_classes : 0.0)));
-            MI355_TRY(logits_aggregate_tiles((const float *)feat, net->num_classes, 0, g.mirrors.data(), nm, g.P[0], g.P[1], g.P[2], o.nonlin,
-                                             use_gauss ? net->gauss_dev : nullptr, agg, (cnt && world == 1) ? cnt : nullptr, g.Zp[0], g.Zp[1],
-                                             g.Zp[2], origins.data(), nb, s, agg2));
+            MI355_TRY(logits_aggregate_tiles((const float *)feat, net->num_classes, 0, tile, grid, origins.data(), nb, s));
             continue;
         }
         for (int i = 0; i < nb; ++i) {
@@ -528,9 +530,8 @@ static int sw_accumulate(mi355_unet *net, const SwVolume &v, const mi355_sw_opts
             const double pv = (double)g.P[0] * g.P[1] * g.P[2];
             ProfScope ps(net, s, agg2 ? "head_aggregate_kernel m2" : "head_aggregate_kernel", 2.0 * pv * nm * fc * net->num_classes,
                          pv * ((net->dtype == MI355_F16 ? 2.0 : 4.0) * nm * fc + 4.0 * (2.0 * net->num_classes + 3.0 + (agg2 ? 2.0 * net->num_classes : 0.0))));
-            MI355_TRY(head_aggregate(net->head, feat, net->dtype, i * nm, g.mirrors.data(), nm, g.P[0], g.P[1], g.P[2], o.nonlin,
-                                     use_gauss ? net->gauss_dev : nullptr, agg, (cnt && world == 1) ? cnt : nullptr,
-                                     g.Zp[0], g.Zp[1], g.Zp[2], td.z0, td.y0, td.x0, s, head_norm, agg2));
+            const int org[3] = {td.z0, td.y0, td.x0};
+            MI355_TRY(head_aggregate(net->head, feat, net->dtype, i * nm, tile, grid, org, s, head_norm));
         }
     }
     return MI355_OK;
@@ -563,9 +564,12 @@ static int sw_partial_folds(const mi355_unet_t *nets, int n_nets, const float *v
         // full normaliser of ONE fold on every rank: cnt[tile] += gaussian for ALL tiles, in tile order (no exchange needed)
         const bool use_gauss = opts->use_gaussian && g.tiles.size() > 1;
         if (use_gauss) MI355_TRY(ensure_gaussian(nets[0], g.P));
-        for (const TileDesc &td : g.tiles)
-            MI355_TRY(cnt_add_tile(use_gauss ? nets[0]->gauss_dev : nullptr, g.P[0], g.P[1], g.P[2], cnt_dev, g.Zp[1], g.Zp[2],
-                                   td.z0, td.y0, td.x0, s));
+        const AggTile tile = {{g.P[0], g.P[1], g.P[2]}, opts->nonlin, use_gauss ? nets[0]->gauss_dev : nullptr, {}};
+        const AggGrid grid = {agg_dev, agg2_dev, cnt_dev, {g.Zp[0], g.Zp[1], g.Zp[2]}};
+        for (const TileDesc &td : g.tiles) {
+            const int org[3] = {td.z0, td.y0, td.x0};
+            MI355_TRY(cnt_add_tile(tile, grid, org, s));
+        }
     }
     // (world == 1: the first fold's aggregation kernels add the normaliser themselves, exactly as mi355_sw_predict does)
     for (int f = 0; f < n_nets; ++f)
@@ -595,13 +599,21 @@ extern "C" int mi355_sw_partial(mi355_unet_t net, const float *vol_dev, int Z, i
     return mi355_sw_partial_folds(&net, 1, vol_dev, Z, Y, X, opts, rank, world, agg_dev, cnt_dev, stream);
 }
 
+// The grid a finish call reads (nothing here writes it), laid out as make_geom does: max(volume, patch) voxels, the volume centred.
+static AggGrid finished_grid(const float *agg, const float *agg2, const float *cnt, const int vol[3], const int32_t patch[3], int pad[3]) {
+    AggGrid grid = {(float *)agg, (float *)agg2, (float *)cnt, {}};
+    for (int k = 0; k < 3; ++k) { grid.Zp[k] = std::max(vol[k], (int)patch[k]); pad[k] = (grid.Zp[k] - vol[k]) / 2; }
+    return grid;
+}
+
 extern "C" int mi355_sw_finish_folds(const float *agg_dev, const float *cnt_dev, int num_classes, int Z, int Y, int X,
                                      const int32_t patch[3], int n_folds, float *probs_dev, void *stream) {
     MI355_REQUIRE(agg_dev && cnt_dev && probs_dev && patch && n_folds >= 1, "bad argument");
     MI355_TRY(bind_device());
-    const int Zp = std::max(Z, patch[0]), Yp = std::max(Y, patch[1]), Xp = std::max(X, patch[2]);
-    MI355_TRY(finish_probs(agg_dev, cnt_dev, num_classes, Z, Y, X, Zp, Yp, Xp, (Zp - Z) / 2, (Yp - Y) / 2, (Xp - X) / 2,
-                           probs_dev, 0, (hipStream_t)stream));
+    const int vol[3] = {Z, Y, X};
+    int pad[3];
+    const AggGrid grid = finished_grid(agg_dev, nullptr, cnt_dev, vol, patch, pad);
+    MI355_TRY(finish_probs(grid, num_classes, vol, pad, probs_dev, 0, (hipStream_t)stream));
     if (n_folds > 1) MI355_TRY(scale_inplace(probs_dev, (int64_t)num_classes * Z * Y * X, (float)n_folds, (hipStream_t)stream));
     return MI355_OK;
 }
@@ -611,9 +623,10 @@ extern "C" int mi355_sw_finish_moments(const float *agg_dev, const float *agg2_d
     MI355_REQUIRE(agg_dev && agg2_dev && cnt_dev && mean_dev && m2_dev && patch && n_folds >= 1 && num_classes >= 1 && Z >= 1 && Y >= 1 && X >= 1,
                   "mi355_sw_finish_moments: bad argument");
     MI355_TRY(bind_device());
-    const int Zp = std::max(Z, patch[0]), Yp = std::max(Y, patch[1]), Xp = std::max(X, patch[2]);
-    return finish_moments(agg_dev, agg2_dev, cnt_dev, num_classes, Z, Y, X, Zp, Yp, Xp, (Zp - Z) / 2, (Yp - Y) / 2, (Xp - X) / 2, n_folds, mean_dev, m2_dev,
-                          (hipStream_t)stream);
+    const int vol[3] = {Z, Y, X};
+    int pad[3];
+    const AggGrid grid = finished_grid(agg_dev, agg2_dev, cnt_dev, vol, patch, pad);
+    return finish_moments(grid, num_classes, vol, pad, n_folds, mean_dev, m2_dev, (hipStream_t)stream);
 }
 
 extern "C" int mi355_sw_finish(const float *agg_dev, const float *cnt_dev, int num_classes, int Z, int Y, int X,
@@ -635,6 +648,8 @@ extern "C" int mi355_sw_predict(const mi355_unet_t *nets, int n_nets, const floa
     void *scratch = nullptr;
     MI355_TRY(device_scratch(SCR_SW_AGG, s, ZYXp * (size_t)(C + 1) * sizeof(float), &scratch));
     float *agg = (float *)scratch, *cnt = agg + ZYXp * C;
+    const AggGrid grid = {agg, nullptr, cnt, {g.Zp[0], g.Zp[1], g.Zp[2]}};
+    const int vol[3] = {Z, Y, X};
     int rc = MI355_OK;
     for (int f = 0; f < n_nets && rc == MI355_OK; ++f) {
         if (nets[f]->num_classes != C) { set_error("fold %d has %d classes, fold 0 has %d", f, nets[f]->num_classes, C); rc = MI355_ERR_INVALID; break; }
@@ -642,8 +657,7 @@ extern "C" int mi355_sw_predict(const mi355_unet_t *nets, int n_nets, const floa
             hipMemsetAsync(cnt, 0, ZYXp * sizeof(float), s) != hipSuccess) { set_error("memset failed"); rc = MI355_ERR_HIP; break; }
         rc = sw_accumulate(nets[f], SwVolume{vol_dev, Z, Y, X}, *opts, g, 0, 1, agg, cnt, s);
         if (rc == MI355_OK)
-            rc = finish_probs(agg, cnt, C, Z, Y, X, g.Zp[0], g.Zp[1], g.Zp[2], g.pad_lo[0], g.pad_lo[1], g.pad_lo[2],
-                              probs_dev, f > 0, s);
+            rc = finish_probs(grid, C, vol, g.pad_lo, probs_dev, f > 0, s);
     }
     // fold mean: np.mean(list_of_fp32_arrays, axis=0) = fp32 running sum in list order, one divide
     if (rc == MI355_OK && n_nets > 1) rc = scale_inplace(probs_dev, (int64_t)C * Z * Y * X, (float)n_nets, s);

@@ -1,4 +1,4 @@
-// Ensemble uncertainty from the two moments the sliding window keeps (elementwise.hip, the M2 aggregation kernels): per-voxel
+// Ensemble uncertainty from the two moments the sliding window keeps (aggregate.hip, the M2 aggregation kernels): per-voxel
 // standard deviation and entropy maps, and the per-channel counts and sums a region summary is built from.  The reference has no
 // counterpart: its confidence (feature_extraction/step5_quality.py:457-500) is a table of literals that depend on nothing.
 #include <cmath>

@@ -3,7 +3,11 @@
 //   unet.hip            the network object, the arena plan, run_block / forward_features, create / destroy / forward / profile
 //   sw_share_plan.hip   pure: tile geometry, what overlapping tiles share as one plan per window, the geometry dry runs
 //   sliding_window.hip  the device side of that plan: the shared stage 0 and level 1 passes, sw_accumulate, mi355_sw_*
-//   single_op.hip       the single-op entry points the tests drive, mi355_conv3d_plan, the wrappers around elementwise.hip
+//   single_op.hip       the single-op entry points the tests drive, mi355_conv3d_plan, the wrappers around the three files below
+// and, behind kernels.h, the kernels around the convolutions by role:
+//   elementwise.hip     norm finalise / apply, tile extraction, layout conversions, export / ensemble / z-score entry points
+//   stage0_gather.hip   the shared stage 0's gathers (row, box, shells), stage0_view_make, stage0_mask
+//   aggregate.hip       the segmentation head, the sliding-window aggregation over one tile term, the normaliser, the finish
 // Types and the few functions that cross those files; a function used in one file is static there.
 #pragma once
 #include <array>

@@ -664,62 +664,6 @@ def _tile_operands(agg, cnt, gauss, ncls, patch, origin, name):
     return gauss, padded, pv
 
 
-def head_aggregate_(feat, weight, bias, mirrors, patch, nonlin, agg, cnt, origin, gauss=None, first_sample=0, scale=None, shift=None,
-                    slope=1.0):
-    """``mi355_head_aggregate``: one tile into agg [ncls, Zp, Yp, Xp] / cnt [Zp, Yp, Xp] (CUDA fp32, in place; cnt may be None).
-    feat: every sample of the forward ([S, PV, C] fp32 or blocked fp16), of which first_sample .. + len(mirrors) - 1 are this tile's;
-    mirrors: masks, bit0 z; nonlin "identity" | "sigmoid" | "softmax"; gauss CUDA fp32 [patch] or None."""
-    f16, n, v, c = _feat_dims(feat)
-    weight, bias = _head_operands(weight, bias, c)
-    mirrors = [int(m) for m in mirrors]
-    gauss, padded, pv = _tile_operands(agg, cnt, gauss, weight.shape[0], patch, origin, "head_aggregate_")
-    if v != pv or first_sample < 0 or first_sample + len(mirrors) > n:
-        raise ValueError("head_aggregate_: feat does not hold the tile's samples")
-    scale, shift = _f32(scale, "scale", n * c), _f32(shift, "shift", n * c)
-    from .predictor import NONLIN
-    _lib.check(_lib.load().mi355_head_aggregate(feat.data_ptr(), int(f16), c, _lib.fptr(weight), _lib.fptr(bias), weight.shape[0], _ptr(scale),
-                                                _ptr(shift), float(slope), int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
-                                                len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss), agg.data_ptr(), _ptr(cnt), _i3(padded),
-                                                _i3(origin), stream_of(feat)), "mi355_head_aggregate")
-
-
-def logits_aggregate_(logits, mirrors, patch, nonlin, agg, cnt, origin, gauss=None, first_sample=0):
-    """``mi355_logits_aggregate``: as ``head_aggregate_`` from logits CUDA fp32 [S, ncls, PV]."""
-    import torch
-    logits = _require_cuda(logits, torch.float32, "logits")
-    n, ncls, v = logits.shape
-    mirrors = [int(m) for m in mirrors]
-    gauss, padded, pv = _tile_operands(agg, cnt, gauss, ncls, patch, origin, "logits_aggregate_")
-    if v != pv or first_sample < 0 or first_sample + len(mirrors) > n:
-        raise ValueError("logits_aggregate_: logits do not hold the tile's samples")
-    from .predictor import NONLIN
-    _lib.check(_lib.load().mi355_logits_aggregate(logits.data_ptr(), ncls, int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
-                                                  len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss), agg.data_ptr(), _ptr(cnt), _i3(padded),
-                                                  _i3(origin), stream_of(logits)), "mi355_logits_aggregate")
-
-
-def logits_aggregate_tiles_(logits, mirrors, patch, nonlin, agg, cnt, origins, gauss=None, first_sample=0):
-    """``mi355_logits_aggregate_tiles``: the tiles at ``origins`` (tile i: samples first_sample + i * len(mirrors) ..) in one launch,
-    bit-identical to ``logits_aggregate_`` tile by tile in that order."""
-    import torch
-    logits = _require_cuda(logits, torch.float32, "logits")
-    n, ncls, v = logits.shape
-    mirrors = [int(m) for m in mirrors]
-    origins = [[int(k) for k in o] for o in origins]
-    if not origins:
-        raise ValueError("logits_aggregate_tiles_: no tile")
-    for o in origins:
-        gauss_dev, padded, pv = _tile_operands(agg, cnt, gauss, ncls, patch, o, "logits_aggregate_tiles_")
-    if v != pv or first_sample < 0 or first_sample + len(origins) * len(mirrors) > n:
-        raise ValueError("logits_aggregate_tiles_: logits do not hold the tiles' samples")
-    flat = [k for o in origins for k in o]
-    from .predictor import NONLIN
-    _lib.check(_lib.load().mi355_logits_aggregate_tiles(logits.data_ptr(), ncls, int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
-                                                        len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss_dev), agg.data_ptr(), _ptr(cnt),
-                                                        _i3(padded), (C.c_int32 * len(flat))(*flat), len(origins), stream_of(logits)),
-               "mi355_logits_aggregate_tiles")
-
-
 def _agg2_operand(agg, agg2, name):
     import torch
     if agg2 is None or not agg2.is_cuda or agg2.dtype != torch.float32 or not agg2.is_contiguous() or agg2.shape != agg.shape:
@@ -729,62 +673,100 @@ def _agg2_operand(agg, agg2, name):
     return agg2
 
 
-def head_aggregate_m2_(feat, weight, bias, mirrors, patch, nonlin, agg, agg2, cnt, origin, gauss=None, first_sample=0, scale=None, shift=None,
-                       slope=1.0):
-    """``mi355_head_aggregate_m2``: ``head_aggregate_`` that also adds the tile's second moment (mean over the mirrors of p^2, times
-    gauss) into agg2 [ncls, Zp, Yp, Xp]; agg and cnt receive what the plain call gives them, bit for bit.  "identity" is refused."""
+# The aggregation wrappers and their _m2 twins: one implementation per pair.  m2: the call is the twin - it takes agg2 and calls the
+# entry point's _m2 twin, which has agg2 behind agg in its arguments; the public function's name, for the messages, follows from it.
+def _aggregate_call(symbol, m2, src, head, mirrors, patch, nonlin, gauss, agg, agg2, cnt, padded, where):
+    from .predictor import NONLIN
+    symbol += "_m2" if m2 else ""
+    moments = [agg2.data_ptr()] if m2 else []
+    _lib.check(getattr(_lib.load(), symbol)(*head, (C.c_int32 * max(len(mirrors), 1))(*mirrors), len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss),
+                                            agg.data_ptr(), *moments, _ptr(cnt), _i3(padded), *where, stream_of(src)), symbol)
+
+
+def _head_aggregate(m2, feat, weight, bias, mirrors, patch, nonlin, agg, agg2, cnt, origin, gauss, first_sample, scale, shift, slope):
+    name = "head_aggregate_m2_" if m2 else "head_aggregate_"
     f16, n, v, c = _feat_dims(feat)
     weight, bias = _head_operands(weight, bias, c)
     mirrors = [int(m) for m in mirrors]
-    gauss, padded, pv = _tile_operands(agg, cnt, gauss, weight.shape[0], patch, origin, "head_aggregate_m2_")
-    agg2 = _agg2_operand(agg, agg2, "head_aggregate_m2_")
+    gauss, padded, pv = _tile_operands(agg, cnt, gauss, weight.shape[0], patch, origin, name)
+    if m2:
+        agg2 = _agg2_operand(agg, agg2, name)
     if v != pv or first_sample < 0 or first_sample + len(mirrors) > n:
-        raise ValueError("head_aggregate_m2_: feat does not hold the tile's samples")
+        raise ValueError(f"{name}: feat does not hold the tile's samples")
     scale, shift = _f32(scale, "scale", n * c), _f32(shift, "shift", n * c)
-    from .predictor import NONLIN
-    _lib.check(_lib.load().mi355_head_aggregate_m2(feat.data_ptr(), int(f16), c, _lib.fptr(weight), _lib.fptr(bias), weight.shape[0], _ptr(scale),
-                                                   _ptr(shift), float(slope), int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
-                                                   len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss), agg.data_ptr(), agg2.data_ptr(),
-                                                   _ptr(cnt), _i3(padded), _i3(origin), stream_of(feat)), "mi355_head_aggregate_m2")
+    head = (feat.data_ptr(), int(f16), c, _lib.fptr(weight), _lib.fptr(bias), weight.shape[0], _ptr(scale), _ptr(shift), float(slope), int(first_sample))
+    _aggregate_call("mi355_head_aggregate", m2, feat, head, mirrors, patch, nonlin, gauss, agg, agg2, cnt, padded, (_i3(origin),))
 
 
-def logits_aggregate_m2_(logits, mirrors, patch, nonlin, agg, agg2, cnt, origin, gauss=None, first_sample=0):
-    """``mi355_logits_aggregate_m2``: as ``head_aggregate_m2_`` from logits CUDA fp32 [S, ncls, PV]."""
+def _logits_aggregate(m2, logits, mirrors, patch, nonlin, agg, agg2, cnt, origin, gauss, first_sample):
     import torch
+    name = "logits_aggregate_m2_" if m2 else "logits_aggregate_"
     logits = _require_cuda(logits, torch.float32, "logits")
     n, ncls, v = logits.shape
     mirrors = [int(m) for m in mirrors]
-    gauss, padded, pv = _tile_operands(agg, cnt, gauss, ncls, patch, origin, "logits_aggregate_m2_")
-    agg2 = _agg2_operand(agg, agg2, "logits_aggregate_m2_")
+    gauss, padded, pv = _tile_operands(agg, cnt, gauss, ncls, patch, origin, name)
+    if m2:
+        agg2 = _agg2_operand(agg, agg2, name)
     if v != pv or first_sample < 0 or first_sample + len(mirrors) > n:
-        raise ValueError("logits_aggregate_m2_: logits do not hold the tile's samples")
-    from .predictor import NONLIN
-    _lib.check(_lib.load().mi355_logits_aggregate_m2(logits.data_ptr(), ncls, int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
-                                                     len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss), agg.data_ptr(), agg2.data_ptr(),
-                                                     _ptr(cnt), _i3(padded), _i3(origin), stream_of(logits)), "mi355_logits_aggregate_m2")
+        raise ValueError(f"{name}: logits do not hold the tile's samples")
+    _aggregate_call("mi355_logits_aggregate", m2, logits, (logits.data_ptr(), ncls, int(first_sample)), mirrors, patch, nonlin, gauss, agg, agg2, cnt, padded, (_i3(origin),))
 
 
-def logits_aggregate_tiles_m2_(logits, mirrors, patch, nonlin, agg, agg2, cnt, origins, gauss=None, first_sample=0):
-    """``mi355_logits_aggregate_tiles_m2``: the tiles at ``origins`` in one launch with the second moment kept; agg2 is bit-identical to
-    ``logits_aggregate_m2_`` tile by tile in that order, and a voxel no tile covers is not written."""
+def _logits_aggregate_tiles(m2, logits, mirrors, patch, nonlin, agg, agg2, cnt, origins, gauss, first_sample):
     import torch
+    name = "logits_aggregate_tiles_m2_" if m2 else "logits_aggregate_tiles_"
     logits = _require_cuda(logits, torch.float32, "logits")
     n, ncls, v = logits.shape
     mirrors = [int(m) for m in mirrors]
     origins = [[int(k) for k in o] for o in origins]
     if not origins:
-        raise ValueError("logits_aggregate_tiles_m2_: no tile")
+        raise ValueError(f"{name}: no tile")
     for o in origins:
-        gauss_dev, padded, pv = _tile_operands(agg, cnt, gauss, ncls, patch, o, "logits_aggregate_tiles_m2_")
-    agg2 = _agg2_operand(agg, agg2, "logits_aggregate_tiles_m2_")
+        gauss_dev, padded, pv = _tile_operands(agg, cnt, gauss, ncls, patch, o, name)
+    if m2:
+        agg2 = _agg2_operand(agg, agg2, name)
     if v != pv or first_sample < 0 or first_sample + len(origins) * len(mirrors) > n:
-        raise ValueError("logits_aggregate_tiles_m2_: logits do not hold the tiles' samples")
+        raise ValueError(f"{name}: logits do not hold the tiles' samples")
     flat = [k for o in origins for k in o]
-    from .predictor import NONLIN
-    _lib.check(_lib.load().mi355_logits_aggregate_tiles_m2(logits.data_ptr(), ncls, int(first_sample), (C.c_int32 * max(len(mirrors), 1))(*mirrors),
-                                                           len(mirrors), _i3(patch), NONLIN[nonlin], _ptr(gauss_dev), agg.data_ptr(), agg2.data_ptr(),
-                                                           _ptr(cnt), _i3(padded), (C.c_int32 * len(flat))(*flat), len(origins), stream_of(logits)),
-               "mi355_logits_aggregate_tiles_m2")
+    _aggregate_call("mi355_logits_aggregate_tiles", m2, logits, (logits.data_ptr(), ncls, int(first_sample)), mirrors, patch, nonlin, gauss_dev, agg, agg2, cnt, padded,
+                    ((C.c_int32 * len(flat))(*flat), len(origins)))
+
+
+def head_aggregate_(feat, weight, bias, mirrors, patch, nonlin, agg, cnt, origin, gauss=None, first_sample=0, scale=None, shift=None,
+                    slope=1.0):
+    """``mi355_head_aggregate``: one tile into agg [ncls, Zp, Yp, Xp] / cnt [Zp, Yp, Xp] (CUDA fp32, in place; cnt may be None).
+    feat: every sample of the forward ([S, PV, C] fp32 or blocked fp16), of which first_sample .. + len(mirrors) - 1 are this tile's;
+    mirrors: masks, bit0 z; nonlin "identity" | "sigmoid" | "softmax"; gauss CUDA fp32 [patch] or None."""
+    _head_aggregate(False, feat, weight, bias, mirrors, patch, nonlin, agg, None, cnt, origin, gauss, first_sample, scale, shift, slope)
+
+
+def logits_aggregate_(logits, mirrors, patch, nonlin, agg, cnt, origin, gauss=None, first_sample=0):
+    """``mi355_logits_aggregate``: as ``head_aggregate_`` from logits CUDA fp32 [S, ncls, PV]."""
+    _logits_aggregate(False, logits, mirrors, patch, nonlin, agg, None, cnt, origin, gauss, first_sample)
+
+
+def logits_aggregate_tiles_(logits, mirrors, patch, nonlin, agg, cnt, origins, gauss=None, first_sample=0):
+    """``mi355_logits_aggregate_tiles``: the tiles at ``origins`` (tile i: samples first_sample + i * len(mirrors) ..) in one launch,
+    bit-identical to ``logits_aggregate_`` tile by tile in that order."""
+    _logits_aggregate_tiles(False, logits, mirrors, patch, nonlin, agg, None, cnt, origins, gauss, first_sample)
+
+
+def head_aggregate_m2_(feat, weight, bias, mirrors, patch, nonlin, agg, agg2, cnt, origin, gauss=None, first_sample=0, scale=None, shift=None,
+                       slope=1.0):
+    """``mi355_head_aggregate_m2``: ``head_aggregate_`` that also adds the tile's second moment (mean over the mirrors of p^2, times
+    gauss) into agg2 [ncls, Zp, Yp, Xp]; agg and cnt receive what the plain call gives them, bit for bit.  "identity" is refused."""
+    _head_aggregate(True, feat, weight, bias, mirrors, patch, nonlin, agg, agg2, cnt, origin, gauss, first_sample, scale, shift, slope)
+
+
+def logits_aggregate_m2_(logits, mirrors, patch, nonlin, agg, agg2, cnt, origin, gauss=None, first_sample=0):
+    """``mi355_logits_aggregate_m2``: as ``head_aggregate_m2_`` from logits CUDA fp32 [S, ncls, PV]."""
+    _logits_aggregate(True, logits, mirrors, patch, nonlin, agg, agg2, cnt, origin, gauss, first_sample)
+
+
+def logits_aggregate_tiles_m2_(logits, mirrors, patch, nonlin, agg, agg2, cnt, origins, gauss=None, first_sample=0):
+    """``mi355_logits_aggregate_tiles_m2``: the tiles at ``origins`` in one launch with the second moment kept; agg2 is bit-identical to
+    ``logits_aggregate_m2_`` tile by tile in that order, and a voxel no tile covers is not written."""
+    _logits_aggregate_tiles(True, logits, mirrors, patch, nonlin, agg, agg2, cnt, origins, gauss, first_sample)
 
 
 def cnt_add_tile_(cnt, patch, origin, gauss=None):

@@ -777,7 +777,7 @@ int mi355_conv3d_wino3_view_ndhwc(const float *x0_dev, int n, int d, int h, int 
                                   const float *bias_host, int cout, int act, float slope, const float *addend_dev,
                                   const mi355_stage0_view *view, float *y_dev, void *stream);
 /* ---- the kernels around the convolutions, one launch each (test aids; no reference counterpart beyond the one named at the
- * kernel in csrc/elementwise.hip).  Each call runs the launcher the network runs and waits for `stream`.  Tensors are taken in
+ * kernel in csrc/elementwise.hip, stage0_gather.hip or aggregate.hip).  Each call runs the launcher the network runs and waits for `stream`.  Tensors are taken in
  * the layout the network holds them in: fp32 plain NDHWC ([N][V][C]), fp16 channel-blocked ([N][C / 8][V][8]), AS IS. ---- */
 /* stats_dev [n][c][2] fp64 (sum, sum of squares over `count` voxels) -> scale_dev / shift_dev [n][c] fp32 with
  * norm(x) = x * scale + shift: biased variance (clamped at 0), eps inside the root.  kind = MI355_NORM_INSTANCE, or

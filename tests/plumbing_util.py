@@ -1,4 +1,4 @@
-"""References, inputs and gates of the single-kernel tests of csrc/elementwise.hip (tests/test_gpu_plumbing.py runs the kernels,
+"""References, inputs and gates of the single-kernel tests of csrc/elementwise.hip, stage0_gather.hip and aggregate.hip (tests/test_gpu_plumbing.py runs the kernels,
 tests/test_plumbing_refs_cpu.py checks on the CPU that these references tell plausible wrong kernels from the right one).
 
 Every reference restates its operation from the contract in csrc/kernels.h / include/mi355_nnunet.h with whole-array numpy

@@ -1,4 +1,4 @@
-"""-m gpu: logits_aggregate_tiles_kernel (csrc/elementwise.hip) - the tiles of one forward aggregated in ONE launch - against the
+"""-m gpu: logits_aggregate_tiles_kernel (csrc/aggregate.hip) - the tiles of one forward aggregated in ONE launch - against the
 sequence of per-tile launches it replaces (mi355_logits_aggregate, pinned by test_gpu_plumbing.py).
 
 Every gate is BIT EQUALITY (np.array_equal on agg and cnt): a voxel receives the terms of the tiles that cover it in list order,

@@ -1,5 +1,5 @@
-"""-m gpu: the kernels of csrc/elementwise.hip around the convolutions, one launch each, against the numpy references of
-tests/plumbing_util.py (whose power test_plumbing_refs_cpu.py proves on these very inputs).
+"""-m gpu: the kernels of csrc/elementwise.hip, stage0_gather.hip and aggregate.hip around the convolutions, one launch each,
+against the numpy references of tests/plumbing_util.py (whose power test_plumbing_refs_cpu.py proves on these very inputs).
 
 The whole-network tests see these kernels only through 1e-3 on probabilities, on cubic patches, with the flip-symmetric
 Gaussian, a 32-channel 3-class head and grids that never wrap.  Here every extent triple is pairwise different, every weight
@@ -267,6 +267,51 @@ def test_head_aggregate(amd, gpu, dtype, nonlin, ncls, c):
         bound[(slice(None),) + box] = (pu.LIPSCHITZ[nonlin] * mean_lb + (0.0 if nonlin == "identity" else pu.T_NONLIN)) * g[None]
         assert_within(agg_d.cpu().numpy(), ref, bound, f"head_aggregate {dtype} {nonlin} ncls {ncls} C {c} {name}")
         assert_bits(cnt_d.cpu().numpy(), cnt, "cnt")
+
+
+FUSED_PATCH, FUSED_PADDED, FUSED_ORIGIN = (8, 8, 16), (12, 8, 24), (4, 0, 8)
+
+
+@pytest.mark.parametrize("n_mirrors", [1, 8])
+@pytest.mark.parametrize("norm", [False, True])
+@pytest.mark.parametrize("c", [32, 24])
+@pytest.mark.parametrize("dtype", ["f32", "f16"])
+def test_head_aggregate_equals_head_logits_then_logits_aggregate(amd, gpu, dtype, c, norm, n_mirrors):
+    """BIT EQUALITY of the fused path with the two-step path, which is what the one tile term of csrc/aggregate.hip is for:
+    head_aggregate_(feat) and logits_aggregate_(head_logits(feat)) leave agg and cnt np.array_equal, and their _m2 twins agg2 as
+    well.  Patch 8 x 8 x 16 at (4, 0, 8) of a 12 x 8 x 24 grid that holds the sentinel pattern (zero inside the tile's box, so
+    that no rounding hides behind a large aggregate); C = 32 (the compile-time channel path) and 24 (the run-time one), fp32 and
+    blocked fp16, with and without scale / shift, 1 and 8 mirrors in the production order, sigmoid and softmax with 3 classes,
+    a random weight map."""
+    mirrors = [0, 4, 2, 6, 1, 5, 3, 7][:n_mirrors]
+    f, w, b, scale, shift = pu.head_case(n_mirrors, int(np.prod(FUSED_PATCH)), c, 3, 860 + c + n_mirrors, dtype == "f16")
+    feat, g_d = _feat(gpu, f, dtype), dev(pu.weight_map(FUSED_PATCH, 861), gpu)
+    sc, sh, slope = (dev(scale, gpu), dev(shift, gpu), float(pu.SLOPE)) if norm else (None, None, 1.0)
+    lg_d = amd.ops.head_logits(feat, w, b, sc, sh, slope)
+    box = tuple(slice(o, o + p) for o, p in zip(FUSED_ORIGIN, FUSED_PATCH))
+    start = [pu.sentinel((3,) + FUSED_PADDED, 862), pu.sentinel((3,) + FUSED_PADDED, 863), pu.sentinel(FUSED_PADDED, 864)]   # agg, agg2, cnt
+    for a in start:
+        a[(Ellipsis,) + box] = 0
+    for nonlin in ("sigmoid", "softmax"):
+        for m2 in (False, True):
+            got = {}
+            for path in ("fused", "two steps"):
+                agg_d, agg2_d, cnt_d = (dev(a, gpu) for a in start)
+                moments = (agg2_d,) if m2 else ()
+                if path == "fused":
+                    (amd.ops.head_aggregate_m2_ if m2 else amd.ops.head_aggregate_)(feat, w, b, mirrors, FUSED_PATCH, nonlin, agg_d, *moments, cnt_d,
+                                                                                      FUSED_ORIGIN, g_d, 0, sc, sh, slope)
+                else:
+                    (amd.ops.logits_aggregate_m2_ if m2 else amd.ops.logits_aggregate_)(lg_d, mirrors, FUSED_PATCH, nonlin, agg_d, *moments, cnt_d,
+                                                                                          FUSED_ORIGIN, g_d, 0)
+                got[path] = [t.cpu().numpy() for t in (agg_d, agg2_d, cnt_d)]
+            for name, a, b2, a0 in zip(("agg", "agg2", "cnt"), got["fused"], got["two steps"], start):
+                what = f"{name}, {nonlin}, m2 {m2}, {dtype}, C {c}, norm {norm}, {n_mirrors} mirrors"
+                assert np.array_equal(a, b2), f"{what}: {int((a != b2).sum())} of {a.size} elements differ between the fused and the two-step path"
+                if name != "agg2" or m2:   # (so that the equality above compares something: every voxel of the box received a term)
+                    assert (a[(Ellipsis,) + box] > 0).all(), f"{what}: a voxel of the tile's box received nothing"
+                else:
+                    assert np.array_equal(a, a0), f"{what}: agg2 was written by a call that does not take it"
 
 
 # ------------------------------------------------------------------ cnt_add_tile and the finish path

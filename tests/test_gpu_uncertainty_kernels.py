@@ -1,4 +1,4 @@
-"""-m gpu: the second-moment (M2) instantiations of the three aggregation kernels of csrc/elementwise.hip, finish_moments_kernel, and
+"""-m gpu: the second-moment (M2) instantiations of the aggregation kernels of csrc/aggregate.hip, finish_moments_kernel, and
 the maps / stats kernels of csrc/uncertainty.hip, one by one.
 
 Shapes are the ones the plumbing tests pin (plumbing_util.AGG_*, MIRROR_LISTS, FINISH_PATCH; test_gpu_aggregate_tiles.py's patch

@@ -40,9 +40,11 @@ def test_new_symbols_are_declared_bound_and_built(amd, unc):
             assert callable(getattr(mod, name)), name
     # the reference lines the header names, and the kernels the issue names
     assert "run_brats2021_inference_singlethread.py:97-128" in header and "step5_quality.py:457-500" in header
-    with open(os.path.join(pkg, "csrc", "elementwise.hip"), encoding="utf-8") as f:
+    with open(os.path.join(pkg, "csrc", "aggregate.hip"), encoding="utf-8") as f:
         src = f.read()
-    assert "template <typename T, bool NORM, int NM = 0, bool M2 = false>" in src and "logits_tile_term<M2>" in src and "finish_moments_kernel" in src
+    # (the M2 instantiations of the per-tile kernel, of the tiles kernel and of the one term both add)
+    assert "template <bool M2, int NM, typename Source>\n__global__ void head_aggregate_kernel" in src and "mirror_step<M2>" in src
+    assert "logits_aggregate_tiles_kernel<decltype(m2)::value>" in src and "finish_moments_kernel" in src
 
 
 def test_the_package_does_not_import_the_module_by_itself():

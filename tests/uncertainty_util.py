@@ -1,5 +1,5 @@
 """float64 restatements of the ensemble-uncertainty definitions (uncertainty.py, csrc/uncertainty.hip, the M2 aggregation kernels of
-csrc/elementwise.hip), for tests/test_gpu_uncertainty_*.py and tests/test_uncertainty_cpu.py.
+csrc/aggregate.hip), for tests/test_gpu_uncertainty_*.py and tests/test_uncertainty_cpu.py.
 
 For one ensemble member, one class k and one voxel v the samples are s = (fold, tile that covers v, mirror) with probability p_s and
 weight w_s = g_t(v) / (cnt(v) n_folds n_mirrors), cnt(v) = sum_t g_t(v):  mean = sum w_s p_s,  m2 = sum w_s p_s^2,
