@@ -53,6 +53,7 @@ EXPORTS = [
     "mi355_head_aggregate_m2", "mi355_uncertainty_maps", "mi355_uncertainty_stats",
     "mi355_live_allocations",
     "mi355_tconv3d_plan",
+    "mi355_conv_s2_split_pack", "mi355_conv3d_s2dma_concat_ndhwc",
 ]
 
 
@@ -350,6 +351,10 @@ def load():
                                                   C.c_int, C.c_int, C.c_float, C.c_int, vp, vp]
     lib.mi355_conv3d_s2dma_hinted_ndhwc.argtypes = [vp, C.POINTER(Stage0View), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
                                                     C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp]
+    lib.mi355_conv3d_s2dma_concat_ndhwc.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
+                                                    C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp]
+    lib.mi355_conv_s2_split_pack.argtypes = [c_float_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint16), C.c_int64]
+    lib.mi355_conv_s2_split_pack.restype = C.c_int64
     lib.mi355_conv3d_wino3_view_ndhwc.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, C.c_int, C.c_int,
                                                   C.c_float, vp, C.POINTER(Stage0View), vp, vp]
     lib.mi355_level1_share_plan.argtypes = [C.c_int, C.c_int, C.c_int, c_int32_p, C.c_double, C.c_int, C.POINTER(Level1ShareNet), C.c_int,

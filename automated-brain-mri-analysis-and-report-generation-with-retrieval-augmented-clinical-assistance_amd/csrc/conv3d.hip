@@ -1117,11 +1117,13 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_wino2_kernel(Wino2Args pa) {
 // brick (12.7 voxels per output), at one voxel fragment per wave every MFMA group would stream its own KiB of weights
 // through the L1, and synchronous staging is not hidden by a second workgroup.  So, with the machinery of the Winograd
 // kernel above: the 8-channel brick is double-buffered and filled by LDS-DMA while the previous chunk is computed, and
-// the weights come through LDS as well - one dz plane of the chunk (9 taps x 64 couts = 18 KiB) per step in a two-slot
-// ring, fetched by DMA one step ahead and shared by the four waves.  The tap loop then holds LDS reads and MFMAs only
-// (8 per tap: 4 channel pairs x 2 cout fragments); the VALU work left is the DMA address arithmetic.
-// Step = (chunk, dz): 72 MFMAs per wave; the barrier that ends it retires the step's DMAs (vmcnt(0)) before anybody
-// reads what they fetched.
+// the weights come through LDS as well - one dz plane of the chunk (9 taps x 64 couts) per step in a two-slot
+// ring, fetched by DMA one step ahead and shared by the four waves.
+// The product runs on the bf16 matrix pipe, 16 x the f32 MFMA rate and apart from the VALU: every fp32 operand is cut into
+// three bf16 pieces and six piece products are summed in fp32 (conv3d_s2dma_body.h; the weights come cut, as the split pack,
+// 27 KiB per plane; the inputs are cut in registers beside the MFMAs).  Two taps side by side are one K = 16 operand.
+// Step = (chunk, dz): 60 MFMAs of 32 cycles per wave (72 f32 MFMAs of 64 before); the barrier that ends it retires the
+// step's weight DMAs before anybody reads what they fetched, the brick's by the end of dz 2.
 // Tile: 2 x 2 x 32 outputs (TXL = 5, brick 5 x 5 x 65) or 2 x 4 x 16 (TXL = 4, brick 5 x 9 x 33) for narrow volumes.
 template <int TXL>
 struct S2Geom {
@@ -1130,7 +1132,8 @@ struct S2Geom {
     static constexpr int RANGES = 28, RSTRIDE = (BV - 64 + 26) / 27;              // DMA ranges [RSTRIDE*r, +64) per quad plane
     static constexpr int PAD = 27 * RSTRIDE + 64 - BV;                            // slots written past the last plane
     static constexpr int BUF_FLOATS = (2 * BV + PAD) * 4;
-    static constexpr int WSLOT_FLOATS = 9 * 2 * 256;                              // one dz plane: 9 taps x 2 cout fragments
+    static constexpr int WPIECE_BYTES = 9 * 2 * 64 * 4 * 2;                       // one dz plane of one bf16 piece: 9 taps x 2 cout fragments
+    static constexpr int WSLOT_FLOATS = 2 * WPIECE_BYTES / 4;                     // a ring slot: the plane's hi and mid pieces (its lo pieces: static LDS)
     static constexpr size_t LDS_BYTES = (size_t)(2 * BUF_FLOATS + 2 * WSLOT_FLOATS + 4 * 64 * 2) * sizeof(float);
 };
 
@@ -1195,6 +1198,47 @@ static void pack_conv_weights_f32(const float *w, int cin, int cin_pad, int cout
                             }
 }
 
+// Split pack of the fp32 stride-2 LDS-DMA kernel (conv3d_s2dma_body.h): every weight cut into three bf16 pieces by truncation,
+//   w = hi + mid + lo exactly,  hi = the upper 16 bits of w, mid = those of w - hi, lo = w - hi - mid (8 bits or fewer: a bf16 value),
+// the rule the kernel cuts its inputs by.  (Exact for zeros and for every finite w whose last bit is a normal fp32: |w| >= 2^-103.
+// A non-finite w does not split: +-inf leaves the residual inf - inf, and the layer's outputs are NaN where fp32 gave +-inf.)
+// Layout (bf16, 16 bits each): [cout_block of 64][chunk of 8][dz][piece: hi, mid, lo][group][nf][lane 0..63][e] with
+//   group 0        = tap dz*9 alone,           e = 0..3: cin = chunk*8 + (lane>>5)*4 + e                       (1 KiB)
+//   group g = 1..4 = taps dz*9 + 2g-1, + 2g,   e = 0..7: tap 2g-1 + (e>>2), cin = chunk*8 + (lane>>5)*4 + (e&3) (2 KiB)
+//   cout = (cout_block*2 + nf)*32 + (lane&31); channels at or beyond cin are zero.
+// A (chunk, dz) plane is 27 KiB: 9 KiB per piece.
+static inline uint16_t bf16_cut(float v, float *rest) {
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    u &= 0xffff0000u;
+    float h;
+    memcpy(&h, &u, 4);
+    *rest = v - h;  // exact
+    return (uint16_t)(u >> 16);
+}
+void pack_conv_weights_s2split(const float *w, int cin, int cin_pad, int cout, std::vector<uint16_t> &out) {
+    const int nchunks = cin_pad / 8, nblk = cout / 64;
+    out.assign((size_t)nblk * nchunks * 3 * 3 * 4608, 0);
+    for (int b = 0; b < nblk; ++b)
+        for (int ch = 0; ch < nchunks; ++ch)
+            for (int dz = 0; dz < 3; ++dz) {
+                uint16_t *plane = &out[(((size_t)b * nchunks + ch) * 3 + dz) * 3 * 4608];
+                for (int g = 0; g < 5; ++g)
+                    for (int nf = 0; nf < 2; ++nf)
+                        for (int lane = 0; lane < 64; ++lane)
+                            for (int e = 0; e < (g ? 8 : 4); ++e) {
+                                const int tap = dz * 9 + (g ? 2 * g - 1 + (e >> 2) : 0);
+                                const int co = (b * 2 + nf) * 32 + (lane & 31), ci = ch * 8 + (lane >> 5) * 4 + (e & 3);
+                                if (ci >= cin) continue;
+                                const size_t o = g ? 512 + (size_t)(g - 1) * 1024 + nf * 512 + lane * 8 + e : (size_t)nf * 256 + lane * 4 + e;
+                                float r1, r2, r3;
+                                plane[o] = bf16_cut(w[((size_t)co * cin + ci) * 27 + tap], &r1);
+                                plane[4608 + o] = bf16_cut(r1, &r2);
+                                plane[2 * 4608 + o] = bf16_cut(r2, &r3);
+                            }
+            }
+}
+
 int conv_pack_layout(int cin, int cin_pad, int cout, int stride, ConvPackLayout *out) {
     MI355_REQUIRE(stride == 1 || stride == 2, "conv stride %d unsupported", stride);
     MI355_REQUIRE(cin_pad >= cin && cin_pad % 4 == 0, "bad cin_pad %d for cin %d", cin_pad, cin);
@@ -1225,6 +1269,11 @@ int conv_weights_upload(DeviceAllocs &mem, const float *w_host, const float *bia
         pack_conv_weights_f32(w_host, cin, cin_pad, cout, cw.cc, cw.nf, packed);
         cw.wp_bytes = packed.size() * sizeof(float);
         MI355_TRY(upload_pack(packed, &cw.wp_dev));
+        if (stride == 2 && cw.cc == 8 && cw.nf == 2) {  // the layers plan_s2dma can take
+            std::vector<uint16_t> split;
+            pack_conv_weights_s2split(w_host, cin, cin_pad, cout, split);
+            MI355_TRY(mem.upload(split.data(), split.size() * sizeof(uint16_t), &cw.wps_dev));
+        }
         if (l.c16) {
             pack_conv_weights_f32(w_host, cin, cin_pad, cout, 16, cw.nf, packed);
             MI355_TRY(upload_pack(packed, &cw.wp16_dev));
@@ -1437,6 +1486,10 @@ static int launch_conv_f32(const ConvWeights &w, const ConvCall &c, const ConvPl
     ConvArgs a;
     a.in0 = c.in0; a.in1 = c.in1; a.C0 = c.C0; a.C1 = c.C1;
     a.wp = p.pack == PACK_WINO2 ? w.wpw_dev : (p.pack == PACK_C16 ? w.wp16_dev : w.wp_dev);
+    if (p.family == FAM_S2DMA) {  // reads the split pack and nothing else
+        MI355_REQUIRE(w.wps_dev != nullptr, "conv %d->%d has no split weight pack", w.cin, w.cout);
+        a.wp = (const float *)w.wps_dev;
+    }
     a.bias = w.bias_dev; a.out = c.out; a.stats = c.stats;
     a.head_w = c.head_w; a.head_b = c.head_b; a.head_out = c.head_out; a.head_ncls = c.head_ncls;
     a.N = c.N; a.Di = c.Di; a.Hi = c.Hi; a.Wi = c.Wi;

@@ -1,5 +1,5 @@
-// The body of conv3_f32_s2dma_kernel, included by conv3d.hip twice: S2DMA_VIEW = 0 is the kernel as it always was, token for token
-// (its listing does not change when the view code below does); S2DMA_VIEW = 1 is conv3_f32_s2dma_kernel_view, which reads its input
+// The body of conv3_f32_s2dma_kernel, included by conv3d.hip twice: S2DMA_VIEW = 0 is the plain kernel (its listing does not
+// change when the view code below does); S2DMA_VIEW = 1 is conv3_f32_s2dma_kernel_view, which reads its input
 // through a stage-0 view (kernels.h S0View): in0 holds only the shells of its samples, every other voxel is read in place from the
 // whole-volume tensor the view names.  Per tile (decode, scalar): the sample's view words, the brick corner's voxel index in the
 // view's tensor and which brick planes / rows / columns lie in a shell - planes and rows as one-hot fields that a piece tests with
@@ -21,6 +21,12 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_s2dma_kernel(Wino2Args pa) {
     typedef S2Geom<TXL> GM;
     constexpr int IX = GM::IX, IY = GM::IY, BV = GM::BV;
     constexpr int S2_BUF_FLOATS = GM::BUF_FLOATS, S2_WSLOT_FLOATS = GM::WSLOT_FLOATS, S2_RSTRIDE = GM::RSTRIDE;
+    constexpr int S2_WPIECE_BYTES = GM::WPIECE_BYTES, S2_WLO_BYTES = GM::WPIECE_BYTES, S2_WPLANE_BYTES = 3 * GM::WPIECE_BYTES;
+    // the lo pieces of the two ring slots: static, beside the dynamic image whose size the plan pins (hi + mid = the old 18 KiB slot)
+    __shared__ __attribute__((aligned(16))) unsigned wlo[2 * S2_WLO_BYTES / 4];
+    typedef unsigned s2u32x4 __attribute__((ext_vector_type(4)));
+    typedef unsigned s2u32x2 __attribute__((ext_vector_type(2)));
+    typedef __bf16 s2bf16x8 __attribute__((ext_vector_type(8)));
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -128,18 +134,22 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_s2dma_kernel(Wino2Args pa) {
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g1,
                                          (__attribute__((address_space(3))) void *)(dst + BV * 4 - 4), 16, 16, 0);
     };
-    // weight DMA: dz plane `dz` of chunk `ch` = 18 KiB contiguous in the pack; KiB i goes to wave i & 3
-    const float *wblk = p.wp + (size_t)blockIdx.y * p.nchunks * (27 * 2 * 256);
-    auto dma_weights = [&](int ch, int dz, float *slot, int i_lo = 0, int i_hi = 5) {
-        const float *wsrc = wblk + ((size_t)ch * 27 + dz * 9) * (2 * 256) + lane * 4;
+    // weight DMA: dz plane `dz` of chunk `ch` = 27 KiB contiguous in the split pack (pack_conv_weights_s2split): KiB 0-8 the hi pieces,
+    // 9-17 the mid pieces - together one slot of the ring -, 18-26 the lo pieces, which go to the slot's half of wlo.  KiB k goes to
+    // wave k & 3, round k >> 2.
+    const char *wblk = (const char *)p.wp + (size_t)blockIdx.y * p.nchunks * (3 * S2_WPLANE_BYTES);
+    auto dma_weights = [&](int ch, int dz, int slot, int i_lo = 0, int i_hi = 7) {
+        const char *wsrc = wblk + ((size_t)ch * 3 + dz) * S2_WPLANE_BYTES + lane * 16;
+        char *whm = (char *)(wring + slot * S2_WSLOT_FLOATS), *wl = (char *)(wlo + slot * (S2_WLO_BYTES / 4));
 #pragma unroll
-        for (int i = 0; i < 5; ++i) {
+        for (int i = 0; i < 7; ++i) {
             if (i < i_lo || i >= i_hi) continue;  // (compile-time at the call sites)
-            // (no branch: KiB 18 and 19 do not exist - waves 2 and 3 fetch KiB 16 and 17 a second time in the last round,
-            //  the same bytes into the same slot as waves 0 and 1)
-            const int kib = wave + 4 * i < 18 ? wave + 4 * i : wave + 4 * i - 2;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(wsrc + kib * 256),
-                                             (__attribute__((address_space(3))) void *)(slot + kib * 256), 16, 0, 0);
+            // (no branch: KiB 27 does not exist - wave 3 fetches KiB 26 a second time in the last round, the same bytes into the
+            //  same place as wave 2)
+            const int kib = wave + 4 * i < 27 ? wave + 4 * i : 26;
+            char *dst = kib < 18 ? whm + kib * 1024 : wl + (kib - 18) * 1024;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(wsrc + kib * 1024),
+                                             (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
         }
     };
 
@@ -150,16 +160,18 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_s2dma_kernel(Wino2Args pa) {
     TileCoord cur = decode(tile);
 #pragma unroll
     for (int k = 0; k < 7; ++k) dma_brick(cur, 0, k, lds);
-    dma_weights(0, 0, wring);
+    dma_weights(0, 0, 0);
     __syncthreads();
 
     int buf = 0, wslot = 0;
     for (; tile < hi; tile += nl) {
-        f32x16 acc[1][2];
+        // acc: the hi x hi products; acc_s: the five small ones (<= 2^-7 of them, so their roundings weigh 2^-7 as much) - added once
+        // per tile, so an output carries one chain's roundings and not six
+        f32x16 acc[1][2], acc_s[2];
 #pragma unroll
         for (int nf = 0; nf < 2; ++nf)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[0][nf][r] = 0.f;
+            for (int r = 0; r < 16; ++r) { acc[0][nf][r] = 0.f; acc_s[nf][r] = 0.f; }
         const int ntile = tile + nl;
         const TileCoord nxt_tile = ntile < hi ? decode(ntile) : cur;
 
@@ -173,55 +185,125 @@ __global__ __launch_bounds__(256, 1) void conv3_f32_s2dma_kernel(Wino2Args pa) {
             float *bufn = lds + (buf ^ 1) * S2_BUF_FLOATS;
 #pragma unroll
             for (int dz = 0; dz < 3; ++dz) {
-                // fetches of the step: the next weight plane and a third of the next chunk's brick - issued from inside the tap loop
-                // (round 4: in front of it, their ~11 DMAs and address arithmetic ran with the matrix pipe idle, once per step)
+                // Fetches of the step, oldest first: the next weight plane (7 rounds of one DMA per wave; rounds 0-3 in front of the
+                // tap loop, where the wave waits for its first LDS reads anyway), then ranges of the next chunk's brick (dz 0: ranges
+                // 0-3, dz 1: 4-6, dz 2: none).  The weights are read in the next step and must have landed at this step's barrier;
+                // the brick is read three steps on.  A step of 60 bf16 MFMAs is shorter than a fetch from HBM takes, so the barrier
+                // leaves the step's brick DMAs - the youngest, two per range - in flight (vmcnt(8), vmcnt(6)) and only dz 2, in front
+                // of the buffer switch, drains them all.
+                // (The waits at the step's end count on this order: exactly 2 * S2_BRICK_N brick DMAs are issued behind the 7 weight
+                // DMAs of the step, and vmcnt retires in order.  A change of the schedule here changes S2_BRICK_RANGES, not a literal.)
+                constexpr int S2_BRICK_RANGES[3] = {4, 3, 0};
+                static_assert(S2_BRICK_RANGES[0] + S2_BRICK_RANGES[1] + S2_BRICK_RANGES[2] == 7, "a wave fetches 7 ranges of a brick");
+                const int S2_BRICK_LO = dz == 0 ? 0 : S2_BRICK_RANGES[0], S2_BRICK_N = S2_BRICK_RANGES[dz];  // (dz: compile-time, the loop is unrolled)
                 auto step_fetch = [&](int piece) {
-                    if (piece < 2) {  // the weight plane's 18 KiB: rounds 0-1, then 2-4
-                        const int lo = piece == 0 ? 0 : 2, hi = piece == 0 ? 2 : 5;
-                        if (dz < 2) dma_weights(ch, dz + 1, wring + (wslot ^ 1) * S2_WSLOT_FLOATS, lo, hi);
-                        else dma_weights(nch, 0, wring + (wslot ^ 1) * S2_WSLOT_FLOATS, lo, hi);
-                    } else {
-                        const int q = piece - 1;
-                        const int k = dz == 0 ? q - 1 : (dz == 1 ? 2 + q : 4 + q);   // dz 0: ranges 0 1 2, dz 1: 3 4, dz 2: 5 6
-                        if (q <= (dz == 0 ? 3 : 2)) dma_brick(nxt, nch, k, bufn);
-                    }
+                    if (piece < 7) {
+                        if (dz < 2) dma_weights(ch, dz + 1, wslot ^ 1, piece, piece + 1);
+                        else dma_weights(nch, 0, wslot ^ 1, piece, piece + 1);
+                    } else if (piece - 7 < S2_BRICK_N) dma_brick(nxt, nch, S2_BRICK_LO + piece - 7, bufn);
                 };
-                const float *wcur = wring + wslot * S2_WSLOT_FLOATS + lane * 4;
-                f32x4 a_cur, a_nxt, b_cur[2], b_nxt[2];
-                a_cur = *(const f32x4 *)(bufc + a_base + dz * IY * IX * 4);
-                b_cur[0] = *(const f32x4 *)(wcur);
-                b_cur[1] = *(const f32x4 *)(wcur + 256);
-                // The next tap's fragments are read BEHIND the first two MFMAs of this tap (round 4).  With an LDS-DMA in flight hipcc
-                // does not count LDS reads (every wait is lgkmcnt(0)): read at the top of the tap, as before, the three reads
-                // were waited for on the spot - their latency exposed nine times a step, which is what kept this kernel's matrix
-                // pipe at 0.72.  Now the wait comes in front of the NEXT tap's first MFMA, six MFMAs later.
+                // The plane's product on the bf16 matrix pipe (DESIGN.md section 5 "split-bf16").  An fp32 value is cut into three
+                // bf16 pieces by truncation, v = v0 + v1 + v2 exactly (8 + 8 + 8 significant bits); the weights arrive cut (the split
+                // pack), the inputs are cut here.  Six of the nine piece products are summed, smallest first, in fp32 inside the MFMA:
+                //   x2 w0, x0 w2, x1 w1, x1 w0, x0 w1, x0 w0        (dropped: x1 w2, x2 w1, x2 w2, each <= 2^-24 |x w|)
+                // One v_mfma_f32_32x32x16_bf16 takes K = 16 = 2 taps x 8 channels: a lane's 8 elements are its quad of tap A, then its
+                // quad of tap B, in both operands.  Group 0 of a plane is tap 0 alone (the input's second half is zero, the weight's a
+                // second copy of tap 0: finite), groups 1-4 are taps (1, 2) (3, 4) (5, 6) (7, 8).  The order of groups and products is
+                // the same in both tile shapes and in the view twin: their outputs agree bit for bit.
+                // Domain: zeros and finite values whose last bit is a normal fp32 (|v| >= 2^-103) split exactly.  A non-finite input
+                // does not survive the split as itself: for +-inf the residual is inf - inf, so the output is NaN where an fp32 product
+                // gave +-inf (NaN stays NaN); the same holds for a non-finite weight through the host split.
+                const char *whm = (const char *)(wring + wslot * S2_WSLOT_FLOATS), *wl = (const char *)(wlo + wslot * (S2_WLO_BYTES / 4));
+                auto read_a = [&](int t) {
+                    const int dy = t / 3, dx = t - dy * 3;
+                    return *(const f32x4 *)(bufc + a_base + ((dz * IY + dy) * IX + dx) * 4);
+                };
+                auto read_b = [&](int g, s2u32x4 (&b)[3][2]) {
 #pragma unroll
-                for (int t = 0; t < 9; ++t) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
+                    for (int pc = 0; pc < 3; ++pc)
 #pragma unroll
                         for (int nf = 0; nf < 2; ++nf) {
-                            acc[0][nf] = __builtin_amdgcn_mfma_f32_32x32x2f32(b_cur[nf][j], a_cur[j], acc[0][nf], 0, 0, 0);
-                            if (j == 0 && nf == 1) {
-                                __builtin_amdgcn_sched_barrier(0);
-                                if (t + 1 < 9) {
-                                    const int dy = (t + 1) / 3, dx = (t + 1) - dy * 3;
-                                    a_nxt = *(const f32x4 *)(bufc + a_base + ((dz * IY + dy) * IX + dx) * 4);
-                                    b_nxt[0] = *(const f32x4 *)(wcur + (t + 1) * 512);
-                                    b_nxt[1] = *(const f32x4 *)(wcur + (t + 1) * 512 + 256);
-                                }
-                                if (t < 5) step_fetch(t);
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
+                            const char *base = pc < 2 ? whm + pc * S2_WPIECE_BYTES : wl;
+                            if (g == 0) {
+                                const s2u32x2 t = *(const s2u32x2 *)(base + nf * 512 + lane * 8);
+                                b[pc][nf][0] = t[0]; b[pc][nf][1] = t[1]; b[pc][nf][2] = t[0]; b[pc][nf][3] = t[1];
+                            } else b[pc][nf] = *(const s2u32x4 *)(base + 1024 + (g - 1) * 2048 + nf * 1024 + lane * 16);
                         }
-                    a_cur = a_nxt; b_cur[0] = b_nxt[0]; b_cur[1] = b_nxt[1];
+                };
+                auto cut = [](float v) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & 0xffff0000u); };
+                auto pk = [](float e0, float e1) {  // the bf16 truncations of e0 (low half) and e1 (high half)
+                    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, e1), __builtin_bit_cast(unsigned, e0), 0x07060302u);
+                };
+                // unit u = values 2u, 2u + 1 of (tap A, tap B) -> dword u of the three pieces; 6 + 5 VALU instructions, the subtractions exact
+                auto split_hi = [&](const f32x4 (&v)[2], int u, s2u32x4 (&x)[3], float (&r)[8]) {
+                    const float e0 = v[u >> 1][(u & 1) * 2], e1 = v[u >> 1][(u & 1) * 2 + 1];
+                    x[0][u] = pk(e0, e1);
+                    r[2 * u] = e0 - cut(e0); r[2 * u + 1] = e1 - cut(e1);
+                    x[1][u] = pk(r[2 * u], r[2 * u + 1]);
+                };
+                auto split_lo = [&](int u, s2u32x4 (&x)[3], const float (&r)[8]) {
+                    x[2][u] = pk(r[2 * u] - cut(r[2 * u]), r[2 * u + 1] - cut(r[2 * u + 1]));
+                };
+                constexpr int PX[6] = {2, 0, 1, 1, 0, 0}, PW[6] = {0, 2, 1, 0, 1, 0};
+                f32x4 ar[2], ar_n[2];
+                s2u32x4 xs[3], xs_n[3], b_cur[3][2], b_nxt[3][2], b_nn[3][2];
+                float rs[8];
+                ar[0] = read_a(0);
+                read_b(0, b_cur);
+#pragma unroll
+                for (int piece = 0; piece < 4; ++piece) step_fetch(piece);
+#pragma unroll
+                for (int pc = 0; pc < 3; ++pc) xs[pc] = s2u32x4{0u, 0u, 0u, 0u};
+                split_hi(ar, 0, xs, rs); split_hi(ar, 1, xs, rs);
+                split_lo(0, xs, rs); split_lo(1, xs, rs);
+                ar[0] = read_a(1); ar[1] = read_a(2);
+                read_b(1, b_nxt);
+                // Per MFMA gap (32 cycles, the VALU free beside it): half a unit of the next group's split behind MFMAs 1-8, the reads of
+                // the group after it behind MFMA 9 - with an LDS-DMA in flight hipcc waits lgkmcnt(0), so they are waited for at the
+                // next group's MFMA 1 -, one fetch piece behind MFMAs 0, 10 and 11 of groups 0-2.
+#pragma unroll
+                for (int g = 0; g < 5; ++g) {
+#pragma unroll
+                    for (int m = 0; m < 12; ++m) {
+                        const int pr = m >> 1, nf = m & 1;
+                        f32x16 &dst = pr == 5 ? acc[0][nf] : acc_s[nf];
+                        dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(s2bf16x8, b_cur[PW[pr]][nf]),
+                                                                      __builtin_bit_cast(s2bf16x8, xs[PX[pr]]), dst, 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (g < 4 && m >= 1 && m <= 8) {
+                            if ((m - 1) & 1) split_lo((m - 1) >> 1, xs_n, rs);
+                            else split_hi(ar, (m - 1) >> 1, xs_n, rs);
+                        }
+                        if (g < 3 && m == 9) {
+                            ar_n[0] = read_a(2 * g + 3); ar_n[1] = read_a(2 * g + 4);
+                            read_b(g + 2, b_nn);
+                        }
+                        if (m == 0 || m >= 10) {
+                            const int piece = 4 + g * 3 + (m == 0 ? 0 : m - 9);
+                            if (piece < 7 + S2_BRICK_N) step_fetch(piece);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+#pragma unroll
+                    for (int pc = 0; pc < 3; ++pc) {
+                        if (g < 4) { xs[pc] = xs_n[pc]; b_cur[pc][0] = b_nxt[pc][0]; b_cur[pc][1] = b_nxt[pc][1]; }
+                        if (g < 3) { b_nxt[pc][0] = b_nn[pc][0]; b_nxt[pc][1] = b_nn[pc][1]; }
+                    }
+                    if (g < 3) { ar[0] = ar_n[0]; ar[1] = ar_n[1]; }
                 }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // explicit: a ds_read is ordered behind an LDS-DMA only by the issuer's vmcnt + a barrier
-                __syncthreads();  // retires the step's DMAs (vmcnt(0)); the other weight slot / brick buffer may be read now
+                // explicit: a ds_read is ordered behind an LDS-DMA only by the issuer's vmcnt + a barrier.  (Raw barrier: a
+                // __syncthreads() would drain the brick DMAs as well.  The MFMAs above have consumed every LDS read of the step.)
+                if (dz == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * S2_BRICK_RANGES[0]) : "memory");
+                else if (dz == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * S2_BRICK_RANGES[1]) : "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");  // the other weight slot may be read now; after dz 2 the other brick buffer as well
                 wslot ^= 1;
             }
             buf ^= 1;
         }
+#pragma unroll
+        for (int nf = 0; nf < 2; ++nf) acc[0][nf] += acc_s[nf];
         ConvArgs q = p;
         q.lx = TXL; q.ly = 6 - TXL; q.lz = 1;  // voxel v = wave * 32 + lane: x = v & (TX-1), y = (v >> TXL) & (TY-1), z = v >> 6
         conv_epilogue<1, 2>(acc, q, cur.n, cur.oz0, cur.oy0, cur.ox0, (int)blockIdx.y * 64);

@@ -19,6 +19,7 @@ struct ConvWeights {
     float *wp16_dev = nullptr;  // second pack with 16-channel chunks for the 512-voxel-tile simple kernel (auto mode)
     float *wpw_dev = nullptr;   // Winograd pack F(2x2,3x3) over (z, y) (stride 1, 16-channel chunks, 32-cout blocks)
     float *wp3_dev = nullptr;   // 3-D Winograd pack F(2x2x2,3x3x3) (conv3d_wino3.hip; stride 1, 16-channel chunks, 32-cout blocks)
+    uint16_t *wps_dev = nullptr;  // split-bf16 pack of the fp32 stride-2 LDS-DMA kernel (pack_conv_weights_s2split; stride 2, cc == 8, nf == 2), 1.5x wp_dev
     float *bias_dev = nullptr;
     float *w_plain_dev = nullptr;  // [cout][cin][27] PyTorch order (direct kernel / tests)
     size_t wp_bytes = 0;
@@ -95,6 +96,7 @@ int conv3d_mfma_f32(const ConvWeights &w, const ConvCall &c, hipStream_t s, cons
 // fill-the-chip rule.  Test aid of the stage-0 views.
 int conv3d_s2dma_f32(const ConvWeights &w, const ConvCall &c, bool force, hipStream_t s, const char **kernel_name = nullptr);
 // F(2x2x2, 3x3x3) kernel (conv3d_wino3.hip)
+void pack_conv_weights_s2split(const float *w, int cin, int cin_pad, int cout, std::vector<uint16_t> &out);  // conv3d.hip
 void pack_conv_weights_wino3(const float *w, int cin, int cin_pad, int cout, std::vector<float> &out);
 bool conv3d_wino3_enabled();
 bool conv3d_wino3_fuses_input_norm(const ConvWeights &w, const ConvCall &c);

@@ -341,6 +341,37 @@ extern "C" int mi355_conv3d_s2dma_hinted_ndhwc(const float *x_dev, const mi355_s
     g_last_conv_kernel = kname ? kname : "";
     return synced(rc, s, "conv");
 }
+// The plain kernel over a virtual concat [x0 | x1] (c0 and c1 multiples of 8): the chunks that come from the second tensor.
+extern "C" int mi355_conv3d_s2dma_concat_ndhwc(const float *x0_dev, const float *x1_dev, int n, int d, int h, int w, int c0, int c1,
+                                               const float *weight_host, const float *bias_host, int cout, int act, float slope, int force,
+                                               int s2_least_padding, float *y_dev, void *stream) {
+    MI355_REQUIRE(x0_dev && x1_dev && y_dev && weight_host && c0 > 0 && c1 > 0 && cout > 0, "mi355_conv3d_s2dma_concat_ndhwc: bad argument");
+    MI355_REQUIRE(act != ACT_LRELU || (slope >= 0.f && slope <= 1.f), "LeakyReLU slope %g outside [0, 1]", (double)slope);
+    MI355_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    DeviceAllocs mem;
+    ConvWeights cw;
+    MI355_TRY(conv_weights_upload(mem, weight_host, bias_host, c0 + c1, c0 + c1, cout, 2, false, &cw));
+    FusedOps f;
+    f.x1 = x1_dev; f.c1 = c1;
+    ConvCall c = make_call<float>(x0_dev, c0 + c1, n, d, h, w, y_dev, nullptr, act, slope, f);
+    c.s2_least_padding = s2_least_padding != 0;
+    const char *kname = nullptr;
+    const int rc = conv3d_s2dma_f32(cw, c, force != 0, s, &kname);
+    g_last_conv_kernel = kname ? kname : "";
+    return synced(rc, s, "conv");
+}
+
+// The split pack conv_weights_upload builds for a stride-2 layer, on the host (test aid of pack_conv_weights_s2split; no device).
+extern "C" int64_t mi355_conv_s2_split_pack(const float *weight_host, int cin, int cin_pad, int cout, uint16_t *out, int64_t out_elems) {
+    MI355_REQUIRE(weight_host && cin > 0 && cin_pad >= cin && cin_pad % 8 == 0 && cout > 0 && cout % 64 == 0 && (out || out_elems == 0),
+                  "mi355_conv_s2_split_pack: bad argument (cin_pad a multiple of 8, cout of 64)");
+    std::vector<uint16_t> pack;
+    pack_conv_weights_s2split(weight_host, cin, cin_pad, cout, pack);
+    if (out_elems >= (int64_t)pack.size()) memcpy(out, pack.data(), pack.size() * sizeof(uint16_t));
+    return (int64_t)pack.size();
+}
+
 extern "C" int mi355_conv3d_s2dma_view_ndhwc(const float *x_dev, const mi355_stage0_view *view, int n, int d, int h, int w, int cin,
                                              const float *weight_host, const float *bias_host, int cout, int act, float slope, int force,
                                              float *y_dev, void *stream) {

@@ -452,17 +452,27 @@ def _stage0_view(src, samples, depth):
     return v, src
 
 
-def conv3d_s2dma_view_ndhwc(x, weight, bias=None, view=None, act=0, slope=0.01, force=True, s2_least_padding=False):
+def conv3d_s2dma_view_ndhwc(x, weight, bias=None, view=None, act=0, slope=0.01, force=True, s2_least_padding=False, x1=None):
     """One stride-2 conv on ``conv3_f32_s2dma_kernel`` or, with ``view`` = (src, samples, depth), on its view twin (test entry point,
     ``mi355_conv3d_s2dma_view_ndhwc``).  x: CUDA fp32 [N,D,H,W,Cin], the dense tile tensor - with a view only its shell voxels are
     read; src: CUDA fp32 [n_wv,Ve0,Ve1,Ve2,Cin]; samples: one dict {wv, origin, faces} per sample of x; weight: numpy [Cout,Cin,3,3,3].
-    s2_least_padding: the call carries the planner's least-padding hint (``mi355_conv3d_s2dma_hinted_ndhwc``)."""
+    s2_least_padding: the call carries the planner's least-padding hint (``mi355_conv3d_s2dma_hinted_ndhwc``).
+    x1: the second half of a virtual concat [x | x1] (``mi355_conv3d_s2dma_concat_ndhwc``; no view then)."""
     import torch
     x = _require_cuda(x, torch.float32, "x")
     n, d, h, w, cin = x.shape
     weight = np.ascontiguousarray(weight, dtype=np.float32)
     cout = weight.shape[0]
     b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+    if x1 is not None:
+        x1 = _require_cuda(x1, torch.float32, "x1")
+        if view is not None or tuple(x1.shape[:4]) != (n, d, h, w):
+            raise ValueError("conv3d_s2dma_view_ndhwc: x1 needs x's [N,D,H,W] and comes without a view")
+        y = torch.full((n, (d - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1, cout), float("nan"), dtype=torch.float32, device=x.device)
+        _lib.check(_lib.load().mi355_conv3d_s2dma_concat_ndhwc(x.data_ptr(), x1.data_ptr(), n, d, h, w, cin, int(x1.shape[4]), _lib.fptr(weight),
+                                                                _lib.fptr(b), cout, act, slope, int(bool(force)), int(bool(s2_least_padding)),
+                                                                y.data_ptr(), stream_of(x)), "mi355_conv3d_s2dma_concat_ndhwc")
+        return y
     v, keep = (None, None) if view is None else _stage0_view(view[0], view[1], view[2])
     if keep is not None and keep.shape[4] != cin:
         raise ValueError("conv3d_s2dma_view_ndhwc: the view's source must have the input's channels")
@@ -473,6 +483,23 @@ def conv3d_s2dma_view_ndhwc(x, weight, bias=None, view=None, act=0, slope=0.01, 
     else:
         _lib.check(_lib.load().mi355_conv3d_s2dma_view_ndhwc(*head, y.data_ptr(), stream_of(x)), "mi355_conv3d_s2dma_view_ndhwc")
     return y
+
+
+def conv_s2_split_pack(weight, cin_pad=None):
+    """The split-bf16 weight pack of an fp32 stride-2 layer (test aid, ``mi355_conv_s2_split_pack``; no GPU needed).  weight: numpy
+    [Cout,Cin,3,3,3], Cout a multiple of 64; cin_pad (default: Cin rounded up to 8) the padded channel count.  Returns a uint16 array
+    [Cout/64, cin_pad/8, 3 (dz), 3 (hi, mid, lo), 4608] of bf16 bit patterns; within a piece: group 0 (tap dz*9 alone) is
+    [nf 2][lane 64][4], groups g = 1..4 (taps dz*9 + 2g-1, 2g) follow at 512 + (g-1)*1024 as [nf 2][lane 64][tap 2][4]."""
+    weight = np.ascontiguousarray(weight, dtype=np.float32)
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    cin_pad = (cin + 7) // 8 * 8 if cin_pad is None else int(cin_pad)
+    lib = _lib.load()
+    n = lib.mi355_conv_s2_split_pack(_lib.fptr(weight), cin, cin_pad, cout, None, 0)
+    if n < 0:
+        _lib.check(int(n), "mi355_conv_s2_split_pack")
+    out = np.zeros(int(n), dtype=np.uint16)
+    lib.mi355_conv_s2_split_pack(_lib.fptr(weight), cin, cin_pad, cout, out.ctypes.data_as(C.POINTER(C.c_uint16)), int(n))
+    return out.reshape(cout // 64, cin_pad // 8, 3, 3, 4608)
 
 
 def conv3d_wino3_view_ndhwc(x0, weight, bias, addend, view=None, act=0, slope=0.01):

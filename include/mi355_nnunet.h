@@ -771,6 +771,16 @@ int mi355_conv3d_s2dma_view_ndhwc(const float *x_dev, const mi355_stage0_view *v
 int mi355_conv3d_s2dma_hinted_ndhwc(const float *x_dev, const mi355_stage0_view *view, int n, int d, int h, int w, int cin,
                                     const float *weight_host, const float *bias_host, int cout, int act, float slope, int force,
                                     int s2_least_padding, float *y_dev, void *stream);
+/* mi355_conv3d_s2dma_hinted_ndhwc without a view over a virtual concat [x0 | x1]: x0_dev [n,d,h,w,c0], x1_dev [n,d,h,w,c1], c0 and c1
+ * multiples of 8, weight_host [cout][c0 + c1][27] (test aid: the channel chunks the kernel fetches from the second tensor). */
+int mi355_conv3d_s2dma_concat_ndhwc(const float *x0_dev, const float *x1_dev, int n, int d, int h, int w, int c0, int c1,
+                                    const float *weight_host, const float *bias_host, int cout, int act, float slope, int force,
+                                    int s2_least_padding, float *y_dev, void *stream);
+/* The second weight pack of an fp32 stride-2 layer (test aid; needs no device): every weight cut into three bf16 pieces, hi + mid + lo
+ * = the weight exactly, in the order the lanes of conv3_f32_s2dma_kernel read them (layout: pack_conv_weights_s2split in conv3d.hip).
+ * weight_host [cout][cin][27]; cin_pad a multiple of 8, cout of 64.  Returns the pack's length in 16-bit elements
+ * (cout/64 * cin_pad/8 * 3 * 13824) and fills `out` when out_elems is at least that; negative on a bad argument. */
+int64_t mi355_conv_s2_split_pack(const float *weight_host, int cin, int cin_pad, int cout, uint16_t *out, int64_t out_elems);
 /* mi355_conv3d_wino3_ndhwc with an addend (conv3_f32_wino3_kernel<3, false>) that is read through a view: addend_dev [n,d,h,w,cout]
  * the dense tile tensor; view (channels = cout) may be NULL. */
 int mi355_conv3d_wino3_view_ndhwc(const float *x0_dev, int n, int d, int h, int w, int c0, const float *weight_host,
