@@ -1,7 +1,9 @@
 """One GPU case per 3x3x3 conv kernel instantiation that the planner selects and no older test runs (plain data: no GPU import).
 
-tests/test_gpu_ops.py and tests/test_gpu_conv_fused.py judge a conv kernel thoroughly once a case reaches it; neither asks whether
-every row of the four row tables (f32_rows, wino3_rows, f16_rows, s2h_rows) is reached.  CASES below are written for the rows
+tests/test_gpu_ops.py and tests/test_gpu_conv_fused.py judge a conv kernel on random data (2e-5 / 2e-3 of the range) once a case
+reaches it; neither asks whether every row of the four row tables (f32_rows, wino3_rows, f16_rows, s2h_rows) is reached.  (The
+Winograd rows, which those modules declare and CASES therefore leaves out, have their exact-integer runs and guard bands in a
+table of their own: tests/wino_exact_util.py GPU_CASES, run by tests/test_gpu_wino_exact.py.)  CASES below are written for the rows
 that a sweep of the dry-run planner selects and that no case of those modules declares; tests/test_conv_rows_cpu.py keeps that
 set closed (a row the planner can select needs a GPU case; a row nothing selects needs an entry in UNPLANNED with its reason) and
 tests/test_gpu_conv_rows.py runs every case.
